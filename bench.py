@@ -13,8 +13,11 @@ reads from an N x 12.5 Mb genome, seed 2).
     python bench.py [--gpus N] [--steps K] [--warmup W]         (N > 1: starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload correct                          (BASELINE configs[3]: `siga correct` k-mer path)
+    python bench.py --full                                      (also the CPU baseline, upload_inclusive and end_to_end legs)
+    python bench.py --dump-outputs DIR                          (the last timed step's outputs as DIR/<name>.npy)
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the headline; whatever else the bench measures runs only
+with --full.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import ctypes as C
@@ -74,7 +77,14 @@ def parse_args():
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--min-overlap", type=int, default=45)
     ap.add_argument("--seed", type=int, default=None, help="default: 1 at N = 1 (configs[1]), 2 at N > 1 (configs[2])")
-    ap.add_argument("--cpu-sample", type=int, default=400000, help="reads timed on the CPU restatement (0 = skip); 400 k = 4 s on 128 threads")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs it does not need: the CPU baseline (--cpu-sample), the "
+                         "upload_inclusive leg (--upload-steps) and the end_to_end leg (unless --no-e2e); --workload correct: "
+                         "the CPU baseline.  Off by default: a plain run does only what its headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all; larger outputs as a fixed, seeded sample of their rows)")
+    ap.add_argument("--cpu-sample", type=int, default=400000, help="with --full: reads timed on the CPU restatement (0 = skip); 400 k = 4 s on 128 threads")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--subbatches", type=int, default=1,
                     help="sub-batches per step (0 = library default for one batch at a time: 4 at this size); sub-batch i's "
@@ -105,11 +115,11 @@ def parse_args():
                     help="A/B aid: set the reads once, so that the locality order is computed in the warm-up only (what round 2 timed)")
     ap.add_argument("--kmer", type=int, default=31, help="--workload correct: k-mer size (31 = code default, 41 = example script)")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the end_to_end leg (N = 1, error-free reads of at most 2 M: the reads as FASTA through the `siga overlap` "
-                         "CLI in a child process, after the timed region)")
+                    help="with --full: skip the end_to_end leg (N = 1, error-free reads of at most 2 M: the reads as FASTA through the "
+                         "`siga overlap` CLI in a child process, after the timed region)")
     ap.add_argument("--upload-steps", type=int, default=30,
-                    help="steps of the upload_inclusive leg after the timed region (every step's reads come from pinned host memory "
-                         "through sigax_batch_upload); 0 = skip")
+                    help="with --full: steps of the upload_inclusive leg after the timed region (every step's reads come from pinned "
+                         "host memory through sigax_batch_upload); 0 = skip")
     ap.add_argument("--error-rate", type=float, default=None,
                     help="substitutions per base: --workload correct default 0.01; --workload overlap default 0 (the BASELINE configs are "
                          "error-free), > 0 shows what uncorrected reads cost (branches in the extraction)")
@@ -241,7 +251,7 @@ def bench_overlap(args):
     # file; rank 0 computes the order once per read set (from the sequences alone; kept beside the index files)
     by_key = ((job_world > 1 and args.shard == "key") or args.key_order) and not by_pos
     order_path = prefix + ".keyorder.npy"
-    whole = (rank == 0 and not have_index) or bool(args.error_rate) or (args.cpu_sample > 0 and world == 1) or \
+    whole = (rank == 0 and not have_index) or bool(args.error_rate) or (args.full and args.cpu_sample > 0 and world == 1) or \
             (by_key and rank == 0 and not os.path.exists(order_path))
 
     def draw(subset):
@@ -338,6 +348,10 @@ def bench_overlap(args):
     class _EdgeView:  # zero-copy view of the library's device edge buffer for torch
         def __init__(self, ptr, n):
             self.__cuda_array_interface__ = {"shape": (n, 4), "typestr": "<i4", "data": (ptr, False), "version": 2}
+
+    class _ByteView:  # ... and of its device substring flags (one byte per read)
+        def __init__(self, ptr, n):
+            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
     stats = _lib.Stats()
     rinfo = _lib.RunInfo()
@@ -485,10 +499,21 @@ def bench_overlap(args):
     ri = rinfo.as_dict()
     nsub_step = max(1, ri["n_sub"])
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the edge records in rank 0's pinned host buffer (every rank's, for
+        # N > 1) and the substring flags of rank 0's reads, still in the batch object's device buffers
+        i_last = (depth + args.warmup + args.steps - 1) % depth
+        edges = host_edges[i_last][:total_edges].numpy() if total_edges else np.zeros((0, 4), dtype=np.int32)
+        d_sub = C.c_void_p()
+        assert lib.sigax_batch_device_outputs(batches[i_last], None, None, C.byref(d_sub), None) == 0, _lib.last_error()
+        substring = torch.as_tensor(_ByteView(d_sub.value, n_local), device=dev).cpu().numpy()
+        write_outputs(args.dump_outputs, {"edges": (edges.view(np.uint32), np.float64, 52000000),
+                                          "substring": (substring, np.float32, 8000000)}, args.seed)
+
     # upload_inclusive: the same steps with every step's reads going up from pinned host memory through sigax_batch_upload
     # (the PCIe-inclusive rate of the device path; the headline keeps the reads resident, as the metric's contract says)
     upl = None
-    if world == 1 and not multi_path and args.upload_steps > 0:
+    if args.full and world == 1 and not multi_path and args.upload_steps > 0:
         h_seqs = torch.from_numpy(np.ascontiguousarray(shard).reshape(-1)).pin_memory()
         h_offs = np.arange(0, (n_local + 1) * L, L, dtype=np.uint64)
         k0 = depth + args.warmup + args.steps
@@ -629,7 +654,7 @@ def bench_overlap(args):
                                       "device_of_rank0": dev_index,
                                       "edge_gather": "sigax_gather_counts + sigax_gather_edges (C-ABI; ncclAllGather + grouped ncclSend/ncclRecv)"
                                                      if comm is not None else "torch.distributed all_gather + gather (%s)" % args.backend}
-        if world == 1 and not multi_path and args.cpu_sample > 0:
+        if args.full and world == 1 and not multi_path and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(prefix, reads, min(args.cpu_sample, n_total), args.min_overlap, st, lib, batch)
 
     for bt in batches:
@@ -638,7 +663,7 @@ def bench_overlap(args):
         torch.cuda.synchronize(dev)
         lib.sigax_comm_destroy(comm)
     pair.close()
-    if rank == 0 and world == 1 and not multi_path and job_world == 1 and not args.no_e2e and not args.error_rate and not by_pos and n_total <= 2000000:
+    if args.full and rank == 0 and world == 1 and not multi_path and job_world == 1 and not args.no_e2e and not args.error_rate and not by_pos and n_total <= 2000000:
         if reads is None:
             reads = draw(None)
         out["end_to_end"] = end_to_end_cli(workdir, reads, args.min_overlap, out.get("cpu_baseline"),
@@ -648,6 +673,23 @@ def bench_overlap(args):
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def write_outputs(dirname, outputs, seed):
+    """--dump-outputs: outputs = {name: (array, dtype, max_bytes)} -> dirname/<name>.npy in that dtype.  An array whose rows
+    would take more than max_bytes is written as a sample of its rows: drawn with `seed`, kept in their order, so the same
+    arguments give the same rows from run to run (the caps add up to less than 64 MB)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, (a, dtype, max_bytes) in outputs.items():
+        a = np.asarray(a)
+        row_bytes = np.dtype(dtype).itemsize * max(1, int(np.prod(a.shape[1:])))
+        keep = max_bytes // row_bytes
+        what = "all %d rows" % a.shape[0]
+        if a.shape[0] > keep:
+            what = "%d of %d rows (seeded sample)" % (keep, a.shape[0])
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(dtype))
+        log("output %s: %s, shape %s, %s" % (name, what, a.shape, np.dtype(dtype).name))
 
 
 E2E_MD5_CONFIGS1 = "f47c833bc3fd5cc5f91daace91c5a345"  # ASQG text of BASELINE configs[1] at -m 45: the oracle's, rounds 1-3's
@@ -816,7 +858,11 @@ def bench_correct(args):
                        "avg_launch_ms": kernel_ms,
                        "note": "latency kernel on cache-resident tables: `achieved` = bytes past L2 (PMC) / launch time; "
                                "`requested_*` = 64 B x the distinct rank-table sectors the k-mer lookups ask for, mostly L2 hits"}
-    if args.cpu_sample > 0:
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the corrected reads and their valid flags (1 = written)
+        write_outputs(args.dump_outputs, {"corrected_reads": (fixed, np.float32, 52000000),
+                                          "valid": (valid, np.float32, 8000000)}, args.seed)
+    if args.full and args.cpu_sample > 0:
         from oracle import pyoracle as po
         po.build()
         sample = min(args.cpu_sample, N, 50000)  # one thread, about 2.5 k reads/s: 20 s
