@@ -12,9 +12,11 @@ from tests.fixtures import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def _run_parity(env_extra, select, seeds=None):
+def _run_parity(env_extra, select, seeds=None, non_acgt=None):
     env = dict(os.environ, **env_extra)
-    if seeds:  # cases of the randomised suite by seed
+    if non_acgt:  # cases of the non-ACGT suite by seed
+        what = [os.path.join(ROOT, "tests", "test_gpu_non_acgt.py") + "::test_non_acgt_case[%d]" % k for k in non_acgt]
+    elif seeds:  # cases of the randomised suite by seed
         what = [os.path.join(ROOT, "tests", "test_gpu_random.py") + "::test_random_case_bit_exact[%d]" % k for k in seeds]
     else:
         what = [os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-k", select]
@@ -164,3 +166,20 @@ def test_extractor_forms_without_the_row_tables():
     _run_parity({"SIGAX_ROWEND": "0"}, None, seeds=(1, 2, 5, 8, 13))
     _run_parity({"SIGAX_ROWEND": "0", "SIGAX_TWO_STEP": "0"}, "hits_and_asqg or non_acgt or duplicate or deep")
     _run_parity({"SIGAX_FORCE_WIDE": "1"}, None, seeds=(2, 3, 8, 21))
+
+
+def test_non_acgt_reads_in_every_kernel_form():
+    """Reads with non-ACGT bytes (tests/test_gpu_non_acgt.py, every case: min-overlaps 12-57, dense and sparse N, 250 and
+    700 bp reads) through the forms that carry their own copy of the '$' checks: the cooperative finder (ranks from LDS),
+    64-bit positions and many superblocks, the one-step finder and extractor, the read order, the 12-mer and deep start
+    tables at other K, the extractor without its row symbols, text or row table, direct maps asked for (refused: stretches
+    are not reads, so the row table serves), one filter/extract workgroup, candidate slots that overflow."""
+    from siga_amd import build as sbuild
+    from tests.golden.make_reads import NON_ACGT_SEEDS as seeds
+    lib = sbuild.build_libsigax(out=os.path.join(ROOT, "build", "libsigax_super12.so"), defines=("SIGAX_SUPER_SHIFT=12",))
+    for env in ({"SIGAX_FIND_COOP": "1"}, {"SIGAX_FORCE_WIDE": "1", "SIGAX_FIND_COOP": "1"},
+                {"SIGAX_FORCE_WIDE": "1", "SIGAX_LIB": lib}, {"SIGAX_TWO_STEP": "0"},
+                {"SIGAX_READ_ORDER": "1", "SIGAX_SUBBATCHES": "3"}, {"SIGAX_FIND_START": "1"}, {"SIGAX_XMAP": "1"},
+                {"SIGAX_ROW_SYMS": "0"}, {"SIGAX_LOOKAHEAD": "0"}, {"SIGAX_ROWEND": "0"}, {"SIGAX_DEEP_K": "13"},
+                {"SIGAX_FX_GRID": "1"}, {"SIGAX_CAND_CAP": "2"}):
+        _run_parity(env, None, non_acgt=seeds)
