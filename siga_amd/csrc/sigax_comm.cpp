@@ -19,7 +19,7 @@
 
 #include "../../include/sigax.h"
 
-int sigax_fail(int code, const char* fmt, ...);  // sigax_api.cpp: sets the thread-local error text, returns code
+int sigax_fail(int code, const char* fmt, ...);  // sigax_index.cpp: sets the thread-local error text, returns code
 
 namespace {
 struct Rccl {

@@ -34,12 +34,7 @@
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "sigax_kernels.h"
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-int sigax_fail(int code, const char* fmt, ...);  // sigax_api.cpp
+#include "sigax_internal.h"
 
 namespace {
 
@@ -132,8 +127,7 @@ struct DevPool {
       }
     }
     if (e == hipSuccess) {
-      static const bool poison = getenv("SIGAX_POOL_POISON") != nullptr;
-      if (poison) e = hipMemset(p, 0xA5, got);
+      if (settings().pool_poison) e = hipMemset(p, 0xA5, got);
       live.push_back({p, got, device});
     } else {
       p = nullptr;
@@ -541,7 +535,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 struct Phase {
   bool on;
   double t;
-  Phase() : on(getenv("SIGAX_BUILD_TIMING") != nullptr), t(now_s()) {}
+  Phase() : on(settings().build_timing), t(now_s()) {}
   void lap(const char* what) {
     if (!on) return;
     hipDeviceSynchronize();
@@ -930,12 +924,8 @@ struct OrderBounds { u32 n, b[9]; };
 // Class = the top bits of the minimizer's hash: 2^20 classes (a batch of a few million reads at a few-fold coverage holds
 // about a million minimizers; reads put side by side only help each other when they really share one).  SIGAX_ORDER_BITS.
 static u32 order_class_bits() {
-  static const u32 bits = [] {
-    const char* env = getenv("SIGAX_ORDER_BITS");
-    const int b = env ? atoi(env) : 20;
-    return (u32)(b < 8 ? 8 : b > 20 ? 20 : b);  // 3 bits of sub-batch + the class share the low 23 bits of a key
-  }();
-  return bits;
+  const int b = settings().order_bits;
+  return (u32)(b < 8 ? 8 : b > 20 ? 20 : b);  // 3 bits of sub-batch + the class share the low 23 bits of a key
 }
 // One thread per read, one wave per workgroup; its `per` reads (one byte range of the batch; 64, or fewer when the reads
 // are long, so that the range fits the LDS tile) are first copied to LDS with coalesced word loads -- round 2's kernel had

@@ -18,7 +18,7 @@
 
 #include "../../include/sigax.h"
 
-int sigax_fail(int code, const char* fmt, ...);  // sigax_api.cpp
+int sigax_fail(int code, const char* fmt, ...);  // sigax_index.cpp
 
 namespace {
 constexpr unsigned KEY_K = 16;

@@ -31,7 +31,7 @@ def _run_batch(pair, seqs, m, flags):
 
 
 def _expected_deep_k(m):
-    """what sigax_index_prepare_overlap builds for min-overlap m (sigax_api.cpp: deep_k_for)"""
+    """what sigax_index_prepare_overlap builds for min-overlap m (sigax_tables.cpp: deep_k_for)"""
     if os.environ.get("SIGAX_FIND_DEEP") == "0":
         return 0
     env = os.environ.get("SIGAX_DEEP_K")
@@ -59,7 +59,7 @@ def _same_blocks(got, want, seqs, what):
     # name reads of the set
     n = len(seqs)
     assert np.all(edges["query"] < n) and np.all(edges["target"] < n), what
-    # reads are not stretches: the direct maps are refused (sigax_api.cpp: plan_row_tables, can_direct)
+    # reads are not stretches: the direct maps are refused (sigax_tables.cpp: plan_row_tables, can_direct)
     assert info["row_direct"] == 0, what
 
 
@@ -123,7 +123,7 @@ def test_non_acgt_case(seed, tmp_path):
         assert np.array_equal(dup["block_offs"], wd["block_offs"])
         assert np.array_equal(blocks_matrix(dup["blocks"]), wd["blocks"])
         assert np.array_equal(dup["substring"].astype(bool), wd["substring"].astype(bool))
-        with pytest.raises(siga_amd.SigaxError) as e:  # stretches are not reads (sigax_api.cpp: sigax_index_check_order)
+        with pytest.raises(siga_amd.SigaxError) as e:  # stretches are not reads (sigax_index.cpp: sigax_index_check_order)
             pair.check_order(0)
         assert e.value.code == _lib.SIGAX_E_STATE
     finally:
