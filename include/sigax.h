@@ -171,7 +171,12 @@ int  sigax_kmer_count_batch(sigax_index*, const char* kmers, uint32_t k, uint64_
  * NULL (FASTA input: every base scores 15).  out_seqs has the layout of seqs and receives the corrected sequence of
  * reads that became all-solid and the unchanged sequence otherwise; valid[r] = CorrectResult::validQC (only those
  * reads are written by PostCorrector, :242-265).  Parameters as the CLI's -k/-x/-i/-O (defaults 31/3/10/1,
- * src/correct_processor.h:15-20).  Forward index only, as the reference. */
+ * src/correct_processor.h:15-20).  Forward index only, as the reference.
+ * A negative kmer_threshold means what it means in the reference, whose CorrectThreshold keeps the two supports as ints and
+ * hands them out as size_t (src/correct_processor.cpp:29-37): a negative support is one no count reaches.  With -1 a
+ * window or base whose phred is below 20 (every one of a FASTA read) is never solid and never corrected, while one at 20 and
+ * above needs support 0; with -2 and below nothing is solid, so no read with at least kmer_size bases is valid.
+ * k-mer counts are kept in 32 bits and saturate at 2^32 - 2; 2^32 - 1 stands for "out of reach", also as count_offset. */
 int  sigax_correct_batch(sigax_index*, const char* seqs, const char* quals, const uint64_t* offs, uint32_t n_reads,
                          uint32_t kmer_size, int32_t kmer_threshold, uint32_t kmer_rounds, uint32_t count_offset,
                          char* out_seqs, uint8_t* valid);

@@ -219,6 +219,30 @@ int orc_correct(void* hf, const char* reads_path, const char* out_path, uint64_t
   return 0;
 }
 
+// correctRead per read in the layout of sigax_correct_batch (include/sigax.h): offs[n+1] into seqs / quals (quals may be
+// NULL: every base scores 15, as a FASTA record does) -> out_seqs (what PostCorrector would write for a valid read, the
+// read itself otherwise) and valid[n].  OpenMP over reads; orc_correct is the same call per record of a file.
+int orc_correct_batch(void* hf, const char* seqs, const char* quals, const uint64_t* offs, uint64_t n, uint64_t k, int threshold,
+                      uint64_t rounds, uint64_t offset, int threads, char* out_seqs, uint8_t* valid) {
+  OrcIndex* f = (OrcIndex*)hf;
+  CorrectParams P;
+  P.kmerSize = k; P.minSupport = threshold; P.maxAttempts = rounds; P.countOffset = offset;
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+#pragma omp parallel for schedule(dynamic, 16)
+#endif
+  for (int64_t i = 0; i < (int64_t)n; ++i) {
+    DNASeq rd;
+    rd.seq.assign(seqs + offs[i], seqs + offs[i + 1]);
+    if (quals) rd.quality.assign(quals + offs[i], quals + offs[i + 1]);
+    std::string out;
+    valid[i] = correctRead(f->b.fm, P, rd, &out) ? 1 : 0;
+    if (out.size() != rd.seq.size()) out = rd.seq;  // cannot happen: corrections are substitutions
+    memcpy(out_seqs + offs[i], out.data(), out.size());
+  }
+  return 0;
+}
+
 // CPU baseline leg: OverlapBuilder::overlap over a batch of reads, OpenMP over reads like
 // parallel_framework.h:38.  Returns seconds; out3 = {blocks, substring reads, N_occ_min}.
 double orc_overlap_batch_timed(void* hf, void* hr, const char* seqs, const uint64_t* offs, uint64_t n,

@@ -50,6 +50,7 @@ def lib():
         L.orc_build_asqg_mt.argtypes = [vp, vp, cp, u64, C.c_int, C.c_int, cp, C.c_int, C.POINTER(C.c_double)]
         L.orc_rmdup.argtypes = [vp, vp, cp, cp, cp]
         L.orc_correct.argtypes = [vp, cp, cp, u64, C.c_int, u64, u64, pu64]
+        L.orc_correct_batch.argtypes = [vp, vp, vp, pu64, u64, u64, C.c_int, u64, u64, C.c_int, vp, vp]
         L.orc_overlap_batch_timed.restype = C.c_double
         L.orc_overlap_batch_timed.argtypes = [vp, vp, cp, pu64, u64, u64, C.c_int, C.c_int, C.c_int, pu64]
         L.orc_overlap_batch.restype = C.c_int64
@@ -183,6 +184,31 @@ def correct(fwd, reads_path, out_path, k=31, threshold=3, rounds=10, offset=1):
     if r != 0:
         raise RuntimeError("orc_correct failed: %d" % r)
     return {"written": int(st[0]), "changed": int(st[1])}
+
+
+def correct_batch(fwd, seqs, quals, k=31, threshold=3, rounds=10, offset=1, threads=0):
+    """KmerCorrector::process per read, in the layout of sigax_correct_batch.  seqs / quals: lists of str/bytes (quals may
+    be None: no qualities), or (uint8 array of concatenated bytes, offsets u64[n+1]) with quals such an array or None.
+    Returns (out_seqs uint8[total], valid uint8[n]): a read that is not valid comes back as it went in."""
+    if isinstance(seqs, tuple):
+        buf, offs = seqs
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        qbuf = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+    else:
+        b, offs = pack_reads(seqs)
+        buf = np.frombuffer(b, dtype=np.uint8)
+        qbuf = None if quals is None else np.frombuffer(pack_reads(quals)[0], dtype=np.uint8)
+    if qbuf is not None and len(qbuf) != len(buf):
+        raise ValueError("qualities and bases differ in length")
+    n = len(offs) - 1
+    out = np.zeros(max(len(buf), 1), dtype=np.uint8)
+    valid = np.zeros(max(n, 1), dtype=np.uint8)
+    r = lib().orc_correct_batch(fwd.h, buf.ctypes.data, None if qbuf is None else qbuf.ctypes.data, _p64(offs), n, k, threshold,
+                                rounds, offset, threads, out.ctypes.data, valid.ctypes.data)
+    if r != 0:
+        raise RuntimeError("orc_correct_batch failed: %d" % r)
+    return out[:len(buf)], valid[:n]
 
 
 def overlap_batch_timed(fwd, rev, reads, min_overlap, irreducible=True, rc=True, threads=0):

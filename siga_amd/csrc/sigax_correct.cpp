@@ -173,8 +173,10 @@ static CorrectArgs correct_args(sigax_index* ix, const unsigned char* d_seqs, co
   ca.offs = d_offs;
   ca.n_reads = n_reads;
   ca.k = kmer_size;
-  ca.low = (uint32_t)std::max(kmer_threshold, 0);       // CorrectThreshold::minSupport (src/correct_processor.cpp:28-31)
-  ca.high = (uint32_t)std::max(kmer_threshold + 1, 0);
+  // CorrectThreshold::minSupport (src/correct_processor.cpp:28-37) keeps two ints and hands them out as size_t: a negative
+  // one is a support no count reaches (-1: low unreachable, high = 0; -2 and below: both unreachable)
+  ca.low = kmer_threshold < 0 ? CORRECT_NEVER : (uint32_t)kmer_threshold;
+  ca.high = kmer_threshold < -1 ? CORRECT_NEVER : (uint32_t)((long long)kmer_threshold + 1);
   ca.cutoff = 20;
   ca.rounds = kmer_rounds;
   ca.offset = count_offset;

@@ -153,13 +153,16 @@ struct EdgeArgs {
   unsigned long long edge_cap;
 };
 
+#define CORRECT_NEVER 0xFFFFFFFFu
 struct CorrectArgs {
   FmStrand fwd;
   const unsigned char* seqs;
   const unsigned char* quals;  // NULL: every base scores Quality::Phred::DEFAULT_SCORE (15)
   const unsigned long long* offs;
   unsigned long long n_reads;
-  uint32_t k, low, high, cutoff, rounds, offset;  // CorrectThreshold: required support low / high (phred >= cutoff)
+  // CorrectThreshold: required support low / high (phred >= cutoff).  CORRECT_NEVER = a support no count reaches (what a
+  // negative threshold is in the reference): kmer_occ's counts saturate one below it
+  uint32_t k, low, high, cutoff, rounds, offset;
   unsigned char* out;    // corrected sequences, same layout as seqs
   unsigned char* valid;  // CorrectResult::validQC; 2 = read longer than the kernel supports
   unsigned long long* dstat;  // [0] reads too long, [1] rank-table sectors asked for, [2] k-mer lookups (4 x u64)

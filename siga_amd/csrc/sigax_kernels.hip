@@ -3531,7 +3531,7 @@ struct CorrectShT {
   unsigned char minph[LMAX];  // min phred of the window starting here (src/correct_processor.cpp:95-103)
   unsigned char redo[LMAX];   // window must be recounted
   unsigned short pref[LMAX + 1];  // solid windows before this one
-  u32 cnt[LMAX];              // occurrences of the window's k-mer (saturated)
+  u32 cnt[LMAX];              // occurrences of the window's k-mer (saturated: kmer_count_sat)
   // the read's bases as 2-bit codes (rank - 1), LAST base first: symbol j at bits 2 (j & 31) of word j / 32, so the k-mer
   // starting at s, in the order the backward search consumes it (= the k-mer table's key), is the 2 k bits from bit
   // 2 (n - s - k) on; two words of zeros behind for the unaligned reads
@@ -3570,6 +3570,13 @@ __global__ __launch_bounds__(256) void k_prefix_build(FmStrand s, void* tab, u32
   else reinterpret_cast<uint2*>(tab)[code] = make_uint2((u32)lo, (u32)cnt);
 }
 
+// A count as kmer_occ returns it: saturated at 2^32 - 2, one below CORRECT_NEVER, so that a threshold of CORRECT_NEVER is
+// out of reach whatever the index holds.  With 32-bit positions an interval has fewer than 2^32 - 1 rows as it is.
+template <bool WIDE>
+__device__ __forceinline__ u32 kmer_count_sat(u64 c) {
+  return WIDE && c > 0xFFFFFFFEull ? 0xFFFFFFFEu : (u32)c;
+}
+
 template <bool WIDE>
 __device__ __forceinline__ u32 kmer_occ(const FmRef& f, const FmTables& tb, const Find2TablesT<WIDE>* t2, const uint32_t* gran2,
                                         const u64* super2, const void* ptab, u32 pk, const unsigned char* seq, u32 s, u32 k, u32 ovpos,
@@ -3599,7 +3606,7 @@ __device__ __forceinline__ u32 kmer_occ(const FmRef& f, const FmTables& tb, cons
     P a0 = 0, a1 = 0, az = 0;
     nsec += 1u;
     if (!deep_lookup<WIDE>(ktab, ktab_slots, k0, k1, a0, a1, az)) return 0u;
-    return (u64)az > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)az;
+    return kmer_count_sat<WIDE>((u64)az);
   }
   if (ktab != nullptr) {
     // the table holds every distinct k-mer of the indexed reads with its number of occurrences (fm_layout.h: the deep start
@@ -3620,7 +3627,7 @@ __device__ __forceinline__ u32 kmer_occ(const FmRef& f, const FmTables& tb, cons
       P a0 = 0, a1 = 0, az = 0;
       nsec += 1u;
       if (!deep_lookup<WIDE>(ktab, ktab_slots, k0, k1, a0, a1, az)) return 0u;
-      return (u64)az > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)az;
+      return kmer_count_sat<WIDE>((u64)az);
     }
   }
   u32 j = k;
@@ -3704,8 +3711,7 @@ __device__ __forceinline__ u32 kmer_occ(const FmRef& f, const FmTables& tb, cons
     --j;
   }
   if (!(hi != (P)~(P)0 && hi >= lo)) return 0u;
-  u64 c = (u64)(hi - lo) + 1ull;
-  return c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)c;
+  return kmer_count_sat<WIDE>((u64)(hi - lo) + 1ull);
 }
 
 template <bool WIDE, int LMAX>

@@ -1,5 +1,10 @@
 """Helpers shared by the BASELINE-sized GPU tests: compare a GPU result with the oracle's batch call, and a numpy
-restatement of Hit2OverlapConverter::convert (src/overlap_builder.cpp:345-375) for the edge records."""
+restatement of Hit2OverlapConverter::convert (src/overlap_builder.cpp:345-375) for the edge records; the corrector's
+cases against the oracle, and its device-resident entry point driven through the HIP runtime."""
+import ctypes as C
+import hashlib
+import os
+
 import numpy as np
 
 COLS = ["capped0_lo", "capped0_hi", "capped1_lo", "capped1_hi", "raw0_lo", "raw0_hi", "raw1_lo", "raw1_hi", "length", "af"]
@@ -70,3 +75,90 @@ def read_sai(path):
         d = body[np.minimum(starts + k, len(body) - 1)].astype(np.int64) - 48
         out = np.where(has, out * 10 + d, out)
     return out.astype(np.uint32)
+
+
+# ---- `siga correct` ------------------------------------------------------------------------------------------------------
+def pack_case(case):
+    """a case of make_reads.correct_case -> (seqs uint8[total], quals uint8[total] or None, offs u64[n+1])"""
+    from oracle import pyoracle as po
+    b, offs = po.pack_reads([s for _, s in case["reads"]])
+    q = None if case["quals"] is None else np.frombuffer("".join(case["quals"]).encode(), dtype=np.uint8)
+    return np.frombuffer(b, dtype=np.uint8), q, offs
+
+
+def correct_oracle(case, index=None):
+    """the oracle's (out_seqs, valid) for a case.  With SIGA_CORRECT_ORACLE_CACHE set to a directory the result is kept
+    there under a hash of the case: tests/test_gpu_wide.py runs every case under many kernel forms and asks once."""
+    from oracle import pyoracle as po
+    seqs, quals, offs = pack_case(case)
+    args = (case["k"], case["threshold"], case["rounds"], case["offset"])
+    cache = os.environ.get("SIGA_CORRECT_ORACLE_CACHE")
+    path = None
+    if cache:
+        h = hashlib.sha1(seqs.tobytes() + b"|" + (quals.tobytes() if quals is not None else b"-") + offs.tobytes() + repr(args).encode())
+        path = os.path.join(cache, "correct_%s.npz" % h.hexdigest()[:20])
+        if os.path.exists(path):
+            z = np.load(path)
+            return z["out"], z["valid"]
+    index = index or po.Index.build([s for _, s in case["reads"]])
+    out, valid = po.correct_batch(index, (seqs, offs), quals, *args)
+    if path:
+        tmp = path + ".%d.tmp.npz" % os.getpid()
+        np.savez(tmp, out=out, valid=valid)
+        os.replace(tmp, path)
+    return out, valid
+
+
+def assert_same_correction(got, want, offs, what=""):
+    """got, want: (out_seqs, valid); every read's bytes and flag must be equal"""
+    go, gv = got
+    wo, wv = want
+    if np.array_equal(gv, wv) and np.array_equal(go, wo):
+        return
+    offs = offs.astype(np.int64)
+    bad_b = np.nonzero(go != wo)[0]
+    r_b = int(np.searchsorted(offs, bad_b[0], side="right") - 1) if len(bad_b) else len(gv)
+    bad_v = np.nonzero(gv != wv)[0]
+    r = min(r_b, int(bad_v[0]) if len(bad_v) else len(gv))
+    a, b = int(offs[r]), int(offs[r + 1])
+    raise AssertionError("%s: %d reads differ in valid[], %d bytes differ; first: read %d, %d bases\n got  valid=%d %s\n want valid=%d %s" % (
+        what, len(bad_v), len(bad_b), r, b - a, gv[r], go[a:b].tobytes().decode("latin-1"), wv[r], wo[a:b].tobytes().decode("latin-1")))
+
+
+def correct_on_device(L, handle, seqs, quals, offs, k, threshold, rounds, offset):
+    """sigax_correct_device on buffers made through the HIP runtime the library itself runs on (torch brings a second copy of
+    it) -> (out_seqs, valid, stat4)"""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    held = []
+
+    def dbuf(nbytes, src=None):
+        q = C.c_void_p()
+        assert hip.hipMalloc(C.byref(q), nbytes) == 0
+        held.append(q)
+        assert hip.hipMemset(q, 0, nbytes) == 0
+        if src is not None:
+            assert hip.hipMemcpy(q, src.ctypes.data, src.nbytes, 1) == 0  # host to device
+        return q
+
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(offs) - 1
+    try:
+        d_seqs, d_offs = dbuf(len(seqs) + 16, seqs), dbuf(offs.nbytes, offs)
+        d_quals = dbuf(len(seqs) + 16, np.ascontiguousarray(quals, dtype=np.uint8)) if quals is not None else None
+        d_out, d_val, d_stat = dbuf(len(seqs) + 16), dbuf(n + 16), dbuf(32)
+        assert hip.hipDeviceSynchronize() == 0
+        from siga_amd import _lib
+        assert L.sigax_correct_device(handle, d_seqs, d_quals, d_offs, n, k, threshold, rounds, offset, d_out, d_val, d_stat, None) == 0, _lib.last_error()
+        assert hip.hipDeviceSynchronize() == 0
+        out, val, stat = np.zeros(len(seqs), dtype=np.uint8), np.zeros(n, dtype=np.uint8), np.zeros(4, dtype=np.uint64)
+        assert hip.hipMemcpy(out.ctypes.data, d_out, len(seqs), 2) == 0 and hip.hipMemcpy(val.ctypes.data, d_val, n, 2) == 0
+        assert hip.hipMemcpy(stat.ctypes.data, d_stat, 32, 2) == 0
+    finally:
+        for q in held:
+            hip.hipFree(q)
+    return out, val, stat

@@ -260,3 +260,172 @@ def non_acgt_case(seed):
     rnd.shuffle(reads)
     return {"reads": [("r%d" % i, s) for i, s in enumerate(reads)], "m": m, "irreducible": seed % 3 != 0,
             "rc": seed % 5 != 0, "dense": dense}
+
+
+# ---- `siga correct` across k, its options and the k-mer lookup forms ------------------------------------------------------
+# k: the k-mer table's range (8..56) and both sides of it, the 13-mer prefix table's k >= pk edge (12, 13, 14), the one- and
+# two-word keys of the table (31, 32, 33), candidates beyond one 64-base chunk (65, 100).
+CORRECT_KS = (7, 8, 12, 13, 14, 31, 32, 33, 55, 56, 57, 65, 100)
+# (kmer threshold -x, rounds -i, count offset -O): the defaults, negative thresholds (a support no count reaches), 0 with
+# qualities (support 0 / 1), one round, no round, offset 0
+CORRECT_OPTIONS = ((3, 10, 1), (-1, 10, 1), (-2, 10, 1), (0, 10, 0), (5, 1, 4), (3, 0, 1), (2, 3, 0))
+# seed -> (k, options, with qualities)
+CORRECT_CASES = {
+    1: (31, (3, 10, 1), False), 2: (32, (-1, 10, 1), False), 3: (33, (2, 3, 0), True), 4: (7, (3, 10, 1), False),
+    5: (8, (5, 1, 4), True), 6: (12, (3, 0, 1), False), 7: (13, (3, 10, 1), True), 8: (14, (0, 10, 0), True),
+    9: (55, (-2, 10, 1), True), 10: (56, (3, 10, 1), False), 11: (57, (2, 3, 0), False), 12: (65, (3, 10, 1), True),
+    13: (100, (5, 1, 4), False), 14: (32, (3, 10, 1), True), 15: (12, (2, 3, 0), False), 16: (57, (-1, 10, 1), True),
+}
+CORRECT_SEEDS = tuple(sorted(CORRECT_CASES))
+CORRECT_LMAX = 200
+
+
+def correct_offsets(k):
+    """offsets (from either read end) of a planted single substitution: the read ends, the eighth candidate and its
+    neighbours, the 32-symbol word edge of the packed key, the window edge"""
+    return sorted({0, 1, 7, 8, 9, 31, 32, 33, k - 2, k - 1, k})
+
+
+def correct_sh0_lengths(k):
+    """read lengths k + 32 j and k + 32 j +- 1 (j >= 1) up to CORRECT_LMAX: window 0's key starts at a 64-bit word edge"""
+    out = []
+    j = 1
+    while k + 32 * j - 1 <= CORRECT_LMAX:
+        out += [L for L in (k + 32 * j - 1, k + 32 * j, k + 32 * j + 1) if L <= CORRECT_LMAX]
+        j += 1
+    return out
+
+
+def fastq_text(named_reads, quals):
+    return "".join("@%s\n%s\n+\n%s\n" % (n, s, q) for (n, s), q in zip(named_reads, quals))
+
+
+def correct_case(seed):
+    """One seeded case of tests/test_gpu_correct_matrix.py: reads of one strand of a random genome with about 1 %
+    substitutions at a coverage that leaves the error-free k-mers well above the threshold, about one read in 30 with an N,
+    plus PLANTED reads: error-free pieces of the genome with a substitution (or two, or an N, or chosen qualities) put where
+    k_correct and kmer_occ change form.  Returns dict(reads=[(name, seq)], quals=[str] or None, k, threshold, rounds,
+    offset, planted=[dict(i=read index, cls=class name, errs=[offsets of the substitutions])])."""
+    rnd = random.Random(9000 + seed)
+    k, (threshold, rounds, offset), with_q = CORRECT_CASES[seed]
+    Lmax = CORRECT_LMAX
+    Lmin = 60 if k <= 33 else 110 if k <= 65 else 150
+    G = 1500 if k <= 8 else 6000 if k < 55 else 3000
+    genome = "".join(rnd.choice("ACGT") for _ in range(G))
+    err = 0.01
+    Lavg = (Lmin + Lmax) // 2
+    n_base = int(max(25 * G / Lavg, 15 * G / ((Lavg - k + 1) * (1 - err) ** k)))
+    assert n_base <= 2400
+
+    def piece(l):
+        p = rnd.randrange(0, G - l + 1)
+        return genome[p:p + l]
+
+    def other(b):
+        return rnd.choice([c for c in "ACGT" if c != b])
+
+    def sub(s, i):
+        return s[:i] + other(s[i]) + s[i + 1:]
+
+    def put(s, i, c):
+        return s[:i] + c + s[i + 1:]
+
+    def length(at_least=0):
+        lo = max(Lmin, at_least)
+        return rnd.randrange(lo, max(Lmax, lo) + 1)
+
+    def base_quals(l):
+        # mostly good bases; about one read in six carries a few below the cutoff of 20
+        q = [rnd.choice((30, 35, 40)) for _ in range(l)]
+        if rnd.random() < 1.0 / 6:
+            for _ in range(rnd.randrange(1, 4)):
+                q[rnd.randrange(l)] = rnd.choice((2, 12, 19))
+        return q
+
+    items = []  # (seq, phreds or None, class or None, errs)
+
+    def add(s, cls=None, errs=(), q=None):
+        items.append((s, (q if q is not None else [40] * len(s)) if with_q else None, cls, list(errs)))
+
+    for _ in range(n_base):
+        s = piece(length())
+        s = "".join(other(b) if rnd.random() < err else b for b in s)
+        if rnd.random() < 1.0 / 30:
+            s = put(s, rnd.randrange(len(s)), "N")
+        add(s, q=base_quals(len(s)))
+    # a single substitution at a given offset from the start, and from the end
+    for o in correct_offsets(k):
+        for from_end in (False, True):
+            for _ in range(4):
+                s = piece(length(k + 34))
+                p = len(s) - 1 - o if from_end else o
+                add(sub(s, p), "sub_end" if from_end else "sub_start", [p])
+    if k >= 10:  # inside the first k bases, beyond the first eight candidates
+        for _ in range(14):
+            p = rnd.randrange(8, k)
+            add(sub(piece(length(k + 34)), p), "first_k_beyond_8", [p])
+    if k > 64:  # ... and beyond the first 64-base chunk
+        for _ in range(10):
+            p = rnd.randrange(64, k)
+            add(sub(piece(length(k + 34)), p), "first_k_beyond_64", [p])
+    # two substitutions closer than k
+    for d in sorted({1, 2, k // 2, k - 1}):
+        for _ in range(3):
+            s = piece(length(2 * k + 2))
+            p = rnd.randrange(0, len(s) - d)
+            add(sub(sub(s, p), p + d), "two_subs", [p, p + d])
+    # reads of k, k + 1, k - 1 bases and of one
+    for L, cls in ((k, "len_k"), (k + 1, "len_k1"), (k - 1, "len_km1")):
+        for j in range(4):
+            s = piece(L)
+            p = rnd.randrange(L)
+            add(sub(s, p) if j >= 2 else s, cls, [p] if j >= 2 else [])
+    add("A", "len_1")
+    add("N", "len_1")
+    # window 0 at a word edge of the packed read
+    for L in correct_sh0_lengths(k):
+        add(piece(L), "sh0_length")
+        for p in (0, k - 1, rnd.randrange(L)):
+            add(sub(piece(L), p), "sh0_length", [p])
+    # one N: in the last 13 bases of a window that holds the error, in its first ones, nowhere near it
+    for _ in range(4):
+        L = length(k + 34)
+        p = rnd.randrange(k, L - k) if L > 2 * k + 1 else k
+        s0 = p - rnd.randrange(0, min(k, p + 1))           # a window [s0, s0 + k) over p
+        s0 = min(s0, L - k)
+        for cls, cand in (("n_window_tail", [s0 + k - 1 - r for r in range(min(13, k))]), ("n_window_head", [s0 + r for r in range(min(4, k))])):
+            cand = [c for c in cand if c != p and 0 <= c < L]
+            add(put(sub(piece(L), p), rnd.choice(cand), "N"), cls, [p])
+        L = length(k + 34)
+        p = rnd.randrange(0, 5)
+        add(put(sub(piece(L), p), L - 1 - rnd.randrange(0, 5), "N"), "n_far", [p])
+        s = piece(L)
+        add(put(s, rnd.randrange(L), "N"), "n_alone")
+    add("N" * 80, "all_n")
+    # what no correction mends: runs of N, and reads that are not of this genome
+    for _ in range(8):
+        s = piece(length(k + 34))
+        a = rnd.randrange(0, len(s) - 3)
+        r = rnd.choice((2, 3))
+        add(s[:a] + "N" * r + s[a + r:], "n_run")
+    for _ in range(20):
+        add("".join(rnd.choice("ACGT") for _ in range(length())), "foreign")
+    if with_q:
+        # the substituted base and its neighbours at phred 19 / 20 / 21: the cutoff of 20 picks `low` or `high`
+        for trio in ((19, 19, 19), (20, 20, 20), (21, 21, 21), (19, 20, 21), (21, 19, 21), (19, 21, 19)):
+            for _ in range(4):
+                s = piece(length(k + 34))
+                p = rnd.randrange(1, len(s) - 1)
+                q = [40] * len(s)
+                q[p - 1:p + 2] = trio
+                add(sub(s, p), "qual_%d_%d_%d" % trio, [p], q=q)
+    # exact duplicates, of planted reads and of the base set
+    for _ in range(20):
+        s, q, cls, errs = rnd.choice(items)
+        items.append((s, q, "duplicate", errs))
+    rnd.shuffle(items)
+    assert len(items) <= 3000
+    return {"reads": [("r%d" % i, it[0]) for i, it in enumerate(items)],
+            "quals": ["".join(chr(33 + v) for v in it[1]) for it in items] if with_q else None,
+            "k": k, "threshold": threshold, "rounds": rounds, "offset": offset,
+            "planted": [dict(i=i, cls=it[2], errs=it[3]) for i, it in enumerate(items) if it[2]]}

@@ -12,9 +12,11 @@ from tests.fixtures import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def _run_parity(env_extra, select, seeds=None, non_acgt=None):
+def _run_parity(env_extra, select, seeds=None, non_acgt=None, correct=None):
     env = dict(os.environ, **env_extra)
-    if non_acgt:  # cases of the non-ACGT suite by seed
+    if correct:  # cases of the corrector's matrix by seed
+        what = [os.path.join(ROOT, "tests", "test_gpu_correct_matrix.py") + "::test_correct_case[%d]" % k for k in correct]
+    elif non_acgt:  # cases of the non-ACGT suite by seed
         what = [os.path.join(ROOT, "tests", "test_gpu_non_acgt.py") + "::test_non_acgt_case[%d]" % k for k in non_acgt]
     elif seeds:  # cases of the randomised suite by seed
         what = [os.path.join(ROOT, "tests", "test_gpu_random.py") + "::test_random_case_bit_exact[%d]" % k for k in seeds]
@@ -136,6 +138,26 @@ def test_correct_without_the_kmer_prefix_table():
     # the prefix table + walk of round 3
     _run_parity({"SIGAX_KMER_TABLE": "0"}, "correct")
     _run_parity({"SIGAX_KMER_TABLE": "0", "SIGAX_FORCE_WIDE": "1"}, "correct_matches")
+
+
+def test_correct_matrix_in_every_lookup_form():
+    """Every case of tests/test_gpu_correct_matrix.py (k = 7 .. 100, seven option sets, planted reads; per read against the
+    oracle) through the forms of kmer_occ that the defaults do not take: without the k-mer table (13-mer prefix table +
+    walk at every k >= 13, the plain walk below), without either table, prefix tables of 8 and of 14 symbols (the k >= pk
+    edge moves to k = 8 and to k = 14), one-step granules in place of two-step lines, 64-bit positions, and those with a
+    superblock every 2^12 symbols.  SIGAX_DEEP_LOAD is left out: the corrector's k-mer table is always sized at two slots
+    per distinct k-mer (sigax_correct.cpp: ensure_kmer_table) and does not read it.  The oracle is asked once per case:
+    the forms share its answers through SIGA_CORRECT_ORACLE_CACHE (tests/bigcheck.py: correct_oracle)."""
+    from siga_amd import build as sbuild
+    from tests.fixtures import CACHE
+    from tests.golden.make_reads import CORRECT_SEEDS as seeds
+    lib = sbuild.build_libsigax(out=os.path.join(ROOT, "build", "libsigax_super12.so"), defines=("SIGAX_SUPER_SHIFT=12",))
+    shared = os.path.join(CACHE, "correct_oracle")
+    os.makedirs(shared, exist_ok=True)
+    for env in ({"SIGAX_KMER_TABLE": "0"}, {"SIGAX_KMER_TABLE": "0", "SIGAX_KMER_PREFIX": "0"},
+                {"SIGAX_KMER_TABLE": "0", "SIGAX_KMER_PREFIX": "8"}, {"SIGAX_KMER_TABLE": "0", "SIGAX_KMER_PREFIX": "14"},
+                {"SIGAX_TWO_STEP": "0"}, {"SIGAX_FORCE_WIDE": "1"}, {"SIGAX_FORCE_WIDE": "1", "SIGAX_LIB": lib}):
+        _run_parity(dict(env, SIGA_CORRECT_ORACLE_CACHE=shared), None, correct=seeds)
 
 
 def test_locality_order_of_the_batch_bit_exact():

@@ -127,3 +127,34 @@ def test_occ_matches_naive_count():
         assert list(fx.fwd.occ(i)) == list(cum[i + 1])
     assert list(fx.fwd.occ(2**64 - 1)) == [0] * 5  # fmindex.cpp:191: ++i wraps to 0
     assert list(fx.fwd.pred()) == [0] + list(np.cumsum([np.sum(bwt == r) for r in range(4)]))
+
+
+@pytest.mark.parametrize("seed", [14, 11])
+def test_correct_batch_is_the_file_form_per_read(seed, tmp_path):
+    """po.correct_batch (per read: out_seqs + valid, the layout of sigax_correct_batch) against orc_correct (the file form,
+    pinned by the tests above it): the valid reads written in input order with the input's names and qualities are
+    orc_correct's file, byte for byte -- a FASTQ case (k = 32) and a FASTA one (k = 57, -x 2 -i 3 -O 0)."""
+    from tests.bigcheck import pack_case
+    from tests.golden import make_reads as mr
+    case = mr.correct_case(seed)
+    reads, quals = case["reads"], case["quals"]
+    assert (quals is not None) == (seed == 14)
+    path = str(tmp_path / ("r.fq" if quals else "r.fa"))
+    with open(path, "w") as f:
+        f.write(mr.fastq_text(reads, quals) if quals else mr.fasta_text(reads))
+    index = po.Index.build([s for _, s in reads])
+    args = dict(k=case["k"], threshold=case["threshold"], rounds=case["rounds"], offset=case["offset"])
+    st = po.correct(index, path, str(tmp_path / "o.ec"), **args)
+    seqs, q, offs = pack_case(case)
+    out, valid = po.correct_batch(index, (seqs, offs), q, **args)
+    text = out.tobytes().decode()
+    kept = [((n, text[int(offs[i]):int(offs[i + 1])]), quals[i] if quals else None) for i, (n, _) in enumerate(reads) if valid[i]]
+    mine = mr.fastq_text([r for r, _ in kept], [x for _, x in kept]) if quals else mr.fasta_text([r for r, _ in kept])
+    assert mine == open(tmp_path / "o.ec").read()
+    assert st["written"] == int(valid.sum()) > 100 and st["changed"] > 100
+    # the list form of the arguments is the array form
+    out2, valid2 = po.correct_batch(index, [s for _, s in reads], quals, **args)
+    assert np.array_equal(out2, out) and np.array_equal(valid2, valid)
+    # reads that are not valid come back as they went in
+    o = offs.astype(np.int64)
+    assert all(np.array_equal(out[o[i]:o[i + 1]], seqs[o[i]:o[i + 1]]) for i in np.nonzero(valid == 0)[0])
