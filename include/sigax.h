@@ -191,6 +191,40 @@ int  sigax_correct_device(sigax_index*, const void* d_seqs, const void* d_quals,
                           uint32_t kmer_size, int32_t kmer_threshold, uint32_t kmer_rounds, uint32_t count_offset,
                           void* d_out_seqs, void* d_valid, void* d_stat4, void* stream);
 
+/* `siga match` for a batch (src/match.cpp:54-62): how often each read occurs in the indexed set, count(w) = occ(w) +
+ * occ(revcomp(w)) with occ = FMIndex::Interval::occurrences (src/fmindex.h:80-86) on the forward index; the second term only
+ * with SIGAX_RC (CLI: absence of --no-opposite-strand), so a reverse-palindromic w counts twice, as in the reference.  A read of
+ * more than max_length bases is split: counts[2r] = count(its first max_length bases), the number of its `VT 0` line, and
+ * counts[2r+1] = count(its last max_length bases), the number of its `VT 1` line; any other read has counts[2r] = count(read)
+ * and counts[2r+1] = SIGAX_MATCH_NONE.  max_length = UINT64_MAX: never split; 0: every non-empty read is split into two empty
+ * patterns, which occur 0 times.  Bytes outside ACGT rank as '$', in w and in its complement.  Reads of any length below 2^32.
+ * flags: SIGAX_RC or 0, anything else is SIGAX_E_ARG.  Exact 64-bit counts.  Works on an index opened without the reverse
+ * strand; n_reads = 0 is SIGAX_OK. */
+#define SIGAX_MATCH_NONE (~0ull)
+int  sigax_match_batch(sigax_index*, const char* seqs, const uint64_t* offs, uint64_t n_reads, uint64_t max_length,
+                       uint32_t flags, uint64_t* counts);
+/* The same with every buffer in device memory, asynchronous on `stream` (a hipStream_t or NULL); allocates nothing.  d_offs
+ * u64[n_reads+1], d_counts u64[2 n_reads], d_stat4 = 4 u64 of device scratch that receive {chains run (non-empty patterns
+ * searched), symbols consumed (counted no further than where the reference's loop stops), rank-table sectors asked for,
+ * reserved (the kernel's work counter)}.  Uses the two-step tables and, when a correction call has left it on the device, the
+ * table of 13-mer intervals; allocates neither.  Counts do not depend on which tables exist. */
+int  sigax_match_device(sigax_index*, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint64_t max_length,
+                        uint32_t flags, void* d_counts, void* d_stat4, void* stream);
+
+/* A stream of batches through sigax_match_device, for a caller that does not link HIP (`siga match`): `slots` sets of device
+ * buffers, pinned host buffers and streams, sized once -- max_reads / max_bases per batch, 0 = from the device's free memory.
+ * submit copies batch `slot`'s reads up, runs the kernel and copies the counts down, all asynchronous on the slot's stream,
+ * so that one slot's copies run beside another's kernel; offs are the n_reads + 1 offsets of the batch's reads in `seqs`
+ * (offs[0] need not be 0: a window of a longer table).  wait returns the slot's counts[2 n_reads], valid until its next
+ * submit, and unless NULL its stat4 (sigax_match_device).  SIGAX_E_CAPACITY: the batch does not fit the slot. */
+typedef struct sigax_matcher sigax_matcher;
+int  sigax_matcher_create(sigax_index*, uint32_t slots, uint64_t max_reads, uint64_t max_bases, sigax_matcher** out);
+void sigax_matcher_destroy(sigax_matcher*);
+int  sigax_matcher_capacity(const sigax_matcher*, uint64_t* max_reads, uint64_t* max_bases);
+int  sigax_matcher_submit(sigax_matcher*, uint32_t slot, const char* seqs, const uint64_t* offs, uint64_t n_reads,
+                          uint64_t max_length, uint32_t flags);
+int  sigax_matcher_wait(sigax_matcher*, uint32_t slot, const uint64_t** counts, uint64_t stat4[4]);
+
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -59,6 +59,8 @@ SYMBOLS = [
     "sigax_batch_download", "sigax_batch_download_edges", "sigax_batch_size_hint", "sigax_batch_kernel_ms", "sigax_batch_run_info", "sigax_build_strand", "sigax_build_session", "sigax_free",
     "sigax_comm_unique_id", "sigax_comm_create", "sigax_comm_destroy", "sigax_gather_counts", "sigax_gather_edges",
     "sigax_locality_keys",
+    "sigax_match_batch", "sigax_match_device", "sigax_matcher_create", "sigax_matcher_destroy", "sigax_matcher_capacity",
+    "sigax_matcher_submit", "sigax_matcher_wait",
 ]
 
 _lib = None
@@ -126,6 +128,14 @@ def lib():
     L.sigax_comm_destroy.restype = None
     L.sigax_gather_counts.argtypes = [vp, u64, vp, vp]
     L.sigax_gather_edges.argtypes = [vp, vp, vp, ci, vp, vp]
+    L.sigax_match_batch.argtypes = [vp, cp, vp, u64, u64, u32, vp]
+    L.sigax_match_device.argtypes = [vp, vp, vp, u64, u64, u32, vp, vp, vp]
+    L.sigax_matcher_create.argtypes = [vp, u32, u64, u64, pvp]
+    L.sigax_matcher_destroy.argtypes = [vp]
+    L.sigax_matcher_destroy.restype = None
+    L.sigax_matcher_capacity.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sigax_matcher_submit.argtypes = [vp, u32, cp, vp, u64, u64, u32]
+    L.sigax_matcher_wait.argtypes = [vp, u32, pvp, C.POINTER(u64 * 4)]
     _lib = L
     return L
 

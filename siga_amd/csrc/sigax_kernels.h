@@ -178,6 +178,21 @@ void launch_correct(const CorrectArgs& a, bool wide, hipStream_t st);
 unsigned long long prefix_table_bytes(bool wide, uint32_t pk);
 void launch_prefix_build(const FmStrand& s, bool wide, void* tab, uint32_t pk, hipStream_t st);
 
+// `siga match` (sigax_match.hip): occurrences of whole reads, or of their first and last max_length bases, on the forward strand
+struct MatchArgs {
+  FmStrand fwd;
+  const unsigned char* seqs;
+  const unsigned long long* offs;        // [n_reads + 1]
+  unsigned long long n_reads;
+  unsigned long long max_length;         // ~0: no read is split
+  uint32_t rc;                           // also count the reverse complement
+  uint32_t pk;                           // symbols of an entry of ptab
+  const void* ptab;                      // the corrector's prefix table when it is resident (launch_prefix_build), or NULL
+  unsigned long long* counts;            // [2 n_reads]: sigax_match_device
+  unsigned long long* dstat;             // 4 u64, zeroed: chains run, symbols consumed, rank-table sectors asked for, the chain counter
+};
+void launch_match(const MatchArgs& a, bool wide, int n_cu, hipStream_t st);
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

@@ -36,6 +36,8 @@ def lib():
         L.sigah_format_asqg.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int]
         L.sigah_format_asqg.restype = C.c_int64
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
+        L.sigah_match_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_char_p,
+                                        C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -103,6 +105,16 @@ def correct_file(reads_path, prefix, output, k=31, threshold=3, rounds=10, offse
     if lib().sigah_correct_file(reads_path.encode(), prefix.encode(), output.encode(), k, threshold, rounds, offset, device,
                                 err, 512) != 0:
         raise RuntimeError("siga correct failed: " + err.value.decode())
+
+
+def match_files(paths, prefix, max_length=None, rc=True, device=0, out=None, batch_reads=0):
+    """`siga match`: FMIndex::load(<prefix>.bwt) + Matcher::run over the files of `paths`, in order; the VT lines go to the file
+    `out`, or to stdout.  max_length None: whole reads.  batch_reads: reads per device batch (0: from the free memory)."""
+    err = C.create_string_buffer(512)
+    arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+    lim = (1 << 64) - 1 if max_length is None else int(max_length)
+    if lib().sigah_match_files(arr, len(paths), prefix.encode(), lim, int(rc), device, (out or "").encode(), batch_reads, err, 512) != 0:
+        raise RuntimeError("siga match failed: " + err.value.decode())
 
 
 def parse_file(path, out_path, parallel=True, threads=4):

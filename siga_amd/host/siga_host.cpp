@@ -2307,6 +2307,115 @@ bool CorrectProcessor::process(const FMIndex& index, const std::string& input, c
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Matcher (src/match.cpp:38-63).  Two device slots (sigax_matcher): batch i's upload and kernel are queued, then batch
+// i - 1's counts are waited for and its lines formatted by the host threads, piece by piece, and written in read order.
+// ------------------------------------------------------------------------------------------------------
+bool Matcher::run(const FMIndex& index, const std::vector<std::string>& inputs, const std::string& output, size_t threads,
+                  size_t batchReads, size_t* processed) const {
+  _error.clear();
+  if (processed) *processed = 0;
+  if (!index.handle()) {
+    _error = "FMIndex not loaded";
+    return false;
+  }
+  FILE* out = output.empty() ? stdout : fopen(output.c_str(), "wb");
+  if (!out) {
+    _error = "Failed to create " + output;
+    return false;
+  }
+  const unsigned nt = host_threads(threads);
+  sigax_matcher* m = nullptr;
+  bool ok = true;
+  auto fail = [&](const std::string& what) {
+    if (ok) _error = what;
+    ok = false;
+  };
+  uint64_t cap_reads = 0, cap_bases = 0;
+  std::vector<std::string> pieces;
+  for (size_t f = 0; f < inputs.size() && ok; ++f) {
+    ReadStore rs;
+    if (!LoadReads(inputs[f], &rs, nt)) {
+      fail("Failed to create DNASeqReader " + inputs[f]);
+      break;
+    }
+    const size_t n = rs.size();
+    if (n == 0) continue;
+    for (size_t i = 0; i < n; ++i)
+      if (rs.offs[i + 1] - rs.offs[i] > 0xFFFFFFFFull) fail("read too long in " + inputs[f]);
+    if (!ok) break;
+    if (!m) {
+      // sized by the first file that has reads: batchReads reads of its mean length (the longest read must fit too)
+      uint64_t maxlen = 0;
+      for (size_t i = 0; i < n; ++i) maxlen = std::max<uint64_t>(maxlen, rs.offs[i + 1] - rs.offs[i]);
+      const uint64_t mean = std::max<uint64_t>(1, rs.offs[n] / n);
+      uint64_t want_reads = batchReads, want_bases = batchReads ? std::max<uint64_t>(batchReads * mean * 2, maxlen) : 0;
+      if (sigax_matcher_create(index.handle(), 2, want_reads, want_bases, &m) != SIGAX_OK) {
+        fail(std::string("match failed: ") + sigax_last_error());
+        break;
+      }
+      sigax_matcher_capacity(m, &cap_reads, &cap_bases);
+    }
+    // batches: as many reads as fit a slot, by number and by bases
+    std::vector<size_t> cut(1, 0);
+    for (size_t b = 0; b < n;) {
+      size_t e = b;
+      while (e < n && e - b < cap_reads && rs.offs[e + 1] - rs.offs[b] <= cap_bases) ++e;
+      if (e == b) {
+        fail("a read of " + inputs[f] + " does not fit the device batch");
+        break;
+      }
+      cut.push_back(e);
+      b = e;
+    }
+    if (!ok) break;
+    const size_t nb = cut.size() - 1;
+    auto drain = [&](size_t i) {  // batch i is on its way: wait for it, format, write
+      const uint64_t* counts = nullptr;
+      if (sigax_matcher_wait(m, (uint32_t)(i & 1), &counts, nullptr) != SIGAX_OK) {
+        fail(std::string("match failed: ") + sigax_last_error());
+        return;
+      }
+      const size_t b = cut[i], cnt = cut[i + 1] - b, np = std::min<size_t>(std::max<size_t>(1, cnt / 4096), 4 * (size_t)nt);
+      pieces.resize(np);
+      parallel_for(np, nt, [&](size_t p) {
+        std::string& t = pieces[p];
+        t.clear();
+        for (size_t k = cnt * p / np; k < cnt * (p + 1) / np; ++k) {
+          const std::string_view name = rs.name(b + k), seq = rs.seq(b + k);
+          for (int side = 0; side < 2; ++side) {
+            const uint64_t c = counts[2 * k + side];
+            if (side == 1 && c == SIGAX_MATCH_NONE) break;
+            t += side ? "VT\t1\t" : "VT\t0\t";
+            t.append(name.data(), name.size());
+            t += '\t';
+            t.append(seq.data(), seq.size());
+            t += '\t';
+            append_u64(t, c);
+            t += '\n';
+          }
+        }
+      });
+      for (const std::string& t : pieces)
+        if (!t.empty() && fwrite(t.data(), 1, t.size(), out) != t.size()) fail("Failed to write " + (output.empty() ? std::string("stdout") : output));
+      if (processed) *processed += cnt;
+    };
+    for (size_t i = 0; i < nb && ok; ++i) {
+      if (sigax_matcher_submit(m, (uint32_t)(i & 1), rs.seqs.data(), rs.offs.data() + cut[i], cut[i + 1] - cut[i], _maxLength,
+                               _rc ? SIGAX_RC : 0u) != SIGAX_OK) {
+        fail(std::string("match failed: ") + sigax_last_error());
+        break;
+      }
+      if (i > 0) drain(i - 1);
+    }
+    if (ok) drain(nb - 1);
+  }
+  if (m) sigax_matcher_destroy(m);
+  if (fflush(out) != 0) fail("Failed to write output");
+  if (out != stdout) fclose(out);
+  return ok;
+}
+
 }  // namespace sigah
 
 // ------------------------------------------------------------------------------------------------------
@@ -2508,6 +2617,25 @@ int sigah_correct_file(const char* reads_path, const char* prefix, const char* o
   sigah::CorrectProcessor proc(o);
   if (!proc.process(fmi, reads_path, output)) {
     if (err && errcap) snprintf(err, errcap, "%s", proc.error().c_str());
+    return -1;
+  }
+  return 0;
+}
+
+// `siga match`: FMIndex::load(prefix.bwt) + Matcher::run over n_paths inputs; out_path "" = stdout; max_length ~0 = no limit;
+// batch_reads 0 = device batches sized from the free memory
+int sigah_match_files(const char* const* paths, uint64_t n_paths, const char* prefix, uint64_t max_length, int rc, int device,
+                      const char* out_path, uint64_t batch_reads, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForward(prefix, fmi, device)) {
+    if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
+    return -1;
+  }
+  std::vector<std::string> inputs;
+  for (uint64_t i = 0; i < n_paths; ++i) inputs.push_back(paths[i]);
+  sigah::Matcher matcher(max_length, rc != 0);
+  if (!matcher.run(fmi, inputs, out_path ? out_path : "", 1, (size_t)batch_reads)) {
+    if (err && errcap) snprintf(err, errcap, "%s", matcher.error().c_str());
     return -1;
   }
   return 0;

@@ -139,6 +139,25 @@ class CorrectProcessor {
   mutable std::string _error;
 };
 
+// `siga match` (src/match.cpp:38-63): for every read of every input, how often it -- or, for a read of more than maxLength
+// bases, its first and its last maxLength bases -- occurs in the indexed reads, both strands unless rc is false.
+class Matcher {
+ public:
+  static const uint64_t kNoLimit = ~0ull;
+  explicit Matcher(uint64_t maxLength = kNoLimit, bool rc = true) : _maxLength(maxLength), _rc(rc) {}
+  // "VT\t0|1\t<name>\t<seq>\t<count>\n" lines in read order to `output` (empty: stdout).  The inputs are read in order; one
+  // that cannot be read ends the run with what came before it written, as in the reference.  batchReads = reads per device
+  // batch (0: from the device's free memory).
+  bool run(const FMIndex& index, const std::vector<std::string>& inputs, const std::string& output = std::string(), size_t threads = 1,
+           size_t batchReads = 0, size_t* processed = nullptr) const;
+  const std::string& error() const { return _error; }
+
+ private:
+  uint64_t _maxLength;
+  bool _rc;
+  mutable std::string _error;
+};
+
 }  // namespace sigah
 
 #endif

@@ -1,4 +1,4 @@
-// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` command line, option for option as the reference
+// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` ... command line, option for option as the reference
 // (src/main.cpp:17-83, src/indexer.cpp:119-156, src/overlap.cpp:66-105).  Exit codes follow the reference:
 // a runner returning -1 exits 255; printing help returns 256, i.e. exit status 0.
 #include <getopt.h>
@@ -76,11 +76,12 @@ static int apply_ini(int argc, char** argv, const option* longopts, std::vector<
 }
 
 static int usage() {
-  printf("siga [index|correct|overlap|rmdup] [OPTION] ... READSFILE\n"
+  printf("siga [index|correct|overlap|rmdup|match] [OPTION] ... READSFILE\n"
          "  index     build the FM-index (.sai/.bwt/.rsai/.rbwt) of READSFILE\n"
          "  overlap   compute pairwise overlaps between all the sequences in READSFILE (GPU)\n"
          "  rmdup     remove duplicated reads (GPU)\n"
          "  correct   k-mer based error correction (GPU)\n"
+         "  match     count the occurrences of every read of READSFILE in the indexed reads (GPU)\n"
          "common options: -s, --ini=FILE (options from FILE, the command line goes over them);\n"
          "                -c, --log4cxx=FILE is accepted and ignored (this build logs to stderr; SIGA_TIMING=1 prints phase\n"
          "                times and the reference's \"processed N sequences\" progress lines)\n");
@@ -377,6 +378,67 @@ static int run_correct(int argc, char** argv) {
   return 0;
 }
 
+static int match_help() {
+  // help text of src/match.cpp:83-94, plus the -l and -t lines it leaves out and --device
+  printf("siga match [OPTION] ... READSFILE\n"
+         "Match reads in READSFILE with ref\n"
+         "\n"
+         "      -h, --help                       display this help and exit\n"
+         "\n"
+         "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
+         "      -l, --max-length=N               match the first and the last N bases of reads longer than N (default: whole reads)\n"
+         "          --no-opposite-strand         treat all reads as forward strand\n"
+         "      -t, --threads=NUM                accepted; the GPU does the counting\n"
+         "          --device=NUM                 GPU to use (default: 0)\n"
+         "\n");
+  return 256;
+}
+
+// src/match.cpp:23-71
+static int run_match(int argc, char** argv) {
+  enum { OPT_NO_RC = 1, OPT_DEVICE };
+  static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},  {"ini", required_argument, nullptr, 's'},
+                                    {"prefix", required_argument, nullptr, 'p'},   {"threads", required_argument, nullptr, 't'},
+                                    {"max-length", required_argument, nullptr, 'l'}, {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC},
+                                    {"device", required_argument, nullptr, OPT_DEVICE}, {"help", no_argument, nullptr, 'h'},
+                                    {nullptr, 0, nullptr, 0}};
+  std::string prefix;
+  uint64_t maxLength = sigah::Matcher::kNoLimit;  // options.get<size_t>("max-length", -1)
+  size_t threads = 1;
+  bool help = false, rc = true;
+  int device = 0, c;
+  std::vector<std::string> ini_store;
+  std::vector<char*> ini_argv;
+  if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
+  argc = (int)ini_argv.size();
+  argv = ini_argv.data();
+  while ((c = getopt_long(argc, argv, "c:s:p:t:l:h", longopts, nullptr)) != -1) {
+    switch (c) {
+      case 'p': prefix = optarg; break;
+      case 't': threads = strtoull(optarg, nullptr, 10); break;
+      case 'l': maxLength = strtoull(optarg, nullptr, 10); break;
+      case OPT_NO_RC: rc = false; break;
+      case OPT_DEVICE: device = atoi(optarg); break;
+      case 'h': help = true; break;
+      default: break;
+    }
+  }
+  if (help || argc - optind < 1) return match_help();
+  std::vector<std::string> inputs(argv + optind, argv + argc);
+  if (prefix.empty()) prefix = sigah::Utils::stem(inputs[0]);
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForward(prefix, fmi, device)) {
+    fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+    return -1;
+  }
+  sigah::Matcher matcher(maxLength, rc);
+  if (!matcher.run(fmi, inputs, std::string(), threads)) {
+    fprintf(stderr, "Failed to match reads: %s\n", matcher.error().c_str());
+    return -1;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage();
   const auto t0 = std::chrono::steady_clock::now();
@@ -386,6 +448,7 @@ int main(int argc, char** argv) {
   else if (cmd == "rmdup") rc = run_rmdup(argc - 1, argv + 1);
   else if (cmd == "correct") rc = run_correct(argc - 1, argv + 1);
   else if (cmd == "overlap") rc = run_overlap(argc - 1, argv + 1);
+  else if (cmd == "match") rc = run_match(argc - 1, argv + 1);
   else return usage();
   if (getenv("SIGA_TIMING"))
     fprintf(stderr, "[siga] %-28s %8.3f s\n", "main() total", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

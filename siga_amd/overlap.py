@@ -27,6 +27,9 @@ def _check(code, where):
         raise SigaxError(code, where)
 
 
+MATCH_NONE = (1 << 64) - 1  # SIGAX_MATCH_NONE; as max_length: never split
+
+
 def pack_reads(seqs):
     if isinstance(seqs, tuple):  # (uint8 array of concatenated bases, offsets u64[n+1]): BASELINE-sized sets, no copies
         buf, offs = seqs
@@ -195,6 +198,22 @@ class FMIndexPair:
         out = np.zeros(len(kmers), dtype=np.uint64)
         _check(_lib.lib().sigax_kmer_count_batch(self._h, buf, k, len(kmers), out.ctypes.data), "sigax_kmer_count_batch")
         return out
+
+    def match(self, seqs, max_length=None, rc=True):
+        """`siga match` for a batch (src/match.cpp:54-62, sigax_match_batch) -> (head, tail), numpy u64 each: head[r] = the
+        number of read r's `VT 0` line; tail = a masked array, its `VT 1` number where the read is split (longer than
+        max_length), masked elsewhere.  max_length None: no read is split."""
+        buf, offs = pack_reads(seqs)
+        n = len(offs) - 1
+        out = np.zeros(2 * n, dtype=np.uint64)
+        if isinstance(buf, np.ndarray):
+            buf = C.c_char_p(buf.ctypes.data) if buf.size else b""
+        lim = MATCH_NONE if max_length is None else int(max_length)
+        _check(_lib.lib().sigax_match_batch(self._h, buf, offs.ctypes.data, n, lim, SIGAX_RC if rc else 0, out.ctypes.data),
+               "sigax_match_batch")
+        lens = offs[1:] - offs[:-1]
+        split = lens > np.uint64(lim)
+        return out[0::2].copy(), np.ma.masked_array(out[1::2].copy(), mask=~split)
 
 
 class OverlapBuilder:
