@@ -312,7 +312,10 @@ int  sigax_batch_run_info(sigax_batch*, sigax_run_info* out);
  * exchange: the variable-length gather of a step's fixed-size edge records to one rank -- what replaces the serial
  * hits -> ASQG pass of src/overlap_builder.cpp:466-483 when one process drives each GPU.  Over RCCL (xGMI between the
  * MI355X of a node): ncclAllGather of the per-rank counts, then grouped ncclSend / ncclRecv of the 16-byte records.
- * Gathered in rank order = read order: the ED order of a one-GPU run.  RCCL is bound at run time; without it these calls
+ * Gathered in rank order.  Where every rank ran a contiguous range of the file's reads (rank r the r-th range) that is the
+ * read order, the ED order of a one-GPU run; where the ranks ran key-range shards under their own ids
+ * (sigax_batch_*_read_ids) it is a permutation of it, and the caller follows the gather with sigax_edges_restore_order
+ * (below).  RCCL is bound at run time; without it these calls
  * fail with SIGAX_E_DEVICE and nothing else in the library is affected.  (The C++ host's `siga overlap --gpus N` drives
  * all GPUs from one process and copies each GPU's records to the host over that GPU's own PCIe link instead.) */
 typedef struct sigax_comm sigax_comm;
@@ -330,6 +333,37 @@ void sigax_comm_destroy(sigax_comm*);
 int  sigax_gather_counts(sigax_comm*, uint64_t n_local, uint64_t* counts, void* stream);
 int  sigax_gather_edges(sigax_comm*, const sigax_edge* d_local, const uint64_t* counts, int root, sigax_edge* d_out,
                         void* stream);
+
+/* ---- Read order of key-sharded edge records (csrc/sigax_order.hip) ---------------------------------------------------------
+ * Batches that run their reads under their own ids emit their records in the batch's order of reads.  Every read is run in one
+ * batch and a batch emits all records of one query contiguously, in hits order, so in the concatenation of the batches'
+ * records every query owns one contiguous run, and the ED order of a one-batch run is the stable order of that list by
+ * `query`.  No counterpart in the reference (one process, reads in file order: src/overlap_builder.cpp:466-483). */
+
+/* bytes of device scratch sigax_edges_restore_order needs; host arithmetic only, no device touched */
+int  sigax_edges_order_workspace(uint64_t n_edges, uint64_t n_reads, uint64_t* bytes);
+/* d_in: n_edges records (at most 2^32), the concatenation of any number of batches' edge records in any batch order
+ * (sigax_batch_device_outputs' d_edges, or sigax_gather_edges' d_out).
+ * d_out: the same records stably ordered by query = the ED order of a one-batch run over the n_reads indexed reads.
+ * d_out must not overlap d_in; both and d_work are 16-byte aligned.
+ * d_query_offs: NULL or u64[n_reads+1]: records of read q are d_out[offs[q] .. offs[q+1]).
+ * d_status: 2 u64 of device memory, written (not added to):
+ *   {records with query >= n_reads, runs beyond the first of a query}.
+ *   When either is non-zero d_out's and d_query_offs' contents are unspecified; no memory outside the buffers is touched.
+ * NULL where a buffer is required, overlapping buffers and a work_bytes below sigax_edges_order_workspace's are SIGAX_E_ARG.
+ * n_edges = 0: SIGAX_OK, d_query_offs all zeros, status zeros (d_in, d_out and d_work may be NULL).
+ * Asynchronous on `stream` (a hipStream_t or NULL); allocates nothing. */
+int  sigax_edges_restore_order(int device, const sigax_edge* d_in, uint64_t n_edges, uint64_t n_reads,
+                               sigax_edge* d_out, uint64_t* d_query_offs, void* d_work, uint64_t work_bytes,
+                               void* d_status, void* stream);
+/* host buffers in and out, synchronous; SIGAX_E_ARG with a text that names which of the two status counts was non-zero */
+int  sigax_edges_restore_order_host(int device, const sigax_edge* in, uint64_t n_edges, uint64_t n_reads,
+                                    sigax_edge* out, uint64_t* query_offs);
+/* Per-read bytes of a batch (sigax_batch_device_outputs' d_substring) to their reads' places: d_out[d_ids[r]] = d_flags[r],
+ * r < n; positions no id names keep their value; d_status: 1 u64 = ids >= n_reads (those are not written).  Asynchronous on
+ * `stream`; allocates nothing. */
+int  sigax_flags_by_read_id(int device, const uint8_t* d_flags, const uint32_t* d_ids, uint64_t n, uint64_t n_reads,
+                            uint8_t* d_out, void* d_status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,7 @@ SYMBOLS = [
     "sigax_locality_keys",
     "sigax_match_batch", "sigax_match_device", "sigax_matcher_create", "sigax_matcher_destroy", "sigax_matcher_capacity",
     "sigax_matcher_submit", "sigax_matcher_wait",
+    "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
 _lib = None
@@ -136,6 +137,10 @@ def lib():
     L.sigax_matcher_capacity.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.sigax_matcher_submit.argtypes = [vp, u32, cp, vp, u64, u64, u32]
     L.sigax_matcher_wait.argtypes = [vp, u32, pvp, C.POINTER(u64 * 4)]
+    L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]
+    L.sigax_edges_restore_order.argtypes = [ci, vp, u64, u64, vp, vp, vp, u64, vp, vp]
+    L.sigax_edges_restore_order_host.argtypes = [ci, vp, u64, u64, vp, vp]
+    L.sigax_flags_by_read_id.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp]
     _lib = L
     return L
 

@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libsigax.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["sigax_kernels.hip", "sigax_api.cpp", "sigax_index.cpp", "sigax_tables.cpp", "sigax_correct.cpp", "sigax_index_build.hip",
-           "sigax_comm.cpp", "sigax_keys.hip", "sigax_match.hip", "sigax_match.cpp"]
+           "sigax_comm.cpp", "sigax_keys.hip", "sigax_match.hip", "sigax_match.cpp", "sigax_order.hip"]
 HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", os.path.join(ROOT, "include", "sigax.h")]
 
 

@@ -3,7 +3,9 @@
 // counts, then grouped ncclSend / ncclRecv of the records (xGMI between the MI355X of one node) -- for callers that run one
 // process per GPU and want the records of a step on ONE device (bench.py --gpus N; a service that post-processes on GPU 0).
 // Replaces the serial hits -> ASQG pass of src/overlap_builder.cpp:466-483 as far as it concerns moving records between
-// devices; the rank order of the gathered records is the read order, so the ED order of a one-GPU run is preserved.
+// devices.  The records arrive in rank order: the read order -- the ED order of a one-GPU run -- where rank r ran the r-th
+// contiguous range of the file's reads; under key-range sharding a permutation of it, which sigax_edges_restore_order
+// (sigax_order.hip) undoes on the root's device.
 //
 // RCCL is bound at run time (dlopen): libsigax.so carries no link-time dependency on it, the one-GPU paths never touch it,
 // and a process that already holds an RCCL (PyTorch ships its own librccl.so) gets THAT one instead of a second copy.

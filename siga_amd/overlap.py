@@ -102,6 +102,67 @@ def _copy_records(ptr, n, dtype):
     return out
 
 
+class ShardedResult(tuple):
+    """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
+    the result of `overlap` does -- `format_asqg` takes it as it is."""
+
+    def __new__(cls, edges, substring):
+        return super().__new__(cls, (edges, substring))
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return super().__getitem__(("edges", "substring").index(key))
+        return super().__getitem__(key)
+
+
+class _DeviceBytes:
+    """device memory through the HIP runtime libsigax.so is bound to (the process may hold a second one, PyTorch's own)"""
+
+    def __init__(self, nbytes, device):
+        hip = _lib.lib()
+        hip.hipSetDevice.argtypes = [C.c_int]
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        hip.hipFree.argtypes = [C.c_void_p]
+        self._hip = hip
+        self.nbytes = int(nbytes)
+        self.ptr = C.c_void_p()
+        self._try(hip.hipSetDevice(device), "hipSetDevice")
+        self._try(hip.hipMalloc(C.byref(self.ptr), max(self.nbytes, 16)), "hipMalloc")
+
+    def _try(self, err, where):
+        if err != 0:
+            raise RuntimeError("%s failed: HIP error %d" % (where, err))
+
+    def at(self, offset):
+        return C.c_void_p(self.ptr.value + offset)
+
+    def upload(self, arr):
+        if arr.nbytes:
+            self._try(self._hip.hipMemcpy(self.ptr, arr.ctypes.data, arr.nbytes, 1), "hipMemcpy")  # host to device
+        return self
+
+    def zero(self):
+        self._try(self._hip.hipMemset(self.ptr, 0, max(self.nbytes, 16)), "hipMemset")
+        return self
+
+    def copy_from_device(self, offset, src, nbytes):
+        if nbytes:
+            self._try(self._hip.hipMemcpy(self.at(offset), src, nbytes, 3), "hipMemcpy")  # device to device
+
+    def download(self, dtype, count):
+        out = np.empty(count, dtype=dtype)
+        if out.nbytes:
+            self._try(self._hip.hipMemcpy(out.ctypes.data, self.ptr, out.nbytes, 2), "hipMemcpy")  # device to host
+        return out
+
+    def free(self):
+        if self.ptr:
+            self._hip.hipFree(self.ptr)
+            self.ptr = C.c_void_p()
+
+
 class FMIndexPair:
     """Both FM-indexes (+ .sai tables) resident on one GPU."""
 
@@ -257,6 +318,78 @@ class OverlapBuilder:
         finally:
             _lib.lib().sigax_result_free(C.byref(res))
         return {"block_offs": block_offs, "blocks": blocks, "substring": substring, "edges": eds, "stats": stats}
+
+    def overlap_sharded(self, seqs, min_overlap, shards):
+        """`overlap(seqs, min_overlap, edges=True)` run shard by shard: `shards` is a list of arrays of read ids that together
+        name every read once (key-range sharding: np.array_split(key_order(locality_keys(...)), N)).  Each shard runs as one
+        batch under its ids, as one rank of a key-sharded run does; the shards' edge records are concatenated in device
+        memory, put back into read order there (sigax_edges_restore_order) and downloaded once, and the substring flags go to
+        their reads' places the same way (sigax_flags_by_read_id).  Returns (edges, substring): the one-batch run's, byte
+        for byte.  The index must know its reads (FMIndexPair.set_reads)."""
+        L = _lib.lib()
+        seqs = list(seqs)
+        n = len(seqs)
+        shards = [np.ascontiguousarray(s, dtype=np.int64).reshape(-1) for s in shards]
+        named = np.concatenate(shards) if shards else np.zeros(0, dtype=np.int64)
+        if len(named) != n or (n and (named.min() < 0 or named.max() >= n or (np.bincount(named, minlength=n) != 1).any())):
+            raise ValueError("shards must name every one of the %d reads exactly once" % n)
+        if getattr(self.fmi, "_resident", False) and min_overlap < getattr(self.fmi, "_deep_for", 1 << 30):
+            self.fmi.prepare_overlap(min_overlap)
+        elif getattr(self.fmi, "_prepare_pending", False):
+            self.fmi.prepare()
+        device = self.fmi.info()["device"]
+        shards = [s.astype(np.uint32) for s in shards if len(s)]
+        bt = C.c_void_p()
+        held = []
+
+        def dev(nbytes):
+            held.append(_DeviceBytes(nbytes, device))
+            return held[-1]
+
+        try:
+            d_sub = dev(n).zero()
+            d_status = dev(16)
+            parts = []  # (device records, how many) per shard, in shard order
+            if shards:
+                _check(L.sigax_batch_create(self.fmi.handle, max(len(s) for s in shards), 0, max(len(seqs[i]) for i in range(n)), C.byref(bt)),
+                       "sigax_batch_create")
+            for ids in shards:
+                buf, offs = pack_reads([seqs[i] for i in ids])
+                d_ids = dev(ids.nbytes).upload(ids)
+                _check(L.sigax_batch_upload(bt, buf, offs.ctypes.data, len(ids), None), "sigax_batch_upload")
+                _check(L.sigax_batch_set_device_read_ids(bt, d_ids.ptr, len(ids)), "sigax_batch_set_device_read_ids")
+                _check(L.sigax_batch_run(bt, 0, min_overlap, self._flags(True), None), "sigax_batch_run")
+                stats = _lib.Stats()
+                _check(L.sigax_batch_finish(bt, None, C.byref(stats)), "sigax_batch_finish")
+                p_sub, p_edges = C.c_void_p(), C.c_void_p()
+                _check(L.sigax_batch_device_outputs(bt, None, None, C.byref(p_sub), C.byref(p_edges)), "sigax_batch_device_outputs")
+                _check(L.sigax_flags_by_read_id(device, p_sub, d_ids.ptr, len(ids), n, d_sub.ptr, d_status.ptr, None), "sigax_flags_by_read_id")
+                if d_status.download(np.uint64, 1)[0]:
+                    raise SigaxError(_lib.SIGAX_E_ARG, "sigax_flags_by_read_id (a read id beyond the reads)")
+                part = dev(int(stats.n_edges) * EDGE_DTYPE.itemsize)  # the batch object's own buffer serves the next shard
+                part.copy_from_device(0, p_edges, part.nbytes)
+                parts.append((part, int(stats.n_edges)))
+            total = sum(k for _, k in parts)
+            d_cat, d_out = dev(total * EDGE_DTYPE.itemsize), dev(total * EDGE_DTYPE.itemsize)
+            at = 0
+            for part, k in parts:
+                d_cat.copy_from_device(at, part.ptr, part.nbytes)
+                at += part.nbytes
+            need = C.c_uint64()
+            _check(L.sigax_edges_order_workspace(total, n, C.byref(need)), "sigax_edges_order_workspace")
+            d_work = dev(need.value)
+            _check(L.sigax_edges_restore_order(device, d_cat.ptr, total, n, d_out.ptr, None, d_work.ptr, need.value, d_status.ptr, None),
+                   "sigax_edges_restore_order")
+            status = d_status.download(np.uint64, 2)  # (the copy waits for the kernels)
+            if status[0] or status[1]:
+                raise RuntimeError("sigax_edges_restore_order refused the shards' records: %d with a query beyond the reads, %d runs "
+                                   "beyond the first of their query" % (status[0], status[1]))
+            return ShardedResult(d_out.download(EDGE_DTYPE, total), d_sub.download(np.uint8, n))
+        finally:
+            if bt:
+                L.sigax_batch_destroy(bt)
+            for d in held:
+                d.free()
 
     def build(self, input_path, min_overlap, output_path=None):
         """HT + VT + ED text exactly as OverlapBuilder::build writes it at -t 1 (src/overlap_builder.cpp:423-483).
