@@ -40,17 +40,20 @@ HOST = os.path.join(HERE, "host")
 HOSTLIB = os.path.join(HERE, "lib", "libsiga_host.so")
 CLI = os.path.join(HERE, "lib", "siga")
 CXX = os.environ.get("CXX", "g++")
+HOST_SOURCES = ["reads.cpp", "strand_index.cpp", "out_file.cpp", "asqg_text.cpp", "overlap_builder.cpp", "correct_match.cpp", "host_capi.cpp"]
+HOST_HEADERS = ["siga_host.hpp", "host_util.hpp", "reads.hpp", "out_file.hpp", "asqg_text.hpp", "sais.hpp", "line_deflate.hpp"]
 
 
 def build_host(force=False, verbose=False):
     """libsiga_host.so (host C++ mirror of the reference classes over the C-ABI) and the `siga` CLI."""
     build_libsigax(force=force, verbose=verbose)
-    deps = [os.path.join(HOST, f) for f in ("siga_host.cpp", "siga_host.hpp", "sais.hpp", "line_deflate.hpp", "siga_main.cpp")] + [LIB]
+    srcs = [os.path.join(HOST, f) for f in HOST_SOURCES]
+    deps = srcs + [os.path.join(HOST, f) for f in HOST_HEADERS + ["siga_main.cpp"]] + [LIB]
     libdir = os.path.dirname(LIB)
     common = [CXX, "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-sign-compare", "-pthread"]
     link = ["-L" + libdir, "-lsigax", "-lz", "-ldl", "-Wl,-rpath,$ORIGIN"]
     if force or _stale(HOSTLIB, deps):
-        cmd = common + ["-shared", "-o", HOSTLIB, os.path.join(HOST, "siga_host.cpp")] + link
+        cmd = common + ["-shared", "-o", HOSTLIB] + srcs + link
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

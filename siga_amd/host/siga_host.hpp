@@ -2,7 +2,10 @@
 // over the C-ABI (include/sigax.h).  Same names, argument meaning and error behaviour as the reference so that a
 // maintainer can swap them in: DNASeq / readers (src/kseq.h), FMIndex (src/fmindex.h, here a handle pair living
 // on the GPU), SuffixArray + BWT writers (src/suffix_array.cpp, src/bwt.cpp), OverlapBuilder
-// (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).
+// (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).  One source file per object: reads.cpp (readers),
+// strand_index.cpp (index builders and writers), overlap_builder.cpp (FMIndex, OverlapBuilder), correct_match.cpp
+// (CorrectProcessor, Matcher), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
+// host_util.hpp are internal to the library.
 #ifndef SIGA_AMD_HOST_SIGA_HOST_HPP_
 #define SIGA_AMD_HOST_SIGA_HOST_HPP_
 

@@ -483,9 +483,64 @@ def test_asqg_text_formatters_without_a_gpu(tmp_path, gz):
     assert got == want
 
 
+def test_asqg_writer_bytes_do_not_depend_on_the_batches(tmp_path, monkeypatch):
+    """AsqgWriter (siga_amd/host/asqg_text.cpp), the one writer of OverlapBuilder::build() and of the hook: the file equals the
+    Python mirror's text, and its BYTES (plain and .gz) do not depend on how many reads come back at a time -- batches below,
+    just under and just over the 4 096-read chunk of VT text, and the whole input as one batch --, on whether the batches' edge
+    records wait for finish() (SIGA_ED_HOLD_BYTES=0), on which thread makes the ED text (SIGA_ED_INLINE=1), or on the thread count."""
+    import gzip
+    import random
+    from siga_amd import host
+    from siga_amd.overlap import EDGE_DTYPE, format_asqg, read_sequences
+    rnd = random.Random(23)
+    n = 9000
+    recs = []
+    for i in range(n):
+        name = "r%d" % i if i % 3 else "read_with_a_much_longer_name_%d_%s" % (i, "x" * rnd.randrange(0, 60))
+        com = rnd.choice(["", " CR:i:%d" % rnd.randrange(100), " BX:Z:ACGT-1 EX:Z:foo", " free text here"])
+        recs.append(">%s%s\n%s\n" % (name, com, "".join(rnd.choice("ACGT") for _ in range(rnd.randrange(30, 61)))))
+    fa = str(tmp_path / "r.fa")
+    open(fa, "w").write("".join(recs))
+    reads = read_sequences(fa)
+    assert len(reads) == n
+    ed = np.zeros(2000, dtype=EDGE_DTYPE)
+    for j in range(len(ed)):
+        q, t = rnd.randrange(n), rnd.randrange(n)
+        ed[j] = (q, t, rnd.randrange(1, min(len(reads[q][2]), len(reads[t][2])) + 1), rnd.randrange(8))
+    sub = np.array([rnd.random() < 0.1 for _ in range(n)], dtype=np.uint8)
+    sub[[4095, 4096, n - 1]] = 1
+    for var in ("SIGA_BATCH_READS", "SIGA_ED_HOLD_BYTES", "SIGA_ED_INLINE", "SIGA_VT_AHEAD"):
+        monkeypatch.delenv(var, raising=False)
+
+    def files(tag, threads=4):
+        got = []
+        for name in ("o.asqg", "o.asqg.gz"):
+            out = str(tmp_path / (tag + name))
+            assert host.format_asqg(fa, sub, ed, 45, out, threads=threads) == n
+            got.append(open(out, "rb").read())
+            os.remove(out)
+        return got
+
+    want = files("unset_")
+    assert want[0].decode("latin-1") == format_asqg(reads, {"substring": sub, "edges": ed}, 45)
+    assert gzip.decompress(want[1]) == want[0]
+    for per in (1000, 4095, 4097, 9000):
+        monkeypatch.setenv("SIGA_BATCH_READS", str(per))
+        assert files("b%d_" % per) == want, per
+    monkeypatch.setenv("SIGA_BATCH_READS", "4097")
+    monkeypatch.setenv("SIGA_ED_HOLD_BYTES", "0")
+    assert files("hold0_") == want
+    monkeypatch.delenv("SIGA_ED_HOLD_BYTES")
+    monkeypatch.setenv("SIGA_ED_INLINE", "1")
+    assert files("inline_") == want
+    monkeypatch.delenv("SIGA_ED_INLINE")
+    for threads in (1, 5):
+        assert files("t%d_" % threads, threads=threads) == want, threads
+
+
 @pytest.mark.parametrize("threads,cap", [(1, None), (3, "1")])
 def test_vt_lines_ahead_give_the_in_order_file(tmp_path, threads, cap, monkeypatch):
-    """VT lines ahead of the batches (siga_host.cpp, VtAhead: text with SS:i:0 and its 1 MiB deflate blocks made before the
+    """VT lines ahead of the batches (siga_amd/host/asqg_text.cpp, VtAhead: text with SS:i:0 and its 1 MiB deflate blocks made before the
     substring flags are known; SIGA_VT_AHEAD=1) against the in-order path and the Python mirror: the .asqg.gz files are
     the same BYTES -- with clean stretches (blocks used as they are), stretches with substring reads (chunks formatted
     again, their blocks deflated by the writer), text taken in pieces that do not line up with the chunks, several waves with

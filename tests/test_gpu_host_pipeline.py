@@ -1,4 +1,4 @@
-"""The host pipeline of `siga overlap` (OverlapBuilder::build, siga_amd/host/siga_host.cpp): many device batches, two in
+"""The host pipeline of `siga overlap` (OverlapBuilder::build, siga_amd/host/overlap_builder.cpp): many device batches, two in
 flight per GPU, several GPUs (rehearsed on one: SIGA_DEVICE_MAP maps every logical GPU of the run to device 0), index
 replicas copied device to device -- the .asqg.gz bytes must not depend on any of it, and the text must be the oracle's."""
 import gzip

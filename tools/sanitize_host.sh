@@ -17,12 +17,13 @@ GCCDIR=$(dirname "$(gcc -print-file-name=libasan.so)")
 python -c "
 from siga_amd import build; build.build_all()
 from oracle import pyoracle; pyoracle.build()" || exit 1
+HOST_SRC=$(ls siga_amd/host/*.cpp | grep -v siga_main.cpp)
 one() { # name, -fsanitize flags, runtime to preload, options env
   name=$1; flags=$2; rt=$3
   O=$ROOT/build/san_$name; mkdir -p $O
   cp -f $LIBDIR/libsigax.so $O/   # -rpath $ORIGIN of the sanitized host library finds the HIP library beside it
   COMMON="g++ -O1 -g -fno-omit-frame-pointer -std=c++17 -fPIC -Wall -Wno-sign-compare -pthread $flags"
-  $COMMON -shared -o $O/libsiga_host.so siga_amd/host/siga_host.cpp -L$O -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
+  $COMMON -shared -o $O/libsiga_host.so $HOST_SRC -L$O -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
   $COMMON -o $O/siga siga_amd/host/siga_main.cpp -L$O -lsiga_host -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
   log=$ROOT/profiles/r04_sanitize_$name.log
   {
@@ -49,7 +50,7 @@ tsan() {
   O=$ROOT/build/san_tsan; mkdir -p $O; rm -f $O/tsan.*
   cp -f $LIBDIR/libsigax.so $O/
   COMMON="g++ -O1 -g -fno-omit-frame-pointer -std=c++17 -fPIC -Wall -Wno-sign-compare -pthread -fsanitize=thread"
-  $COMMON -shared -o $O/libsiga_host.so siga_amd/host/siga_host.cpp -L$O -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
+  $COMMON -shared -o $O/libsiga_host.so $HOST_SRC -L$O -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
   $COMMON -o $O/siga siga_amd/host/siga_main.cpp -L$O -lsiga_host -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
   $COMMON -o $O/tsan_driver tools/tsan_driver.cpp -L$O -lsiga_host -lsigax -lz -ldl -Wl,-rpath,'$ORIGIN' || return 1
   log=$ROOT/profiles/r04_sanitize_tsan.log
