@@ -225,6 +225,54 @@ int  sigax_matcher_submit(sigax_matcher*, uint32_t slot, const char* seqs, const
                           uint64_t max_length, uint32_t flags);
 int  sigax_matcher_wait(sigax_matcher*, uint32_t slot, const uint64_t** counts, uint64_t stat4[4]);
 
+/* ---- `siga preqc`: index rows back to text, and the k-mer count distribution (csrc/sigax_spectrum.hip) ---------------------
+ * FMIndex::getString(i) (src/fmindex.cpp:292-313) for many rows of strand `which` (0 forward, 1 reverse: SIGAX_E_STATE on an
+ * index opened without it): the walk backwards from BWT row i to the first symbol of rank 0, i.e. the text in front of that
+ * row's suffix -- for a row below n_strings a whole read (on the reverse strand, reversed), or its last ACGT piece when it holds
+ * other bytes.  Lengths are not known before the walk, hence two passes: the lengths pass, then -- after the caller's prefix
+ * sum -- the write pass.  Every walk is bounded by max_len: one that would be longer stops there, keeps the max_len symbols
+ * nearest its row, and is counted.  A row >= n_symbols gives length 0 and is counted.  The bytes do not depend on which of
+ * the index's optional tables exist.
+ *
+ * sigax_string_lengths_device: d_rows u64[n] -> d_lens u32[n] and, unless NULL, d_stretch u64[n] = Occ('$') before the row
+ * the walk ended at: the index of the string's stretch among all stretches in suffix order, what the .sai table is indexed by
+ * (for ACGT-only read sets sai[that] is the read's id); SIGAX_NO_STRETCH for a walk that was cut or never started.
+ * d_status2 = 2 u64, written (not added to): {rows out of range, walks cut at max_len}.
+ * sigax_get_strings_device: string i's bytes, in text order, to d_seqs[d_offs[i] .. d_offs[i+1]) (d_offs u64[n+1]); a row
+ * whose slot is not its length is not written and counted in d_status3[2] (d_status3[0..1] as above).
+ * Both are asynchronous on `stream` (a hipStream_t or NULL) and allocate nothing. */
+#define SIGAX_NO_STRETCH (~0ull)
+int  sigax_string_lengths_device(sigax_index*, int which, const void* d_rows, uint64_t n, uint32_t max_len, void* d_lens,
+                                 void* d_stretch, void* d_status2, void* stream);
+int  sigax_get_strings_device(sigax_index*, int which, const void* d_rows, uint64_t n, uint32_t max_len, const void* d_offs,
+                              void* d_seqs, void* d_status3, void* stream);
+/* Host buffers, synchronous: *seqs (the strings back to back, one '\0' after the last) and *offs (u64[n+1]) are malloc'd,
+ * release with sigax_free; stretch = NULL or u64[n] of the caller's. */
+int  sigax_get_strings(sigax_index*, int which, const uint64_t* rows, uint64_t n, uint32_t max_len, char** seqs,
+                       uint64_t** offs, uint64_t* stretch);
+
+/* KmerDistribution::sample's loop (src/kmerdistr.cpp:12-33) for a batch of strings: a string of fewer than k bytes is skipped;
+ * otherwise for j = k .. len-1: w = s[j-k, j), count = occ(w) + occ(revcomp(w)) on the forward index (both strands always, as
+ * the reference; occ = FMIndex::Interval::occurrences), hist[min(count, n_bins-1)] += 1.  As in the reference j stops BEFORE
+ * len: the window that ends at the string's last base is never counted and a string of exactly k bases contributes no window,
+ * though its bases count in L = the sum of the lengths of the strings with len >= k.  Bytes outside ACGT rank as '$', in w and in
+ * its complement (as sigax_match_*).  Exact 64-bit counts; the bins are u64 and are ADDED to, so a caller accumulates over batches
+ * (and zeroes them first).  stat4, written: {strings with len >= k, L, windows counted, rank-table sectors asked for}.
+ * k = 0 or n_bins = 0: SIGAX_E_ARG; n_reads = 0: SIGAX_OK.  Works on an index opened without the reverse strand.  Uses the
+ * two-step tables and, when a correction call has left it on the device, the table of 13-mer intervals; allocates neither.
+ * The device form is asynchronous on `stream` and allocates nothing: d_work = sigax_kmer_spectrum_workspace bytes of scratch. */
+int  sigax_kmer_spectrum_workspace(uint64_t n_reads, uint64_t* bytes);
+int  sigax_kmer_spectrum_device(sigax_index*, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint32_t k, uint64_t n_bins,
+                                void* d_hist, void* d_stat4, void* d_work, uint64_t work_bytes, void* stream);
+/* host strings (seqs/offs as in sigax_match_batch), host bins; stat4 may be NULL */
+int  sigax_kmer_spectrum_batch(sigax_index*, const char* seqs, const uint64_t* offs, uint64_t n_reads, uint32_t k, uint64_t n_bins,
+                               uint64_t* hist, uint64_t stat4[4]);
+/* rows of the forward strand -> their strings (walks bounded by max_len) -> spectrum; the strings never leave the device */
+int  sigax_kmer_spectrum_rows(sigax_index*, const uint64_t* rows, uint64_t n, uint32_t k, uint32_t max_len, uint64_t n_bins,
+                              uint64_t* hist, uint64_t stat4[4]);
+/* rows of strings of up to max_len bytes one sigax_kmer_spectrum_rows call can take with the device's free memory now */
+int  sigax_kmer_spectrum_rows_hint(sigax_index*, uint32_t max_len, uint64_t n_bins, uint64_t* max_rows);
+
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

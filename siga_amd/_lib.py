@@ -61,6 +61,8 @@ SYMBOLS = [
     "sigax_locality_keys",
     "sigax_match_batch", "sigax_match_device", "sigax_matcher_create", "sigax_matcher_destroy", "sigax_matcher_capacity",
     "sigax_matcher_submit", "sigax_matcher_wait",
+    "sigax_string_lengths_device", "sigax_get_strings_device", "sigax_get_strings", "sigax_kmer_spectrum_workspace",
+    "sigax_kmer_spectrum_device", "sigax_kmer_spectrum_batch", "sigax_kmer_spectrum_rows", "sigax_kmer_spectrum_rows_hint",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -137,6 +139,14 @@ def lib():
     L.sigax_matcher_capacity.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.sigax_matcher_submit.argtypes = [vp, u32, cp, vp, u64, u64, u32]
     L.sigax_matcher_wait.argtypes = [vp, u32, pvp, C.POINTER(u64 * 4)]
+    L.sigax_string_lengths_device.argtypes = [vp, ci, vp, u64, u32, vp, vp, vp, vp]
+    L.sigax_get_strings_device.argtypes = [vp, ci, vp, u64, u32, vp, vp, vp, vp]
+    L.sigax_get_strings.argtypes = [vp, ci, vp, u64, u32, pvp, pvp, vp]
+    L.sigax_kmer_spectrum_workspace.argtypes = [u64, C.POINTER(u64)]
+    L.sigax_kmer_spectrum_device.argtypes = [vp, vp, vp, u64, u32, u64, vp, vp, vp, u64, vp]
+    L.sigax_kmer_spectrum_batch.argtypes = [vp, cp, vp, u64, u32, u64, vp, vp]
+    L.sigax_kmer_spectrum_rows.argtypes = [vp, vp, u64, u32, u32, u64, vp, vp]
+    L.sigax_kmer_spectrum_rows_hint.argtypes = [vp, u32, u64, C.POINTER(u64)]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_edges_restore_order.argtypes = [ci, vp, u64, u64, vp, vp, vp, u64, vp, vp]
     L.sigax_edges_restore_order_host.argtypes = [ci, vp, u64, u64, vp, vp]

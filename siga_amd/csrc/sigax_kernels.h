@@ -193,6 +193,36 @@ struct MatchArgs {
 };
 void launch_match(const MatchArgs& a, bool wide, int n_cu, hipStream_t st);
 
+// `siga preqc` (sigax_spectrum.hip).  Rows of strand s back to text: out == NULL is the lengths pass (lens, and unless NULL
+// stretch), else the write pass (offs, out).  status (zeroed by the caller): rows out of range, walks cut, slots of the wrong size.
+struct WalkArgs {
+  FmStrand s;
+  const unsigned long long* rows;        // [n]
+  unsigned long long n;
+  uint32_t max_len;
+  uint32_t* lens;                        // [n]
+  unsigned long long* stretch;           // [n] or NULL: Occ('$', end row - 1), ~0 for a walk that was cut or never started
+  const unsigned long long* offs;        // [n + 1]
+  unsigned char* out;
+  unsigned long long* status;
+};
+void launch_walk(const WalkArgs& a, bool wide, hipStream_t st);
+// k-mer count distribution of a batch of strings on the forward strand, both strands of every window
+struct SpectrumArgs {
+  FmStrand fwd;
+  const unsigned char* seqs;
+  const unsigned long long* offs;        // [n_reads + 1]
+  unsigned long long n_reads;
+  unsigned long long n_bins;
+  uint32_t k;
+  uint32_t pk;                           // symbols of an entry of ptab
+  const void* ptab;                      // the corrector's prefix table when it is resident (launch_prefix_build), or NULL
+  unsigned long long* hist;              // [n_bins], added to
+  unsigned long long* dstat;             // 4 u64, zeroed: strings with len >= k, their bases, windows counted, rank-table sectors asked for
+  unsigned long long* counter;           // 1 u64, zeroed: the kernel's string counter
+};
+void launch_spectrum(const SpectrumArgs& a, bool wide, int n_cu, hipStream_t st);
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

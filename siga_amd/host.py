@@ -38,6 +38,8 @@ def lib():
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
         L.sigah_match_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_char_p,
                                         C.c_uint64, C.c_char_p, C.c_uint64]
+        L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
+                                  C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -115,6 +117,16 @@ def match_files(paths, prefix, max_length=None, rc=True, device=0, out=None, bat
     lim = (1 << 64) - 1 if max_length is None else int(max_length)
     if lib().sigah_match_files(arr, len(paths), prefix.encode(), lim, int(rc), device, (out or "").encode(), batch_reads, err, 512) != 0:
         raise RuntimeError("siga match failed: " + err.value.decode())
+
+
+def preqc(prefix, k=31, samples=50000, seed=1, all_reads=False, max_count=1024, device=0, out=None, batch_rows=0):
+    """`siga preqc`: FMIndex::load(<prefix>.bwt) + KmerSpectrum over `samples` rows drawn from std::mt19937_64(seed), or over every
+    read once (all_reads); the JSON object goes to the file `out`, or to stdout.  batch_rows: rows per device batch (0: from the
+    free memory)."""
+    err = C.create_string_buffer(512)
+    if lib().sigah_preqc(prefix.encode(), k, samples, seed, int(all_reads), max_count, device, (out or "").encode(), batch_rows,
+                         err, 512) != 0:
+        raise RuntimeError("siga preqc failed: " + err.value.decode())
 
 
 def parse_file(path, out_path, parallel=True, threads=4):

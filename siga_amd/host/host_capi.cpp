@@ -219,6 +219,30 @@ int sigah_match_files(const char* const* paths, uint64_t n_paths, const char* pr
   return 0;
 }
 
+// `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty
+int sigah_preqc(const char* prefix, uint64_t k, uint64_t samples, uint64_t seed, int all, uint64_t max_count, int device,
+                const char* out_path, uint64_t batch_rows, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!load_index(fmi, prefix, device, true, err, errcap)) return -1;
+  sigah::KmerSpectrum::Options o;
+  o.kmerSize = k;
+  o.samples = samples;
+  o.seed = seed;
+  o.all = all != 0;
+  o.maxCount = max_count;
+  sigah::KmerSpectrum spectrum(o);
+  if (!spectrum.run(fmi, (size_t)batch_rows)) {
+    if (err && errcap) snprintf(err, errcap, "%s", spectrum.error().c_str());
+    return -1;
+  }
+  const std::string text = spectrum.json();
+  FILE* f = out_path && out_path[0] ? fopen(out_path, "wb") : stdout;
+  const bool ok = f && fwrite(text.data(), 1, text.size(), f) == text.size() && fflush(f) == 0;
+  if (f && f != stdout) fclose(f);
+  if (!ok && err && errcap) snprintf(err, errcap, "Failed to write %s", out_path && out_path[0] ? out_path : "stdout");
+  return ok ? 0 : -1;
+}
+
 // test hook: parse a reads file with the parallel loader (mode 0) or the record-at-a-time DNASeqReader (mode 1) and dump
 // "name\tcomment\tseq\tquality\n" per read; mode 2: the parallel loader and the edge converter's read table, "rank\tlength\n"
 // per read; returns the number of reads or -1

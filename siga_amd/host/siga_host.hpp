@@ -4,7 +4,7 @@
 // on the GPU), SuffixArray + BWT writers (src/suffix_array.cpp, src/bwt.cpp), OverlapBuilder
 // (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).  One source file per object: reads.cpp (readers),
 // strand_index.cpp (index builders and writers), overlap_builder.cpp (FMIndex, OverlapBuilder), correct_match.cpp
-// (CorrectProcessor, Matcher), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
+// (CorrectProcessor, Matcher), kmer_spectrum.cpp (KmerSpectrum), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
 // host_util.hpp are internal to the library.
 #ifndef SIGA_AMD_HOST_SIGA_HOST_HPP_
 #define SIGA_AMD_HOST_SIGA_HOST_HPP_
@@ -159,6 +159,37 @@ class Matcher {
   uint64_t _maxLength;
   bool _rc;
   mutable std::string _error;
+};
+
+// `siga preqc`: the k-mer count distribution of strings drawn from the index itself (KmerDistribution::sample,
+// src/kmerdistr.cpp:7-36: FMIndex::getString of a row, then occ(w) + occ(revcomp(w)) for its windows), the number one reads
+// `siga correct -x` off.  The reads file is not needed: the strings come back out of the .bwt.
+class KmerSpectrum {
+ public:
+  struct Options {
+    size_t kmerSize, samples, seed, maxCount;  // -k, -n (the reference's _samples), --seed, --max-count
+    bool all;                                  // --all: every read once (rows 0 .. n_strings - 1) instead of sampled rows
+    Options() : kmerSize(31), samples(50000), seed(1), maxCount(1024), all(false) {}
+  };
+  explicit KmerSpectrum(const Options& options) : _options(options), _strings(0), _bases(0), _windows(0), _rows(0) {}
+  // walks the rows and counts their windows on the GPU, batch by batch (batchRows = rows per device batch, 0: from the
+  // device's free memory); one histogram accumulates over the batches
+  bool run(const FMIndex& index, size_t batchRows = 0);
+  // histogram()[c] = windows whose k-mer occurs c times, both strands together; the last entry = maxCount or more
+  const std::vector<uint64_t>& histogram() const { return _hist; }
+  uint64_t strings() const { return _strings; }  // strings of at least k bases
+  uint64_t bases() const { return _bases; }      // their bases (what KmerDistribution::sample returns)
+  uint64_t windows() const { return _windows; }
+  // {"KmerDistribution": {"k", "mode", "samples", "seed", "strings", "bases", "windows", "max_count", "distribution": [[count,
+  // windows], ...]}} and a newline; the distribution lists the non-empty bins in ascending order
+  std::string json() const;
+  const std::string& error() const { return _error; }
+
+ private:
+  Options _options;
+  std::vector<uint64_t> _hist;
+  uint64_t _strings, _bases, _windows, _rows;
+  std::string _error;
 };
 
 }  // namespace sigah

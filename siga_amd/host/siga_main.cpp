@@ -1,4 +1,4 @@
-// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` ... command line, option for option as the reference
+// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga preqc` ... command line, option for option as the reference
 // (src/main.cpp:17-83, src/indexer.cpp:119-156, src/overlap.cpp:66-105).  Exit codes follow the reference:
 // a runner returning -1 exits 255; printing help returns 256, i.e. exit status 0.
 #include <getopt.h>
@@ -76,12 +76,13 @@ static int apply_ini(int argc, char** argv, const option* longopts, std::vector<
 }
 
 static int usage() {
-  printf("siga [index|correct|overlap|rmdup|match] [OPTION] ... READSFILE\n"
+  printf("siga [index|correct|overlap|rmdup|preqc|match] [OPTION] ... READSFILE\n"
          "  index     build the FM-index (.sai/.bwt/.rsai/.rbwt) of READSFILE\n"
          "  overlap   compute pairwise overlaps between all the sequences in READSFILE (GPU)\n"
          "  rmdup     remove duplicated reads (GPU)\n"
          "  correct   k-mer based error correction (GPU)\n"
          "  match     count the occurrences of every read of READSFILE in the indexed reads (GPU)\n"
+         "  preqc     pre-assembly quality checks: the k-mer count distribution of the indexed reads (GPU)\n"
          "common options: -s, --ini=FILE (options from FILE, the command line goes over them);\n"
          "                -c, --log4cxx=FILE is accepted and ignored (this build logs to stderr; SIGA_TIMING=1 prints phase\n"
          "                times and the reference's \"processed N sequences\" progress lines)\n");
@@ -439,6 +440,91 @@ static int run_match(int argc, char** argv) {
   return 0;
 }
 
+static int preqc_help() {
+  // help text of src/preqc.cpp:209-222, plus the options of the k-mer distribution the reference computes no further than
+  // GenomeEstimator::estimate's null index
+  printf("siga preqc [OPTION] READSFILE\n"
+         "Preform pre-assembly quality checks\n"
+         "\n"
+         "      -h, --help                       display this help and exit\n"
+         "\n"
+         "      -o, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the name of the index file (.bwt)\n"
+         "      -k, --kmer=N                     the length of the k-mers to count (default: 31)\n"
+         "      -n, --samples=N                  draw N rows of the index and count the k-mers of their strings (default: 50000)\n"
+         "          --seed=N                     seed of the std::mt19937_64 that draws the rows (default: 1)\n"
+         "          --all                        count every read once instead of sampled rows\n"
+         "          --max-count=N                counts of N and more share the last bin (default: 1024)\n"
+         "      -t, --threads=NUM                accepted; the GPU does the counting\n"
+         "          --device=NUM                 GPU to use (default: 0)\n"
+         "          --simple                     not built: the metrics that do not need the FM-index (and the QualityScores\n"
+         "                                       block) are a host pass over FASTQ qualities with an unseeded sampler\n"
+         "\n"
+         "Prints {\"KmerDistribution\": {...}} on stdout: windows by the number of times their k-mer occurs in the reads, both\n"
+         "strands together.  READSFILE only names the index; the strings are read back out of it.\n"
+         "\n");
+  return 256;
+}
+
+// src/preqc.cpp:20-60, 227-236: the k-mer distribution of GenomeEstimator, with an index
+static int run_preqc(int argc, char** argv) {
+  enum { OPT_SIMPLE = 1, OPT_SEED, OPT_ALL, OPT_MAX_COUNT, OPT_DEVICE };
+  static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},  {"ini", required_argument, nullptr, 's'},
+                                    {"prefix", required_argument, nullptr, 'o'},   {"threads", required_argument, nullptr, 't'},
+                                    {"kmer", required_argument, nullptr, 'k'},     {"samples", required_argument, nullptr, 'n'},
+                                    {"seed", required_argument, nullptr, OPT_SEED}, {"all", no_argument, nullptr, OPT_ALL},
+                                    {"max-count", required_argument, nullptr, OPT_MAX_COUNT}, {"simple", no_argument, nullptr, OPT_SIMPLE},
+                                    {"device", required_argument, nullptr, OPT_DEVICE}, {"help", no_argument, nullptr, 'h'},
+                                    {nullptr, 0, nullptr, 0}};
+  std::string prefix;
+  sigah::KmerSpectrum::Options o;
+  bool help = false, simple = false;
+  int device = 0, c;
+  std::vector<std::string> ini_store;
+  std::vector<char*> ini_argv;
+  if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
+  argc = (int)ini_argv.size();
+  argv = ini_argv.data();
+  while ((c = getopt_long(argc, argv, "c:s:o:t:k:n:h", longopts, nullptr)) != -1) {
+    switch (c) {
+      case 'o': prefix = optarg; break;
+      case 't': break;
+      case 'k': o.kmerSize = strtoull(optarg, nullptr, 10); break;
+      case 'n': o.samples = strtoull(optarg, nullptr, 10); break;
+      case OPT_SEED: o.seed = strtoull(optarg, nullptr, 10); break;
+      case OPT_ALL: o.all = true; break;
+      case OPT_MAX_COUNT: o.maxCount = strtoull(optarg, nullptr, 10); break;
+      case OPT_SIMPLE: simple = true; break;
+      case OPT_DEVICE: device = atoi(optarg); break;
+      case 'h': help = true; break;
+      default: break;
+    }
+  }
+  if (help || argc - optind != 1) return preqc_help();
+  std::string input = argv[optind];
+  if (prefix.empty()) prefix = sigah::Utils::stem(input);
+  if (simple) {
+    fprintf(stderr, "Failed to do pre-assembly quality checks for reads %s: --simple is not built\n", input.c_str());
+    return -1;
+  }
+  if (o.maxCount == 0 || o.maxCount > (1ull << 28)) {
+    fprintf(stderr, "Failed to do pre-assembly quality checks for reads %s: --max-count must be between 1 and 2^28\n", input.c_str());
+    return -1;
+  }
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForward(prefix, fmi, device)) {
+    fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+    return -1;
+  }
+  sigah::KmerSpectrum spectrum(o);
+  if (!spectrum.run(fmi)) {
+    fprintf(stderr, "Failed to do pre-assembly quality checks for reads %s: %s\n", input.c_str(), spectrum.error().c_str());
+    return -1;
+  }
+  const std::string text = spectrum.json();
+  if (fwrite(text.data(), 1, text.size(), stdout) != text.size()) return -1;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage();
   const auto t0 = std::chrono::steady_clock::now();
@@ -449,6 +535,7 @@ int main(int argc, char** argv) {
   else if (cmd == "correct") rc = run_correct(argc - 1, argv + 1);
   else if (cmd == "overlap") rc = run_overlap(argc - 1, argv + 1);
   else if (cmd == "match") rc = run_match(argc - 1, argv + 1);
+  else if (cmd == "preqc") rc = run_preqc(argc - 1, argv + 1);
   else return usage();
   if (getenv("SIGA_TIMING"))
     fprintf(stderr, "[siga] %-28s %8.3f s\n", "main() total", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

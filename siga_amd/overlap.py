@@ -28,6 +28,8 @@ def _check(code, where):
 
 
 MATCH_NONE = (1 << 64) - 1  # SIGAX_MATCH_NONE; as max_length: never split
+NO_STRETCH = (1 << 64) - 1  # SIGAX_NO_STRETCH
+MAX_STRING_LEN = (1 << 32) - 1  # get_strings / kmer_spectrum: walks as long as the index's longest stretch
 
 
 def pack_reads(seqs):
@@ -275,6 +277,49 @@ class FMIndexPair:
         lens = offs[1:] - offs[:-1]
         split = lens > np.uint64(lim)
         return out[0::2].copy(), np.ma.masked_array(out[1::2].copy(), mask=~split)
+
+    def get_strings(self, rows, which=0, max_len=MAX_STRING_LEN, stretch=False):
+        """FMIndex::getString (src/fmindex.cpp:292-313, sigax_get_strings) for many BWT rows of strand `which` -> list of
+        bytes, the text in front of each row's suffix; with stretch=True -> (that list, u64 array of the strings' stretch
+        indexes: what the .sai table is indexed by, NO_STRETCH where a walk was cut at max_len or the row is out of range)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = len(rows)
+        seqs, offs = C.c_void_p(), C.c_void_p()
+        st = np.zeros(n, dtype=np.uint64) if stretch else None
+        _check(_lib.lib().sigax_get_strings(self._h, which, rows.ctypes.data, n, int(max_len), C.byref(seqs), C.byref(offs),
+                                            st.ctypes.data if stretch else None), "sigax_get_strings")
+        try:
+            o = np.ctypeslib.as_array(C.cast(offs, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            text = C.string_at(seqs, int(o[-1]))
+        finally:
+            _lib.lib().sigax_free(seqs)
+            _lib.lib().sigax_free(offs)
+        out = [text[int(o[i]):int(o[i + 1])] for i in range(n)]
+        return (out, st) if stretch else out
+
+    def kmer_spectrum(self, k, n_bins=1024, seqs=None, rows=None, max_len=MAX_STRING_LEN, hist=None):
+        """KmerDistribution::sample's loop (src/kmerdistr.cpp:12-33) over strings (`seqs`, sigax_kmer_spectrum_batch) or over the
+        strings of BWT rows of the forward strand (`rows`, sigax_kmer_spectrum_rows: they never leave the device) ->
+        (hist u64[n_bins], stats dict).  hist[c] = windows whose k-mer occurs c times on both strands together, the last bin
+        "n_bins - 1 or more"; pass a previous call's `hist` to accumulate into it."""
+        if (seqs is None) == (rows is None):
+            raise ValueError("give either seqs or rows")
+        if hist is None:
+            hist = np.zeros(int(n_bins), dtype=np.uint64)
+        elif hist.dtype != np.uint64 or len(hist) != int(n_bins) or not hist.flags.c_contiguous:
+            raise ValueError("hist must be a contiguous uint64 array of n_bins entries")
+        stat = np.zeros(4, dtype=np.uint64)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.uint64)
+            _check(_lib.lib().sigax_kmer_spectrum_rows(self._h, rows.ctypes.data, len(rows), int(k), int(max_len), int(n_bins),
+                                                       hist.ctypes.data, stat.ctypes.data), "sigax_kmer_spectrum_rows")
+        else:
+            buf, offs = pack_reads(seqs)
+            if isinstance(buf, np.ndarray):
+                buf = C.c_char_p(buf.ctypes.data) if buf.size else b""
+            _check(_lib.lib().sigax_kmer_spectrum_batch(self._h, buf, offs.ctypes.data, len(offs) - 1, int(k), int(n_bins),
+                                                        hist.ctypes.data, stat.ctypes.data), "sigax_kmer_spectrum_batch")
+        return hist, {"strings": int(stat[0]), "bases": int(stat[1]), "windows": int(stat[2]), "sectors": int(stat[3])}
 
 
 class OverlapBuilder:
