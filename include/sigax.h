@@ -104,7 +104,8 @@ void sigax_stream_destroy(int device, void* stream);
 /* FMIndex::load x2 + SuffixArray::load x2 (src/overlap.cpp:41-42, src/overlap_builder.cpp:466).  The .sai
  * paths may be NULL when SIGAX_EDGES is never requested.  rbwt_path NULL or "": the forward strand alone -- what
  * `siga index --no-reverse` writes and `siga correct` loads (src/correct.cpp:41-47) -- serving sigax_occ_batch (which = 0),
- * sigax_kmer_count_batch and sigax_correct_*; overlap runs on such an index fail with SIGAX_E_STATE. */
+ * sigax_kmer_count_batch and sigax_correct_*; overlap runs on such an index fail with SIGAX_E_STATE.  With sai_path given
+ * beside it, the forward .sai table is loaded too: what sigax_locate_* needs (rsai_path is not read). */
 int  sigax_index_open(const char* bwt_path, const char* rbwt_path, const char* sai_path, const char* rsai_path,
                       int device, sigax_index** out);
 /* Same from memory: RL units exactly as in the .bwt payload (src/rlstring.h:10-63), read ids of the .sai lines
@@ -272,6 +273,53 @@ int  sigax_kmer_spectrum_rows(sigax_index*, const uint64_t* rows, uint64_t n, ui
                               uint64_t* hist, uint64_t stat4[4]);
 /* rows of strings of up to max_len bytes one sigax_kmer_spectrum_rows call can take with the device's free memory now */
 int  sigax_kmer_spectrum_rows_hint(sigax_index*, uint32_t max_len, uint64_t n_bins, uint64_t* max_rows);
+
+/* ---- `siga locate`: where every query occurs (csrc/sigax_locate.hip) ----------------------------------------------------------
+ * The other half of the FM-index: an occurrence of w is a row p of w's suffix-array interval; the number of LF steps from p back
+ * to the first symbol of rank 0 is the occurrence's offset in its read, and sai[Occ('$') before that row] is the read.  Nothing
+ * is stored for it beyond the forward strand and its .sai table.  No counterpart in the reference.
+ *
+ * Needs an index opened with the forward .sai table (also one opened without the reverse strand: sigax_index_open with
+ * rbwt_path NULL and sai_path given) whose reads hold ACGT only -- the check of sigax_index_check_order, C['A'] == n_strings:
+ * with other bytes a stretch is a piece of a read, and locating would need a table from stretch to (read, piece offset), which
+ * the index does not carry.  SIGAX_E_STATE otherwise.
+ *
+ * Queries as in sigax_match_batch (seqs, offs u64[n_queries + 1], each below 2^32 bytes).  totals[q] = what sigax_match_batch
+ * returns as counts[2q] with max_length = UINT64_MAX and the same flags, for every query: bytes outside ACGT rank as '$', an
+ * empty query gives 0, a reverse-palindromic one counts twice with SIGAX_RC.  Hits are LISTED for query q iff it is non-empty,
+ * all ACGT and totals[q] <= max_hits; otherwise qflags[q] says why not and hit_offs[q+1] == hit_offs[q].  hits[hit_offs[q] ..
+ * hit_offs[q+1]) holds the rows of the query's interval in ascending row order, then -- with SIGAX_RC -- the rows of its reverse
+ * complement's interval in ascending row order, flagged SIGAX_HIT_REV.  The order depends on the index's bytes alone, not on
+ * which of its optional tables exist.  A walk of more than max_len steps, or one that leaves the table (a damaged index), is
+ * cut: flagged SIGAX_HIT_CUT, read = offset = 0xFFFFFFFF, and counted.  max_hits is 32 bits: a query lists fewer than 2^32 hits.
+ *
+ * sigax_locate_device: every buffer in device memory, asynchronous on `stream` (a hipStream_t or NULL), allocates nothing.
+ * d_offs u64[n+1], d_totals u64[n], d_qflags u32[n], d_hit_offs u64[n+1], d_hits sigax_hit[hits_cap] (16-byte aligned), d_rows
+ * NULL or u64[hits_cap]: the BWT row of each hit, in the same places.  d_status4 = 4 u64, written (not added to): {hits listed =
+ * hit_offs[n], walks cut at max_len, rank-table sectors asked for, reserved}.  d_work = sigax_locate_workspace(n) bytes of
+ * scratch, 16-byte aligned.  When the hits listed exceed hits_cap, d_totals, d_qflags, d_hit_offs and status[0] are still
+ * complete, no hit and no row is written and nothing outside the buffers is touched: a caller reads status[0], sizes its
+ * buffers and calls again.  hits_cap may be any value the buffers hold, UINT64_MAX for "room enough" included: the call walks
+ * min(hits_cap, n_queries * max_hits) slots, and SIGAX_E_ARG if that is above (2^31 - 1) * 256 or n_queries above 2^32 - 1 (a
+ * hit names its query in 32 bits).  flags other than SIGAX_RC or 0 and a NULL where a buffer is required: SIGAX_E_ARG;
+ * n_queries = 0: SIGAX_OK.  Uses the two-step tables and, when a correction call has left it on the device, the table of
+ * 13-mer intervals; allocates neither. */
+typedef struct sigax_hit { uint32_t query, read, offset, flags; } sigax_hit;  /* 16 bytes */
+#define SIGAX_HIT_REV       1u   /* read[offset, offset+len) == revcomp(query) */
+#define SIGAX_HIT_CUT       2u   /* walk stopped at max_len: read = offset = 0xFFFFFFFF */
+/* per-query flags */
+#define SIGAX_LOCATE_SKIPPED  1u /* query empty or holds a byte outside ACGT: no hits listed */
+#define SIGAX_LOCATE_OVER     2u /* total > max_hits: no hits listed */
+int  sigax_locate_workspace(uint64_t n_queries, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_locate_device(sigax_index*, const void* d_seqs, const void* d_offs, uint64_t n_queries, uint32_t flags,
+                         uint32_t max_hits, uint32_t max_len, void* d_totals, void* d_qflags, void* d_hit_offs, void* d_hits,
+                         void* d_rows, uint64_t hits_cap, void* d_status4, void* d_work, uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous: searches and scans, reads the number of hits listed, allocates exactly that many and walks.
+ * *totals u64[n], *qflags u32[n], *hit_offs u64[n+1] and *hits sigax_hit[(*hit_offs)[n]] are malloc'd; release with sigax_free.
+ * offs[0] need not be 0 (a window of a longer table).  Runs on a stream of its own: calls from several host threads overlap. */
+int  sigax_locate_batch(sigax_index*, const char* seqs, const uint64_t* offs, uint64_t n_queries, uint32_t flags,
+                        uint32_t max_hits, uint32_t max_len, uint64_t** totals, uint32_t** qflags, uint64_t** hit_offs,
+                        sigax_hit** hits);
 
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).

@@ -19,7 +19,12 @@ BLOCK_DTYPE = np.dtype([
     ("raw0_lo", "<u8"), ("raw0_hi", "<u8"), ("raw1_lo", "<u8"), ("raw1_hi", "<u8"),
     ("length", "<u4"), ("af", "<u4"), ("reserved", "<u8")])
 EDGE_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("length", "<u4"), ("af", "<u4")])
-assert BLOCK_DTYPE.itemsize == 80 and EDGE_DTYPE.itemsize == 16
+HIT_DTYPE = np.dtype([("query", "<u4"), ("read", "<u4"), ("offset", "<u4"), ("flags", "<u4")])  # sigax_hit
+assert BLOCK_DTYPE.itemsize == 80 and EDGE_DTYPE.itemsize == 16 and HIT_DTYPE.itemsize == 16
+SIGAX_HIT_REV = 1
+SIGAX_HIT_CUT = 2
+SIGAX_LOCATE_SKIPPED = 1
+SIGAX_LOCATE_OVER = 2
 
 
 class Stats(C.Structure):
@@ -63,6 +68,7 @@ SYMBOLS = [
     "sigax_matcher_submit", "sigax_matcher_wait",
     "sigax_string_lengths_device", "sigax_get_strings_device", "sigax_get_strings", "sigax_kmer_spectrum_workspace",
     "sigax_kmer_spectrum_device", "sigax_kmer_spectrum_batch", "sigax_kmer_spectrum_rows", "sigax_kmer_spectrum_rows_hint",
+    "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -147,6 +153,9 @@ def lib():
     L.sigax_kmer_spectrum_batch.argtypes = [vp, cp, vp, u64, u32, u64, vp, vp]
     L.sigax_kmer_spectrum_rows.argtypes = [vp, vp, u64, u32, u32, u64, vp, vp]
     L.sigax_kmer_spectrum_rows_hint.argtypes = [vp, u32, u64, C.POINTER(u64)]
+    L.sigax_locate_workspace.argtypes = [u64, C.POINTER(u64)]
+    L.sigax_locate_device.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
+    L.sigax_locate_batch.argtypes = [vp, cp, vp, u64, u32, u32, u32, pvp, pvp, pvp, pvp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_edges_restore_order.argtypes = [ci, vp, u64, u64, vp, vp, vp, u64, vp, vp]
     L.sigax_edges_restore_order_host.argtypes = [ci, vp, u64, u64, vp, vp]

@@ -550,6 +550,19 @@ extern "C" int sigax_index_open_mem(const uint8_t* runs, uint64_t n_runs, const 
       }
     }
     ix->n_sai = n_strings;
+  } else if (sai && fwd_only) {
+    // the forward table alone: what sigax_locate_* names the reads with
+    for (u64 i = 0; i < n_strings; ++i)
+      if (sai[i] >= n_strings) {
+        sigax_index_close(ix);
+        return sigax_fail(SIGAX_E_IO, ".sai table: read id %u at row %llu, the index holds %llu strings", sai[i], i, (u64)n_strings);
+      }
+    int rc = upload(sai, n_strings * 4, (void**)&ix->d_sai[0], &ix->device_bytes);
+    if (rc != SIGAX_OK) {
+      sigax_index_close(ix);
+      return rc;
+    }
+    ix->n_sai = n_strings;
   }
   clk.lap(".sai check + upload");
   if (fwd_only) {
@@ -573,7 +586,12 @@ extern "C" int sigax_index_open(const char* bwt_path, const char* rbwt_path, con
     u64 ns = 0, nsym = 0, nruns = 0;
     const uint8_t* runs = nullptr;
     if ((rc = parse_bwt(fb, bwt_path, &ns, &nsym, &runs, &nruns)) != SIGAX_OK) return rc;
-    return sigax_index_open_mem(runs, nruns, nullptr, 0, nsym, ns, nullptr, nullptr, device, out);
+    std::vector<uint32_t> sai;  // with the forward .sai table the index also serves sigax_locate_*
+    if (sai_path && sai_path[0]) {
+      if ((rc = load_sai(sai_path, &sai)) != SIGAX_OK) return rc;
+      if (sai.size() != ns) return sigax_fail(SIGAX_E_IO, ".sai table (%zu entries) does not match the %llu strings of the .bwt", sai.size(), ns);
+    }
+    return sigax_index_open_mem(runs, nruns, nullptr, 0, nsym, ns, sai.empty() ? nullptr : sai.data(), nullptr, device, out);
   }
   std::vector<uint8_t> fb, rb;
   std::vector<uint32_t> sai, rsai;

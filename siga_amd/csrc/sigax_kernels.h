@@ -223,6 +223,38 @@ struct SpectrumArgs {
 };
 void launch_spectrum(const SpectrumArgs& a, bool wide, int n_cu, hipStream_t st);
 
+// `siga locate` (sigax_locate.hip).  Search: the two chains of every query -> chains[2q + strand] = {lower row, width}
+// (zeroed by the caller: a chain that dies, or is not run, leaves its zeros).  Finish: totals, per-query flags and the widths
+// that are listed (cnt), which launch_scan turns into hit_offs.  Walk: one LF walk per listed row -> its hit record.
+struct LocateArgs {
+  FmStrand fwd;
+  const unsigned char* seqs;
+  const unsigned long long* offs;        // [n_queries + 1]
+  unsigned long long n_queries;
+  uint32_t rc;                           // also the reverse complement's chain
+  uint32_t pk;                           // symbols of an entry of ptab
+  const void* ptab;                      // the corrector's prefix table when it is resident (launch_prefix_build), or NULL
+  uint32_t max_hits, max_len;
+  ulonglong2* chains;                    // [2 n_queries]
+  unsigned long long* totals;            // [n_queries]
+  uint32_t* qflags;                      // [n_queries]
+  uint32_t* cnt;                         // [n_queries]: hits listed per query
+  const unsigned long long* hit_offs;    // [n_queries + 1] (walk)
+  sigax_hit* hits;                       // [hits_cap]
+  unsigned long long* rows;              // [hits_cap] or NULL
+  unsigned long long hits_cap;
+  const uint32_t* sai;                   // [n_sai]
+  unsigned long long n_sai;
+  unsigned long long* status;            // 4 u64: [0] written by the scan; [1] walks cut and [2] sectors are added to (zeroed by the caller)
+  unsigned long long* counters;          // 2 u64, zeroed: the search's chain counter, one reserved
+};
+void launch_locate_search(const LocateArgs& a, bool wide, int n_cu, hipStream_t st);
+void launch_locate_finish(const LocateArgs& a, hipStream_t st);
+void launch_locate_walk(const LocateArgs& a, bool wide, hipStream_t st);
+// the slots the walk launches a lane for, min(hits_cap, n_queries * max_hits), and the most a grid of 256-lane workgroups holds
+unsigned long long locate_walk_slots(unsigned long long n_queries, uint32_t max_hits, unsigned long long hits_cap);
+static const unsigned long long LOCATE_MAX_SLOTS = 0x7FFFFFFFull * 256ull;
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

@@ -1,7 +1,7 @@
 // siga_amd/csrc/sigax_rank.h -- device helpers shared by the kernels that walk the forward strand symbol by symbol
-// (sigax_match.hip, sigax_spectrum.hip): byte -> rank, Occ out of a one-step granule, the pair counts of a two-step line
-// (fm_layout.h), and the wave reductions they report their statistics with.  Device code only; every translation unit
-// gets its own copy.
+// (sigax_match.hip, sigax_spectrum.hip, sigax_locate.hip): byte -> rank, Occ out of a one-step granule, the pair counts of a
+// two-step line (fm_layout.h), and the wave reductions they report their statistics with.  Device code only; every
+// translation unit gets its own copy.
 #ifndef SIGA_AMD_SIGAX_RANK_H_
 #define SIGA_AMD_SIGAX_RANK_H_
 

@@ -36,6 +36,9 @@ namespace {
 // ---- rows to text ---------------------------------------------------------------------------------------------------
 // -> symbols walked; *cut: stopped by max_len or by a row outside the table; *stretch: Occ('$', end row - 1), ~0 when cut.
 // WRITE: the symbols go down backwards from `end`.
+// (k_locate_walk of sigax_locate.hip spells the same step out around its hit record -- it tests p >= S.n at the top of the
+// loop, which is this loop's test after the step plus one for the first row: a change to the step or to the cut conditions
+// here is a change there)
 template <bool WIDE, bool WRITE>
 __device__ __forceinline__ u32 walk_row(const FmStrand& S, const u64* C, u64 row, u32 max_len, unsigned char* end, bool* cut,
                                         u64* stretch, u32* n_sec) {

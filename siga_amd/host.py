@@ -38,6 +38,8 @@ def lib():
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
         L.sigah_match_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_char_p,
                                         C.c_uint64, C.c_char_p, C.c_uint64]
+        L.sigah_locate_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                         C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -117,6 +119,18 @@ def match_files(paths, prefix, max_length=None, rc=True, device=0, out=None, bat
     lim = (1 << 64) - 1 if max_length is None else int(max_length)
     if lib().sigah_match_files(arr, len(paths), prefix.encode(), lim, int(rc), device, (out or "").encode(), batch_reads, err, 512) != 0:
         raise RuntimeError("siga match failed: " + err.value.decode())
+
+
+def locate_files(paths, prefix, rc=True, max_hits=1000, max_len=None, device=0, out=None, batch_queries=0):
+    """`siga locate`: FMIndex::loadForwardSai(<prefix>.bwt, <prefix>.sai) + Locator::run over the query files of `paths`, in
+    order; the QT and HT lines go to the file `out`, or to stdout.  max_len None: walks of any length.  batch_queries: queries
+    per device batch (0: the default)."""
+    err = C.create_string_buffer(512)
+    arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+    lim = (1 << 32) - 1 if max_len is None else int(max_len)
+    if lib().sigah_locate_files(arr, len(paths), prefix.encode(), int(max_hits), lim, int(rc), device, (out or "").encode(),
+                                batch_queries, err, 512) != 0:
+        raise RuntimeError("siga locate failed: " + err.value.decode())
 
 
 def preqc(prefix, k=31, samples=50000, seed=1, all_reads=False, max_count=1024, device=0, out=None, batch_rows=0):

@@ -219,6 +219,24 @@ int sigah_match_files(const char* const* paths, uint64_t n_paths, const char* pr
   return 0;
 }
 
+// `siga locate`: FMIndex::loadForwardSai + Locator::run over n_paths inputs; out_path "" = stdout; batch_queries 0 = the default
+int sigah_locate_files(const char* const* paths, uint64_t n_paths, const char* prefix, uint32_t max_hits, uint32_t max_length, int rc,
+                       int device, const char* out_path, uint64_t batch_queries, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {
+    if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
+    return -1;
+  }
+  std::vector<std::string> inputs;
+  for (uint64_t i = 0; i < n_paths; ++i) inputs.push_back(paths[i]);
+  sigah::Locator locator(max_hits, max_length, rc != 0);
+  if (!locator.run(fmi, inputs, out_path ? out_path : "", 1, (size_t)batch_queries)) {
+    if (err && errcap) snprintf(err, errcap, "%s", locator.error().c_str());
+    return -1;
+  }
+  return 0;
+}
+
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty
 int sigah_preqc(const char* prefix, uint64_t k, uint64_t samples, uint64_t seed, int all, uint64_t max_count, int device,
                 const char* out_path, uint64_t batch_rows, char* err, uint64_t errcap) {

@@ -37,6 +37,14 @@ bool FMIndex::loadForward(const std::string& prefix, FMIndex& fmi, int device) {
   }
   return sigax_index_open((prefix + ".bwt").c_str(), nullptr, nullptr, nullptr, device, &fmi._h) == SIGAX_OK;
 }
+// ... with <prefix>.sai beside it: the table that names the reads of `siga locate`'s hits
+bool FMIndex::loadForwardSai(const std::string& prefix, FMIndex& fmi, int device) {
+  if (fmi._h) {
+    sigax_index_close(fmi._h);
+    fmi._h = nullptr;
+  }
+  return sigax_index_open((prefix + ".bwt").c_str(), nullptr, (prefix + ".sai").c_str(), nullptr, device, &fmi._h) == SIGAX_OK;
+}
 
 uint64_t FMIndex::length() const {
   sigax_index_info inf;

@@ -4,7 +4,7 @@
 // on the GPU), SuffixArray + BWT writers (src/suffix_array.cpp, src/bwt.cpp), OverlapBuilder
 // (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).  One source file per object: reads.cpp (readers),
 // strand_index.cpp (index builders and writers), overlap_builder.cpp (FMIndex, OverlapBuilder), correct_match.cpp
-// (CorrectProcessor, Matcher), kmer_spectrum.cpp (KmerSpectrum), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
+// (CorrectProcessor, Matcher), locate.cpp (Locator), kmer_spectrum.cpp (KmerSpectrum), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
 // host_util.hpp are internal to the library.
 #ifndef SIGA_AMD_HOST_SIGA_HOST_HPP_
 #define SIGA_AMD_HOST_SIGA_HOST_HPP_
@@ -77,6 +77,7 @@ class FMIndex {
   ~FMIndex();
   static bool load(const std::string& prefix, FMIndex& fmi, int device = 0);
   static bool loadForward(const std::string& prefix, FMIndex& fmi, int device = 0);  // <prefix>.bwt alone (`siga correct`)
+  static bool loadForwardSai(const std::string& prefix, FMIndex& fmi, int device = 0);  // <prefix>.bwt + <prefix>.sai (`siga locate`)
   sigax_index* handle() const { return _h; }
   uint64_t length() const;
 
@@ -157,6 +158,33 @@ class Matcher {
 
  private:
   uint64_t _maxLength;
+  bool _rc;
+  mutable std::string _error;
+};
+
+// `siga locate`: for every query of every input, where it occurs in the indexed reads -- read index (0-based position in the
+// indexed set), offset and strand -- both strands unless rc is false.  No counterpart in the reference.  The index needs its
+// .sai table (FMIndex::load or FMIndex::loadForwardSai) and reads of ACGT only: run() fails with the library's message otherwise.
+class Locator {
+ public:
+  static const uint32_t kNoLimit = 0xFFFFFFFFu;  // the library's MAX_STRING_LEN: walks as long as the index's longest read
+  explicit Locator(uint32_t maxHits = 1000, uint32_t maxLength = kNoLimit, bool rc = true) : _maxHits(maxHits), _maxLength(maxLength), _rc(rc) {}
+  // Per query, in input order: "QT\t<name>\t<query length>\t<total>\t<listed>\n", then "HT\t<name>\t<read index>\t<offset>\t<+|->\n"
+  // per listed hit in the library's order (sigax_locate_batch) to `output` (empty: stdout).  A query that is empty, holds a byte
+  // outside ACGT or occurs more than maxHits times lists nothing; a hit whose walk was cut at maxLength prints "*" for its
+  // read and offset.  The inputs are read in order; one that cannot be read ends the run with what came before it written.
+  // batchQueries = queries per device batch (0: 2^18).
+  bool run(const FMIndex& index, const std::vector<std::string>& inputs, const std::string& output = std::string(), size_t threads = 1,
+           size_t batchQueries = 0, size_t* processed = nullptr) const {
+    return run(index.handle(), inputs, output, threads, batchQueries, processed);
+  }
+  // the same over the library's handle (what a host without the FMIndex class holds)
+  bool run(sigax_index* index, const std::vector<std::string>& inputs, const std::string& output = std::string(), size_t threads = 1,
+           size_t batchQueries = 0, size_t* processed = nullptr) const;
+  const std::string& error() const { return _error; }
+
+ private:
+  uint32_t _maxHits, _maxLength;
   bool _rc;
   mutable std::string _error;
 };

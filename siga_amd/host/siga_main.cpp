@@ -1,4 +1,4 @@
-// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga preqc` ... command line, option for option as the reference
+// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga locate` / `siga preqc` ... command line, option for option as the reference
 // (src/main.cpp:17-83, src/indexer.cpp:119-156, src/overlap.cpp:66-105).  Exit codes follow the reference:
 // a runner returning -1 exits 255; printing help returns 256, i.e. exit status 0.
 #include <getopt.h>
@@ -76,12 +76,13 @@ static int apply_ini(int argc, char** argv, const option* longopts, std::vector<
 }
 
 static int usage() {
-  printf("siga [index|correct|overlap|rmdup|preqc|match] [OPTION] ... READSFILE\n"
+  printf("siga [index|correct|overlap|rmdup|preqc|locate|match] [OPTION] ... READSFILE\n"
          "  index     build the FM-index (.sai/.bwt/.rsai/.rbwt) of READSFILE\n"
          "  overlap   compute pairwise overlaps between all the sequences in READSFILE (GPU)\n"
          "  rmdup     remove duplicated reads (GPU)\n"
          "  correct   k-mer based error correction (GPU)\n"
          "  match     count the occurrences of every read of READSFILE in the indexed reads (GPU)\n"
+         "  locate    list where every sequence of QUERYFILE occurs in the indexed reads: read, offset, strand (GPU)\n"
          "  preqc     pre-assembly quality checks: the k-mer count distribution of the indexed reads (GPU)\n"
          "common options: -s, --ini=FILE (options from FILE, the command line goes over them);\n"
          "                -c, --log4cxx=FILE is accepted and ignored (this build logs to stderr; SIGA_TIMING=1 prints phase\n"
@@ -440,6 +441,76 @@ static int run_match(int argc, char** argv) {
   return 0;
 }
 
+static int locate_help() {
+  printf("siga locate [OPTION] ... QUERYFILE...\n"
+         "List where the sequences of QUERYFILE occur in the indexed reads\n"
+         "\n"
+         "      -h, --help                       display this help and exit\n"
+         "\n"
+         "      -p, --prefix=PREFIX              use PREFIX instead of prefix of QUERYFILE for the names of the index files (.bwt, .sai)\n"
+         "          --no-opposite-strand         do not look for the reverse complement of the queries\n"
+         "          --max-hits=N                 list the hits of queries that occur at most N times (default: 1000)\n"
+         "          --max-length=N               give up on a hit more than N bases into its read (default: no limit)\n"
+         "      -t, --threads=NUM                accepted; the GPU does the searching\n"
+         "          --device=NUM                 GPU to use (default: 0)\n"
+         "\n"
+         "Prints per query, in input order, QT <name> <query length> <occurrences> <hits listed> and then one line\n"
+         "HT <name> <read> <offset> <+|-> per hit, tab-separated: <read> is the 0-based position of the read in the indexed\n"
+         "set (the reads file is not opened), read[offset, offset + length) is the query (+) or its reverse complement (-).\n"
+         "A query with a base outside ACGT, or with more than --max-hits occurrences, lists no hits; a hit given up on at\n"
+         "--max-length prints * for <read> and <offset>.\n"
+         "Needs <prefix>.sai and an index of reads that hold ACGT only: with other bases a row of the index is a piece of a\n"
+         "read, and the index carries no table from pieces to reads.\n"
+         "\n");
+  return 256;
+}
+
+static int run_locate(int argc, char** argv) {
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_MAX_HITS, OPT_MAX_LENGTH };
+  static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},  {"ini", required_argument, nullptr, 's'},
+                                    {"prefix", required_argument, nullptr, 'p'},   {"threads", required_argument, nullptr, 't'},
+                                    {"max-hits", required_argument, nullptr, OPT_MAX_HITS}, {"max-length", required_argument, nullptr, OPT_MAX_LENGTH},
+                                    {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
+                                    {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
+  std::string prefix;
+  uint64_t maxHits = 1000, maxLength = sigah::Locator::kNoLimit;
+  size_t threads = 1;
+  bool help = false, rc = true;
+  int device = 0, c;
+  std::vector<std::string> ini_store;
+  std::vector<char*> ini_argv;
+  if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
+  argc = (int)ini_argv.size();
+  argv = ini_argv.data();
+  while ((c = getopt_long(argc, argv, "c:s:p:t:h", longopts, nullptr)) != -1) {
+    switch (c) {
+      case 'p': prefix = optarg; break;
+      case 't': threads = strtoull(optarg, nullptr, 10); break;
+      case OPT_MAX_HITS: maxHits = strtoull(optarg, nullptr, 10); break;
+      case OPT_MAX_LENGTH: maxLength = strtoull(optarg, nullptr, 10); break;
+      case OPT_NO_RC: rc = false; break;
+      case OPT_DEVICE: device = atoi(optarg); break;
+      case 'h': help = true; break;
+      default: break;
+    }
+  }
+  if (help || argc - optind < 1) return locate_help();
+  std::vector<std::string> inputs(argv + optind, argv + argc);
+  if (prefix.empty()) prefix = sigah::Utils::stem(inputs[0]);
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {
+    fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+    return -1;
+  }
+  const uint64_t top = 0xFFFFFFFFull;  // the library counts a query's listed hits, and a walk's steps, in 32 bits
+  sigah::Locator locator((uint32_t)std::min(maxHits, top), (uint32_t)std::min(maxLength, top), rc);
+  if (!locator.run(fmi, inputs, std::string(), threads)) {
+    fprintf(stderr, "Failed to locate queries: %s\n", locator.error().c_str());
+    return -1;
+  }
+  return 0;
+}
+
 static int preqc_help() {
   // help text of src/preqc.cpp:209-222, plus the options of the k-mer distribution the reference computes no further than
   // GenomeEstimator::estimate's null index
@@ -535,6 +606,7 @@ int main(int argc, char** argv) {
   else if (cmd == "correct") rc = run_correct(argc - 1, argv + 1);
   else if (cmd == "overlap") rc = run_overlap(argc - 1, argv + 1);
   else if (cmd == "match") rc = run_match(argc - 1, argv + 1);
+  else if (cmd == "locate") rc = run_locate(argc - 1, argv + 1);
   else if (cmd == "preqc") rc = run_preqc(argc - 1, argv + 1);
   else return usage();
   if (getenv("SIGA_TIMING"))

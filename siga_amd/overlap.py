@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BLOCK_DTYPE, EDGE_DTYPE, SIGAX_DUPLICATE, SIGAX_EDGES, SIGAX_IRREDUCIBLE, SIGAX_RC
+from ._lib import BLOCK_DTYPE, EDGE_DTYPE, HIT_DTYPE, SIGAX_DUPLICATE, SIGAX_EDGES, SIGAX_IRREDUCIBLE, SIGAX_RC
 
 
 class SigaxError(RuntimeError):
@@ -186,6 +186,18 @@ class FMIndexPair:
         return pair
 
     @classmethod
+    def load_forward(cls, prefix, device=0, with_sai=True):
+        """<prefix>.bwt alone (what `siga index --no-reverse` writes), with <prefix>.sai unless with_sai is False: serves occ,
+        kmer_counts, correct, match, kmer_spectrum and -- with the .sai table -- locate; overlap runs fail on it."""
+        h = C.c_void_p()
+        sai = (prefix + ".sai").encode() if with_sai else None
+        _check(_lib.lib().sigax_index_open((prefix + ".bwt").encode(), None, sai, None, device, C.byref(h)), "sigax_index_open")
+        pair = cls(h.value)
+        pair._prepare_pending = False
+        pair._resident = False
+        return pair
+
+    @classmethod
     def from_memory(cls, runs, rruns, n_symbols, n_strings, sai=None, rsai=None, device=0, resident=True):
         runs = np.ascontiguousarray(runs, dtype=np.uint8)
         rruns = np.ascontiguousarray(rruns, dtype=np.uint8)
@@ -277,6 +289,30 @@ class FMIndexPair:
         lens = offs[1:] - offs[:-1]
         split = lens > np.uint64(lim)
         return out[0::2].copy(), np.ma.masked_array(out[1::2].copy(), mask=~split)
+
+    def locate(self, seqs, rc=True, max_hits=1000, max_len=MAX_STRING_LEN):
+        """Where every query occurs in the indexed reads (sigax_locate_batch) -> (totals u64[n], qflags u32[n], hit_offs
+        u64[n+1], hits): totals[q] = match(seqs, rc=rc)'s head; hits (HIT_DTYPE: query, read, offset, flags) of query q are
+        hits[hit_offs[q]:hit_offs[q+1]], listed iff the query is non-empty, all ACGT (else qflags & SIGAX_LOCATE_SKIPPED) and
+        occurs at most max_hits times (else qflags & SIGAX_LOCATE_OVER): read[offset:offset+len] == query, or its reverse
+        complement where flags & SIGAX_HIT_REV.  Walks of more than max_len steps are cut (flags & SIGAX_HIT_CUT).  Needs the
+        .sai table and reads of ACGT only."""
+        buf, offs = pack_reads(seqs)
+        n = len(offs) - 1
+        if isinstance(buf, np.ndarray):
+            buf = C.c_char_p(buf.ctypes.data) if buf.size else b""
+        t, f, o, h = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(_lib.lib().sigax_locate_batch(self._h, buf, offs.ctypes.data, n, SIGAX_RC if rc else 0, int(max_hits), int(max_len),
+                                             C.byref(t), C.byref(f), C.byref(o), C.byref(h)), "sigax_locate_batch")
+        try:
+            totals = _copy_records(t, n, np.dtype(np.uint64))
+            qflags = _copy_records(f, n, np.dtype(np.uint32))
+            hit_offs = _copy_records(o, n + 1, np.dtype(np.uint64))
+            hits = _copy_records(h, int(hit_offs[-1]), HIT_DTYPE)
+        finally:
+            for p in (t, f, o, h):
+                _lib.lib().sigax_free(p)
+        return totals, qflags, hit_offs, hits
 
     def get_strings(self, rows, which=0, max_len=MAX_STRING_LEN, stretch=False):
         """FMIndex::getString (src/fmindex.cpp:292-313, sigax_get_strings) for many BWT rows of strand `which` -> list of
