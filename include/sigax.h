@@ -321,6 +321,58 @@ int  sigax_locate_batch(sigax_index*, const char* seqs, const uint64_t* offs, ui
                         uint32_t max_hits, uint32_t max_len, uint64_t** totals, uint32_t** qflags, uint64_t** hit_offs,
                         sigax_hit** hits);
 
+/* ---- `siga unitig`: unbranched chains of overlaps compacted (csrc/sigax_unitig.hip) ----------------------------------------------
+ * The fixpoint of Bigraph::simplify (src/bigraph.cpp:341-414, Vertex::merge at :131-202) over the edge records of an overlap
+ * run, without an index: every chain of reads joined by SIMPLE records becomes one unitig.
+ *
+ * Input: n_reads reads (lengths u32[n_reads], bases seqs / offs u64[n_reads + 1] by read id), n_edges sigax_edge records in
+ * any order, each overlap once (what Hit2OverlapConverter leaves), and min_overlap.  A read has two ends, B (prefix, the
+ * reference's ANTISENSE) and E (suffix, SENSE): a record touches `query` at E if af bit0 is clear, else at B, and `target` at B
+ * if af bit1 is clear, else at E.  A record is IGNORED as malformed when a read id is >= n_reads, af is none of 0, 3, 5, 6,
+ * length is 0 or above the shorter of its reads; otherwise ignored as low when length < min_overlap (Bigraph::load's filter).
+ * A kept record is a containment when length equals the length of one of its reads, a self edge when query == target.  The
+ * degree of a read end is the number of kept records that touch it, a containment counting at both ends of both its reads.  A
+ * record is simple iff it is kept, no containment, no self edge and both ends it touches have degree 1 (:356-362).
+ *
+ * A unitig is a connected component of the reads under simple records: a path (a single read included) or a cycle.  A path
+ * starts at its terminal with the smaller id and walks to the other; a read entered through B is placed forward, one entered
+ * through E reverse-complemented (A<->T, C<->G, other bytes as they are); the first read is forward iff it is left through
+ * E, a single read is forward.  offset[0] = 0, offset[i+1] = offset[i] + L[i] - overlap(i, i+1), the unitig has offset[last] +
+ * L[last] bases: the first read whole, then of every next read the last L - overlap bases as placed.  A cycle starts at its
+ * smallest id, placed forward and left through E, and walks until the next record would enter the start again: that record
+ * is not merged, the unitig is flagged SIGAX_UNITIG_CIRCULAR and carries its overlap (the reference cuts such a cycle where
+ * its hash map happens to begin: DESIGN.md 9d).  Unitigs are numbered by ascending id of their first read.
+ *
+ * Output, sized for the worst case so that one call is enough: seq_offs u64[n_reads + 1] and lay_offs u64[n_reads + 1], of
+ * which entries 0 .. n_unitigs are written (unitig u has bases useqs[seq_offs[u] .. seq_offs[u+1]) and placements
+ * layout[lay_offs[u] .. lay_offs[u+1])); uflags u32[n_reads], entries 0 .. n_unitigs - 1: bit0 SIGAX_UNITIG_CIRCULAR, the upper
+ * 31 bits the closing overlap (uflags >> 1; overlaps are below 2^31); layout sigax_placement[n_reads], all written; useqs
+ * offs[n_reads] - offs[0] bytes, of which seq_offs[n_unitigs] are written, or NULL for the layout alone.  status6 = 6 u64,
+ * written (not added to): {unitigs, unitig bases, records ignored as malformed, records below min_overlap, simple records
+ * merged (a cycle's closing record is not), cycles}.
+ *
+ * sigax_unitigs_device: every buffer in device memory, asynchronous on `stream` (a hipStream_t or NULL), allocates nothing.
+ * d_edges, d_layout, d_useqs and d_work are 16-byte aligned, d_offs, d_seq_offs, d_lay_offs and d_status6 8-byte aligned;
+ * d_work = sigax_unitigs_workspace bytes of scratch (some 190 bytes per read).  Whatever the records hold, nothing outside the buffers is touched, and every loop has a bound the host knows: list
+ * ranking by pointer jumping runs ceil(log2 n_reads) + 1 rounds, twice.  n_reads >= 2^31, n_edges > 2^32, a NULL where a
+ * buffer is required, a misaligned buffer and a work_bytes below sigax_unitigs_workspace's: SIGAX_E_ARG.  n_reads = 0:
+ * SIGAX_OK, status zeros (when d_status6 is given).  Needs no index. */
+typedef struct sigax_placement { uint32_t read, flags; uint64_t offset; } sigax_placement; /* 16 bytes */
+#define SIGAX_PLACED_REV      1u   /* the read lies reverse-complemented in its unitig */
+#define SIGAX_UNITIG_CIRCULAR 1u   /* unitig flag, bit0; the closing overlap is uflags >> 1 */
+int  sigax_unitigs_workspace(uint64_t n_reads, uint64_t n_edges, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                          const void* d_offs, uint64_t n_reads, uint32_t min_overlap, void* d_seq_offs, void* d_lay_offs,
+                          void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_status6, void* d_work,
+                          uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous.  offs[0] need not be 0.  *seq_offs u64[n_unitigs + 1], *lay_offs u64[n_unitigs + 1], *uflags
+ * u32[n_unitigs], *layout sigax_placement[n_reads] and *useqs (unitig bases; pass useqs = NULL for the layout alone) are
+ * malloc'd; release with sigax_free.  The six counts: sigax_unitigs_last_status. */
+int  sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                        const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, uint64_t* n_unitigs, uint64_t** seq_offs,
+                        uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs);
+/* the six counts (status6 above) of this thread's last successful sigax_unitigs_host call, whose signature has no room for them */
+int  sigax_unitigs_last_status(uint64_t status6[6]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -20,11 +20,14 @@ BLOCK_DTYPE = np.dtype([
     ("length", "<u4"), ("af", "<u4"), ("reserved", "<u8")])
 EDGE_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("length", "<u4"), ("af", "<u4")])
 HIT_DTYPE = np.dtype([("query", "<u4"), ("read", "<u4"), ("offset", "<u4"), ("flags", "<u4")])  # sigax_hit
-assert BLOCK_DTYPE.itemsize == 80 and EDGE_DTYPE.itemsize == 16 and HIT_DTYPE.itemsize == 16
+PLACEMENT_DTYPE = np.dtype([("read", "<u4"), ("flags", "<u4"), ("offset", "<u8")])  # sigax_placement
+assert BLOCK_DTYPE.itemsize == 80 and EDGE_DTYPE.itemsize == 16 and HIT_DTYPE.itemsize == 16 and PLACEMENT_DTYPE.itemsize == 16
 SIGAX_HIT_REV = 1
 SIGAX_HIT_CUT = 2
 SIGAX_LOCATE_SKIPPED = 1
 SIGAX_LOCATE_OVER = 2
+SIGAX_PLACED_REV = 1
+SIGAX_UNITIG_CIRCULAR = 1
 
 
 class Stats(C.Structure):
@@ -69,6 +72,7 @@ SYMBOLS = [
     "sigax_string_lengths_device", "sigax_get_strings_device", "sigax_get_strings", "sigax_kmer_spectrum_workspace",
     "sigax_kmer_spectrum_device", "sigax_kmer_spectrum_batch", "sigax_kmer_spectrum_rows", "sigax_kmer_spectrum_rows_hint",
     "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
+    "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -156,6 +160,12 @@ def lib():
     L.sigax_locate_workspace.argtypes = [u64, C.POINTER(u64)]
     L.sigax_locate_device.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
     L.sigax_locate_batch.argtypes = [vp, cp, vp, u64, u32, u32, u32, pvp, pvp, pvp, pvp]
+    L.sigax_unitigs_workspace.argtypes = [u64, u64, C.POINTER(u64)]
+    L.sigax_unitigs_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.sigax_unitigs_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(u64), pvp, pvp, pvp, pvp, pvp]
+    L.sigax_unitigs_last_status.argtypes = [vp]
+    # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
+    L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_edges_restore_order.argtypes = [ci, vp, u64, u64, vp, vp, vp, u64, vp, vp]
     L.sigax_edges_restore_order_host.argtypes = [ci, vp, u64, u64, vp, vp]

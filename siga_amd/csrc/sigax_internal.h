@@ -44,6 +44,12 @@ struct DevGuard {
   }
 };
 
+// Measurement aid of tools/unitig_bench.py, exported but not part of include/sigax.h and not stable: the bases pass of
+// sigax_unitigs_device alone, over the scratch a call with the same reads and records left in d_work.  It cannot tell whether
+// such a call was made; the pass bounds every access all the same.  Same argument checks as sigax_unitigs_device.
+extern "C" int sigax_unitigs_bases_device(int device, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint64_t n_edges, void* d_useqs,
+                                          void* d_work, uint64_t work_bytes, void* stream);
+
 #pragma GCC visibility push(hidden)
 
 // ------------------------------------------------------------------------------------------------------

@@ -255,6 +255,39 @@ void launch_locate_walk(const LocateArgs& a, bool wide, hipStream_t st);
 unsigned long long locate_walk_slots(unsigned long long n_queries, uint32_t max_hits, unsigned long long hits_cap);
 static const unsigned long long LOCATE_MAX_SLOTS = 0x7FFFFFFFull * 256ull;
 
+// `siga unitig` (sigax_unitig.hip): unbranched chains of overlaps compacted.  State 2r + e = read r left through end e (0 = B,
+// prefix; 1 = E, suffix).  Everything below `status` is the caller's scratch (sigax_unitig.cpp lays it out).
+enum { UNI_C_BAD = 0, UNI_C_LOW = 1, UNI_C_SIMPLE = 2, UNI_C_CYCLES = 3 };
+struct UnitigArgs {
+  const sigax_edge* edges;
+  unsigned long long n_edges, n_reads;
+  const uint32_t* lengths;               // [n_reads]
+  const unsigned char* seqs;
+  const unsigned long long* offs;        // [n_reads + 1]
+  uint32_t min_overlap;
+  unsigned long long* seq_offs;          // [n_reads + 1]
+  unsigned long long* lay_offs;          // [n_reads + 1]
+  uint32_t* uflags;                      // [n_reads]
+  sigax_placement* layout;               // [n_reads]
+  unsigned char* useqs;                  // offs[n_reads] - offs[0] bytes, or NULL: layout only
+  unsigned long long* status;            // 6 u64, written
+  uint32_t* deg;                         // [2 n_reads], zeroed: kept records per read end
+  uint2* link;                           // [2 n_reads], 0xFF-filled: {end touched on the other read, overlap} of an end's simple record
+  void* rank[2];                         // 2 x uint4[2 n_reads]: the ranking's ping-pong buffers ...
+  unsigned long long* dist[2];           // 2 x [2 n_reads] ... and their base distances
+  uint32_t* closing;                     // [n_reads], zeroed: a cut cycle's unitig flags, at its smallest read
+  uint32_t* cnt;                         // 4 x [n_reads + 1]: per read {is a head, its unitig's reads, bases low, bases high}
+  unsigned long long* scan;              // 4 x [n_reads + 1]: their prefix sums
+  unsigned long long* partial;           // scan_partials_needed(n_reads) u64
+  unsigned long long* scan_total;        // 1 u64
+  unsigned long long* dst;               // [n_reads + 1]: where in useqs the bases placement i adds begin; [n_reads] = all bases
+  unsigned long long* src;               // [n_reads]: the byte of seqs that goes there; bit 63: descending and complemented
+  unsigned long long* counts;            // 4 u64, zeroed: UNI_C_*
+};
+unsigned unitig_rounds(unsigned long long n_reads);  // ceil(log2 n_reads) + 1: the pointer-jumping launches of one ranking
+void launch_unitigs(const UnitigArgs& a, hipStream_t st);
+void launch_unitig_bases(const UnitigArgs& a, hipStream_t st);  // the last phase alone, over what launch_unitigs left (sigax_unitigs_bases_device)
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

@@ -1,0 +1,240 @@
+// siga_amd/csrc/sigax_unitig.cpp -- `siga unitig` on the device: the entry points of sigax_unitig.hip.
+#include <cstring>
+
+#include "sigax_internal.h"
+
+static_assert(sizeof(sigax_placement) == 16, "sigax_placement must be 16 bytes");
+
+namespace {
+
+// where the pieces of the caller's scratch lie (every piece 16-byte aligned)
+struct UnitigWork {
+  u64 rank[2], dist[2], link, dst, src, scan, partial, scan_total, counts, deg, closing, cnt, bytes;
+  u64 zero_from, zero_bytes;  // deg, closing and counts lie together: one memset
+};
+UnitigWork unitig_work(u64 n) {
+  UnitigWork w;
+  u64 at = 0;
+  auto take = [&](u64 bytes) {
+    const u64 here = at;
+    at += (bytes + 15) & ~15ull;
+    return here;
+  };
+  for (int k = 0; k < 2; ++k) w.rank[k] = take(2 * n * 16);
+  for (int k = 0; k < 2; ++k) w.dist[k] = take(2 * n * 8);
+  w.link = take(2 * n * 8);
+  w.dst = take((n + 1) * 8);
+  w.src = take(n * 8);
+  w.scan = take(4 * (n + 1) * 8);
+  w.partial = take(scan_partials_needed(n) * 8);
+  w.scan_total = take(8);
+  w.zero_from = at;
+  w.counts = take(4 * 8);
+  w.deg = take(2 * n * 4);
+  w.closing = take(n * 4);
+  w.zero_bytes = at - w.zero_from;
+  w.cnt = take(4 * (n + 1) * 4);
+  w.bytes = at;
+  return w;
+}
+
+UnitigArgs unitig_args(const sigax_edge* d_edges, u64 n_edges, const void* d_lengths, const void* d_seqs, const void* d_offs, u64 n,
+                       uint32_t min_overlap, void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                       void* d_status6, void* d_work) {
+  const UnitigWork w = unitig_work(n);
+  char* base = (char*)d_work;
+  UnitigArgs a;
+  a.edges = d_edges;
+  a.n_edges = n_edges;
+  a.n_reads = n;
+  a.lengths = (const uint32_t*)d_lengths;
+  a.seqs = (const unsigned char*)d_seqs;
+  a.offs = (const u64*)d_offs;
+  a.min_overlap = min_overlap;
+  a.seq_offs = (u64*)d_seq_offs;
+  a.lay_offs = (u64*)d_lay_offs;
+  a.uflags = (uint32_t*)d_uflags;
+  a.layout = d_layout;
+  a.useqs = (unsigned char*)d_useqs;
+  a.status = (u64*)d_status6;
+  a.deg = (uint32_t*)(base + w.deg);
+  a.link = (uint2*)(base + w.link);
+  for (int k = 0; k < 2; ++k) {
+    a.rank[k] = base + w.rank[k];
+    a.dist[k] = (u64*)(base + w.dist[k]);
+  }
+  a.closing = (uint32_t*)(base + w.closing);
+  a.cnt = (uint32_t*)(base + w.cnt);
+  a.scan = (u64*)(base + w.scan);
+  a.partial = (u64*)(base + w.partial);
+  a.scan_total = (u64*)(base + w.scan_total);
+  a.dst = (u64*)(base + w.dst);
+  a.src = (u64*)(base + w.src);
+  a.counts = (u64*)(base + w.counts);
+  return a;
+}
+
+int unitig_limits(u64 n_reads, u64 n_edges) {
+  if (n_reads >= (1ull << 31)) return sigax_fail(SIGAX_E_ARG, "2^31 reads or more: a state names a read end in 32 bits");
+  if (n_edges > (1ull << 32)) return sigax_fail(SIGAX_E_ARG, "more than 2^32 records");
+  return SIGAX_OK;
+}
+
+thread_local u64 t_last_status[6] = {0, 0, 0, 0, 0, 0};
+
+}  // namespace
+
+extern "C" int sigax_unitigs_workspace(uint64_t n_reads, uint64_t n_edges, uint64_t* bytes) {
+  if (!bytes) return sigax_fail(SIGAX_E_ARG, "bad argument");
+  const int rc = unitig_limits(n_reads, n_edges);
+  if (rc != SIGAX_OK) return rc;
+  *bytes = unitig_work(n_reads).bytes;
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                    const void* d_offs, uint64_t n_reads, uint32_t min_overlap, void* d_seq_offs, void* d_lay_offs,
+                                    void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_status6, void* d_work,
+                                    uint64_t work_bytes, void* stream) {
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  if (n_reads && (!d_lengths || !d_seqs || !d_offs || !d_seq_offs || !d_lay_offs || !d_uflags || !d_layout || !d_status6 || !d_work ||
+                  (n_edges && !d_edges)))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (n_reads && (((uintptr_t)d_edges | (uintptr_t)d_layout | (uintptr_t)d_useqs | (uintptr_t)d_work) & 15))
+    return sigax_fail(SIGAX_E_ARG, "d_edges, d_layout, d_useqs and d_work must be 16-byte aligned");
+  if (n_reads && (((uintptr_t)d_offs | (uintptr_t)d_seq_offs | (uintptr_t)d_lay_offs | (uintptr_t)d_status6) & 7))
+    return sigax_fail(SIGAX_E_ARG, "d_offs, d_seq_offs, d_lay_offs and d_status6 must be 8-byte aligned");
+  const UnitigWork w = unitig_work(n_reads);
+  if (n_reads && work_bytes < w.bytes)
+    return sigax_fail(SIGAX_E_ARG, "workspace of %llu bytes, %llu needed (sigax_unitigs_workspace)", (u64)work_bytes, w.bytes);
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t st = (hipStream_t)stream;
+  if (n_reads == 0) {
+    if (d_status6) HIP_TRY(hipMemsetAsync(d_status6, 0, 48, st));
+    return SIGAX_OK;
+  }
+  const UnitigArgs a = unitig_args(d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, d_seq_offs, d_lay_offs, d_uflags,
+                                   d_layout, d_useqs, d_status6, d_work);
+  char* base = (char*)d_work;
+  HIP_TRY(hipMemsetAsync(base + w.zero_from, 0, (size_t)w.zero_bytes, st));
+  HIP_TRY(hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st));
+  launch_unitigs(a, st);
+  HIP_TRY(hipGetLastError());
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_bases_device(int device, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint64_t n_edges,
+                                          void* d_useqs, void* d_work, uint64_t work_bytes, void* stream) {
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  if (n_reads && (!d_seqs || !d_offs || !d_useqs || !d_work)) return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (n_reads && ((((uintptr_t)d_useqs | (uintptr_t)d_work) & 15) || ((uintptr_t)d_offs & 7)))
+    return sigax_fail(SIGAX_E_ARG, "d_useqs and d_work must be 16-byte aligned, d_offs 8-byte aligned");
+  if (n_reads && work_bytes < unitig_work(n_reads).bytes) return sigax_fail(SIGAX_E_ARG, "workspace too small (sigax_unitigs_workspace)");
+  HIP_TRY(hipSetDevice(device));
+  if (n_reads == 0) return SIGAX_OK;
+  const UnitigArgs a = unitig_args(nullptr, n_edges, nullptr, d_seqs, d_offs, n_reads, 0, nullptr, nullptr, nullptr, nullptr, d_useqs, nullptr, d_work);
+  launch_unitig_bases(a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_last_status(uint64_t status6[6]) {
+  if (!status6) return sigax_fail(SIGAX_E_ARG, "bad argument");
+  for (int k = 0; k < 6; ++k) status6[k] = t_last_status[k];
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                  const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, uint64_t* n_unitigs, uint64_t** seq_offs,
+                                  uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs) {
+  if (!n_unitigs || !seq_offs || !lay_offs || !uflags || !layout || (n_reads && (!lengths || !seqs || !offs)) || (n_edges && !edges))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  *n_unitigs = 0;
+  *seq_offs = nullptr;
+  *lay_offs = nullptr;
+  *uflags = nullptr;
+  *layout = nullptr;
+  if (useqs) *useqs = nullptr;
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  const u64 n = n_reads;
+  for (u64 i = 0; i < n; ++i)
+    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] != lengths[i]) return sigax_fail(SIGAX_E_ARG, "read %llu: offsets and length disagree", i);
+  // offs[0] need not be 0 (a window of a longer table): the device gets the window's bytes and offsets from 0
+  const u64 b0 = n ? offs[0] : 0, nb = n ? offs[n] - b0 : 0;
+  std::vector<uint64_t> rebased;
+  if (b0) {
+    rebased.resize((size_t)n + 1);
+    for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
+    offs = rebased.data();
+  }
+  u64 status[6] = {0, 0, 0, 0, 0, 0};
+  DevGuard g;
+  void *d_edges = nullptr, *d_lengths = nullptr, *d_seqs = nullptr, *d_offs = nullptr, *d_so = nullptr, *d_lo = nullptr, *d_uf = nullptr,
+       *d_lay = nullptr, *d_us = nullptr, *d_status = nullptr, *d_work = nullptr;
+  if (n) {
+    HIP_TRY(hipSetDevice(device));
+    const u64 wb = unitig_work(n).bytes;
+    HIP_TRY(g.alloc(&d_edges, (size_t)n_edges * sizeof(sigax_edge)));
+    HIP_TRY(g.alloc(&d_lengths, (size_t)n * 4));
+    HIP_TRY(g.alloc(&d_seqs, (size_t)nb + 16));
+    HIP_TRY(g.alloc(&d_offs, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_so, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_lo, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_uf, (size_t)n * 4));
+    HIP_TRY(g.alloc(&d_lay, (size_t)n * sizeof(sigax_placement)));
+    if (useqs) HIP_TRY(g.alloc(&d_us, (size_t)nb + 16));
+    HIP_TRY(g.alloc(&d_status, 48));
+    HIP_TRY(g.alloc(&d_work, (size_t)wb));
+    if (n_edges) HIP_TRY(hipMemcpy(d_edges, edges, (size_t)n_edges * sizeof(sigax_edge), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (nb) HIP_TRY(hipMemcpy(d_seqs, seqs + b0, (size_t)nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    const int rc = sigax_unitigs_device(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, d_so, d_lo, d_uf,
+                                        (sigax_placement*)d_lay, d_us, d_status, d_work, wb, nullptr);
+    if (rc != SIGAX_OK) return rc;
+    HIP_TRY(hipMemcpy(status, d_status, 48, hipMemcpyDeviceToHost));  // (waits for the null stream's kernels)
+    if (status[0] > n || status[1] > nb) return sigax_fail(SIGAX_E_DEVICE, "unitig counts beyond their buffers");
+  }
+  const u64 nu = status[0], bases = status[1];
+  uint64_t* h_so = (uint64_t*)malloc(((size_t)nu + 1) * 8);
+  uint64_t* h_lo = (uint64_t*)malloc(((size_t)nu + 1) * 8);
+  uint32_t* h_uf = (uint32_t*)malloc(nu ? (size_t)nu * 4 : 4);
+  sigax_placement* h_lay = (sigax_placement*)malloc(n ? (size_t)n * sizeof(sigax_placement) : sizeof(sigax_placement));
+  char* h_us = useqs ? (char*)malloc(bases ? (size_t)bases : 1) : nullptr;
+  auto drop = [&] {
+    free(h_so);
+    free(h_lo);
+    free(h_uf);
+    free(h_lay);
+    free(h_us);
+  };
+  if (!h_so || !h_lo || !h_uf || !h_lay || (useqs && !h_us)) {
+    drop();
+    return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
+  }
+  h_so[0] = 0;
+  h_lo[0] = 0;
+  hipError_t e = hipSuccess;
+  if (n) {
+    e = hipMemcpy(h_so, d_so, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_lo, d_lo, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nu) e = hipMemcpy(h_uf, d_uf, (size_t)nu * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_lay, d_lay, (size_t)n * sizeof(sigax_placement), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && useqs && bases) e = hipMemcpy(h_us, d_us, (size_t)bases, hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) {
+    drop();
+    return sigax_fail(SIGAX_E_DEVICE, "copying the unitigs: %s", hipGetErrorString(e));
+  }
+  for (int k = 0; k < 6; ++k) t_last_status[k] = status[k];
+  *n_unitigs = nu;
+  *seq_offs = h_so;
+  *lay_offs = h_lo;
+  *uflags = h_uf;
+  *layout = h_lay;
+  if (useqs) *useqs = h_us;
+  return SIGAX_OK;
+}

@@ -1,0 +1,382 @@
+// siga_amd/csrc/sigax_unitig.hip -- `siga unitig` on the device (gfx950 / CDNA4, wave64): every unbranched chain of overlaps
+// compacted into one sequence, the fixpoint of the reference's Bigraph::simplify (src/bigraph.cpp:341-414, Vertex::merge at
+// :131-202) over the edge records of an overlap run.  The rules are in include/sigax.h and DESIGN.md 9d; the restatement the
+// tests hold this against is tests/unitig_cases.py::expected.
+//
+// A read has two ends, B = 0 (prefix) and E = 1 (suffix); state 2r + e = "read r, left through end e".
+//   k_uni_degree  one lane per record: the kept ones add to deg[2r + e] of the ends they touch (atomics), the ignored ones
+//                 are counted
+//   k_uni_links   one lane per record: a simple record writes link[end] = {the end it touches on the other read, len} at both
+//                 its ends.  An end of degree 1 is touched by one kept record, so no two lanes write one entry.
+//   k_uni_init / k_uni_jump   list ranking by pointer jumping over the 2 n states, ping-pong buffers, `rounds` =
+//                 ceil(log2 n) + 1 launches the host counts: a state carries {state reached, hops, smallest read id on the way,
+//                 bases on the way}.  A state that still has a successor after the last round lies on a cycle, and has
+//                 then been round it at least once: its smallest id is the cycle's.
+//   k_uni_cut     the lane of that read's state (m, B) takes the link into m's B end out, at both its ends, and notes the
+//                 overlap it closed; ranking runs once more (its launches leave at once when no cycle was cut)
+//   k_uni_heads   one lane per read: which of its two directions leads to the head of its unitig (the terminal with the
+//                 smaller id), and for a head the unitig's reads and bases; launch_scan turns these into unitig numbers,
+//                 layout offsets and sequence offsets
+//   k_uni_place   one lane per read: its placement record (one 16-byte store), for a head the unitig's table entries, and
+//                 where the bases it contributes go
+//   k_uni_bases   the bytes.  The stretches the placements contribute lie back to back in the output, in layout order, and
+//                 most are short (27 bases on average at BASELINE configs[1]): a wave takes 64 consecutive placements,
+//                 keeps their {destination, source, direction} in LDS, and its lanes take consecutive 16-byte pieces of the
+//                 destination range the 64 cover.  A piece that lies in one stretch is one 16-byte load (ascending, or
+//                 descending and complemented for a reverse placement) and one 16-byte store; a piece over several
+//                 stretches is gathered byte by byte; the range's unaligned head and tail are byte stores.
+// No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
+// consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
+// beyond the 64 descriptors, no MFMA.
+#include <hip/hip_runtime.h>
+
+#include "sigax_kernels.h"
+
+namespace {
+typedef unsigned long long u64;
+typedef uint32_t u32;
+
+constexpr u32 NIL = 0xFFFFFFFFu;
+
+// ---- phase 1, 2: records ----
+// what a record is: 0 malformed, 1 below min_overlap, 2 kept; for a kept one the two ends it touches and its kind
+struct RecClass {
+  u32 kind, sq, st;  // states 2q + end, 2t + end
+  bool contain, self;
+};
+__device__ __forceinline__ RecClass classify(const uint4 rec, const UnitigArgs& A) {
+  RecClass c;
+  c.kind = 0;
+  c.sq = c.st = 0;
+  c.contain = c.self = false;
+  const u32 q = rec.x, t = rec.y, len = rec.z, af = rec.w;
+  if ((u64)q >= A.n_reads || (u64)t >= A.n_reads) return c;
+  if (af > 7u || ((af >> 2) & 1u) != ((af ^ (af >> 1)) & 1u)) return c;
+  const u32 lq = A.lengths[q], lt = A.lengths[t];
+  if (len == 0u || len > (lq < lt ? lq : lt)) return c;
+  if (len < A.min_overlap) {
+    c.kind = 1;
+    return c;
+  }
+  c.kind = 2;
+  c.sq = 2u * q + ((af & 1u) ? 0u : 1u);
+  c.st = 2u * t + ((af & 2u) ? 1u : 0u);
+  c.contain = len == lq || len == lt;
+  c.self = q == t;
+  return c;
+}
+
+__device__ __forceinline__ u64 wave_total(u64 v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_uni_degree(UnitigArgs A) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 bad = 0, low = 0;
+  if (i < A.n_edges) {
+    const RecClass c = classify(reinterpret_cast<const uint4*>(A.edges)[i], A);
+    bad = c.kind == 0u;
+    low = c.kind == 1u;
+    if (c.kind == 2u) {
+      if (c.contain) {  // both directions (src/bigraph.cpp:497-522): every end of both reads
+        atomicAdd(&A.deg[c.sq & ~1u], 1u);
+        atomicAdd(&A.deg[c.sq | 1u], 1u);
+        atomicAdd(&A.deg[c.st & ~1u], 1u);
+        atomicAdd(&A.deg[c.st | 1u], 1u);
+      } else {
+        atomicAdd(&A.deg[c.sq], 1u);
+        atomicAdd(&A.deg[c.st], 1u);
+      }
+    }
+  }
+  const u64 tb = wave_total(bad), tl = wave_total(low);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (tb) atomicAdd(&A.counts[UNI_C_BAD], tb);
+    if (tl) atomicAdd(&A.counts[UNI_C_LOW], tl);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_uni_links(UnitigArgs A) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 simple = 0;
+  if (i < A.n_edges) {
+    const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
+    const RecClass c = classify(rec, A);
+    if (c.kind == 2u && !c.contain && !c.self && A.deg[c.sq] == 1u && A.deg[c.st] == 1u) {
+      A.link[c.sq] = make_uint2(c.st, rec.z);
+      A.link[c.st] = make_uint2(c.sq, rec.z);
+      simple = 1;
+    }
+  }
+  const u64 ts = wave_total(simple);
+  if ((threadIdx.x & 63u) == 0u && ts) atomicAdd(&A.counts[UNI_C_SIMPLE], ts);
+}
+
+// ---- phase 3, 4: list ranking ----
+// rk[s] = {successor or NIL, state reached so far, hops so far, smallest read id so far}; dist[s] = bases so far: a hop
+// into read y over an overlap of len adds L[y] - len.  second: the ranking after the cut, which has nothing to do when
+// nothing was cut.
+__global__ __launch_bounds__(256) void k_uni_init(UnitigArgs A, uint4* __restrict__ rk, u64* __restrict__ dist, int second) {
+  if (second && A.counts[UNI_C_CYCLES] == 0ull) return;
+  const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (s >= 2 * A.n_reads) return;
+  const uint2 lk = A.link[s];
+  const u32 r = (u32)(s >> 1);
+  if (lk.x == NIL || (u64)lk.x >= 2 * A.n_reads) {
+    rk[s] = make_uint4(NIL, (u32)s, 0u, r);
+    dist[s] = 0;
+  } else {
+    const u32 y = lk.x >> 1, nx = lk.x ^ 1u;
+    rk[s] = make_uint4(nx, nx, 1u, r < y ? r : y);
+    dist[s] = (u64)A.lengths[y] - lk.y;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_uni_jump(UnitigArgs A, const uint4* __restrict__ in, const u64* __restrict__ din,
+                                                  uint4* __restrict__ out, u64* __restrict__ dout, int second) {
+  if (second && A.counts[UNI_C_CYCLES] == 0ull) return;
+  const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (s >= 2 * A.n_reads) return;
+  uint4 a = in[s];
+  u64 d = din[s];
+  if (a.x != NIL) {
+    const uint4 b = in[a.x];
+    d += din[a.x];
+    a = make_uint4(b.x, b.y, a.z + b.z, a.w < b.w ? a.w : b.w);
+  }
+  out[s] = a;
+  dout[s] = d;
+}
+
+__global__ __launch_bounds__(256) void k_uni_cut(UnitigArgs A, const uint4* __restrict__ rk) {
+  const u64 m = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 cut = 0;
+  if (m < A.n_reads) {
+    const uint4 a = rk[2 * m];
+    if (a.x != NIL && a.w == (u32)m) {  // on a cycle, and its smallest read: the one lane of the cycle that acts
+      const uint2 lk = A.link[2 * m];
+      if (lk.x != NIL && (u64)lk.x < 2 * A.n_reads) {
+        A.link[2 * m] = make_uint2(NIL, 0u);
+        A.link[lk.x] = make_uint2(NIL, 0u);
+        A.closing[m] = SIGAX_UNITIG_CIRCULAR | (lk.y << 1);
+        cut = 1;
+      }
+    }
+  }
+  const u64 tc = wave_total(cut);
+  if ((threadIdx.x & 63u) == 0u && tc) atomicAdd(&A.counts[UNI_C_CYCLES], tc);
+}
+
+// ---- phase 5: heads ----
+// the direction of read r that leads to its unitig's head: the terminal with the smaller id (a read on its own: B, so that
+// it is entered through B and placed forward)
+__device__ __forceinline__ u32 head_dir(const uint4 a0, const uint4 a1) { return (a0.y >> 1) <= (a1.y >> 1) ? 0u : 1u; }
+
+__global__ __launch_bounds__(256) void k_uni_heads(UnitigArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (r >= A.n_reads) return;
+  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+  const u32 d = head_dir(a0, a1);
+  const uint4 to = d ? a1 : a0, away = d ? a0 : a1;
+  u32 one = 0, reads = 0;
+  u64 bases = 0;
+  if (to.z == 0u && to.x == NIL) {  // nothing between r and the head: r is it
+    one = 1;
+    reads = away.z + 1u;
+    bases = (u64)A.lengths[r] + dist[2 * r + (d ^ 1u)];
+  }
+  A.cnt[r] = one;
+  A.cnt[A.n_reads + 1 + r] = reads;
+  A.cnt[2 * (A.n_reads + 1) + r] = (u32)bases;
+  A.cnt[3 * (A.n_reads + 1) + r] = (u32)(bases >> 32);
+}
+
+// ---- phase 6: placements ----
+__global__ __launch_bounds__(256) void k_uni_place(UnitigArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  if (r >= n) return;
+  const u64 *unum = A.scan, *layr = A.scan + (n + 1), *lo = A.scan + 2 * (n + 1), *hi = A.scan + 3 * (n + 1);
+  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+  const u32 d = head_dir(a0, a1);
+  const uint4 to = d ? a1 : a0;
+  const u64 h = to.y >> 1;  // the head
+  if (h >= n) return;
+  const u64 off = dist[2 * r + d], slot = layr[h] + to.z, seq0 = lo[h] + (hi[h] << 32);
+  if (slot < n) {
+    // entered through the end it is left through on the way to the head: through B = forward
+    reinterpret_cast<uint4*>(A.layout)[slot] = make_uint4((u32)r, d ? SIGAX_PLACED_REV : 0u, (u32)off, (u32)(off >> 32));
+    // the bases r adds: its last L - len, len = the overlap with the read before it
+    const uint2 lk = A.link[2 * r + d];
+    const u64 skip = lk.x == NIL ? 0ull : (u64)lk.y, L = A.lengths[r], b0 = A.offs[r];
+    A.dst[slot] = seq0 + off + skip;
+    A.src[slot] = (d ? b0 + L - 1ull - skip : b0 + skip) | ((u64)d << 63);
+  }
+  if (to.z == 0u && to.x == NIL) {  // the head writes its unitig's entries
+    const u64 u = unum[r];
+    if (u < n) {
+      A.seq_offs[u] = seq0;
+      A.lay_offs[u] = layr[r];
+      A.uflags[u] = A.closing[r];
+    }
+  }
+  if (r == 0) {
+    const u64 U = unum[n], bases = lo[n] + (hi[n] << 32);
+    if (U <= n) {
+      A.seq_offs[U] = bases;
+      A.lay_offs[U] = layr[n];
+    }
+    A.dst[n] = bases;
+    const u64 cyc = A.counts[UNI_C_CYCLES], simple = A.counts[UNI_C_SIMPLE];
+    A.status[0] = U;
+    A.status[1] = bases;
+    A.status[2] = A.counts[UNI_C_BAD];
+    A.status[3] = A.counts[UNI_C_LOW];
+    A.status[4] = simple - (cyc < simple ? cyc : simple);  // a cycle's closing record is not merged
+    A.status[5] = cyc;
+  }
+}
+
+// ---- phase 7: bases ----
+__device__ __forceinline__ u32 comp_byte(u32 b) {
+  return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
+}
+
+struct BaseSh {
+  u64 dst[4][65];
+  u64 src[4][64];
+};
+
+__global__ __launch_bounds__(256) void k_uni_bases(UnitigArgs A) {
+  __shared__ BaseSh sh;
+  const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const u64 n = A.n_reads, first = ((u64)blockIdx.x * 4u + wave) * 64u;  // the wave's first placement
+  const bool live = first < n;
+  // bytes of reads: nothing beyond src_end is read, nothing beyond dst_cap written (sum of the unitigs <= sum of the reads)
+  const u64 src_end = A.offs[n], dst_cap = src_end - A.offs[0];
+  const u32 cnt = live ? (u32)(n - first < 64 ? n - first : 64) : 0u;
+  if (lane < cnt) {
+    sh.dst[wave][lane] = A.dst[first + lane];
+    sh.src[wave][lane] = A.src[first + lane];
+  }
+  if (live && lane == 0) sh.dst[wave][cnt] = A.dst[first + cnt];
+  __syncthreads();
+  if (!live) return;
+  const u64* D = sh.dst[wave];
+  const u64* S = sh.src[wave];
+  const u64 lo = D[0];
+  u64 hi = D[cnt];
+  if (hi > dst_cap) hi = dst_cap;
+  if (lo >= hi) return;
+  unsigned char* out = A.useqs;
+  // the source byte of destination byte p, p in stretch k
+  auto fetch = [&](u64 p, u32 k) -> u32 {
+    const u64 s = S[k], rel = p - D[k];
+    const bool rev = (s >> 63) != 0ull;
+    const u64 at = rev ? (s & ~(1ull << 63)) - rel : s + rel;
+    if (at >= src_end) return 'N';  // (no consistent input comes here)
+    const u32 b = A.seqs[at];
+    return rev ? comp_byte(b) : b;
+  };
+  // stretch of destination byte p: the last k with D[k] <= p (D ascends over a wave's stretches)
+  auto find = [&](u64 p) -> u32 {
+    u32 a = 0, b = cnt;
+    while (b - a > 1u) {  // at most 6 steps
+      const u32 m = (a + b) >> 1;
+      if (D[m] <= p) a = m;
+      else b = m;
+    }
+    return a;
+  };
+  // pieces of 16 bytes on the output's own 16-byte grid (the caller's buffer is 16-byte aligned: sigax.h)
+  const u64 p0 = lo & ~15ull, pieces = (hi - p0 + 15) >> 4;
+  for (u64 c = lane; c < pieces; c += 64) {
+    const u64 b = p0 + 16 * c;
+    if (b >= lo && b + 16 <= hi) {
+      u32 k = find(b);
+      uint4 v;
+      if (D[k + 1] >= b + 16) {  // one stretch: one 16-byte load
+        const u64 s = S[k], rel = b - D[k];
+        const bool rev = (s >> 63) != 0ull;
+        const u64 at = rev ? (s & ~(1ull << 63)) - rel : s + rel;  // first byte's source; a reverse stretch goes down from it
+        const u64 from = rev ? at - 15ull : at;
+        if (rev ? (at < 15ull || at >= src_end) : (at + 16 > src_end)) {
+          unsigned char t[16];
+          for (u32 j = 0; j < 16; ++j) t[j] = (unsigned char)fetch(b + j, k);
+          __builtin_memcpy(&v, t, 16);
+        } else {
+          uint4 w;
+          __builtin_memcpy(&w, A.seqs + from, 16);  // (no alignment promised: the compiler picks the access)
+          if (rev) {
+            // byte j of the piece = complement of byte 15 - j of the load
+            const u32 x[4] = {w.w, w.z, w.y, w.x};
+            u32 y[4];
+            for (u32 q = 0; q < 4; ++q) {
+              const u32 e = x[q];
+              y[q] = comp_byte(e >> 24) | (comp_byte((e >> 16) & 255u) << 8) | (comp_byte((e >> 8) & 255u) << 16) | (comp_byte(e & 255u) << 24);
+            }
+            v = make_uint4(y[0], y[1], y[2], y[3]);
+          } else {
+            v = w;
+          }
+        }
+      } else {
+        unsigned char t[16];
+        for (u32 j = 0; j < 16; ++j) {
+          const u64 p = b + j;
+          while (k + 1 < cnt && D[k + 1] <= p) ++k;  // (at most cnt steps over the piece)
+          t[j] = (unsigned char)fetch(p, k);
+        }
+        __builtin_memcpy(&v, t, 16);
+      }
+      *reinterpret_cast<uint4*>(out + b) = v;
+    } else {  // the range's head or tail: byte stores
+      const u64 from = b < lo ? lo : b, to = b + 16 < hi ? b + 16 : hi;
+      if (from < to) {
+        u32 k = find(from);
+        for (u64 p = from; p < to; ++p) {
+          while (k + 1 < cnt && D[k + 1] <= p) ++k;
+          out[p] = (unsigned char)fetch(p, k);
+        }
+      }
+    }
+  }
+}
+
+unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
+}  // namespace
+
+unsigned unitig_rounds(unsigned long long n_reads) {
+  unsigned r = 0;
+  while ((1ull << r) < n_reads) ++r;  // ceil(log2 n)
+  return r + 1;
+}
+
+void launch_unitigs(const UnitigArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads, ns = 2 * n;
+  if (n == 0) return;
+  if (a.n_edges) {
+    hipLaunchKernelGGL(k_uni_degree, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_uni_links, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+  }
+  const unsigned rounds = unitig_rounds(n);
+  uint4* rk[2] = {reinterpret_cast<uint4*>(a.rank[0]), reinterpret_cast<uint4*>(a.rank[1])};
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(k_uni_init, dim3(blocks_of(ns)), dim3(256), 0, st, a, rk[0], a.dist[0], pass);
+    for (unsigned r = 0; r < rounds; ++r)
+      hipLaunchKernelGGL(k_uni_jump, dim3(blocks_of(ns)), dim3(256), 0, st, a, (const uint4*)rk[r & 1], (const u64*)a.dist[r & 1], rk[(r & 1) ^ 1],
+                         a.dist[(r & 1) ^ 1], pass);
+    if (pass == 0) hipLaunchKernelGGL(k_uni_cut, dim3(blocks_of(n)), dim3(256), 0, st, a, (const uint4*)rk[rounds & 1]);
+  }
+  const uint4* fin = rk[rounds & 1];
+  const u64* fdist = a.dist[rounds & 1];
+  hipLaunchKernelGGL(k_uni_heads, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
+  for (int k = 0; k < 4; ++k) launch_scan(a.cnt + (u64)k * (n + 1), n, a.partial, a.scan + (u64)k * (n + 1), a.scan_total, st);
+  hipLaunchKernelGGL(k_uni_place, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
+  if (a.useqs) hipLaunchKernelGGL(k_uni_bases, dim3(blocks_of(n)), dim3(256), 0, st, a);
+}
+
+void launch_unitig_bases(const UnitigArgs& a, hipStream_t st) {
+  if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
+}

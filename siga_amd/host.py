@@ -40,6 +40,8 @@ def lib():
                                         C.c_uint64, C.c_char_p, C.c_uint64]
         L.sigah_locate_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                          C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
+        L.sigah_unitig_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                        C.c_uint64, C.c_char_p, C.c_uint64]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -131,6 +133,15 @@ def locate_files(paths, prefix, rc=True, max_hits=1000, max_len=None, device=0, 
     if lib().sigah_locate_files(arr, len(paths), prefix.encode(), int(max_hits), lim, int(rc), device, (out or "").encode(),
                                 batch_queries, err, 512) != 0:
         raise RuntimeError("siga locate failed: " + err.value.decode())
+
+
+def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreducible=True, rc=True, device=0, piece_reads=0):
+    """`siga unitig`: FMIndex::load + Unitigger::run; the FASTA goes to the file `out`, or to stdout, the placements to the file
+    `layout` when one is named.  piece_reads: reads per overlap call (0: 2^20); the result does not depend on it."""
+    err = C.create_string_buffer(512)
+    if lib().sigah_unitig_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device, (out or "").encode(),
+                               (layout or "").encode(), piece_reads, err, 512) != 0:
+        raise RuntimeError("siga unitig failed: " + err.value.decode())
 
 
 def preqc(prefix, k=31, samples=50000, seed=1, all_reads=False, max_count=1024, device=0, out=None, batch_rows=0):

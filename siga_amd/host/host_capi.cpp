@@ -237,6 +237,24 @@ int sigah_locate_files(const char* const* paths, uint64_t n_paths, const char* p
   return 0;
 }
 
+// `siga unitig`: FMIndex::load + Unitigger::run; fasta_path "" = stdout, layout_path "" = no layout file; piece_reads = reads per
+// overlap call (0: the default)
+int sigah_unitig_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                      const char* fasta_path, const char* layout_path, uint64_t piece_reads, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::load(prefix, fmi, device)) {
+    if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
+    return -1;
+  }
+  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  unitigger.setPieceReads((size_t)piece_reads);
+  if (!unitigger.run(fmi, reads_path, (size_t)min_overlap, fasta_path ? fasta_path : "", layout_path ? layout_path : "")) {
+    if (err && errcap) snprintf(err, errcap, "%s", unitigger.error().c_str());
+    return -1;
+  }
+  return 0;
+}
+
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty
 int sigah_preqc(const char* prefix, uint64_t k, uint64_t samples, uint64_t seed, int all, uint64_t max_count, int device,
                 const char* out_path, uint64_t batch_rows, char* err, uint64_t errcap) {

@@ -4,7 +4,7 @@
 // on the GPU), SuffixArray + BWT writers (src/suffix_array.cpp, src/bwt.cpp), OverlapBuilder
 // (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).  One source file per object: reads.cpp (readers),
 // strand_index.cpp (index builders and writers), overlap_builder.cpp (FMIndex, OverlapBuilder), correct_match.cpp
-// (CorrectProcessor, Matcher), locate.cpp (Locator), kmer_spectrum.cpp (KmerSpectrum), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
+// (CorrectProcessor, Matcher), locate.cpp (Locator), kmer_spectrum.cpp (KmerSpectrum), unitig.cpp (Unitigger), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
 // host_util.hpp are internal to the library.
 #ifndef SIGA_AMD_HOST_SIGA_HOST_HPP_
 #define SIGA_AMD_HOST_SIGA_HOST_HPP_
@@ -187,6 +187,32 @@ class Locator {
   uint32_t _maxHits, _maxLength;
   bool _rc;
   mutable std::string _error;
+};
+
+// `siga unitig`: the first step of the reference's `siga assemble`, Bigraph::simplify (src/bigraph.cpp:341-414), on the GPU: the
+// reads go through the overlap stages, their edge records stay records (no ASQG), and every unbranched chain of them becomes
+// one unitig (sigax_unitigs_host; the rules in include/sigax.h).  One GPU.
+class Unitigger {
+ public:
+  explicit Unitigger(bool irreducible = true, bool rc = true) : _irreducible(irreducible), _rc(rc), _unitigs(0), _bases(0), _merged(0), _cycles(0) {}
+  // One FASTA record per unitig, in the library's numbering, to `fasta` (empty: stdout): ">unitig-<n> KC:i:<reads>", the tag
+  // only when the unitig holds more than one read, " circular=<closing overlap>" behind it for a cycle, the bases on one line.
+  // `layout` not empty: one line "unitig-<n>\t<read name>\t<+|->\t<offset>" per placement to that file.
+  bool run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta = std::string(),
+           const std::string& layout = std::string(), size_t threads = 1);
+  // reads per overlap call (0: 2^20); the records do not depend on it
+  void setPieceReads(size_t n) { _piece = n; }
+  uint64_t unitigs() const { return _unitigs; }
+  uint64_t bases() const { return _bases; }
+  uint64_t merged() const { return _merged; }  // simple records merged
+  uint64_t cycles() const { return _cycles; }
+  const std::string& error() const { return _error; }
+
+ private:
+  bool _irreducible, _rc;
+  uint64_t _unitigs, _bases, _merged, _cycles;
+  size_t _piece = 0;
+  std::string _error;
 };
 
 // `siga preqc`: the k-mer count distribution of strings drawn from the index itself (KmerDistribution::sample,

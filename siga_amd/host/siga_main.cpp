@@ -1,4 +1,4 @@
-// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga locate` / `siga preqc` ... command line, option for option as the reference
+// siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga locate` / `siga preqc` / `siga unitig` ... command line, option for option as the reference
 // (src/main.cpp:17-83, src/indexer.cpp:119-156, src/overlap.cpp:66-105).  Exit codes follow the reference:
 // a runner returning -1 exits 255; printing help returns 256, i.e. exit status 0.
 #include <getopt.h>
@@ -76,13 +76,14 @@ static int apply_ini(int argc, char** argv, const option* longopts, std::vector<
 }
 
 static int usage() {
-  printf("siga [index|correct|overlap|rmdup|preqc|locate|match] [OPTION] ... READSFILE\n"
+  printf("siga [index|correct|overlap|rmdup|preqc|locate|unitig|match] [OPTION] ... READSFILE\n"
          "  index     build the FM-index (.sai/.bwt/.rsai/.rbwt) of READSFILE\n"
          "  overlap   compute pairwise overlaps between all the sequences in READSFILE (GPU)\n"
          "  rmdup     remove duplicated reads (GPU)\n"
          "  correct   k-mer based error correction (GPU)\n"
          "  match     count the occurrences of every read of READSFILE in the indexed reads (GPU)\n"
          "  locate    list where every sequence of QUERYFILE occurs in the indexed reads: read, offset, strand (GPU)\n"
+         "  unitig    overlap READSFILE and compact every unbranched chain of overlaps into one sequence (GPU)\n"
          "  preqc     pre-assembly quality checks: the k-mer count distribution of the indexed reads (GPU)\n"
          "common options: -s, --ini=FILE (options from FILE, the command line goes over them);\n"
          "                -c, --log4cxx=FILE is accepted and ignored (this build logs to stderr; SIGA_TIMING=1 prints phase\n"
@@ -511,6 +512,78 @@ static int run_locate(int argc, char** argv) {
   return 0;
 }
 
+static int unitig_help() {
+  printf("siga unitig [OPTION] ... READSFILE\n"
+         "Overlap the reads of READSFILE and write the unitigs: every unbranched chain of overlaps merged into one sequence\n"
+         "\n"
+         "      -h, --help                       display this help and exit\n"
+         "\n"
+         "      -m, --min-overlap=LEN            minimum overlap required between two reads (default: 45)\n"
+         "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
+         "      -o, --out=FILE                   write the unitigs to FILE (default: <prefix>.unitigs.fa)\n"
+         "          --layout=FILE                also write one line per read to FILE: unitig, read name, + or -, offset\n"
+         "      -x, --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges)\n"
+         "          --no-opposite-strand         treat all reads as forward strand\n"
+         "      -t, --threads=NUM                host threads that parse READSFILE (default: 1)\n"
+         "          --device=NUM                 GPU to use (default: 0)\n"
+         "\n"
+         "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
+         "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
+         "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
+         "\n");
+  return 256;
+}
+
+static int run_unitig(int argc, char** argv) {
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT };
+  static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
+                                    {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
+                                    {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, 'x'},
+                                    {"out", required_argument, nullptr, 'o'},         {"layout", required_argument, nullptr, OPT_LAYOUT},
+                                    {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
+                                    {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
+  std::string prefix, out, layout;
+  size_t threads = 1, minOverlap = 45;
+  bool exhaustive = false, norc = false, help = false;
+  int device = 0, c;
+  std::vector<std::string> ini_store;
+  std::vector<char*> ini_argv;
+  if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
+  argc = (int)ini_argv.size();
+  argv = ini_argv.data();
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:xh", longopts, nullptr)) != -1) {
+    switch (c) {
+      case 'p': prefix = optarg; break;
+      case 't': threads = strtoull(optarg, nullptr, 10); break;
+      case 'm': minOverlap = strtoull(optarg, nullptr, 10); break;
+      case 'o': out = optarg; break;
+      case 'x': exhaustive = true; break;
+      case OPT_LAYOUT: layout = optarg; break;
+      case OPT_NO_RC: norc = true; break;
+      case OPT_DEVICE: device = atoi(optarg); break;
+      case 'h': help = true; break;
+      default: break;
+    }
+  }
+  if (help || argc - optind != 1) return unitig_help();
+  std::string input = argv[optind];
+  if (prefix.empty()) prefix = sigah::Utils::stem(input);
+  if (out.empty()) out = prefix + ".unitigs.fa";
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::load(prefix, fmi, device)) {
+    fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+    return -1;
+  }
+  sigah::Unitigger unitigger(!exhaustive, !norc);
+  if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
+    fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
+    return -1;
+  }
+  fprintf(stderr, "%llu unitigs, %llu bases, %llu overlaps merged, %llu circular\n", (unsigned long long)unitigger.unitigs(),
+          (unsigned long long)unitigger.bases(), (unsigned long long)unitigger.merged(), (unsigned long long)unitigger.cycles());
+  return 0;
+}
+
 static int preqc_help() {
   // help text of src/preqc.cpp:209-222, plus the options of the k-mer distribution the reference computes no further than
   // GenomeEstimator::estimate's null index
@@ -608,6 +681,7 @@ int main(int argc, char** argv) {
   else if (cmd == "match") rc = run_match(argc - 1, argv + 1);
   else if (cmd == "locate") rc = run_locate(argc - 1, argv + 1);
   else if (cmd == "preqc") rc = run_preqc(argc - 1, argv + 1);
+  else if (cmd == "unitig") rc = run_unitig(argc - 1, argv + 1);
   else return usage();
   if (getenv("SIGA_TIMING"))
     fprintf(stderr, "[siga] %-28s %8.3f s\n", "main() total", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

@@ -1,0 +1,135 @@
+// siga_amd/host/unitig.cpp -- Unitigger (`siga unitig`): the reads through the overlap stages, their edge records compacted into unitigs.
+#include <cstdio>
+
+#include "asqg_text.hpp"
+#include "host_util.hpp"
+#include "reads.hpp"
+#include "siga_host.hpp"
+
+namespace sigah {
+
+namespace {
+// what sigax_unitigs_host gave back; the arrays are the library's (sigax_free)
+struct Unitigs {
+  uint64_t n = 0;
+  uint64_t *seq_offs = nullptr, *lay_offs = nullptr;
+  uint32_t* uflags = nullptr;
+  sigax_placement* layout = nullptr;
+  char* useqs = nullptr;
+  Unitigs() = default;
+  Unitigs(const Unitigs&) = delete;
+  Unitigs& operator=(const Unitigs&) = delete;
+  ~Unitigs() {
+    sigax_free(seq_offs);
+    sigax_free(lay_offs);
+    sigax_free(uflags);
+    sigax_free(layout);
+    sigax_free(useqs);
+  }
+};
+
+bool write_all(FILE* f, const std::string& t) { return t.empty() || fwrite(t.data(), 1, t.size(), f) == t.size(); }
+}  // namespace
+
+// The reads go through OverlapBuilder's device stages (sigax_overlap_batch: finder, filter, extractor, edge records) a piece
+// at a time under their ids in the file; no VT or ED line is formatted.  The collected records and the reads then make one
+// sigax_unitigs_host call.
+bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta, const std::string& layout,
+                    size_t threads) {
+  _error.clear();
+  _unitigs = _bases = _merged = _cycles = 0;
+  auto fail = [&](const std::string& e) { return _error = e, false; };
+  if (!index.handle()) return fail("FMIndex not loaded");
+  const HostSettings hs;
+  const unsigned nt = host_threads(threads, hs);
+  ReadStore reads;
+  if (!LoadReads(input, &reads, nt, hs)) return fail("Failed to read file " + input);
+  const size_t n = reads.size();
+  std::vector<uint32_t> lengths, ranks;
+  name_ranks(reads, nt, &lengths, &ranks);
+  if (n > 0 && sigax_index_set_reads(index.handle(), lengths.data(), ranks.data(), n) != SIGAX_OK)
+    return fail(std::string("failed to load suffix array index: ") + sigax_last_error());
+  sigax_index_info inf;
+  if (sigax_index_info_get(index.handle(), &inf) != SIGAX_OK) return fail(sigax_last_error());
+  const uint32_t flags = SIGAX_EDGES | (_irreducible ? SIGAX_IRREDUCIBLE : 0u) | (_rc ? SIGAX_RC : 0u);
+  std::vector<sigax_edge> edges;
+  std::vector<uint64_t> offs;
+  const size_t per = _piece ? _piece : (size_t)1 << 20;
+  for (size_t base = 0; base < n; base += per) {
+    const size_t cnt = std::min(per, n - base);
+    offs.resize(cnt + 1);
+    for (size_t i = 0; i <= cnt; ++i) offs[i] = reads.offs[base + i] - reads.offs[base];
+    sigax_result res;
+    if (sigax_overlap_batch(index.handle(), reads.seqs.data() + reads.offs[base], offs.data(), (uint32_t)cnt, (uint32_t)base, (uint32_t)minOverlap,
+                            flags, &res) != SIGAX_OK)
+      return fail(std::string("overlap failed: ") + sigax_last_error());
+    edges.insert(edges.end(), res.edges, res.edges + res.n_edges);
+    sigax_result_free(&res);
+  }
+  Unitigs u;
+  if (sigax_unitigs_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap, &u.n,
+                         &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs) != SIGAX_OK)
+    return fail(std::string("unitig failed: ") + sigax_last_error());
+  uint64_t status[6];
+  sigax_unitigs_last_status(status);
+  _unitigs = status[0];
+  _bases = status[1];
+  _merged = status[4];
+  _cycles = status[5];
+  // ">unitig-<n>[ KC:i:<reads>][ circular=<closing overlap>]": the coverage tag only above 1, as FastaVisitor writes it
+  // (src/bigraph_visitors.cpp:248-257)
+  FILE* out = fasta.empty() ? stdout : fopen(fasta.c_str(), "wb");
+  if (!out) return fail("Failed to create " + fasta);
+  std::string t;
+  bool ok = true;
+  for (uint64_t k = 0; k < u.n && ok; ++k) {
+    const uint64_t cnt = u.lay_offs[k + 1] - u.lay_offs[k];
+    t += ">unitig-";
+    append_u64(t, k);
+    if (cnt > 1) {
+      t += " KC:i:";
+      append_u64(t, cnt);
+    }
+    if (u.uflags[k] & SIGAX_UNITIG_CIRCULAR) {
+      t += " circular=";
+      append_u64(t, u.uflags[k] >> 1);
+    }
+    t += '\n';
+    t.append(u.useqs + u.seq_offs[k], u.seq_offs[k + 1] - u.seq_offs[k]);
+    t += '\n';
+    if (t.size() >= ((size_t)1 << 20) || k + 1 == u.n) {
+      ok = write_all(out, t);
+      t.clear();
+    }
+  }
+  if (fflush(out) != 0) ok = false;
+  if (out != stdout) fclose(out);
+  if (!ok) return fail("Failed to write " + (fasta.empty() ? std::string("stdout") : fasta));
+  if (layout.empty()) return true;
+  // "unitig-<n>\t<read name>\t<+|->\t<offset>", placements in layout order
+  FILE* lf = fopen(layout.c_str(), "wb");
+  if (!lf) return fail("Failed to create " + layout);
+  t.clear();
+  for (uint64_t k = 0; k < u.n && ok; ++k) {
+    for (uint64_t p = u.lay_offs[k]; p < u.lay_offs[k + 1]; ++p) {
+      const sigax_placement& pl = u.layout[p];
+      const std::string_view name = reads.name(pl.read);
+      t += "unitig-";
+      append_u64(t, k);
+      t += '\t';
+      t.append(name.data(), name.size());
+      t += (pl.flags & SIGAX_PLACED_REV) ? "\t-\t" : "\t+\t";
+      append_u64(t, pl.offset);
+      t += '\n';
+    }
+    if (t.size() >= ((size_t)1 << 20) || k + 1 == u.n) {
+      ok = write_all(lf, t);
+      t.clear();
+    }
+  }
+  if (fclose(lf) != 0) ok = false;
+  if (!ok) return fail("Failed to write " + layout);
+  return true;
+}
+
+}  // namespace sigah

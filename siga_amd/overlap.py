@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BLOCK_DTYPE, EDGE_DTYPE, HIT_DTYPE, SIGAX_DUPLICATE, SIGAX_EDGES, SIGAX_IRREDUCIBLE, SIGAX_RC
+from ._lib import BLOCK_DTYPE, EDGE_DTYPE, HIT_DTYPE, PLACEMENT_DTYPE, SIGAX_DUPLICATE, SIGAX_EDGES, SIGAX_IRREDUCIBLE, SIGAX_RC
 
 
 class SigaxError(RuntimeError):
@@ -101,6 +101,43 @@ def _copy_records(ptr, n, dtype):
     out = np.empty(n, dtype=dtype)
     if n:
         C.memmove(out.ctypes.data, ptr, n * dtype.itemsize)
+    return out
+
+
+def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
+    """Unbranched chains of overlaps compacted (sigax_unitigs_host, the rules in include/sigax.h): `edges` EDGE_DTYPE records
+    of an overlap run, reads as lengths u32[n], bases `seqs` (bytes or uint8 array) and offs u64[n+1] by read id -> dict(
+    seq_offs u64[U+1], lay_offs u64[U+1], uflags u32[U], layout PLACEMENT_DTYPE[n], useqs uint8 array (None with
+    bases=False), status u64[6]).  Unitig u is useqs[seq_offs[u]:seq_offs[u+1]], its reads layout[lay_offs[u]:lay_offs[u+1]];
+    uflags & SIGAX_UNITIG_CIRCULAR marks a cycle, uflags >> 1 is its closing overlap.  status = {unitigs, unitig bases,
+    records ignored as malformed, records below min_overlap, simple records merged, cycles}.  Needs no index."""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(lengths)
+    if len(offs) != n + 1:
+        raise ValueError("offs must have len(lengths) + 1 entries")
+    if isinstance(seqs, np.ndarray):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+    else:
+        buf = bytes(seqs)
+    L = _lib.lib()
+    nu = C.c_uint64()
+    so, lo, uf, lay, us = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(L.sigax_unitigs_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+                                offs.ctypes.data, n, int(min_overlap), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf), C.byref(lay),
+                                C.byref(us) if bases else None), "sigax_unitigs_host")
+    try:
+        u = int(nu.value)
+        status = np.zeros(6, dtype=np.uint64)
+        _check(L.sigax_unitigs_last_status(status.ctypes.data), "sigax_unitigs_last_status")
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "layout": _copy_records(lay, n, PLACEMENT_DTYPE), "status": status}
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+    finally:
+        for p in (so, lo, uf, lay, us):
+            L.sigax_free(p)
     return out
 
 
