@@ -44,6 +44,23 @@ struct DevGuard {
   }
 };
 
+// owns the host arrays a call hands to its caller (who returns them with sigax_free) until the call has succeeded
+struct HostGuard {
+  std::vector<void*> ptrs;
+  bool ok = true;
+  ~HostGuard() {
+    for (void* p : ptrs) free(p);
+  }
+  template <typename T>
+  T* alloc(size_t bytes) {
+    void* p = malloc(bytes ? bytes : 1);
+    ok = ok && p != nullptr;
+    ptrs.push_back(p);
+    return (T*)p;
+  }
+  void release() { ptrs.clear(); }
+};
+
 // Measurement aid of tools/unitig_bench.py, exported but not part of include/sigax.h and not stable: the bases pass of
 // sigax_unitigs_device alone, over the scratch a call with the same reads and records left in d_work.  It cannot tell whether
 // such a call was made; the pass bounds every access all the same.  Same argument checks as sigax_unitigs_device.
@@ -188,6 +205,43 @@ struct sigax_index {
   bool split_strands;  // two-step tables too large to gather from both at once: one finder launch per strand
   bool fwd_only;       // opened without the reverse strand (what `siga correct` needs: src/correct.cpp loads <prefix>.bwt alone)
 };
+
+// The corrector's prefix table for a launch on `st`, if a correction call has built it (none is ever allocated for a match,
+// spectrum or locate call): *ptab = NULL, *pk = 0 without one.  Its build may still be running on that call's stream, so `st`
+// waits for it.
+inline int ptab_for_stream(sigax_index* ix, hipStream_t st, const void** ptab, uint32_t* pk) {
+  *ptab = nullptr;
+  *pk = 0;
+  std::lock_guard<std::mutex> lock(*ix->enqueue_mu);
+  if (ix->d_ptab && ix->ptab_k) {
+    if (ix->ptab_ev) HIP_TRY(hipStreamWaitEvent(st, ix->ptab_ev, 0));
+    *ptab = ix->d_ptab;
+    *pk = ix->ptab_k;
+  }
+  return SIGAX_OK;
+}
+
+// The strings of a _batch call (n >= 1 of them, `noun` each in the error text) to the device on `st`: offsets checked -- none
+// descending, no item longer than max_item -- then *d_seqs (the bytes, 16 of slack behind them) and *d_offs allocated in `g`
+// and copied.  offs[0] need not be 0 (a window of a longer table): the device gets the window's bytes and offsets from 0.
+inline int stage_strings(DevGuard& g, const char* seqs, const uint64_t* offs, u64 n, u64 max_item, const char* noun, hipStream_t st,
+                         unsigned char** d_seqs, u64** d_offs) {
+  for (u64 i = 0; i < n; ++i)
+    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] > max_item) return sigax_fail(SIGAX_E_ARG, "%s %llu: bad offsets", noun, i);
+  const u64 b0 = offs[0], nb = offs[n] - b0;
+  std::vector<uint64_t> rebased;
+  if (b0) {
+    rebased.resize((size_t)n + 1);
+    for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
+    offs = rebased.data();
+  }
+  HIP_TRY(g.alloc((void**)d_seqs, nb + 16));
+  HIP_TRY(g.alloc((void**)d_offs, ((size_t)n + 1) * 8));
+  HIP_TRY(hipMemcpyAsync(*d_seqs, seqs + b0, nb, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(*d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+  if (b0) HIP_TRY(hipStreamSynchronize(st));  // `rebased` is about to go
+  return SIGAX_OK;
+}
 
 // ---- sigax_tables.cpp: row tables, direct maps, stretch texts, deep start tables ----
 struct RowTabGeom {

@@ -42,7 +42,7 @@ LocateArgs locate_args(sigax_index* ix, const unsigned char* d_seqs, const u64* 
   la.offs = d_offs;
   la.n_queries = n;
   la.rc = (flags & SIGAX_RC) ? 1u : 0u;
-  la.pk = 0;
+  la.pk = 0;  // (locate_search_enqueue looks for the table)
   la.ptab = nullptr;
   la.max_hits = max_hits;
   la.max_len = max_len;
@@ -68,16 +68,8 @@ int locate_search_enqueue(sigax_index* ix, LocateArgs& la, u64* d_hit_offs, void
   HIP_TRY(hipMemsetAsync(la.status, 0, 32, st));
   HIP_TRY(hipMemsetAsync(la.chains, 0, (size_t)la.n_queries * 32, st));
   HIP_TRY(hipMemsetAsync(la.counters, 0, 16, st));
-  {
-    // the corrector's prefix table, if a correction call has built it: never allocated here.  Its build may still be
-    // running on that call's stream.
-    std::lock_guard<std::mutex> lock(*ix->enqueue_mu);
-    if (ix->d_ptab && ix->ptab_k) {
-      if (ix->ptab_ev) HIP_TRY(hipStreamWaitEvent(st, ix->ptab_ev, 0));
-      la.ptab = ix->d_ptab;
-      la.pk = ix->ptab_k;
-    }
-  }
+  const int rp = ptab_for_stream(ix, st, &la.ptab, &la.pk);
+  if (rp != SIGAX_OK) return rp;
   launch_locate_search(la, ix->wide, ix->n_cu, st);
   launch_locate_finish(la, st);
   launch_scan(la.cnt, la.n_queries, (u64*)(base + w.partial), d_hit_offs, la.status, st);  // status[0] = hit_offs[n]
@@ -140,16 +132,7 @@ extern "C" int sigax_locate_batch(sigax_index* ix, const char* seqs, const uint6
   const int ru = locate_usable(ix);
   if (ru != SIGAX_OK) return ru;
   HIP_TRY(hipSetDevice(ix->device));
-  for (u64 i = 0; i < n_queries; ++i)
-    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] > 0xFFFFFFFFull) return sigax_fail(SIGAX_E_ARG, "query %llu: bad offsets", i);
-  // offs[0] need not be 0 (a window of a longer table): the device gets the window's bytes and offsets from 0
-  const u64 n = n_queries, b0 = n ? offs[0] : 0, nb = n ? offs[n] - b0 : 0;
-  std::vector<uint64_t> rebased;
-  if (b0) {
-    rebased.resize((size_t)n + 1);
-    for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
-    offs = rebased.data();
-  }
+  const u64 n = n_queries;
   u64 n_hits = 0;
   DevGuard g;
   unsigned char* d_seqs = nullptr;
@@ -167,17 +150,15 @@ extern "C" int sigax_locate_batch(sigax_index* ix, const char* seqs, const uint6
   } sg{&st};
   if (n) {
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIP_TRY(g.alloc((void**)&d_seqs, nb + 16));
-    HIP_TRY(g.alloc((void**)&d_offs, ((size_t)n + 1) * 8));
+    int rc = stage_strings(g, seqs, offs, n, 0xFFFFFFFFull, "query", st, &d_seqs, &d_offs);
+    if (rc != SIGAX_OK) return rc;
     HIP_TRY(g.alloc((void**)&d_totals, (size_t)n * 8));
     HIP_TRY(g.alloc((void**)&d_qflags, (size_t)n * 4));
     HIP_TRY(g.alloc((void**)&d_hit_offs, ((size_t)n + 1) * 8));
     HIP_TRY(g.alloc((void**)&d_status, 32));
     HIP_TRY(g.alloc(&d_work, (size_t)locate_work(n).bytes));
-    HIP_TRY(hipMemcpyAsync(d_seqs, seqs + b0, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     LocateArgs la = locate_args(ix, d_seqs, d_offs, n, flags, max_hits, max_len, d_totals, d_qflags, d_hit_offs, d_status, d_work);
-    int rc = locate_search_enqueue(ix, la, d_hit_offs, d_work, st);
+    rc = locate_search_enqueue(ix, la, d_hit_offs, d_work, st);
     if (rc != SIGAX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(&n_hits, d_status, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -188,20 +169,12 @@ extern "C" int sigax_locate_batch(sigax_index* ix, const char* seqs, const uint6
       if (rc != SIGAX_OK) return rc;
     }
   }
-  uint64_t* h_totals = (uint64_t*)malloc(n ? (size_t)n * 8 : 8);
-  uint32_t* h_qflags = (uint32_t*)malloc(n ? (size_t)n * 4 : 4);
-  uint64_t* h_offs = (uint64_t*)malloc(((size_t)n + 1) * 8);
-  sigax_hit* h_hits = (sigax_hit*)malloc(n_hits ? (size_t)n_hits * sizeof(sigax_hit) : sizeof(sigax_hit));
-  auto drop = [&] {
-    free(h_totals);
-    free(h_qflags);
-    free(h_offs);
-    free(h_hits);
-  };
-  if (!h_totals || !h_qflags || !h_offs || !h_hits) {
-    drop();
-    return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
-  }
+  HostGuard hg;
+  uint64_t* h_totals = hg.alloc<uint64_t>((size_t)n * 8);
+  uint32_t* h_qflags = hg.alloc<uint32_t>((size_t)n * 4);
+  uint64_t* h_offs = hg.alloc<uint64_t>(((size_t)n + 1) * 8);
+  sigax_hit* h_hits = hg.alloc<sigax_hit>((size_t)n_hits * sizeof(sigax_hit));
+  if (!hg.ok) return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
   h_offs[0] = 0;
   hipError_t e = hipSuccess;
   if (n) {
@@ -211,10 +184,8 @@ extern "C" int sigax_locate_batch(sigax_index* ix, const char* seqs, const uint6
     if (e == hipSuccess && n_hits) e = hipMemcpyAsync(h_hits, d_hits, (size_t)n_hits * sizeof(sigax_hit), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
-  if (e != hipSuccess) {
-    drop();
-    return sigax_fail(SIGAX_E_DEVICE, "copying the hits: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return sigax_fail(SIGAX_E_DEVICE, "copying the hits: %s", hipGetErrorString(e));
+  hg.release();
   *totals = h_totals;
   *qflags = h_qflags;
   *hit_offs = h_offs;

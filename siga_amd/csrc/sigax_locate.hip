@@ -11,10 +11,11 @@
 //                    offset in its read, Occ('$') before that row indexes the .sai table, whose entry is the read
 //
 // Shape of the search: k_match's.  Chains die at very different depths, so lanes are not tied to chains: persistent grid, a
-// wave reserves LOC_GRAB chain numbers at a time from one global counter, a lane whose chain ended takes the wave's next one
+// wave reserves GRAB chain numbers at a time from one global counter, a lane whose chain ended takes the wave's next one
 // in the same loop iteration.  The pattern's bytes are read in place.  Two symbols per pair of gathers where the two-step
 // lines exist, one-step granules otherwise, a start from the corrector's table of 13-mer intervals when it is resident and
-// the chain has that many ACGT symbols: the intervals are the same whichever tables exist.
+// the chain has that many ACGT symbols: the intervals are the same whichever tables exist.  The step, the start, the
+// constants and the reservation are sigax_rank.h's, the ones k_match and k_spectrum run.
 //
 // Shape of the walk.  One lane per hit slot, plain launch: the lane finds its (query, strand, row) by binary search in
 // hit_offs, walks one 64-byte granule gather per LF step (one-step granules only, the step of k_walk) and writes its record
@@ -31,40 +32,19 @@ static_assert(sizeof(sigax_hit) == 16, "sigax_hit must be 16 bytes");
 
 namespace {
 
-#define LOC_GRAB 64u  // chain numbers a wave reserves at a time
-
-template <bool WIDE>
-struct LocSh {
-  typedef typename PosOf<WIDE>::type P;
-  u64 C[5], T[5];  // FMIndex::_pred and the symbol totals
-  P Cc[4][4];      // Cc[c][e] = Occ(e, C[c]): the constants of a double step
-};
-
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
   typedef typename PosOf<WIDE>::type P;
-  __shared__ LocSh<WIDE> sh;
+  __shared__ SearchSh<WIDE> sh;
   const FmStrand& S = A.fwd;
-  const bool have2 = S.gran2 != nullptr && (!WIDE || S.super2 != nullptr);
-  if (threadIdx.x < 5) {
-    sh.C[threadIdx.x] = S.C[threadIdx.x];
-    sh.T[threadIdx.x] = S.total[threadIdx.x];
-  }
-  if (threadIdx.x < 16) {
-    const u32 c = threadIdx.x >> 2, e = threadIdx.x & 3u;
-    u64 pc = S.C[c + 1];
-    pc = pc > S.n ? S.n : pc;
-    sh.Cc[c][e] = (P)gran_rank<WIDE>(S, gran_load(S, pc), pc, e + 1u);
-  }
+  const bool have2 = have_two_step<WIDE>(S);
+  search_sh_fill(sh, S);
   __syncthreads();
 
-  const u32 lane = threadIdx.x & 63u;
-  const u64 lt = (1ull << lane) - 1ull;
   const u32 nvar = A.rc ? 2u : 1u;  // chains per query: chain = query * nvar + strand
   const u64 n_chains = A.n_queries * nvar;
 
-  u64 wnext = 0, wend = 0;  // the wave's reserved chain numbers (wave-uniform)
-  bool drained = false;     // the global counter has run out
+  ChainGrab grab;
   // a lane's chain: pattern w[0, len), i symbols consumed
   bool active = false, rcv = false;
   const unsigned char* w = nullptr;
@@ -73,7 +53,7 @@ __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
   P lo = 0, hi = 0;
   u32 n_sec = 0;
 
-  auto valid = [&]() { return hi != (P)~(P)0 && hi >= lo; };
+  auto valid = [&]() { return interval_valid(lo, hi); };
   // symbol j in the order the chain consumes them: the pattern backwards as given, forwards and complemented for its
   // reverse complement
   auto sym = [&](u32 j) {
@@ -84,23 +64,10 @@ __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
   for (;;) {
     // ---- lanes without a chain take the wave's next chain numbers ----
     for (;;) {
-      const u64 need = __ballot(!active);
-      if (need == 0ull) break;
-      if (wnext >= wend) {
-        if (drained) break;
-        u64 b = 0;
-        if (lane == 0) b = atomicAdd(&A.counters[0], (u64)LOC_GRAB);
-        b = first_lane64(b);
-        if (b >= n_chains) {
-          drained = true;
-          break;
-        }
-        wnext = b;
-        wend = b + LOC_GRAB < n_chains ? b + LOC_GRAB : n_chains;
-      }
-      const u32 avail = (u32)(wend - wnext), wanted = (u32)__popcll(need), mine = (u32)__popcll(need & lt);
-      if (!active && mine < avail) {
-        const u64 chain = wnext + mine;
+      bool got;
+      u64 chain;
+      if (!grab_chains(grab, &A.counters[0], n_chains, !active, got, chain)) break;
+      if (got) {
         const u64 q = chain / nvar;
         const u64 b0 = A.offs[q], b1 = A.offs[q + 1];
         if (b1 > b0) {  // an empty pattern has no occurrence (Interval::occurrences of "")
@@ -109,46 +76,15 @@ __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
           out = 2 * q + (rcv ? 1u : 0u);
           w = A.seqs + b0;
           len = (u32)(b1 - b0);
-          bool started = false;
-          if (A.ptab != nullptr && len >= A.pk) {
-            // the prefix table's entry of the first pk symbols, the first one consumed in the lowest two bits (k_prefix_build)
-            u32 code = 0;
-            bool acgt = true;
-            for (u32 j = 0; j < A.pk; ++j) {
-              const u32 r = sym(j);
-              acgt = acgt && r != 0u;
-              code |= ((r - 1u) & 3u) << (2u * j);
-            }
-            if (acgt) {
-              u64 cnt;
-              if (WIDE) {
-                const ulonglong2 e = reinterpret_cast<const ulonglong2*>(A.ptab)[code];
-                lo = (P)e.x;
-                cnt = e.y;
-              } else {
-                const uint2 e = reinterpret_cast<const uint2*>(A.ptab)[code];
-                lo = (P)e.x;
-                cnt = e.y;
-              }
-              n_sec += 1u;
-              hi = lo + (P)cnt - 1;
-              if (cnt == 0) {
-                lo = 1;
-                hi = 0;
-              }
-              i = A.pk;
-              started = true;
-            }
-          }
-          if (!started) {  // Interval::init (src/fmindex.h:90-93)
-            const u32 r0 = sym(0);
-            lo = (P)sh.C[r0];
-            hi = lo + (P)sh.T[r0] - 1;
+          if (A.ptab != nullptr && len >= A.pk && ptab_start<WIDE>(A.ptab, A.pk, sym, lo, hi)) {
+            n_sec += 1u;
+            i = A.pk;
+          } else {
+            search_init(sh, sym(0), lo, hi);
             i = 1;
           }
         }
       }
-      wnext += wanted < avail ? wanted : avail;
     }
     if (__ballot(active) == 0ull) break;
 
@@ -156,40 +92,9 @@ __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
     //      else one symbol off one-step granules (as k_match) ----
     if (active && i < len && valid()) {
       const u32 r = sym(i);
-      const u64 pl = (u64)lo > S.n ? S.n : (u64)lo, pu0 = (u64)hi + 1ull, pu = pu0 > S.n ? S.n : pu0;
       u32 e = 0;
       if (have2 && len - i >= 2u && r != 0u) e = sym(i + 1u);
-      if (e != 0u) {
-        // Occ(e, C[r] + Occ(r, p)) = Cc[r][e] + R2(e, r, p) (fm_layout.h)
-        const bool two = (pl >> 6) != (pu >> 6);
-        const Gran2 ga = gran2_load(S.gran2, pl, r);
-        Gran2 gb = ga;
-        if (two) gb = gran2_load(S.gran2, pu, r);
-        n_sec += two ? 4u : 2u;
-        u32 l1, l2, u1, u2;
-        rank2(ga, (u32)pl & 63u, r, e, l1, l2);
-        rank2(gb, (u32)pu & 63u, r, e, u1, u2);
-        P L2 = (P)l2, U2 = (P)u2;
-        if (WIDE) {
-          const u32 col = 4u + (r - 1u) * 4u + (e - 1u);
-          L2 += (P)S.super2[(pl >> SIGAX_SUPER_SHIFT) * 20 + col];
-          U2 += (P)S.super2[(pu >> SIGAX_SUPER_SHIFT) * 20 + col];
-        }
-        const P pb = (P)sh.C[e] + sh.Cc[r - 1u][e - 1u];
-        lo = pb + L2;  // an interval that symbol r emptied comes out empty after the pair (R2 over no rows)
-        hi = pb + U2 - 1;
-        i += 2u;
-      } else {
-        const bool two = (pl >> 7) != (pu >> 7);
-        const Gran1 qa = gran_load(S, pl);
-        Gran1 qb = qa;
-        if (two) qb = gran_load(S, pu);
-        n_sec += two ? 2u : 1u;
-        const P pb = (P)sh.C[r];
-        lo = pb + (P)gran_rank<WIDE>(S, qa, pl, r);      // getOcc(c, lower - 1)
-        hi = pb + (P)gran_rank<WIDE>(S, qb, pu, r) - 1;  // getOcc(c, upper)
-        i += 1u;
-      }
+      i += search_step<WIDE>(S, sh, r, e, lo, hi, n_sec);
     }
     // ---- a chain that is done leaves its interval, in the iteration of its last step; the lane is free ----
     if (active && (i >= len || !valid())) {
@@ -199,7 +104,7 @@ __global__ __launch_bounds__(256) void k_locate_search(LocateArgs A) {
   }
 
   const u64 t_sec = wave_sum((u64)n_sec);
-  if (lane == 0 && t_sec) atomicAdd(&A.status[2], t_sec);
+  if ((threadIdx.x & 63u) == 0 && t_sec) atomicAdd(&A.status[2], t_sec);
 }
 
 __global__ __launch_bounds__(256) void k_locate_finish(LocateArgs A) {
@@ -280,27 +185,14 @@ __global__ __launch_bounds__(256) void k_locate_walk(LocateArgs A) {
   }
 }
 
-template <typename K>
-unsigned persistent_cap(K kernel, int n_cu) {
-  int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 2;
-  }
-  return (unsigned)(n_cu > 0 ? n_cu : 256) * (unsigned)per_cu;
-}
-
 }  // namespace
 
 void launch_locate_search(const LocateArgs& a, bool wide, int n_cu, hipStream_t st) {
   if (a.n_queries == 0) return;
   // persistent grid: as many workgroups as the device holds at once, no more than the chains can keep busy
-  const unsigned long long cap = wide ? persistent_cap(k_locate_search<true>, n_cu) : persistent_cap(k_locate_search<false>, n_cu);
   const unsigned long long want = (a.n_queries * 2ull + 255) / 256;
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (wide) hipLaunchKernelGGL(k_locate_search<true>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_locate_search<false>, dim3(grid), dim3(256), 0, st, a);
+  if (wide) launch_persistent(k_locate_search<true>, a, want, n_cu, st);
+  else launch_persistent(k_locate_search<false>, a, want, n_cu, st);
 }
 
 void launch_locate_finish(const LocateArgs& a, hipStream_t st) {

@@ -11,18 +11,8 @@ static int match_enqueue(sigax_index* ix, const unsigned char* d_seqs, const u64
   ma.n_reads = n_reads;
   ma.max_length = max_length;
   ma.rc = (flags & SIGAX_RC) ? 1u : 0u;
-  ma.ptab = nullptr;
-  ma.pk = 0;
-  {
-    // the corrector's prefix table, if a correction call has built it: never allocated for a match call.  Its build may
-    // still be running on that call's stream.
-    std::lock_guard<std::mutex> lock(*ix->enqueue_mu);
-    if (ix->d_ptab && ix->ptab_k) {
-      if (ix->ptab_ev) HIP_TRY(hipStreamWaitEvent(st, ix->ptab_ev, 0));
-      ma.ptab = ix->d_ptab;
-      ma.pk = ix->ptab_k;
-    }
-  }
+  const int rp = ptab_for_stream(ix, st, &ma.ptab, &ma.pk);
+  if (rp != SIGAX_OK) return rp;
   ma.counts = d_counts;
   ma.dstat = d_stat;
   launch_match(ma, ix->wide, ix->n_cu, st);
@@ -44,18 +34,13 @@ extern "C" int sigax_match_batch(sigax_index* ix, const char* seqs, const uint64
   if (!ix || (flags & ~SIGAX_RC) || (n_reads && (!seqs || !offs || !counts))) return sigax_fail(SIGAX_E_ARG, "bad argument");
   HIP_TRY(hipSetDevice(ix->device));
   if (n_reads == 0) return SIGAX_OK;
-  for (u64 i = 0; i < n_reads; ++i)
-    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] > 0xFFFFFFFFull) return sigax_fail(SIGAX_E_ARG, "read %llu: bad offsets", i);
-  const u64 nb = offs[n_reads];
   unsigned char* d_seqs = nullptr;
   u64 *d_offs = nullptr, *d_counts = nullptr, *d_stat = nullptr;
   DevGuard g;
-  HIP_TRY(g.alloc((void**)&d_seqs, nb + 16));
-  HIP_TRY(g.alloc((void**)&d_offs, ((size_t)n_reads + 1) * 8));
+  const int rs = stage_strings(g, seqs, offs, n_reads, 0xFFFFFFFFull, "read", (hipStream_t)0, &d_seqs, &d_offs);
+  if (rs != SIGAX_OK) return rs;
   HIP_TRY(g.alloc((void**)&d_counts, (size_t)n_reads * 16));
   HIP_TRY(g.alloc((void**)&d_stat, 32));
-  HIP_TRY(hipMemcpy(d_seqs, seqs, nb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice));
   const int rc = match_enqueue(ix, d_seqs, d_offs, n_reads, max_length, flags, d_counts, d_stat, (hipStream_t)0);
   if (rc != SIGAX_OK) return rc;
   HIP_TRY(hipStreamSynchronize((hipStream_t)0));

@@ -8,9 +8,9 @@
 //
 // Shape.  Chains differ in length by orders of magnitude (a read with an error dies a few symbols past the point where its
 // suffix becomes unique, a read of the index walks to its end, a contig walks 100 000 symbols), so lanes are not tied to
-// chains: the grid is persistent, a wave reserves MATCH_GRAB chain numbers at a time from one global counter, and a lane
-// whose interval emptied or whose pattern ended adds its count and takes the wave's next chain number in the same loop
-// iteration -- every lane of a wave has a live chain until the counter runs out.
+// chains: the grid is persistent, a wave reserves GRAB chain numbers at a time from one global counter (grab_chains,
+// sigax_rank.h), and a lane whose interval emptied or whose pattern ended adds its count and takes the wave's next chain
+// number in the same loop iteration -- every lane of a wave has a live chain until the counter runs out.
 // The pattern is read in place, through a two-word (16-byte) window per lane that slides in the direction the chain
 // consumes: backwards through the read for the pattern as read, FORWARDS for its reverse complement -- backward search
 // of revcomp(w) consumes comp(w[0]), comp(w[1]), ... -- so no reversed copy exists anywhere, and no pattern length is too
@@ -18,23 +18,15 @@
 // With the two-step table (fm_layout.h) two symbols go per pair of gathers; a pair with a symbol of rank 0, an odd last
 // symbol, and indexes without the table take one-step granules.  When the corrector's prefix table is resident a chain of
 // at least that many symbols, all of them ACGT, starts from its entry.  Counts are the same whichever tables exist.
-// Integer work only, bound by gather latency; no MFMA.
+// The step, the start from the table and the workgroup's constants are sigax_rank.h's, shared with sigax_spectrum.hip and
+// sigax_locate.hip; what is this file's own is how a chain's symbols are fetched.  Integer work only, bound by gather
+// latency; no MFMA.
 #include <hip/hip_runtime.h>
 
 #include "sigax_kernels.h"
 #include "sigax_rank.h"
 
 namespace {
-
-#define MATCH_GRAB 64u  // chain numbers a wave reserves at a time: one atomic per 64 chains, and the last waves of a launch
-                        // are never more than 64 chains apart
-
-template <bool WIDE>
-struct MatchSh {
-  typedef typename PosOf<WIDE>::type P;
-  u64 C[5], T[5];  // FMIndex::_pred and the symbol totals
-  P Cc[4][4];      // Cc[c][e] = Occ(e, C[c]): the constants of a double step
-};
 
 // ---- the pattern, read in place -------------------------------------------------------------------------------------
 // Positions are VIRTUAL byte offsets: offset in seqs + (address of seqs & 7), so that word w of the window is the aligned
@@ -69,31 +61,19 @@ __global__ __launch_bounds__(256) void k_match_init(const u64* offs, u64 n_reads
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
   typedef typename PosOf<WIDE>::type P;
-  __shared__ MatchSh<WIDE> sh;
+  __shared__ SearchSh<WIDE> sh;
   const FmStrand& S = A.fwd;
-  const bool have2 = S.gran2 != nullptr && (!WIDE || S.super2 != nullptr);
-  if (threadIdx.x < 5) {
-    sh.C[threadIdx.x] = S.C[threadIdx.x];
-    sh.T[threadIdx.x] = S.total[threadIdx.x];
-  }
-  if (threadIdx.x < 16) {
-    const u32 c = threadIdx.x >> 2, e = threadIdx.x & 3u;
-    u64 pc = S.C[c + 1];
-    pc = pc > S.n ? S.n : pc;
-    sh.Cc[c][e] = (P)gran_rank<WIDE>(S, gran_load(S, pc), pc, e + 1u);
-  }
+  const bool have2 = have_two_step<WIDE>(S);
+  search_sh_fill(sh, S);
   __syncthreads();
 
-  const u32 lane = threadIdx.x & 63u;
-  const u64 lt = (1ull << lane) - 1ull;
   const u32 nvar = (A.rc ? 2u : 1u) * (A.max_length == ~0ull ? 1u : 2u);  // chains per read: chain = read * nvar + variant
   const u64 n_chains = A.n_reads * nvar;
   const u64 align = (u64)(uintptr_t)A.seqs & 7ull;
   const unsigned char* base = A.seqs - align;
   const u64 buf_lo = align + A.offs[0], buf_hi = align + A.offs[A.n_reads];
 
-  u64 wnext = 0, wend = 0;  // the wave's reserved chain numbers (wave-uniform)
-  bool drained = false;     // the global counter has run out
+  ChainGrab grab;
   // a lane's chain
   bool active = false;
   bool rcv = false;
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
   Win win = {0, 0, 0};
   u32 n_run = 0, n_sym = 0, n_sec = 0;
 
-  auto valid = [&]() { return hi != (P)~(P)0 && hi >= lo; };
+  auto valid = [&]() { return interval_valid(lo, hi); };
   // the chain has consumed k symbols: move on, sliding the window when its first word has been left
   auto advance = [&](u32 k) {
     pos = rcv ? pos + k : pos - k;
@@ -122,23 +102,10 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
   for (;;) {
     // ---- lanes without a chain take the wave's next chain numbers ----
     for (;;) {
-      const u64 need = __ballot(!active);
-      if (need == 0ull) break;
-      if (wnext >= wend) {
-        if (drained) break;
-        u64 b = 0;
-        if (lane == 0) b = atomicAdd(&A.dstat[3], (u64)MATCH_GRAB);
-        b = first_lane64(b);
-        if (b >= n_chains) {
-          drained = true;
-          break;
-        }
-        wnext = b;
-        wend = b + MATCH_GRAB < n_chains ? b + MATCH_GRAB : n_chains;
-      }
-      const u32 avail = (u32)(wend - wnext), wanted = (u32)__popcll(need), mine = (u32)__popcll(need & lt);
-      if (!active && mine < avail) {
-        const u64 chain = wnext + mine;
+      bool got;
+      u64 chain;
+      if (!grab_chains(grab, &A.dstat[3], n_chains, !active, got, chain)) break;
+      if (got) {
         const u64 rd = chain / nvar;
         const u32 var = (u32)(chain - rd * nvar);
         rcv = A.rc && (var & 1u);
@@ -162,55 +129,31 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
           win.w1 = win_word(base, rcv ? win.i0 + 1u : win.i0 - 1u, seg_lo, seg_hi, buf_lo, buf_hi);
           bool started = false;
           if (A.ptab != nullptr && rem >= A.pk) {
-            // the prefix table's entry of the first pk symbols, the first one consumed in the lowest two bits (k_prefix_build)
+            // the attempt slides the window over the pk symbols; they are taken back when one of them is not ACGT
             const Win w_save = win;
             const u64 pos_save = pos;
             const u32 rem_save = rem;
-            u32 code = 0;
-            bool acgt = true;
-            for (u32 i = 0; i < A.pk; ++i) {
+            started = ptab_start<WIDE>(A.ptab, A.pk, [&](u32) {
               const u32 r = rank_at(pos);
-              acgt = acgt && r != 0u;
-              code |= ((r - 1u) & 3u) << (2u * i);
               advance(1);
-            }
-            if (acgt) {
-              u64 cnt;
-              if (WIDE) {
-                const ulonglong2 e = reinterpret_cast<const ulonglong2*>(A.ptab)[code];
-                lo = (P)e.x;
-                cnt = e.y;
-              } else {
-                const uint2 e = reinterpret_cast<const uint2*>(A.ptab)[code];
-                lo = (P)e.x;
-                cnt = e.y;
-              }
+              return r;
+            }, lo, hi);
+            if (started) {
               n_sec += 1u;
-              hi = lo + (P)cnt - 1;
-              if (cnt == 0) {  // the reference stopped somewhere in these symbols, after one at the least
-                lo = 1;
-                hi = 0;
-                n_sym += 1u;
-              } else {
-                n_sym += A.pk;
-              }
-              started = true;
+              n_sym += valid() ? A.pk : 1u;
             } else {
               win = w_save;
               pos = pos_save;
               rem = rem_save;
             }
           }
-          if (!started) {  // Interval::init (src/fmindex.h:90-93)
-            const u32 r0 = rank_at(pos);
-            lo = (P)sh.C[r0];
-            hi = lo + (P)sh.T[r0] - 1;
+          if (!started) {
+            search_init(sh, rank_at(pos), lo, hi);
             n_sym += 1u;
             advance(1);
           }
         }
       }
-      wnext += wanted < avail ? wanted : avail;
     }
     if (__ballot(active) == 0ull) break;
 
@@ -221,51 +164,18 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
         active = false;
       } else {
         const u32 r = rank_at(pos);
-        const u64 pl = (u64)lo > S.n ? S.n : (u64)lo, pu0 = (u64)hi + 1ull, pu = pu0 > S.n ? S.n : pu0;
         u32 e = 0;
         if (have2 && rem >= 2u && r != 0u) e = rank_at(rcv ? pos + 1u : pos - 1u);
-        if (e != 0u) {
-          // two symbols from the two positions of the first step (fm_layout.h): Occ(e, C[r] + Occ(r, p)) = Cc[r][e] + R2(e, r, p)
-          const bool two = (pl >> 6) != (pu >> 6);
-          const Gran2 ga = gran2_load(S.gran2, pl, r);
-          Gran2 gb = ga;
-          if (two) gb = gran2_load(S.gran2, pu, r);
-          n_sec += two ? 4u : 2u;
-          u32 l1, l2, u1, u2;
-          rank2(ga, (u32)pl & 63u, r, e, l1, l2);
-          rank2(gb, (u32)pu & 63u, r, e, u1, u2);
-          P L1 = (P)l1, L2 = (P)l2, U1 = (P)u1, U2 = (P)u2;
-          if (WIDE) {
-            const u64* sl = S.super2 + (pl >> SIGAX_SUPER_SHIFT) * 20;
-            const u64* su = S.super2 + (pu >> SIGAX_SUPER_SHIFT) * 20;
-            const u32 col = 4u + (r - 1u) * 4u + (e - 1u);
-            L1 += (P)sl[r - 1u]; U1 += (P)su[r - 1u];
-            L2 += (P)sl[col]; U2 += (P)su[col];
-          }
-          const P pb = (P)sh.C[e] + sh.Cc[r - 1u][e - 1u];
-          lo = pb + L2;
-          hi = pb + U2 - 1;
-          // an interval that symbol r emptied comes out empty after the pair (R2 over no rows); the reference stopped there
-          n_sym += U1 > L1 ? 2u : 1u;
-          advance(2);
-        } else {
-          const bool two = (pl >> 7) != (pu >> 7);
-          const Gran1 qa = gran_load(S, pl);
-          Gran1 qb = qa;
-          if (two) qb = gran_load(S, pu);
-          n_sec += two ? 2u : 1u;
-          const P pb = (P)sh.C[r];
-          lo = pb + (P)gran_rank<WIDE>(S, qa, pl, r);       // getOcc(c, lower - 1)
-          hi = pb + (P)gran_rank<WIDE>(S, qb, pu, r) - 1;   // getOcc(c, upper)
-          n_sym += 1u;
-          advance(1);
-        }
+        bool first_left;
+        const u32 k = search_step<WIDE>(S, sh, r, e, lo, hi, n_sec, &first_left);
+        n_sym += first_left ? k : 1u;  // the reference stopped at a symbol that emptied the interval
+        advance(k);
       }
     }
   }
 
   const u64 t_run = wave_sum(n_run), t_sym = wave_sum(n_sym), t_sec = wave_sum(n_sec);
-  if (lane == 0) {
+  if ((threadIdx.x & 63u) == 0) {
     atomicAdd(&A.dstat[0], t_run);
     atomicAdd(&A.dstat[1], t_sym);
     atomicAdd(&A.dstat[2], t_sec);
@@ -278,16 +188,7 @@ void launch_match(const MatchArgs& a, bool wide, int n_cu, hipStream_t st) {
   if (a.n_reads == 0) return;
   hipLaunchKernelGGL(k_match_init, dim3((unsigned)((a.n_reads + 255) / 256)), dim3(256), 0, st, a.offs, a.n_reads, a.max_length, a.counts);
   // persistent grid: as many workgroups as the device holds at once, no more than the chains can keep busy
-  int per_cu = 0;
-  const hipError_t e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_match<true>, 256, 0)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_match<false>, 256, 0);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 2;
-  }
-  const unsigned long long chains = a.n_reads * 4ull;
-  const unsigned long long want = (chains + 255) / 256, cap = (unsigned long long)(n_cu > 0 ? n_cu : 256) * (unsigned)per_cu;
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (wide) hipLaunchKernelGGL(k_match<true>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_match<false>, dim3(grid), dim3(256), 0, st, a);
+  const unsigned long long want = (a.n_reads * 4ull + 255) / 256;
+  if (wide) launch_persistent(k_match<true>, a, want, n_cu, st);
+  else launch_persistent(k_match<false>, a, want, n_cu, st);
 }

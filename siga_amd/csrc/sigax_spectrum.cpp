@@ -98,13 +98,10 @@ extern "C" int sigax_get_strings(sigax_index* ix, int which, const uint64_t* row
                                           &d_seqs, &total);
     if (rc != SIGAX_OK) return rc;
   }
-  char* h_seqs = (char*)malloc((size_t)total + 1);
-  uint64_t* h_offs = (uint64_t*)malloc(((size_t)n + 1) * 8);
-  if (!h_seqs || !h_offs) {
-    free(h_seqs);
-    free(h_offs);
-    return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
-  }
+  HostGuard hg;
+  char* h_seqs = hg.alloc<char>((size_t)total + 1);
+  uint64_t* h_offs = hg.alloc<uint64_t>(((size_t)n + 1) * 8);
+  if (!hg.ok) return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
   h_offs[0] = 0;
   h_seqs[total] = '\0';
   hipError_t e = hipSuccess;
@@ -113,11 +110,8 @@ extern "C" int sigax_get_strings(sigax_index* ix, int which, const uint64_t* row
     if (e == hipSuccess && total) e = hipMemcpy(h_seqs, d_seqs, (size_t)total, hipMemcpyDeviceToHost);
     if (e == hipSuccess && stretch) e = hipMemcpy(stretch, d_stretch, (size_t)n * 8, hipMemcpyDeviceToHost);
   }
-  if (e != hipSuccess) {
-    free(h_seqs);
-    free(h_offs);
-    return sigax_fail(SIGAX_E_DEVICE, "copying the strings: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return sigax_fail(SIGAX_E_DEVICE, "copying the strings: %s", hipGetErrorString(e));
+  hg.release();
   *seqs = h_seqs;
   *offs = h_offs;
   return SIGAX_OK;
@@ -142,18 +136,8 @@ static int spectrum_enqueue(sigax_index* ix, const unsigned char* d_seqs, const 
   sa.n_reads = n_reads;
   sa.n_bins = n_bins;
   sa.k = k;
-  sa.ptab = nullptr;
-  sa.pk = 0;
-  {
-    // the corrector's prefix table, if a correction call has built it: never allocated here.  Its build may still be
-    // running on that call's stream.
-    std::lock_guard<std::mutex> lock(*ix->enqueue_mu);
-    if (ix->d_ptab && ix->ptab_k) {
-      if (ix->ptab_ev) HIP_TRY(hipStreamWaitEvent(st, ix->ptab_ev, 0));
-      sa.ptab = ix->d_ptab;
-      sa.pk = ix->ptab_k;
-    }
-  }
+  const int rp = ptab_for_stream(ix, st, &sa.ptab, &sa.pk);
+  if (rp != SIGAX_OK) return rp;
   sa.hist = d_hist;
   sa.dstat = d_stat;
   sa.counter = d_work;
@@ -197,16 +181,11 @@ extern "C" int sigax_kmer_spectrum_batch(sigax_index* ix, const char* seqs, cons
   HIP_TRY(hipSetDevice(ix->device));
   if (stat4) memset(stat4, 0, 32);
   if (n_reads == 0) return SIGAX_OK;
-  for (u64 i = 0; i < n_reads; ++i)
-    if (offs[i + 1] < offs[i]) return sigax_fail(SIGAX_E_ARG, "string %llu: bad offsets", i);
-  const u64 nb = offs[n_reads];
   unsigned char* d_seqs = nullptr;
   u64* d_offs = nullptr;
   DevGuard g;
-  HIP_TRY(g.alloc((void**)&d_seqs, nb + 16));
-  HIP_TRY(g.alloc((void**)&d_offs, ((size_t)n_reads + 1) * 8));
-  HIP_TRY(hipMemcpy(d_seqs, seqs, nb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice));
+  const int rs = stage_strings(g, seqs, offs, n_reads, ~0ull, "string", (hipStream_t)0, &d_seqs, &d_offs);
+  if (rs != SIGAX_OK) return rs;
   return spectrum_to_host(ix, g, d_seqs, d_offs, n_reads, k, n_bins, hist, stat4);
 }
 

@@ -21,8 +21,9 @@
 // its window in one loop, a (double) step of each per iteration: the two gathers are independent and in flight together,
 // and the window's bin is known in the lane without any per-window array or cross-lane traffic.  Chains start from the
 // corrector's table of 13-mer intervals when it is resident, k >= 13 and the 13 symbols are ACGT; two symbols go per pair
-// of gathers where the two-step lines exist (as k_match).  Bins below SPEC_LOW are counted in LDS (u64, 8 KB per
-// workgroup) and flushed once when the workgroup ends; the rare higher ones go to global memory directly.  Bins are ADDED to.
+// of gathers where the two-step lines exist (the start and the step of sigax_rank.h, as k_match).  Bins below SPEC_LOW
+// are counted in LDS (u64, 8 KB per workgroup) and flushed once when the workgroup ends; the rare higher ones go to global
+// memory directly.  Bins are ADDED to.
 // Integer work only, bound by gather latency; no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -108,9 +109,7 @@ __global__ __launch_bounds__(256) void k_walk(WalkArgs A) {
 // ---- k-mer spectrum -------------------------------------------------------------------------------------------------
 template <bool WIDE>
 struct SpecSh {
-  typedef typename PosOf<WIDE>::type P;
-  u64 C[5], T[5];  // FMIndex::_pred and the symbol totals
-  P Cc[4][4];      // Cc[c][e] = Occ(e, C[c]): the constants of a double step
+  SearchSh<WIDE> s;
   u64 low[SPEC_LOW];
 };
 
@@ -126,111 +125,41 @@ template <bool WIDE>
 struct SpecChain {
   typename PosOf<WIDE>::type lo, hi;
   u32 i;  // symbols consumed
-  __device__ __forceinline__ bool valid() const { typedef typename PosOf<WIDE>::type P; return hi != (P)~(P)0 && hi >= lo; }
+  __device__ __forceinline__ bool valid() const { return interval_valid(lo, hi); }
   __device__ __forceinline__ bool live(u32 k) const { return i < k && valid(); }
   __device__ __forceinline__ u64 count() const { return valid() ? (u64)(hi - lo) + 1ull : 0ull; }
 };
 
 template <bool WIDE, bool RC>
-__device__ __forceinline__ void chain_start(const SpectrumArgs& A, const SpecSh<WIDE>& sh, const unsigned char* w, SpecChain<WIDE>& c,
+__device__ __forceinline__ void chain_start(const SpectrumArgs& A, const SearchSh<WIDE>& sh, const unsigned char* w, SpecChain<WIDE>& c,
                                             u32* n_sec) {
-  typedef typename PosOf<WIDE>::type P;
-  if (A.ptab != nullptr && A.k >= A.pk) {
-    // the prefix table's entry of the first pk symbols, the first one consumed in the lowest two bits (k_prefix_build)
-    u32 code = 0;
-    bool acgt = true;
-    for (u32 i = 0; i < A.pk; ++i) {
-      const u32 r = win_rank<RC>(w, A.k, i);
-      acgt = acgt && r != 0u;
-      code |= ((r - 1u) & 3u) << (2u * i);
-    }
-    if (acgt) {
-      u64 cnt;
-      if (WIDE) {
-        const ulonglong2 e = reinterpret_cast<const ulonglong2*>(A.ptab)[code];
-        c.lo = (P)e.x;
-        cnt = e.y;
-      } else {
-        const uint2 e = reinterpret_cast<const uint2*>(A.ptab)[code];
-        c.lo = (P)e.x;
-        cnt = e.y;
-      }
-      *n_sec += 1u;
-      c.hi = c.lo + (P)cnt - 1;
-      if (cnt == 0) {
-        c.lo = 1;
-        c.hi = 0;
-      }
-      c.i = A.pk;
-      return;
-    }
+  auto sym = [&](u32 i) { return win_rank<RC>(w, A.k, i); };
+  if (A.ptab != nullptr && A.k >= A.pk && ptab_start<WIDE>(A.ptab, A.pk, sym, c.lo, c.hi)) {
+    *n_sec += 1u;
+    c.i = A.pk;
+  } else {
+    search_init(sh, sym(0), c.lo, c.hi);
+    c.i = 1;
   }
-  const u32 r0 = win_rank<RC>(w, A.k, 0);  // Interval::init (src/fmindex.h:90-93)
-  c.lo = (P)sh.C[r0];
-  c.hi = c.lo + (P)sh.T[r0] - 1;
-  c.i = 1;
 }
 
 // one step of a live chain: two symbols off a pair of two-step lines where they exist and both are ACGT, else one symbol
 // off one-step granules (as k_match)
 template <bool WIDE, bool RC>
-__device__ __forceinline__ void chain_step(const SpectrumArgs& A, const SpecSh<WIDE>& sh, bool have2, const unsigned char* w,
+__device__ __forceinline__ void chain_step(const SpectrumArgs& A, const SearchSh<WIDE>& sh, bool have2, const unsigned char* w,
                                            SpecChain<WIDE>& c, u32* n_sec) {
-  typedef typename PosOf<WIDE>::type P;
-  const FmStrand& S = A.fwd;
   const u32 r = win_rank<RC>(w, A.k, c.i);
-  const u64 pl = (u64)c.lo > S.n ? S.n : (u64)c.lo, pu0 = (u64)c.hi + 1ull, pu = pu0 > S.n ? S.n : pu0;
   u32 e = 0;
   if (have2 && A.k - c.i >= 2u && r != 0u) e = win_rank<RC>(w, A.k, c.i + 1u);
-  if (e != 0u) {
-    // Occ(e, C[r] + Occ(r, p)) = Cc[r][e] + R2(e, r, p) (fm_layout.h)
-    const bool two = (pl >> 6) != (pu >> 6);
-    const Gran2 ga = gran2_load(S.gran2, pl, r);
-    Gran2 gb = ga;
-    if (two) gb = gran2_load(S.gran2, pu, r);
-    *n_sec += two ? 4u : 2u;
-    u32 l1, l2, u1, u2;
-    rank2(ga, (u32)pl & 63u, r, e, l1, l2);
-    rank2(gb, (u32)pu & 63u, r, e, u1, u2);
-    P L2 = (P)l2, U2 = (P)u2;
-    if (WIDE) {
-      const u32 col = 4u + (r - 1u) * 4u + (e - 1u);
-      L2 += (P)S.super2[(pl >> SIGAX_SUPER_SHIFT) * 20 + col];
-      U2 += (P)S.super2[(pu >> SIGAX_SUPER_SHIFT) * 20 + col];
-    }
-    const P pb = (P)sh.C[e] + sh.Cc[r - 1u][e - 1u];
-    c.lo = pb + L2;  // an interval that symbol r emptied comes out empty after the pair (R2 over no rows)
-    c.hi = pb + U2 - 1;
-    c.i += 2u;
-  } else {
-    const bool two = (pl >> 7) != (pu >> 7);
-    const Gran1 qa = gran_load(S, pl);
-    Gran1 qb = qa;
-    if (two) qb = gran_load(S, pu);
-    *n_sec += two ? 2u : 1u;
-    const P pb = (P)sh.C[r];
-    c.lo = pb + (P)gran_rank<WIDE>(S, qa, pl, r);      // getOcc(c, lower - 1)
-    c.hi = pb + (P)gran_rank<WIDE>(S, qb, pu, r) - 1;  // getOcc(c, upper)
-    c.i += 1u;
-  }
+  c.i += search_step<WIDE>(A.fwd, sh, r, e, c.lo, c.hi, *n_sec);
 }
 
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_spectrum(SpectrumArgs A) {
-  typedef typename PosOf<WIDE>::type P;
   __shared__ SpecSh<WIDE> sh;
   const FmStrand& S = A.fwd;
-  const bool have2 = S.gran2 != nullptr && (!WIDE || S.super2 != nullptr);
-  if (threadIdx.x < 5) {
-    sh.C[threadIdx.x] = S.C[threadIdx.x];
-    sh.T[threadIdx.x] = S.total[threadIdx.x];
-  }
-  if (threadIdx.x < 16) {
-    const u32 c = threadIdx.x >> 2, e = threadIdx.x & 3u;
-    u64 pc = S.C[c + 1];
-    pc = pc > S.n ? S.n : pc;
-    sh.Cc[c][e] = (P)gran_rank<WIDE>(S, gran_load(S, pc), pc, e + 1u);
-  }
+  const bool have2 = have_two_step<WIDE>(S);
+  search_sh_fill(sh.s, S);
   for (u32 b = threadIdx.x; b < SPEC_LOW; b += 256) sh.low[b] = 0;
   __syncthreads();
 
@@ -253,13 +182,13 @@ __global__ __launch_bounds__(256) void k_spectrum(SpectrumArgs A) {
     for (u64 x = lane; x < nwin; x += 64) {
       const unsigned char* w = A.seqs + b0 + x;
       SpecChain<WIDE> f, r;
-      chain_start<WIDE, false>(A, sh, w, f, &n_sec);
-      chain_start<WIDE, true>(A, sh, w, r, &n_sec);
+      chain_start<WIDE, false>(A, sh.s, w, f, &n_sec);
+      chain_start<WIDE, true>(A, sh.s, w, r, &n_sec);
       for (;;) {
         const bool lf = f.live(A.k), lr = r.live(A.k);
         if (!lf && !lr) break;
-        if (lf) chain_step<WIDE, false>(A, sh, have2, w, f, &n_sec);
-        if (lr) chain_step<WIDE, true>(A, sh, have2, w, r, &n_sec);
+        if (lf) chain_step<WIDE, false>(A, sh.s, have2, w, f, &n_sec);
+        if (lr) chain_step<WIDE, true>(A, sh.s, have2, w, r, &n_sec);
       }
       const u64 cnt = f.count() + r.count();
       const u64 bin = cnt < top ? cnt : top;
@@ -300,15 +229,7 @@ void launch_walk(const WalkArgs& a, bool wide, hipStream_t st) {
 void launch_spectrum(const SpectrumArgs& a, bool wide, int n_cu, hipStream_t st) {
   if (a.n_reads == 0) return;
   // persistent grid: as many workgroups as the device holds at once, no more than one wave per string
-  int per_cu = 0;
-  const hipError_t e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spectrum<true>, 256, 0)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spectrum<false>, 256, 0);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    per_cu = 2;
-  }
-  const unsigned long long want = (a.n_reads + 3) / 4, cap = (unsigned long long)(n_cu > 0 ? n_cu : 256) * (unsigned)per_cu;
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (wide) hipLaunchKernelGGL(k_spectrum<true>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_spectrum<false>, dim3(grid), dim3(256), 0, st, a);
+  const unsigned long long want = (a.n_reads + 3) / 4;
+  if (wide) launch_persistent(k_spectrum<true>, a, want, n_cu, st);
+  else launch_persistent(k_spectrum<false>, a, want, n_cu, st);
 }
