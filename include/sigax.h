@@ -373,6 +373,65 @@ int  sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t n_edges, c
                         uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs);
 /* the six counts (status6 above) of this thread's last successful sigax_unitigs_host call, whose signature has no room for them */
 int  sigax_unitigs_last_status(uint64_t status6[6]);
+
+/* ---- `siga unitig -x`: tip trimming, and the graph between the unitigs (csrc/sigax_unitig.hip) ------------------------------------
+ * What the reference's `assemble` does after its first simplify(): TrimVisitor (src/bigraph_visitors.cpp:1119-1161) and
+ * simplify() in turn, --cut-terminal rounds (src/assembler.cpp:138-159), and the records that are left between the vertices
+ * (PREFIX-graph.asqg.gz, :238).  Everything not said here is as in the block above: record classification, B/E ends, degrees,
+ * simple records, rings, orientation, offsets, numbering.
+ *
+ * sigax_trim_opts: max_rounds (the reference's -x; at most 64), min_branch_length L (-n), min_branch_coverage C (-C;
+ * 0xFFFFFFFF = no coverage test, the reference's default of -1), reserved = 0.
+ *
+ * Every read starts alive.  One round r = 1, 2, ...: a record is LIVE if it is kept and both its reads are alive; degrees,
+ * simple records, links, the ring cut and the unitigs follow the rules above over the alive reads and the live records only.
+ * A unitig's left end is the outward end of its first placed read (that read's B end if it is placed forward, its E end if
+ * reversed), its right end the outward end of its last placed read; dL and dR are the degrees of those two read ends.  A
+ * ring's two ends each carry its closing record, so a ring is never a dead end.  The unitig is removed in this round iff
+ *   dL == 0 or dR == 0,  and  its bases <= L,  and, when C is given,  (K - 1) * max(L, 1) <= (max(C, 1) - 1) * bases
+ * with K its number of reads, compared in u64.  The last is Point::avg(vertex) <= Point::avg(C, L) (:37-44) cross-multiplied;
+ * it agrees with the reference's two double divisions whenever bases * L < 2^52 (two different quotients with denominators
+ * bases and L differ by at least 1 / (bases * L), more than the rounding of either).  A removed unitig counts as an ISLAND if dL and dR are both 0,
+ * else as a DEAD END.  Every decision of a round uses the state at its start; all reads of a removed unitig get removed[read]
+ * = r.  A round that removes nothing ends the loop and is not counted.
+ *
+ * Result: the unitigs of the alive reads under the live records after the last round, in the shape of the sigax_unitigs_*
+ * output, except: layout holds the alive reads only, lay_offs[n_unitigs] is their count (entries of layout beyond it are not
+ * written); removed u32[n_reads] is 0 for a kept read, else the round in which it went.  max_rounds = 0 gives exactly the
+ * sigax_unitigs_* result with removed all zero.
+ *
+ * Lifted records: after the last round every live record that was not merged (records at branched ends, containments, self
+ * edges, a ring's closing record) becomes one sigax_edge over unitigs, in input record order.  Read end e (B = 0, E = 1) of a
+ * read placed with flags & SIGAX_PLACED_REV = v is unitig end e ^ v.  query = the unitig of the record's query, target = that
+ * of its target, length unchanged, af bit0 = the query's unitig end is B, bit1 = the target's unitig end is E, bit2 = bit0 ^
+ * bit1.  A read in a live containment is a single forward unitig, so that record's af stays.  Coordinates follow from
+ * (length, af, unitig lengths) as they do for reads.
+ *
+ * status12 = 12 u64, written: 0-5 the six counts above for the final graph, 6 rounds that removed something, 7 islands
+ * removed, 8 dead ends removed, 9 reads removed, 10 kept records dropped because one of their reads was removed, 11 lifted
+ * records written (0 without d_uedges).
+ *
+ * sigax_unitigs_trim_device: as sigax_unitigs_device -- asynchronous on `stream`, allocates nothing, never waits for the
+ * device.  It enqueues max_rounds rounds; the launches of a round after one that removed nothing return at once on a device
+ * counter.  d_removed u32[n_reads]; d_uedges NULL (no graph) or room for n_edges records, 16-byte aligned; d_status12 8-byte
+ * aligned; d_work = sigax_unitigs_trim_workspace(n_reads, n_edges, d_uedges != NULL) bytes.  Refusals as above, and
+ * max_rounds > 64 or reserved != 0: SIGAX_E_ARG.  Whatever the records hold, nothing outside the buffers is touched. */
+typedef struct sigax_trim_opts { uint32_t max_rounds, min_branch_length, min_branch_coverage, reserved; } sigax_trim_opts;
+#define SIGAX_TRIM_NO_COVERAGE 0xFFFFFFFFu
+int  sigax_unitigs_trim_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_trim_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                               const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                               void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                               void* d_removed, sigax_edge* d_uedges, void* d_status12, void* d_work, uint64_t work_bytes,
+                               void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_host.  *layout has lay_offs[n_unitigs] entries, *removed u32[n_reads], *uedges
+ * status12[11] records (pass uedges = NULL for no graph); all malloc'd, release with sigax_free.  status12 is filled.  It reads each
+ * round's outcome and stops after the first round that removed nothing. */
+int  sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                             const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                             uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                             sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
+                             uint64_t status12[12]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

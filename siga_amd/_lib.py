@@ -28,6 +28,12 @@ SIGAX_LOCATE_SKIPPED = 1
 SIGAX_LOCATE_OVER = 2
 SIGAX_PLACED_REV = 1
 SIGAX_UNITIG_CIRCULAR = 1
+SIGAX_TRIM_NO_COVERAGE = 0xFFFFFFFF
+TRIM_MAX_ROUNDS = 64
+
+
+class TrimOpts(C.Structure):  # sigax_trim_opts
+    _fields_ = [(n, C.c_uint32) for n in ("max_rounds", "min_branch_length", "min_branch_coverage", "reserved")]
 
 
 class Stats(C.Structure):
@@ -73,6 +79,7 @@ SYMBOLS = [
     "sigax_kmer_spectrum_device", "sigax_kmer_spectrum_batch", "sigax_kmer_spectrum_rows", "sigax_kmer_spectrum_rows_hint",
     "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
     "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
+    "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -164,6 +171,10 @@ def lib():
     L.sigax_unitigs_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(u64), pvp, pvp, pvp, pvp, pvp]
     L.sigax_unitigs_last_status.argtypes = [vp]
+    L.sigax_unitigs_trim_workspace.argtypes = [u64, u64, ci, C.POINTER(u64)]
+    L.sigax_unitigs_trim_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(TrimOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.sigax_unitigs_trim_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(TrimOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp, pvp,
+                                          pvp, vp]
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
     L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]

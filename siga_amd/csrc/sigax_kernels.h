@@ -284,9 +284,36 @@ struct UnitigArgs {
   unsigned long long* src;               // [n_reads]: the byte of seqs that goes there; bit 63: descending and complemented
   unsigned long long* counts;            // 4 u64, zeroed: UNI_C_*
 };
+// tip trimming and the lifted records (sigax_unitigs_trim_*): the unitig call's block and what the rounds and the lift need.  A
+// block of its own, so that the kernels of sigax_unitigs_device keep the argument block they had.
+struct UnitigTrimArgs : UnitigArgs {
+  uint32_t* removed;                     // [n_reads], zeroed before round 1: the round in which a read went, 0 = alive
+  uint32_t* verdict;                     // [n_reads]: a round's decision, under the unitig's head
+  uint32_t* umap;                        // [n_reads]: (unitig << 1) | placed reversed, 0xFFFFFFFF for a removed read
+  unsigned long long* trim;              // TRIM_WORDS u64, zeroed before round 1: the TRIM_C_* counters (trim_slot), the lifted records at
+                                         // TRIM_LIFTED, and at TRIM_ROUND0 + r whether round r removed something
+  uint32_t round;                        // 1 .. max_rounds: a trim round; 0: the pass that writes the result
+  uint32_t min_branch_length, min_branch_coverage;
+  sigax_edge* uedges;                    // [n_edges], or NULL: no lifted records
+  uint32_t* eflag;                       // [n_edges]: the record is lifted
+  unsigned long long* escan;             // [n_edges + 1]: where
+  unsigned long long* epartial;          // scan_partials_needed(n_edges) u64
+};
+// A trim counter is TRIM_SLOTS partial sums 256 bytes apart, a wave adding to the slot of its number: where most unitigs go
+// in a round nearly every wave adds, and adds to one address serialise.
+enum { TRIM_C_ISLANDS = 0, TRIM_C_DEAD_ENDS = 1, TRIM_C_READS = 2, TRIM_C_DROPPED = 3, TRIM_COUNTERS = 4, TRIM_SLOTS = 32, TRIM_STRIDE = 32,
+       TRIM_LIFTED = TRIM_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, TRIM_ROUND0 = TRIM_LIFTED + 8, TRIM_MAX_ROUNDS = 64,
+       TRIM_WORDS = TRIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
+static const uint32_t TRIM_NO_COVERAGE = 0xFFFFFFFFu;
 unsigned unitig_rounds(unsigned long long n_reads);  // ceil(log2 n_reads) + 1: the pointer-jumping launches of one ranking
 void launch_unitigs(const UnitigArgs& a, hipStream_t st);
 void launch_unitig_bases(const UnitigArgs& a, hipStream_t st);  // the last phase alone, over what launch_unitigs left (sigax_unitigs_bases_device)
+// one trim round (a.round >= 1): the graph of the alive reads, the verdict per unitig, removed[] marked.  Its launches leave at
+// once when the round before it removed nothing.  The caller resets deg, closing, counts and link before each round and
+// before the launch_unitigs_trim (a.round = 0) that writes the result; launch_unitig_lift then writes uedges and status[6 .. 11].
+void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st);
+void launch_unitigs_trim(const UnitigTrimArgs& a, hipStream_t st);
+void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st);
 
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);

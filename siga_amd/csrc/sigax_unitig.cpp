@@ -74,6 +74,33 @@ UnitigArgs unitig_args(const sigax_edge* d_edges, u64 n_edges, const void* d_len
   return a;
 }
 
+// the trim calls' scratch: the unitig call's, then what the rounds and the lifted records need
+struct TrimWork {
+  UnitigWork u;
+  u64 trim, verdict, umap, eflag, escan, epartial, bytes;
+};
+TrimWork trim_work(u64 n, u64 n_edges, bool graph) {
+  TrimWork w;
+  w.u = unitig_work(n);
+  u64 at = w.u.bytes;
+  auto take = [&](u64 bytes) {
+    const u64 here = at;
+    at += (bytes + 15) & ~15ull;
+    return here;
+  };
+  w.trim = take(TRIM_WORDS * 8);
+  w.verdict = take(n * 4);
+  w.umap = take(n * 4);
+  w.eflag = w.escan = w.epartial = at;
+  if (graph) {
+    w.eflag = take(n_edges * 4);
+    w.escan = take((n_edges + 1) * 8);
+    w.epartial = take(scan_partials_needed(n_edges) * 8);
+  }
+  w.bytes = at;
+  return w;
+}
+
 int unitig_limits(u64 n_reads, u64 n_edges) {
   if (n_reads >= (1ull << 31)) return sigax_fail(SIGAX_E_ARG, "2^31 reads or more: a state names a read end in 32 bits");
   if (n_edges > (1ull << 32)) return sigax_fail(SIGAX_E_ARG, "more than 2^32 records");
@@ -81,6 +108,13 @@ int unitig_limits(u64 n_reads, u64 n_edges) {
 }
 
 thread_local u64 t_last_status[6] = {0, 0, 0, 0, 0, 0};
+
+int trim_opts_ok(const sigax_trim_opts* o) {
+  if (!o) return sigax_fail(SIGAX_E_ARG, "NULL where the trim options are required");
+  if (o->reserved != 0) return sigax_fail(SIGAX_E_ARG, "sigax_trim_opts.reserved must be 0");
+  if (o->max_rounds > TRIM_MAX_ROUNDS) return sigax_fail(SIGAX_E_ARG, "max_rounds %u: at most %d", o->max_rounds, (int)TRIM_MAX_ROUNDS);
+  return SIGAX_OK;
+}
 
 }  // namespace
 
@@ -236,5 +270,201 @@ extern "C" int sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t 
   *uflags = h_uf;
   *layout = h_lay;
   if (useqs) *useqs = h_us;
+  return SIGAX_OK;
+}
+
+// ---- tip trimming and the lifted records ----
+extern "C" int sigax_unitigs_trim_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, uint64_t* bytes) {
+  if (!bytes) return sigax_fail(SIGAX_E_ARG, "bad argument");
+  const int rc = unitig_limits(n_reads, n_edges);
+  if (rc != SIGAX_OK) return rc;
+  *bytes = trim_work(n_reads, n_edges, want_graph != 0).bytes;
+  return SIGAX_OK;
+}
+
+// paced: the host form's loop -- it reads each round's flag and stops after the first round that removed nothing, where the
+// device form enqueues every round and lets the idle ones leave at once
+static int unitigs_trim_run(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                            const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts, void* d_seq_offs,
+                            void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, sigax_edge* d_uedges,
+                            void* d_status12, void* d_work, uint64_t work_bytes, void* stream, bool paced) {
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  const int ro = trim_opts_ok(opts);
+  if (ro != SIGAX_OK) return ro;
+  if (n_reads && (!d_lengths || !d_seqs || !d_offs || !d_seq_offs || !d_lay_offs || !d_uflags || !d_layout || !d_removed || !d_status12 ||
+                  !d_work || (n_edges && !d_edges)))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (n_reads && (((uintptr_t)d_edges | (uintptr_t)d_layout | (uintptr_t)d_useqs | (uintptr_t)d_uedges | (uintptr_t)d_work) & 15))
+    return sigax_fail(SIGAX_E_ARG, "d_edges, d_layout, d_useqs, d_uedges and d_work must be 16-byte aligned");
+  if (n_reads && (((uintptr_t)d_offs | (uintptr_t)d_seq_offs | (uintptr_t)d_lay_offs | (uintptr_t)d_status12) & 7))
+    return sigax_fail(SIGAX_E_ARG, "d_offs, d_seq_offs, d_lay_offs and d_status12 must be 8-byte aligned");
+  if (n_reads && ((uintptr_t)d_removed & 3)) return sigax_fail(SIGAX_E_ARG, "d_removed must be 4-byte aligned");
+  const TrimWork w = trim_work(n_reads, n_edges, d_uedges != nullptr);
+  if (n_reads && work_bytes < w.bytes)
+    return sigax_fail(SIGAX_E_ARG, "workspace of %llu bytes, %llu needed (sigax_unitigs_trim_workspace)", (u64)work_bytes, w.bytes);
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t st = (hipStream_t)stream;
+  if (n_reads == 0) {
+    if (d_status12) HIP_TRY(hipMemsetAsync(d_status12, 0, 96, st));
+    return SIGAX_OK;
+  }
+  UnitigTrimArgs a;
+  static_cast<UnitigArgs&>(a) = unitig_args(d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, d_seq_offs, d_lay_offs, d_uflags,
+                                            d_layout, d_useqs, d_status12, d_work);
+  char* base = (char*)d_work;
+  a.removed = (uint32_t*)d_removed;
+  a.trim = (u64*)(base + w.trim);
+  a.verdict = (uint32_t*)(base + w.verdict);
+  a.umap = (uint32_t*)(base + w.umap);
+  a.round = 0;
+  a.min_branch_length = opts->min_branch_length;
+  a.min_branch_coverage = opts->min_branch_coverage;
+  a.uedges = d_uedges;
+  a.eflag = (uint32_t*)(base + w.eflag);
+  a.escan = (u64*)(base + w.escan);
+  a.epartial = (u64*)(base + w.epartial);
+  HIP_TRY(hipMemsetAsync(d_removed, 0, (size_t)n_reads * 4, st));
+  HIP_TRY(hipMemsetAsync(a.trim, 0, TRIM_WORDS * 8, st));
+  auto reset = [&]() -> hipError_t {  // every pass over degrees, links and counts of its own
+    const hipError_t e = hipMemsetAsync(base + w.u.zero_from, 0, (size_t)w.u.zero_bytes, st);
+    return e != hipSuccess ? e : hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st);
+  };
+  for (uint32_t r = 1; r <= opts->max_rounds; ++r) {
+    a.round = r;
+    HIP_TRY(reset());
+    launch_trim_round(a, st);
+    if (paced) {
+      u64 flag = 0;
+      HIP_TRY(hipMemcpyAsync(&flag, a.trim + TRIM_ROUND0 + r, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (flag == 0) break;
+    }
+  }
+  a.round = 0;  // the unitigs of what is left
+  HIP_TRY(reset());
+  launch_unitigs_trim(a, st);
+  launch_unitig_lift(a, st);
+  HIP_TRY(hipGetLastError());
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_trim_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                         const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                                         void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                         void* d_removed, sigax_edge* d_uedges, void* d_status12, void* d_work, uint64_t work_bytes,
+                                         void* stream) {
+  return unitigs_trim_run(device, d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, opts, d_seq_offs, d_lay_offs, d_uflags,
+                          d_layout, d_useqs, d_removed, d_uedges, d_status12, d_work, work_bytes, stream, false);
+}
+
+extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                       const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                                       uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                       sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
+                                       uint64_t status12[12]) {
+  if (!n_unitigs || !seq_offs || !lay_offs || !uflags || !layout || !removed || !status12 || (n_reads && (!lengths || !seqs || !offs)) ||
+      (n_edges && !edges))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  *n_unitigs = 0;
+  *seq_offs = nullptr;
+  *lay_offs = nullptr;
+  *uflags = nullptr;
+  *layout = nullptr;
+  *removed = nullptr;
+  if (useqs) *useqs = nullptr;
+  if (uedges) *uedges = nullptr;
+  for (int k = 0; k < 12; ++k) status12[k] = 0;
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  const int ro = trim_opts_ok(opts);
+  if (ro != SIGAX_OK) return ro;
+  const u64 n = n_reads;
+  for (u64 i = 0; i < n; ++i)
+    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] != lengths[i]) return sigax_fail(SIGAX_E_ARG, "read %llu: offsets and length disagree", i);
+  const u64 b0 = n ? offs[0] : 0, nb = n ? offs[n] - b0 : 0;
+  std::vector<uint64_t> rebased;
+  if (b0) {
+    rebased.resize((size_t)n + 1);
+    for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
+    offs = rebased.data();
+  }
+  u64 status[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  DevGuard g;
+  void *d_edges = nullptr, *d_lengths = nullptr, *d_seqs = nullptr, *d_offs = nullptr, *d_so = nullptr, *d_lo = nullptr, *d_uf = nullptr,
+       *d_lay = nullptr, *d_us = nullptr, *d_rm = nullptr, *d_ue = nullptr, *d_status = nullptr, *d_work = nullptr;
+  if (n) {
+    HIP_TRY(hipSetDevice(device));
+    const u64 wb = trim_work(n, n_edges, uedges != nullptr).bytes;
+    HIP_TRY(g.alloc(&d_edges, (size_t)n_edges * sizeof(sigax_edge)));
+    HIP_TRY(g.alloc(&d_lengths, (size_t)n * 4));
+    HIP_TRY(g.alloc(&d_seqs, (size_t)nb + 16));
+    HIP_TRY(g.alloc(&d_offs, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_so, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_lo, ((size_t)n + 1) * 8));
+    HIP_TRY(g.alloc(&d_uf, (size_t)n * 4));
+    HIP_TRY(g.alloc(&d_lay, (size_t)n * sizeof(sigax_placement)));
+    if (useqs) HIP_TRY(g.alloc(&d_us, (size_t)nb + 16));
+    HIP_TRY(g.alloc(&d_rm, (size_t)n * 4));
+    if (uedges) HIP_TRY(g.alloc(&d_ue, (size_t)n_edges * sizeof(sigax_edge) + 16));
+    HIP_TRY(g.alloc(&d_status, 96));
+    HIP_TRY(g.alloc(&d_work, (size_t)wb));
+    if (n_edges) HIP_TRY(hipMemcpy(d_edges, edges, (size_t)n_edges * sizeof(sigax_edge), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (nb) HIP_TRY(hipMemcpy(d_seqs, seqs + b0, (size_t)nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    const int rc = unitigs_trim_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, opts, d_so, d_lo, d_uf,
+                                    (sigax_placement*)d_lay, d_us, d_rm, (sigax_edge*)d_ue, d_status, d_work, wb, nullptr, true);
+    if (rc != SIGAX_OK) return rc;
+    HIP_TRY(hipMemcpy(status, d_status, 96, hipMemcpyDeviceToHost));  // (waits for the null stream's kernels)
+    if (status[0] > n || status[1] > nb || status[9] > n || status[11] > n_edges)
+      return sigax_fail(SIGAX_E_DEVICE, "unitig counts beyond their buffers");
+  }
+  const u64 nu = status[0], bases = status[1], placed = n - status[9], ne = uedges ? status[11] : 0;
+  uint64_t* h_so = (uint64_t*)malloc(((size_t)nu + 1) * 8);
+  uint64_t* h_lo = (uint64_t*)malloc(((size_t)nu + 1) * 8);
+  uint32_t* h_uf = (uint32_t*)malloc(nu ? (size_t)nu * 4 : 4);
+  sigax_placement* h_lay = (sigax_placement*)malloc(placed ? (size_t)placed * sizeof(sigax_placement) : sizeof(sigax_placement));
+  char* h_us = useqs ? (char*)malloc(bases ? (size_t)bases : 1) : nullptr;
+  uint32_t* h_rm = (uint32_t*)malloc(n ? (size_t)n * 4 : 4);
+  sigax_edge* h_ue = uedges ? (sigax_edge*)malloc(ne ? (size_t)ne * sizeof(sigax_edge) : sizeof(sigax_edge)) : nullptr;
+  auto drop = [&] {
+    free(h_so);
+    free(h_lo);
+    free(h_uf);
+    free(h_lay);
+    free(h_us);
+    free(h_rm);
+    free(h_ue);
+  };
+  if (!h_so || !h_lo || !h_uf || !h_lay || !h_rm || (useqs && !h_us) || (uedges && !h_ue)) {
+    drop();
+    return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
+  }
+  h_so[0] = 0;
+  h_lo[0] = 0;
+  hipError_t e = hipSuccess;
+  if (n) {
+    e = hipMemcpy(h_so, d_so, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_lo, d_lo, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nu) e = hipMemcpy(h_uf, d_uf, (size_t)nu * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && placed) e = hipMemcpy(h_lay, d_lay, (size_t)placed * sizeof(sigax_placement), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && useqs && bases) e = hipMemcpy(h_us, d_us, (size_t)bases, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_rm, d_rm, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && ne) e = hipMemcpy(h_ue, d_ue, (size_t)ne * sizeof(sigax_edge), hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) {
+    drop();
+    return sigax_fail(SIGAX_E_DEVICE, "copying the unitigs: %s", hipGetErrorString(e));
+  }
+  for (int k = 0; k < 12; ++k) status12[k] = status[k];
+  *n_unitigs = nu;
+  *seq_offs = h_so;
+  *lay_offs = h_lo;
+  *uflags = h_uf;
+  *layout = h_lay;
+  *removed = h_rm;
+  if (useqs) *useqs = h_us;
+  if (uedges) *uedges = h_ue;
   return SIGAX_OK;
 }

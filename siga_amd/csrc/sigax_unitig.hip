@@ -25,10 +25,20 @@
 //                 destination range the 64 cover.  A piece that lies in one stretch is one 16-byte load (ascending, or
 //                 descending and complemented for a reverse placement) and one 16-byte store; a piece over several
 //                 stretches is gathered byte by byte; the range's unaligned head and tail are byte stores.
+// Tip trimming and the graph between the unitigs (sigax_unitigs_trim_*; tests/trim_cases.py::expected_trim): the
+// kernels above as <TRIM = true> skip reads with removed[r] != 0 and the records that touch one, and
+//   k_trim_decide one lane per read: a head judges its unitig by its two end degrees, its bases and its reads (what
+//                 k_uni_heads left) and writes the verdict under its own id; islands and dead ends are counted
+//   k_trim_mark   one lane per read: it finds its head through the final rank entry and takes the verdict into removed[]
+//   k_lift_flag / k_lift_write   one lane per record: a live record that is no link of the final graph is flagged, launch_scan
+//                 gives it its place, and it is written over unitig ids and unitig ends (one 16-byte load, one 16-byte store)
+// A round's launches leave at once when the round before it removed nothing (idle_round).
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
 // consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
 // beyond the 64 descriptors, no MFMA.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "sigax_kernels.h"
 
@@ -71,14 +81,45 @@ __device__ __forceinline__ u64 wave_total(u64 v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void k_uni_degree(UnitigArgs A) {
+// TRIM: the kernels of sigax_unitigs_trim_*: reads with removed[r] != 0 are not there, nor are the records that touch one.
+// They take the longer argument block; TRIM = false is sigax_unitigs_device's code as it was, over the block it had.
+template <bool TRIM>
+using ArgsOf = std::conditional_t<TRIM, UnitigTrimArgs, UnitigArgs>;
+// a trim round after one that removed nothing has nothing to do (as k_uni_init(second) when no cycle was cut)
+template <bool TRIM>
+__device__ __forceinline__ bool idle_round(const ArgsOf<TRIM>& A) {
+  if constexpr (TRIM) return A.round > 1u && A.trim[TRIM_ROUND0 + A.round - 1u] == 0ull;
+  return false;
+}
+// where this wave adds to trim counter c
+__device__ __forceinline__ u64* trim_slot(const UnitigTrimArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  return A.trim + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 trim_count(const UnitigTrimArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.trim[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+// both reads of a kept record alive
+template <bool TRIM>
+__device__ __forceinline__ bool live_pair(const ArgsOf<TRIM>& A, const RecClass& c) {
+  if constexpr (TRIM) return (A.removed[c.sq >> 1] | A.removed[c.st >> 1]) == 0u;
+  return true;
+}
+
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
+  if (idle_round<TRIM>(A)) return;
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  u32 bad = 0, low = 0;
+  u32 bad = 0, low = 0, dropped = 0;
   if (i < A.n_edges) {
     const RecClass c = classify(reinterpret_cast<const uint4*>(A.edges)[i], A);
     bad = c.kind == 0u;
     low = c.kind == 1u;
-    if (c.kind == 2u) {
+    if (c.kind == 2u && !live_pair<TRIM>(A, c)) {
+      dropped = 1;
+    } else if (c.kind == 2u) {
       if (c.contain) {  // both directions (src/bigraph.cpp:497-522): every end of both reads
         atomicAdd(&A.deg[c.sq & ~1u], 1u);
         atomicAdd(&A.deg[c.sq | 1u], 1u);
@@ -95,15 +136,21 @@ __global__ __launch_bounds__(256) void k_uni_degree(UnitigArgs A) {
     if (tb) atomicAdd(&A.counts[UNI_C_BAD], tb);
     if (tl) atomicAdd(&A.counts[UNI_C_LOW], tl);
   }
+  if constexpr (TRIM) {
+    const u64 td = wave_total(dropped);
+    if ((threadIdx.x & 63u) == 0u && td && A.round == 0u) atomicAdd(trim_slot(A, TRIM_C_DROPPED), td);
+  }
 }
 
-__global__ __launch_bounds__(256) void k_uni_links(UnitigArgs A) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_links(ArgsOf<TRIM> A) {
+  if (idle_round<TRIM>(A)) return;
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
   u32 simple = 0;
   if (i < A.n_edges) {
     const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
     const RecClass c = classify(rec, A);
-    if (c.kind == 2u && !c.contain && !c.self && A.deg[c.sq] == 1u && A.deg[c.st] == 1u) {
+    if (c.kind == 2u && !c.contain && !c.self && live_pair<TRIM>(A, c) && A.deg[c.sq] == 1u && A.deg[c.st] == 1u) {
       A.link[c.sq] = make_uint2(c.st, rec.z);
       A.link[c.st] = make_uint2(c.sq, rec.z);
       simple = 1;
@@ -117,7 +164,9 @@ __global__ __launch_bounds__(256) void k_uni_links(UnitigArgs A) {
 // rk[s] = {successor or NIL, state reached so far, hops so far, smallest read id so far}; dist[s] = bases so far: a hop
 // into read y over an overlap of len adds L[y] - len.  second: the ranking after the cut, which has nothing to do when
 // nothing was cut.
-__global__ __launch_bounds__(256) void k_uni_init(UnitigArgs A, uint4* __restrict__ rk, u64* __restrict__ dist, int second) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_init(ArgsOf<TRIM> A, uint4* __restrict__ rk, u64* __restrict__ dist, int second) {
+  if (idle_round<TRIM>(A)) return;
   if (second && A.counts[UNI_C_CYCLES] == 0ull) return;
   const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
   if (s >= 2 * A.n_reads) return;
@@ -133,8 +182,10 @@ __global__ __launch_bounds__(256) void k_uni_init(UnitigArgs A, uint4* __restric
   }
 }
 
-__global__ __launch_bounds__(256) void k_uni_jump(UnitigArgs A, const uint4* __restrict__ in, const u64* __restrict__ din,
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_jump(ArgsOf<TRIM> A, const uint4* __restrict__ in, const u64* __restrict__ din,
                                                   uint4* __restrict__ out, u64* __restrict__ dout, int second) {
+  if (idle_round<TRIM>(A)) return;
   if (second && A.counts[UNI_C_CYCLES] == 0ull) return;
   const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
   if (s >= 2 * A.n_reads) return;
@@ -149,7 +200,9 @@ __global__ __launch_bounds__(256) void k_uni_jump(UnitigArgs A, const uint4* __r
   dout[s] = d;
 }
 
-__global__ __launch_bounds__(256) void k_uni_cut(UnitigArgs A, const uint4* __restrict__ rk) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_cut(ArgsOf<TRIM> A, const uint4* __restrict__ rk) {
+  if (idle_round<TRIM>(A)) return;
   const u64 m = (u64)blockIdx.x * 256u + threadIdx.x;
   u32 cut = 0;
   if (m < A.n_reads) {
@@ -173,15 +226,19 @@ __global__ __launch_bounds__(256) void k_uni_cut(UnitigArgs A, const uint4* __re
 // it is entered through B and placed forward)
 __device__ __forceinline__ u32 head_dir(const uint4 a0, const uint4 a1) { return (a0.y >> 1) <= (a1.y >> 1) ? 0u : 1u; }
 
-__global__ __launch_bounds__(256) void k_uni_heads(UnitigArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_heads(ArgsOf<TRIM> A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+  if (idle_round<TRIM>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   if (r >= A.n_reads) return;
+  bool alive = true;
+  if constexpr (TRIM) alive = A.removed[r] == 0u;  // a removed read lies alone in the ranking: it heads nothing
   const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
   const u32 d = head_dir(a0, a1);
   const uint4 to = d ? a1 : a0, away = d ? a0 : a1;
   u32 one = 0, reads = 0;
   u64 bases = 0;
-  if (to.z == 0u && to.x == NIL) {  // nothing between r and the head: r is it
+  if (alive && to.z == 0u && to.x == NIL) {  // nothing between r and the head: r is it
     one = 1;
     reads = away.z + 1u;
     bases = (u64)A.lengths[r] + dist[2 * r + (d ^ 1u)];
@@ -193,32 +250,41 @@ __global__ __launch_bounds__(256) void k_uni_heads(UnitigArgs A, const uint4* __
 }
 
 // ---- phase 6: placements ----
-__global__ __launch_bounds__(256) void k_uni_place(UnitigArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_place(ArgsOf<TRIM> A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.n_reads;
   if (r >= n) return;
   const u64 *unum = A.scan, *layr = A.scan + (n + 1), *lo = A.scan + 2 * (n + 1), *hi = A.scan + 3 * (n + 1);
-  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
-  const u32 d = head_dir(a0, a1);
-  const uint4 to = d ? a1 : a0;
-  const u64 h = to.y >> 1;  // the head
-  if (h >= n) return;
-  const u64 off = dist[2 * r + d], slot = layr[h] + to.z, seq0 = lo[h] + (hi[h] << 32);
-  if (slot < n) {
-    // entered through the end it is left through on the way to the head: through B = forward
-    reinterpret_cast<uint4*>(A.layout)[slot] = make_uint4((u32)r, d ? SIGAX_PLACED_REV : 0u, (u32)off, (u32)(off >> 32));
-    // the bases r adds: its last L - len, len = the overlap with the read before it
-    const uint2 lk = A.link[2 * r + d];
-    const u64 skip = lk.x == NIL ? 0ull : (u64)lk.y, L = A.lengths[r], b0 = A.offs[r];
-    A.dst[slot] = seq0 + off + skip;
-    A.src[slot] = (d ? b0 + L - 1ull - skip : b0 + skip) | ((u64)d << 63);
+  bool alive = true;
+  if constexpr (TRIM) {  // a removed read has no placement and heads nothing
+    alive = A.removed[r] == 0u;
+    if (!alive) A.umap[r] = NIL;
   }
-  if (to.z == 0u && to.x == NIL) {  // the head writes its unitig's entries
-    const u64 u = unum[r];
-    if (u < n) {
-      A.seq_offs[u] = seq0;
-      A.lay_offs[u] = layr[r];
-      A.uflags[u] = A.closing[r];
+  if (alive) {
+    const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+    const u32 d = head_dir(a0, a1);
+    const uint4 to = d ? a1 : a0;
+    const u64 h = to.y >> 1;  // the head
+    if (h >= n) return;
+    const u64 off = dist[2 * r + d], slot = layr[h] + to.z, seq0 = lo[h] + (hi[h] << 32);
+    if (slot < n) {
+      // entered through the end it is left through on the way to the head: through B = forward
+      reinterpret_cast<uint4*>(A.layout)[slot] = make_uint4((u32)r, d ? SIGAX_PLACED_REV : 0u, (u32)off, (u32)(off >> 32));
+      // the bases r adds: its last L - len, len = the overlap with the read before it
+      const uint2 lk = A.link[2 * r + d];
+      const u64 skip = lk.x == NIL ? 0ull : (u64)lk.y, L = A.lengths[r], b0 = A.offs[r];
+      A.dst[slot] = seq0 + off + skip;
+      A.src[slot] = (d ? b0 + L - 1ull - skip : b0 + skip) | ((u64)d << 63);
+    }
+    if constexpr (TRIM) A.umap[r] = ((u32)unum[h] << 1) | d;
+    if (to.z == 0u && to.x == NIL) {  // the head writes its unitig's entries
+      const u64 u = unum[r];
+      if (u < n) {
+        A.seq_offs[u] = seq0;
+        A.lay_offs[u] = layr[r];
+        A.uflags[u] = A.closing[r];
+      }
     }
   }
   if (r == 0) {
@@ -228,6 +294,9 @@ __global__ __launch_bounds__(256) void k_uni_place(UnitigArgs A, const uint4* __
       A.lay_offs[U] = layr[n];
     }
     A.dst[n] = bases;
+    if constexpr (TRIM) {  // the placements are those of the alive reads: k_uni_bases<true> stops after them
+      if (layr[n] < n) A.dst[layr[n]] = bases;
+    }
     const u64 cyc = A.counts[UNI_C_CYCLES], simple = A.counts[UNI_C_SIMPLE];
     A.status[0] = U;
     A.status[1] = bases;
@@ -248,13 +317,19 @@ struct BaseSh {
   u64 src[4][64];
 };
 
-__global__ __launch_bounds__(256) void k_uni_bases(UnitigArgs A) {
+template <bool TRIM>
+__global__ __launch_bounds__(256) void k_uni_bases(ArgsOf<TRIM> A) {
   __shared__ BaseSh sh;
   const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const u64 n = A.n_reads, first = ((u64)blockIdx.x * 4u + wave) * 64u;  // the wave's first placement
+  u64 n = A.n_reads;
+  if constexpr (TRIM) {  // the placements of the alive reads (k_uni_place<true> closed dst after them)
+    const u64 placed = A.scan[(A.n_reads + 1) + A.n_reads];
+    if (placed < n) n = placed;
+  }
+  const u64 first = ((u64)blockIdx.x * 4u + wave) * 64u;  // the wave's first placement
   const bool live = first < n;
   // bytes of reads: nothing beyond src_end is read, nothing beyond dst_cap written (sum of the unitigs <= sum of the reads)
-  const u64 src_end = A.offs[n], dst_cap = src_end - A.offs[0];
+  const u64 src_end = A.offs[A.n_reads], dst_cap = src_end - A.offs[0];
   const u32 cnt = live ? (u32)(n - first < 64 ? n - first : 64) : 0u;
   if (lane < cnt) {
     sh.dst[wave][lane] = A.dst[first + lane];
@@ -344,7 +419,133 @@ __global__ __launch_bounds__(256) void k_uni_bases(UnitigArgs A) {
   }
 }
 
+// ---- tip trimming: one round's verdicts and marks (TrimVisitor, src/bigraph_visitors.cpp:1119-1161) ----
+// One lane per read.  A head judges its unitig: its left end is the end the head is entered through (nothing links there),
+// its right end the state the walk away from the head stops in; a ring's two ends each carry its closing record.
+__global__ __launch_bounds__(256) void k_trim_decide(UnitigTrimArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<true>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 island = 0, dead_end = 0;
+  if (r < n) {
+    u32 v = 0;
+    if (A.removed[r] == 0u && A.cnt[r] != 0u) {
+      const u64 K = A.cnt[n + 1 + r], bases = (u64)A.cnt[2 * (n + 1) + r] | ((u64)A.cnt[3 * (n + 1) + r] << 32);
+      const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+      const u32 d = head_dir(a0, a1);
+      const u32 last = (d ? a0 : a1).y;
+      const u32 dl = A.deg[2 * r + d], dr = (u64)last < 2 * n ? A.deg[last] : 1u;
+      const u64 L = A.min_branch_length, C = A.min_branch_coverage;
+      if ((dl == 0u || dr == 0u) && bases <= L &&
+          (A.min_branch_coverage == TRIM_NO_COVERAGE || (K - 1ull) * (L ? L : 1ull) <= ((C ? C : 1ull) - 1ull) * bases)) {
+        v = 1;
+        island = dl == 0u && dr == 0u;
+        dead_end = island ^ 1u;
+      }
+    }
+    A.verdict[r] = v;
+  }
+  const u64 ti = wave_total(island), td = wave_total(dead_end);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (ti) atomicAdd(trim_slot(A, TRIM_C_ISLANDS), ti);
+    if (td) atomicAdd(trim_slot(A, TRIM_C_DEAD_ENDS), td);
+  }
+}
+
+// One lane per read: the verdict lies under its head, which the final rank entry names.
+__global__ __launch_bounds__(256) void k_trim_mark(UnitigTrimArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<true>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 gone = 0;
+  if (r < n && A.removed[r] == 0u) {
+    const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+    const u64 h = (head_dir(a0, a1) ? a1 : a0).y >> 1;
+    if (h < n && A.verdict[h] != 0u) {
+      A.removed[r] = A.round;
+      gone = 1;
+    }
+  }
+  const u64 tg = wave_total(gone);
+  if ((threadIdx.x & 63u) == 0u && tg) {
+    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
+    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+  }
+}
+
+// ---- the records that were not merged, over unitigs ----
+// lifted: kept, both reads alive, and not a link of the final graph (a ring's closing record was one and was cut: lifted)
+__device__ __forceinline__ bool lifted(const UnitigTrimArgs& A, const RecClass& c) {
+  if (c.kind != 2u || !live_pair<true>(A, c)) return false;
+  const bool simple = !c.contain && !c.self && A.deg[c.sq] == 1u && A.deg[c.st] == 1u;
+  return !(simple && A.link[c.sq].x == c.st);
+}
+
+__global__ __launch_bounds__(256) void k_lift_flag(UnitigTrimArgs A) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n_edges) return;
+  A.eflag[i] = lifted(A, classify(reinterpret_cast<const uint4*>(A.edges)[i], A)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_lift_write(UnitigTrimArgs A) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n_edges || A.eflag[i] == 0u) return;
+  const u64 at = A.escan[i];
+  if (at >= A.n_edges) return;
+  const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
+  const RecClass c = classify(rec, A);  // (kept: the flag says so)
+  const u32 mq = A.umap[c.sq >> 1], mt = A.umap[c.st >> 1];
+  // read end e of a read placed reversed is the other end of its unitig
+  const u32 eq = (c.sq ^ mq) & 1u, et = (c.st ^ mt) & 1u;
+  const u32 b0 = eq == 0u, b1 = et == 1u;
+  reinterpret_cast<uint4*>(A.uedges)[at] = make_uint4(mq >> 1, mt >> 1, rec.z, b0 | (b1 << 1) | ((b0 ^ b1) << 2));
+}
+
+__global__ void k_trim_status(UnitigTrimArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.trim[TRIM_ROUND0 + r] != 0ull;
+  A.status[6] = rounds;
+  A.status[7] = trim_count(A, TRIM_C_ISLANDS);
+  A.status[8] = trim_count(A, TRIM_C_DEAD_ENDS);
+  A.status[9] = trim_count(A, TRIM_C_READS);
+  A.status[10] = trim_count(A, TRIM_C_DROPPED);
+  A.status[11] = A.uedges ? A.trim[TRIM_LIFTED] : 0ull;
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
+
+// degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
+template <bool TRIM>
+unsigned launch_graph(const ArgsOf<TRIM>& a, hipStream_t st) {
+  const u64 n = a.n_reads, ns = 2 * n;
+  if (a.n_edges) {
+    hipLaunchKernelGGL(k_uni_degree<TRIM>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_uni_links<TRIM>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+  }
+  const unsigned rounds = unitig_rounds(n);
+  uint4* rk[2] = {reinterpret_cast<uint4*>(a.rank[0]), reinterpret_cast<uint4*>(a.rank[1])};
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(k_uni_init<TRIM>, dim3(blocks_of(ns)), dim3(256), 0, st, a, rk[0], a.dist[0], pass);
+    for (unsigned r = 0; r < rounds; ++r)
+      hipLaunchKernelGGL(k_uni_jump<TRIM>, dim3(blocks_of(ns)), dim3(256), 0, st, a, (const uint4*)rk[r & 1], (const u64*)a.dist[r & 1], rk[(r & 1) ^ 1],
+                         a.dist[(r & 1) ^ 1], pass);
+    if (pass == 0) hipLaunchKernelGGL(k_uni_cut<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, (const uint4*)rk[rounds & 1]);
+  }
+  return rounds & 1;
+}
+
+template <bool TRIM>
+void launch_unitigs_t(const ArgsOf<TRIM>& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  const unsigned f = launch_graph<TRIM>(a, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  const u64* fdist = a.dist[f];
+  hipLaunchKernelGGL(k_uni_heads<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
+  for (int k = 0; k < 4; ++k) launch_scan(a.cnt + (u64)k * (n + 1), n, a.partial, a.scan + (u64)k * (n + 1), a.scan_total, st);
+  hipLaunchKernelGGL(k_uni_place<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
+  if (a.useqs) hipLaunchKernelGGL(k_uni_bases<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a);
+}
 }  // namespace
 
 unsigned unitig_rounds(unsigned long long n_reads) {
@@ -354,29 +555,33 @@ unsigned unitig_rounds(unsigned long long n_reads) {
 }
 
 void launch_unitigs(const UnitigArgs& a, hipStream_t st) {
-  const u64 n = a.n_reads, ns = 2 * n;
-  if (n == 0) return;
-  if (a.n_edges) {
-    hipLaunchKernelGGL(k_uni_degree, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_uni_links, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
-  }
-  const unsigned rounds = unitig_rounds(n);
-  uint4* rk[2] = {reinterpret_cast<uint4*>(a.rank[0]), reinterpret_cast<uint4*>(a.rank[1])};
-  for (int pass = 0; pass < 2; ++pass) {
-    hipLaunchKernelGGL(k_uni_init, dim3(blocks_of(ns)), dim3(256), 0, st, a, rk[0], a.dist[0], pass);
-    for (unsigned r = 0; r < rounds; ++r)
-      hipLaunchKernelGGL(k_uni_jump, dim3(blocks_of(ns)), dim3(256), 0, st, a, (const uint4*)rk[r & 1], (const u64*)a.dist[r & 1], rk[(r & 1) ^ 1],
-                         a.dist[(r & 1) ^ 1], pass);
-    if (pass == 0) hipLaunchKernelGGL(k_uni_cut, dim3(blocks_of(n)), dim3(256), 0, st, a, (const uint4*)rk[rounds & 1]);
-  }
-  const uint4* fin = rk[rounds & 1];
-  const u64* fdist = a.dist[rounds & 1];
-  hipLaunchKernelGGL(k_uni_heads, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
-  for (int k = 0; k < 4; ++k) launch_scan(a.cnt + (u64)k * (n + 1), n, a.partial, a.scan + (u64)k * (n + 1), a.scan_total, st);
-  hipLaunchKernelGGL(k_uni_place, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
-  if (a.useqs) hipLaunchKernelGGL(k_uni_bases, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  if (a.n_reads) launch_unitigs_t<false>(a, st);
+}
+
+void launch_unitigs_trim(const UnitigTrimArgs& a, hipStream_t st) {
+  if (a.n_reads && a.removed) launch_unitigs_t<true>(a, st);
 }
 
 void launch_unitig_bases(const UnitigArgs& a, hipStream_t st) {
-  if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
+  if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases<false>, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
+}
+
+void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  const unsigned f = launch_graph<true>(a, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<true>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+}
+
+void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  if (a.uedges && a.n_edges) {
+    hipLaunchKernelGGL(k_lift_flag, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
+    hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, a);
 }

@@ -90,9 +90,8 @@ static inline char* put_u64(char* p, uint64_t v) {
   return p;
 }
 static const size_t kEdgeLineExtra = 3 + 2 + 6 * 21 + 4;
-static char* write_edge(char* p, const sigax_edge& e, const ReadStore& reads, const uint32_t* lengths) {
-  const std::string_view qn = reads.name(e.query), tn = reads.name(e.target);
-  uint64_t ql = lengths[e.query], tl = lengths[e.target], len = e.length;
+static inline char* write_edge_line(char* p, const sigax_edge& e, const std::string_view qn, const std::string_view tn, uint64_t ql, uint64_t tl) {
+  const uint64_t len = e.length;
   uint64_t s0 = ql - len, e0 = ql - 1, s1 = 0, e1 = len - 1;
   if (e.af & 1u) { uint64_t t = s0; s0 = ql - e0 - 1; e0 = ql - t - 1; }
   if (e.af & 2u) { uint64_t t = s1; s1 = tl - e1 - 1; e1 = tl - t - 1; }
@@ -112,6 +111,14 @@ static char* write_edge(char* p, const sigax_edge& e, const ReadStore& reads, co
   *p++ = (e.af & 4u) ? '1' : '0';
   *p++ = ' '; *p++ = '0'; *p++ = '\n';
   return p;
+}
+static char* write_edge(char* p, const sigax_edge& e, const ReadStore& reads, const uint32_t* lengths) {
+  return write_edge_line(p, e, reads.name(e.query), reads.name(e.target), lengths[e.query], lengths[e.target]);
+}
+void append_edge_line(std::string& o, const sigax_edge& e, std::string_view qn, std::string_view tn, uint64_t ql, uint64_t tl) {
+  const size_t at = o.size();
+  o.resize(at + qn.size() + tn.size() + kEdgeLineExtra);
+  o.resize((size_t)(write_edge_line(&o[at], e, qn, tn, ql, tl) - o.data()));
 }
 
 

@@ -7,6 +7,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -19,6 +20,8 @@
 namespace sigah {
 
 std::string asqg_header(size_t minOverlap);
+// one ED line, as the writer below formats a record, over two vertices given by name and length (the unitig graph of `siga unitig`)
+void append_edge_line(std::string& o, const sigax_edge& e, std::string_view qn, std::string_view tn, uint64_t ql, uint64_t tl);
 
 // ReadInfo{name,length} of the edge converter (src/overlap_builder.cpp:333-343) as lengths + rank of each name under
 // std::string operator< (equal names, equal rank).  A sample sort on the host threads: names enter as (first eight bytes,

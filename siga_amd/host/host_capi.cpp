@@ -239,20 +239,43 @@ int sigah_locate_files(const char* const* paths, uint64_t n_paths, const char* p
 
 // `siga unitig`: FMIndex::load + Unitigger::run; fasta_path "" = stdout, layout_path "" = no layout file; piece_reads = reads per
 // overlap call (0: the default)
-int sigah_unitig_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
-                      const char* fasta_path, const char* layout_path, uint64_t piece_reads, char* err, uint64_t errcap) {
+static int unitig_file(sigah::Unitigger& unitigger, const char* reads_path, const char* prefix, uint64_t min_overlap, int device,
+                       const char* fasta_path, const char* layout_path, uint64_t piece_reads, char* err, uint64_t errcap) {
   sigah::FMIndex fmi;
   if (!sigah::FMIndex::load(prefix, fmi, device)) {
     if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
     return -1;
   }
-  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
   unitigger.setPieceReads((size_t)piece_reads);
   if (!unitigger.run(fmi, reads_path, (size_t)min_overlap, fasta_path ? fasta_path : "", layout_path ? layout_path : "")) {
     if (err && errcap) snprintf(err, errcap, "%s", unitigger.error().c_str());
     return -1;
   }
   return 0;
+}
+int sigah_unitig_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                      const char* fasta_path, const char* layout_path, uint64_t piece_reads, char* err, uint64_t errcap) {
+  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  return unitig_file(unitigger, reads_path, prefix, min_overlap, device, fasta_path, layout_path, piece_reads, err, errcap);
+}
+// ... with tip trimming (cut_terminal rounds, min_branch_coverage -1: no coverage test), the unitig graph (graph_path "" = none)
+// and the removed reads (removed_path "" = none); status8 (unless NULL) = {unitigs, bases, merged, circular, trim rounds, islands,
+// dead ends, reads removed}
+int sigah_unitig_trim_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                           const char* fasta_path, const char* layout_path, uint64_t piece_reads, uint64_t cut_terminal,
+                           uint64_t min_branch_length, int64_t min_branch_coverage, const char* graph_path, const char* removed_path,
+                           uint64_t* status8, char* err, uint64_t errcap) {
+  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  unitigger.setTrim((size_t)cut_terminal, (size_t)min_branch_length, (long)min_branch_coverage);
+  unitigger.setGraph(graph_path ? graph_path : "");
+  unitigger.setRemoved(removed_path ? removed_path : "");
+  const int r = unitig_file(unitigger, reads_path, prefix, min_overlap, device, fasta_path, layout_path, piece_reads, err, errcap);
+  if (r == 0 && status8) {
+    const uint64_t s[8] = {unitigger.unitigs(), unitigger.bases(),    unitigger.merged(),   unitigger.cycles(),
+                           unitigger.trimRounds(), unitigger.islands(), unitigger.deadEnds(), unitigger.readsRemoved()};
+    for (int k = 0; k < 8; ++k) status8[k] = s[k];
+  }
+  return r;
 }
 
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty

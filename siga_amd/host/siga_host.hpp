@@ -191,7 +191,8 @@ class Locator {
 
 // `siga unitig`: the first step of the reference's `siga assemble`, Bigraph::simplify (src/bigraph.cpp:341-414), on the GPU: the
 // reads go through the overlap stages, their edge records stay records (no ASQG), and every unbranched chain of them becomes
-// one unitig (sigax_unitigs_host; the rules in include/sigax.h).  One GPU.
+// one unitig (sigax_unitigs_host; the rules in include/sigax.h).  With setTrim / setGraph / setRemoved also the loop that follows
+// in assemble (TrimVisitor and simplify() in turn) and the graph between the unitigs (sigax_unitigs_trim_host).  One GPU.
 class Unitigger {
  public:
   explicit Unitigger(bool irreducible = true, bool rc = true) : _irreducible(irreducible), _rc(rc), _unitigs(0), _bases(0), _merged(0), _cycles(0) {}
@@ -202,6 +203,24 @@ class Unitigger {
            const std::string& layout = std::string(), size_t threads = 1);
   // reads per overlap call (0: 2^20); the records do not depend on it
   void setPieceReads(size_t n) { _piece = n; }
+  // Tip trimming as the reference's `assemble` does it (TrimVisitor and simplify() in turn, src/assembler.cpp:138-159): up to
+  // `rounds` rounds (-x; 0, the default: none, and the output is the one without this call) remove every dead end and island
+  // of at most minBranchLength bases (-n) and, with minBranchCoverage >= 0 (-C; -1: no such test), of low coverage
+  // (sigax_unitigs_trim_host; the rules in include/sigax.h).
+  void setTrim(size_t rounds, size_t minBranchLength, long minBranchCoverage = -1) {
+    _rounds = rounds;
+    _minBranchLength = minBranchLength;
+    _minBranchCoverage = minBranchCoverage;
+  }
+  // The graph between the unitigs as ASQG (gzip when the name ends in .gz): the header, "VT\tunitig-<n>\t<bases>\tSS:i:0" with
+  // "\tCR:i:<reads>" for more than one read, then one ED line per record that was not merged, over unitig names and lengths.
+  void setGraph(const std::string& path) { _graph = path; }
+  // one "name\tround" line per removed read, in read order
+  void setRemoved(const std::string& path) { _removed = path; }
+  uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something
+  uint64_t islands() const { return _islands; }
+  uint64_t deadEnds() const { return _deadEnds; }
+  uint64_t readsRemoved() const { return _readsRemoved; }
   uint64_t unitigs() const { return _unitigs; }
   uint64_t bases() const { return _bases; }
   uint64_t merged() const { return _merged; }  // simple records merged
@@ -212,6 +231,10 @@ class Unitigger {
   bool _irreducible, _rc;
   uint64_t _unitigs, _bases, _merged, _cycles;
   size_t _piece = 0;
+  size_t _rounds = 0, _minBranchLength = 150;
+  long _minBranchCoverage = -1;
+  std::string _graph, _removed;
+  uint64_t _trimRounds = 0, _islands = 0, _deadEnds = 0, _readsRemoved = 0;
   std::string _error;
 };
 

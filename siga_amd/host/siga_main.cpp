@@ -1,6 +1,7 @@
 // siga_amd/host/siga_main.cpp -- `siga index` / `siga overlap` / `siga match` / `siga locate` / `siga preqc` / `siga unitig` ... command line, option for option as the reference
 // (src/main.cpp:17-83, src/indexer.cpp:119-156, src/overlap.cpp:66-105).  Exit codes follow the reference:
 // a runner returning -1 exits 255; printing help returns 256, i.e. exit status 0.
+#include <cerrno>
 #include <getopt.h>
 #include <unistd.h>
 
@@ -522,10 +523,18 @@ static int unitig_help() {
          "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
          "      -o, --out=FILE                   write the unitigs to FILE (default: <prefix>.unitigs.fa)\n"
          "          --layout=FILE                also write one line per read to FILE: unitig, read name, + or -, offset\n"
-         "      -x, --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges)\n"
+         "          --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges)\n"
          "          --no-opposite-strand         treat all reads as forward strand\n"
          "      -t, --threads=NUM                host threads that parse READSFILE (default: 1)\n"
          "          --device=NUM                 GPU to use (default: 0)\n"
+         "\n"
+         "Trimming parameters (as `siga assemble`):\n"
+         "      -x, --cut-terminal=N             cut off terminal branches (dead ends and islands) in N rounds (default: 0, none)\n"
+         "      -n, --min-branch-length=LEN      remove terminal branches only if they are at most LEN bases in length (default: 150)\n"
+         "      -C, --min-branch-coverage=N      ... and only if their coverage, (reads - 1) / bases, is at most (N - 1) / LEN\n"
+         "          --graph=FILE                 write the graph between the unitigs to FILE as ASQG (gzip if it ends in .gz):\n"
+         "                                       one VT line per unitig, one ED line per overlap that was not merged\n"
+         "          --removed=FILE               write one line per removed read to FILE: read name, the round it went in\n"
          "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
@@ -534,16 +543,34 @@ static int unitig_help() {
   return 256;
 }
 
+// the numeric argument of a trimming option: digits only, at most `most` (`-x` was once --exhaustive's short form and took no
+// argument: `siga unitig -x reads.fa` must not read the file name as a number)
+static bool unitig_number(const char* arg, const char* option, unsigned long long most, size_t* out) {
+  char* end = nullptr;
+  errno = 0;
+  const unsigned long long v = strtoull(arg, &end, 10);
+  if (arg[0] < '0' || arg[0] > '9' || *end != '\0' || errno != 0 || v > most) {
+    fprintf(stderr, "siga unitig: %s needs a number from 0 to %llu, got '%s'\n", option, most, arg);
+    return false;
+  }
+  *out = (size_t)v;
+  return true;
+}
+
 static int run_unitig(int argc, char** argv) {
-  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT };
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
-                                    {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, 'x'},
+                                    {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
                                     {"out", required_argument, nullptr, 'o'},         {"layout", required_argument, nullptr, OPT_LAYOUT},
+                                    {"cut-terminal", required_argument, nullptr, 'x'}, {"min-branch-length", required_argument, nullptr, 'n'},
+                                    {"min-branch-coverage", required_argument, nullptr, 'C'}, {"graph", required_argument, nullptr, OPT_GRAPH},
+                                    {"removed", required_argument, nullptr, OPT_REMOVED},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix, out, layout;
-  size_t threads = 1, minOverlap = 45;
+  std::string prefix, out, layout, graph, removed;
+  size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150;
+  long minBranchCoverage = -1;
   bool exhaustive = false, norc = false, help = false;
   int device = 0, c;
   std::vector<std::string> ini_store;
@@ -551,13 +578,23 @@ static int run_unitig(int argc, char** argv) {
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:xh", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:h", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
       case 'm': minOverlap = strtoull(optarg, nullptr, 10); break;
       case 'o': out = optarg; break;
-      case 'x': exhaustive = true; break;
+      case 'x': if (!unitig_number(optarg, "-x, --cut-terminal", 64, &cutTerminal)) return 1; break;
+      case 'n': if (!unitig_number(optarg, "-n, --min-branch-length", 0xFFFFFFFFull, &minBranchLength)) return 1; break;
+      case 'C': {
+        size_t v = 0;
+        if (!unitig_number(optarg, "-C, --min-branch-coverage", 0xFFFFFFFEull, &v)) return 1;
+        minBranchCoverage = (long)v;
+        break;
+      }
+      case OPT_EXHAUSTIVE: exhaustive = true; break;
+      case OPT_GRAPH: graph = optarg; break;
+      case OPT_REMOVED: removed = optarg; break;
       case OPT_LAYOUT: layout = optarg; break;
       case OPT_NO_RC: norc = true; break;
       case OPT_DEVICE: device = atoi(optarg); break;
@@ -575,12 +612,18 @@ static int run_unitig(int argc, char** argv) {
     return -1;
   }
   sigah::Unitigger unitigger(!exhaustive, !norc);
+  unitigger.setTrim(cutTerminal, minBranchLength, minBranchCoverage);
+  unitigger.setGraph(graph);
+  unitigger.setRemoved(removed);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
   }
   fprintf(stderr, "%llu unitigs, %llu bases, %llu overlaps merged, %llu circular\n", (unsigned long long)unitigger.unitigs(),
           (unsigned long long)unitigger.bases(), (unsigned long long)unitigger.merged(), (unsigned long long)unitigger.cycles());
+  if (cutTerminal)
+    fprintf(stderr, "%llu trim rounds, %llu islands and %llu dead ends removed, %llu reads\n", (unsigned long long)unitigger.trimRounds(),
+            (unsigned long long)unitigger.islands(), (unsigned long long)unitigger.deadEnds(), (unsigned long long)unitigger.readsRemoved());
   return 0;
 }
 

@@ -16,6 +16,8 @@ struct Unitigs {
   uint32_t* uflags = nullptr;
   sigax_placement* layout = nullptr;
   char* useqs = nullptr;
+  uint32_t* removed = nullptr;  // the two of sigax_unitigs_trim_host
+  sigax_edge* uedges = nullptr;
   Unitigs() = default;
   Unitigs(const Unitigs&) = delete;
   Unitigs& operator=(const Unitigs&) = delete;
@@ -25,11 +27,54 @@ struct Unitigs {
     sigax_free(uflags);
     sigax_free(layout);
     sigax_free(useqs);
+    sigax_free(removed);
+    sigax_free(uedges);
   }
 };
 
 bool write_all(FILE* f, const std::string& t) { return t.empty() || fwrite(t.data(), 1, t.size(), f) == t.size(); }
 }  // namespace
+
+// The unitig graph as ASQG: the header, one VT line per unitig, one ED line per lifted record (AsqgWriter's formatter over the
+// unitigs' names and lengths).
+static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t n_uedges, size_t minOverlap) {
+  OutFile out(path);
+  if (!out.ok()) return false;
+  out.write(asqg_header(minOverlap));
+  std::string t;
+  std::vector<std::string> names((size_t)u.n);
+  for (uint64_t k = 0; k < u.n; ++k) {
+    names[k] = "unitig-";
+    append_u64(names[k], k);
+    const uint64_t cnt = u.lay_offs[k + 1] - u.lay_offs[k];
+    t += "VT\t";
+    t += names[k];
+    t += '\t';
+    t.append(u.useqs + u.seq_offs[k], u.seq_offs[k + 1] - u.seq_offs[k]);
+    t += "\tSS:i:0";
+    if (cnt > 1) {
+      t += "\tCR:i:";
+      append_u64(t, cnt);
+    }
+    t += '\n';
+    if (t.size() >= ((size_t)1 << 20)) {
+      out.write(t);
+      t.clear();
+    }
+  }
+  for (uint64_t i = 0; i < n_uedges; ++i) {
+    const sigax_edge& e = u.uedges[i];
+    if (e.query >= u.n || e.target >= u.n) return false;
+    append_edge_line(t, e, names[e.query], names[e.target], u.seq_offs[e.query + 1] - u.seq_offs[e.query],
+                     u.seq_offs[e.target + 1] - u.seq_offs[e.target]);
+    if (t.size() >= ((size_t)1 << 20)) {
+      out.write(t);
+      t.clear();
+    }
+  }
+  out.write(t);
+  return out.close();
+}
 
 // The reads go through OverlapBuilder's device stages (sigax_overlap_batch: finder, filter, extractor, edge records) a piece
 // at a time under their ids in the file; no VT or ED line is formatted.  The collected records and the reads then make one
@@ -37,7 +82,7 @@ bool write_all(FILE* f, const std::string& t) { return t.empty() || fwrite(t.dat
 bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta, const std::string& layout,
                     size_t threads) {
   _error.clear();
-  _unitigs = _bases = _merged = _cycles = 0;
+  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -67,15 +112,34 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  if (sigax_unitigs_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap, &u.n,
-                         &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs) != SIGAX_OK)
-    return fail(std::string("unitig failed: ") + sigax_last_error());
-  uint64_t status[6];
-  sigax_unitigs_last_status(status);
+  uint64_t status[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
+  if (trim) {
+    if (_rounds > 64) return fail("at most 64 trim rounds");
+    if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
+    sigax_trim_opts opts;
+    opts.max_rounds = (uint32_t)_rounds;
+    opts.min_branch_length = (uint32_t)_minBranchLength;
+    opts.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
+    opts.reserved = 0;
+    if (sigax_unitigs_trim_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,
+                                &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed,
+                                _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else {
+    if (sigax_unitigs_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,
+                           &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+    sigax_unitigs_last_status(status);
+  }
   _unitigs = status[0];
   _bases = status[1];
   _merged = status[4];
   _cycles = status[5];
+  _trimRounds = status[6];
+  _islands = status[7];
+  _deadEnds = status[8];
+  _readsRemoved = status[9];
   // ">unitig-<n>[ KC:i:<reads>][ circular=<closing overlap>]": the coverage tag only above 1, as FastaVisitor writes it
   // (src/bigraph_visitors.cpp:248-257)
   FILE* out = fasta.empty() ? stdout : fopen(fasta.c_str(), "wb");
@@ -105,6 +169,24 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   if (fflush(out) != 0) ok = false;
   if (out != stdout) fclose(out);
   if (!ok) return fail("Failed to write " + (fasta.empty() ? std::string("stdout") : fasta));
+  if (!_graph.empty() && !write_graph_file(_graph, u, status[11], minOverlap)) return fail("Failed to write " + _graph);
+  if (!_removed.empty()) {
+    FILE* rf = fopen(_removed.c_str(), "wb");
+    if (!rf) return fail("Failed to create " + _removed);
+    t.clear();
+    for (size_t r = 0; r < n; ++r)
+      if (u.removed[r]) {
+        const std::string_view name = reads.name(r);
+        t.append(name.data(), name.size());
+        t += '\t';
+        append_u64(t, u.removed[r]);
+        t += '\n';
+      }
+    ok = write_all(rf, t);
+    if (fclose(rf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _removed);
+    t.clear();
+  }
   if (layout.empty()) return true;
   // "unitig-<n>\t<read name>\t<+|->\t<offset>", placements in layout order
   FILE* lf = fopen(layout.c_str(), "wb");

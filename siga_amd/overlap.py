@@ -141,6 +141,49 @@ def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
     return out
 
 
+def unitigs_trim(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, graph=True, bases=True,
+                 device=0):
+    """`unitigs` after tip trimming, with the graph between the unitigs (sigax_unitigs_trim_host, the rules in include/sigax.h):
+    up to max_rounds rounds (the reference's -x) remove every unitig that is a dead end or an island of at most
+    min_branch_length bases (-n) and, unless min_branch_coverage (-C) is None, of low coverage.  -> the dict of `unitigs`
+    (layout holds the kept reads only) plus removed u32[n] (0, or the round a read went in), uedges EDGE_DTYPE (the records
+    that were not merged, over unitig ids and unitig ends; None with graph=False) and status u64[12]: the six counts of
+    `unitigs`, then {rounds that removed something, islands, dead ends, reads removed, kept records dropped with a removed
+    read, lifted records}.  max_rounds = 0 is `unitigs` itself."""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(lengths)
+    if len(offs) != n + 1:
+        raise ValueError("offs must have len(lengths) + 1 entries")
+    if isinstance(seqs, np.ndarray):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+    else:
+        buf = bytes(seqs)
+    L = _lib.lib()
+    opts = _lib.TrimOpts(int(max_rounds), int(min_branch_length),
+                         _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), 0)
+    nu = C.c_uint64()
+    so, lo, uf, lay, us, rm, ue = (C.c_void_p() for _ in range(7))
+    status = np.zeros(12, dtype=np.uint64)
+    _check(L.sigax_unitigs_trim_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+                                     offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf),
+                                     C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ue) if graph else None,
+                                     status.ctypes.data), "sigax_unitigs_trim_host")
+    try:
+        u = int(nu.value)
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32))}
+        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
+    finally:
+        for p in (so, lo, uf, lay, us, rm, ue):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
