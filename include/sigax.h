@@ -432,6 +432,78 @@ int  sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edg
                              uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                              sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
                              uint64_t status12[12]);
+/* ---- `siga unitig -x -d`: non-maximal overlap cutting in the rounds (csrc/sigax_unitig.hip) ---------------------------------------
+ * The second visitor of a round of the reference's default `assemble` loop (src/assembler.cpp:166-221): MaximumOverlapVisitor
+ * (src/bigraph_visitors.cpp:410-512; -d, --max-overlap-carefully, -N, -G, -T) before TrimVisitor, each followed by simplify().
+ * LoopRemoveVisitor, ChimericVisitor and the paired and linked-read visitors are not restated.  Everything not said here is as
+ * in the `siga unitig -x` block above: record classes, B/E ends, degrees, simple records, rings, orientation, numbering, the
+ * trim verdict, lifted records.
+ *
+ * sigax_prune_opts: max_rounds, min_branch_length, min_branch_coverage as in sigax_trim_opts; delta (-d), careful (0 or 1),
+ * reserved = 0, num_reads N (-N; at least n_reads, so that no unitig holds more reads than N), genome_size G (-G; not 0 when
+ * delta > 0), uniq_threshold T (-T).
+ *
+ * State: removed[read] as above, and cut[i] per record: 0, or the round in which record i was cut.  A record is LIVE if it is
+ * kept, not cut, and both its reads are alive.  Degrees, links, unitigs, trim verdicts and lifting run over live records only.
+ *
+ * One round r = 1, 2, ...:
+ *   CUT STEP   the unitigs of the current state are built; every cut is decided from that state alone; cut records get
+ *              cut[i] = r.
+ *   TRIM STEP  exactly the trim round above, over the state the cut step left (the reference's simplify() between the two
+ *              visitors: here everything is recomputed from the reads); removed reads get removed[read] = r.
+ * A round in which neither step changed anything ends the loop and is not counted.  At most max_rounds (<= 64) rounds run.
+ *
+ * The cut verdict.  PARTICIPANTS are the live records that are not containments (the reference asserts a graph without
+ * containments; here a containment sets no maximum and is never cut).  A record touches the two states (read ends) its
+ * classification names.  max[s] = the largest length among the participants that touch state s.  U(s) = the unitig of the
+ * read of s.  unique(U) iff score >= T, with
+ *   score = (N - K) * (log(G - bases) - log(G - 2 * bases)) - K * log(2.0)
+ * in double as :441-450 writes it, K = the reads of U, bases = its bases; for bases < G <= 2 * bases the second logarithm is
+ * log(0.001), as there; for bases >= G the reference's unsigned difference wraps and its expression means nothing: such a
+ * unitig counts as NOT unique.  The device's log need not round as the host's does: a score within rounding of T may fall on
+ * either side.
+ * Record i, touching s and t, is a CANDIDATE FROM s iff unique(U(s)) and max[s] - length_i >= delta.
+ *   careful = 0: record i is cut iff it is a candidate from s or from t.
+ *   careful = 1: a candidate from s is HELD BACK
+ *     when U(s) != U(t): if some participant j touches t, has its other end in U(s) (at either end of it: the reference
+ *       compares vertices, not edges, :478-483; record i itself and parallel records between the two unitigs count), and has
+ *       max[t] - length_j < delta;
+ *     when U(s) == U(t) (a self edge of the merged vertex): if some participant of length max[s] at s has both its ends in U(s).
+ *     Record i is cut iff it is a candidate from some side and not held back on that side.
+ * delta must be >= 1 to cut: delta = 0 means no cut step, and the result is exactly that of sigax_unitigs_trim_* with cut all
+ * zero.  (The reference's delta = 0 keeps one record per end, and which one depends on the tie order of std::sort; that is not
+ * restated.  The self-edge rule above differs from the reference only where such a tie decides there.)  delta = 1 keeps every
+ * longest record of an end and cuts all shorter ones.
+ *
+ * status16 = 16 u64, written: 0-11 as status12, with 6 = rounds that changed something (cut or removed) and 10 = uncut kept
+ * records dropped because one of their reads was removed; 12 records cut, 13 rounds in which something was cut, 14 unique
+ * unitigs seen by the first round's cut step, 15 = 0.
+ *
+ * sigax_unitigs_prune_device: sigax_unitigs_trim_device with these options, d_cut u32[n_edges] (4-byte aligned) and d_status16.
+ * Asynchronous on `stream`, allocates nothing, never waits for the device; it enqueues max_rounds rounds, whose launches return
+ * at once after a round that changed nothing.  d_work = sigax_unitigs_prune_workspace(n_reads, n_edges, d_uedges != NULL,
+ * careful) bytes: the trim call's scratch, and per read 12 bytes (20 with careful), per record nothing without careful and with
+ * it 8 bytes per slot of a table of the first power of two >= 4 n_edges slots (32 to 64 bytes per record).  Refusals as for the trim call, and
+ * careful > 1, reserved != 0, num_reads < n_reads, genome_size == 0 with delta > 0: SIGAX_E_ARG.  Whatever the records hold,
+ * nothing outside the buffers is touched. */
+typedef struct sigax_prune_opts {
+  uint32_t max_rounds, min_branch_length, min_branch_coverage, delta, careful, reserved;
+  uint64_t num_reads, genome_size;
+  double uniq_threshold;
+} sigax_prune_opts;
+int  sigax_unitigs_prune_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_prune_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts,
+                                void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status16, void* d_work,
+                                uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_trim_host, plus *cut u32[n_edges] (malloc'd, sigax_free) and status16.  It stops
+ * after the first round that changed nothing. */
+int  sigax_unitigs_prune_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                              const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts,
+                              uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                              sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                              uint64_t status16[16]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -36,6 +36,11 @@ class TrimOpts(C.Structure):  # sigax_trim_opts
     _fields_ = [(n, C.c_uint32) for n in ("max_rounds", "min_branch_length", "min_branch_coverage", "reserved")]
 
 
+class PruneOpts(C.Structure):  # sigax_prune_opts
+    _fields_ = ([(n, C.c_uint32) for n in ("max_rounds", "min_branch_length", "min_branch_coverage", "delta", "careful", "reserved")] +
+                [("num_reads", C.c_uint64), ("genome_size", C.c_uint64), ("uniq_threshold", C.c_double)])
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_reads", "n_candidate_blocks", "n_blocks", "n_edges", "n_occ_find", "n_occ_extract", "n_substring",
@@ -80,6 +85,7 @@ SYMBOLS = [
     "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
     "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
+    "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -175,6 +181,11 @@ def lib():
     L.sigax_unitigs_trim_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(TrimOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_trim_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(TrimOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp, pvp,
                                           pvp, vp]
+    L.sigax_unitigs_prune_workspace.argtypes = [u64, u64, ci, ci, C.POINTER(u64)]
+    L.sigax_unitigs_prune_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(PruneOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             u64, vp]
+    L.sigax_unitigs_prune_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(PruneOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp,
+                                           pvp, pvp, pvp, vp]
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
     L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]

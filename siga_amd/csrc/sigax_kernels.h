@@ -305,6 +305,25 @@ enum { TRIM_C_ISLANDS = 0, TRIM_C_DEAD_ENDS = 1, TRIM_C_READS = 2, TRIM_C_DROPPE
        TRIM_LIFTED = TRIM_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, TRIM_ROUND0 = TRIM_LIFTED + 8, TRIM_MAX_ROUNDS = 64,
        TRIM_WORDS = TRIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
 static const uint32_t TRIM_NO_COVERAGE = 0xFFFFFFFFu;
+// non-maximal overlap cutting (sigax_unitigs_prune_*): the trim block and what a round's cut step needs.  Again a block of its
+// own: the kernels of the two older entry points keep theirs.
+struct UnitigPruneArgs : UnitigTrimArgs {
+  uint32_t* cut;                         // [n_edges], zeroed before round 1: the round in which a record was cut, 0 = not cut
+  uint32_t* maxlen;                      // [2 n_reads], cleared by the cut step: the longest participant at a read end; NULL in every
+                                         // other pass (the degree kernel then takes no maximum)
+  uint32_t* maxself;                     // [2 n_reads], cleared (careful): the longest participant at a read end with both ends in one unitig
+  uint32_t* uniq;                        // [n_reads]: the unitig counts as unique, under its head
+  unsigned long long* keys;              // key_cap u64, all ones when empty (careful): (read end << 32) | head of the unitig at the other end, of
+                                         // every participant within delta of that read end's maximum; open addressing
+  unsigned long long key_cap;            // a power of two >= 4 n_edges: at most 2 n_edges keys go in
+  unsigned long long* prune;             // PRUNE_WORDS u64, zeroed before round 1: the PRUNE_C_* counters, slotted as the trim counters
+                                         // are, and at PRUNE_ROUND0 + r whether round r cut something
+  uint32_t delta, careful;
+  unsigned long long num_reads, genome_size;
+  double uniq_threshold;
+};
+enum { PRUNE_C_CUT = 0, PRUNE_C_UNIQUE = 1, PRUNE_COUNTERS = 2, PRUNE_ROUND0 = PRUNE_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+       PRUNE_WORDS = PRUNE_ROUND0 + TRIM_MAX_ROUNDS + 8 };
 unsigned unitig_rounds(unsigned long long n_reads);  // ceil(log2 n_reads) + 1: the pointer-jumping launches of one ranking
 void launch_unitigs(const UnitigArgs& a, hipStream_t st);
 void launch_unitig_bases(const UnitigArgs& a, hipStream_t st);  // the last phase alone, over what launch_unitigs left (sigax_unitigs_bases_device)
@@ -314,6 +333,14 @@ void launch_unitig_bases(const UnitigArgs& a, hipStream_t st);  // the last phas
 void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st);
 void launch_unitigs_trim(const UnitigTrimArgs& a, hipStream_t st);
 void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st);
+// one round's cut step (a.round >= 1, a.maxlen set): the graph of the live records, the longest participant per read end, the
+// verdict per unitig, cut[] marked.  Then launch_prune_trim_round (a.maxlen = NULL): launch_trim_round over the records that are
+// not cut.  Both leave at once when the round before changed nothing.  The caller resets as for launch_trim_round; the cut step
+// clears maxlen, maxself and keys itself.  launch_unitigs_prune / launch_unitig_prune_lift: the result, and status[6 .. 15].
+void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st);
+void launch_prune_trim_round(const UnitigPruneArgs& a, hipStream_t st);
+void launch_unitigs_prune(const UnitigPruneArgs& a, hipStream_t st);
+void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st);
 
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);

@@ -101,6 +101,35 @@ TrimWork trim_work(u64 n, u64 n_edges, bool graph) {
   return w;
 }
 
+// the prune calls' scratch: the trim calls', then what a round's cut step needs
+struct PruneWork {
+  TrimWork t;
+  u64 prune, maxlen, uniq, maxself, keys, key_cap, bytes;
+};
+PruneWork prune_work(u64 n, u64 n_edges, bool graph, bool careful) {
+  PruneWork w;
+  w.t = trim_work(n, n_edges, graph);
+  u64 at = w.t.bytes;
+  auto take = [&](u64 bytes) {
+    const u64 here = at;
+    at += (bytes + 15) & ~15ull;
+    return here;
+  };
+  w.prune = take(PRUNE_WORDS * 8);
+  w.maxlen = take(2 * n * 4);
+  w.uniq = take(n * 4);
+  w.maxself = w.keys = at;
+  w.key_cap = 0;
+  if (careful) {
+    w.maxself = take(2 * n * 4);
+    w.key_cap = 16;
+    while (w.key_cap < 4 * n_edges) w.key_cap <<= 1;
+    w.keys = take(w.key_cap * 8);
+  }
+  w.bytes = at;
+  return w;
+}
+
 int unitig_limits(u64 n_reads, u64 n_edges) {
   if (n_reads >= (1ull << 31)) return sigax_fail(SIGAX_E_ARG, "2^31 reads or more: a state names a read end in 32 bits");
   if (n_edges > (1ull << 32)) return sigax_fail(SIGAX_E_ARG, "more than 2^32 records");
@@ -113,6 +142,16 @@ int trim_opts_ok(const sigax_trim_opts* o) {
   if (!o) return sigax_fail(SIGAX_E_ARG, "NULL where the trim options are required");
   if (o->reserved != 0) return sigax_fail(SIGAX_E_ARG, "sigax_trim_opts.reserved must be 0");
   if (o->max_rounds > TRIM_MAX_ROUNDS) return sigax_fail(SIGAX_E_ARG, "max_rounds %u: at most %d", o->max_rounds, (int)TRIM_MAX_ROUNDS);
+  return SIGAX_OK;
+}
+
+int prune_opts_ok(const sigax_prune_opts* o, u64 n_reads) {
+  if (!o) return sigax_fail(SIGAX_E_ARG, "NULL where the prune options are required");
+  if (o->reserved != 0) return sigax_fail(SIGAX_E_ARG, "sigax_prune_opts.reserved must be 0");
+  if (o->careful > 1) return sigax_fail(SIGAX_E_ARG, "careful %u: 0 or 1", o->careful);
+  if (o->max_rounds > TRIM_MAX_ROUNDS) return sigax_fail(SIGAX_E_ARG, "max_rounds %u: at most %d", o->max_rounds, (int)TRIM_MAX_ROUNDS);
+  if (o->num_reads < n_reads) return sigax_fail(SIGAX_E_ARG, "num_reads %llu below the %llu reads given", (u64)o->num_reads, n_reads);
+  if (o->delta > 0 && o->genome_size == 0) return sigax_fail(SIGAX_E_ARG, "genome_size must be given with delta > 0");
   return SIGAX_OK;
 }
 
@@ -358,14 +397,23 @@ extern "C" int sigax_unitigs_trim_device(int device, const sigax_edge* d_edges, 
                           d_layout, d_useqs, d_removed, d_uedges, d_status12, d_work, work_bytes, stream, false);
 }
 
-extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
-                                       const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
-                                       uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
-                                       sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
-                                       uint64_t status12[12]) {
-  if (!n_unitigs || !seq_offs || !lay_offs || !uflags || !layout || !removed || !status12 || (n_reads && (!lengths || !seqs || !offs)) ||
-      (n_edges && !edges))
+static int unitigs_prune_run(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                             const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts, void* d_seq_offs,
+                             void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, void* d_cut,
+                             sigax_edge* d_uedges, void* d_status16, void* d_work, uint64_t work_bytes, void* stream, bool paced);
+
+// The host form of both calls.  The trim call passes opts, and NULL for popts and cut; `status` then holds 12 counts.  The prune call
+// passes popts and cut, and NULL for opts; `status` then holds 16.
+static int unitigs_rounds_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                               const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                               const sigax_prune_opts* popts, uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs,
+                               uint32_t** uflags, sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut,
+                               sigax_edge** uedges, uint64_t* status_out) {
+  const int n_status = popts ? 16 : 12;
+  if (!n_unitigs || !seq_offs || !lay_offs || !uflags || !layout || !removed || !status_out || (popts && !cut) ||
+      (n_reads && (!lengths || !seqs || !offs)) || (n_edges && !edges))
     return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (cut) *cut = nullptr;
   *n_unitigs = 0;
   *seq_offs = nullptr;
   *lay_offs = nullptr;
@@ -374,10 +422,10 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
   *removed = nullptr;
   if (useqs) *useqs = nullptr;
   if (uedges) *uedges = nullptr;
-  for (int k = 0; k < 12; ++k) status12[k] = 0;
+  for (int k = 0; k < n_status; ++k) status_out[k] = 0;
   const int rl = unitig_limits(n_reads, n_edges);
   if (rl != SIGAX_OK) return rl;
-  const int ro = trim_opts_ok(opts);
+  const int ro = popts ? prune_opts_ok(popts, n_reads) : trim_opts_ok(opts);
   if (ro != SIGAX_OK) return ro;
   const u64 n = n_reads;
   for (u64 i = 0; i < n; ++i)
@@ -389,13 +437,14 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
     for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
     offs = rebased.data();
   }
-  u64 status[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  u64 status[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   DevGuard g;
   void *d_edges = nullptr, *d_lengths = nullptr, *d_seqs = nullptr, *d_offs = nullptr, *d_so = nullptr, *d_lo = nullptr, *d_uf = nullptr,
-       *d_lay = nullptr, *d_us = nullptr, *d_rm = nullptr, *d_ue = nullptr, *d_status = nullptr, *d_work = nullptr;
+       *d_lay = nullptr, *d_us = nullptr, *d_rm = nullptr, *d_ct = nullptr, *d_ue = nullptr, *d_status = nullptr, *d_work = nullptr;
   if (n) {
     HIP_TRY(hipSetDevice(device));
-    const u64 wb = trim_work(n, n_edges, uedges != nullptr).bytes;
+    const u64 wb = popts ? prune_work(n, n_edges, uedges != nullptr, popts->careful != 0).bytes : trim_work(n, n_edges, uedges != nullptr).bytes;
+    if (popts) HIP_TRY(g.alloc(&d_ct, (size_t)n_edges * 4 + 16));
     HIP_TRY(g.alloc(&d_edges, (size_t)n_edges * sizeof(sigax_edge)));
     HIP_TRY(g.alloc(&d_lengths, (size_t)n * 4));
     HIP_TRY(g.alloc(&d_seqs, (size_t)nb + 16));
@@ -407,16 +456,19 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
     if (useqs) HIP_TRY(g.alloc(&d_us, (size_t)nb + 16));
     HIP_TRY(g.alloc(&d_rm, (size_t)n * 4));
     if (uedges) HIP_TRY(g.alloc(&d_ue, (size_t)n_edges * sizeof(sigax_edge) + 16));
-    HIP_TRY(g.alloc(&d_status, 96));
+    HIP_TRY(g.alloc(&d_status, (size_t)n_status * 8));
     HIP_TRY(g.alloc(&d_work, (size_t)wb));
     if (n_edges) HIP_TRY(hipMemcpy(d_edges, edges, (size_t)n_edges * sizeof(sigax_edge), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice));
     if (nb) HIP_TRY(hipMemcpy(d_seqs, seqs + b0, (size_t)nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    const int rc = unitigs_trim_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, opts, d_so, d_lo, d_uf,
-                                    (sigax_placement*)d_lay, d_us, d_rm, (sigax_edge*)d_ue, d_status, d_work, wb, nullptr, true);
+    const int rc = popts ? unitigs_prune_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, popts, d_so,
+                                             d_lo, d_uf, (sigax_placement*)d_lay, d_us, d_rm, d_ct, (sigax_edge*)d_ue, d_status, d_work, wb,
+                                             nullptr, true)
+                         : unitigs_trim_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, opts, d_so, d_lo,
+                                            d_uf, (sigax_placement*)d_lay, d_us, d_rm, (sigax_edge*)d_ue, d_status, d_work, wb, nullptr, true);
     if (rc != SIGAX_OK) return rc;
-    HIP_TRY(hipMemcpy(status, d_status, 96, hipMemcpyDeviceToHost));  // (waits for the null stream's kernels)
+    HIP_TRY(hipMemcpy(status, d_status, (size_t)n_status * 8, hipMemcpyDeviceToHost));  // (waits for the null stream's kernels)
     if (status[0] > n || status[1] > nb || status[9] > n || status[11] > n_edges)
       return sigax_fail(SIGAX_E_DEVICE, "unitig counts beyond their buffers");
   }
@@ -427,6 +479,7 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
   sigax_placement* h_lay = (sigax_placement*)malloc(placed ? (size_t)placed * sizeof(sigax_placement) : sizeof(sigax_placement));
   char* h_us = useqs ? (char*)malloc(bases ? (size_t)bases : 1) : nullptr;
   uint32_t* h_rm = (uint32_t*)malloc(n ? (size_t)n * 4 : 4);
+  uint32_t* h_ct = cut ? (uint32_t*)malloc(n_edges ? (size_t)n_edges * 4 : 4) : nullptr;
   sigax_edge* h_ue = uedges ? (sigax_edge*)malloc(ne ? (size_t)ne * sizeof(sigax_edge) : sizeof(sigax_edge)) : nullptr;
   auto drop = [&] {
     free(h_so);
@@ -435,9 +488,10 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
     free(h_lay);
     free(h_us);
     free(h_rm);
+    free(h_ct);
     free(h_ue);
   };
-  if (!h_so || !h_lo || !h_uf || !h_lay || !h_rm || (useqs && !h_us) || (uedges && !h_ue)) {
+  if (!h_so || !h_lo || !h_uf || !h_lay || !h_rm || (cut && !h_ct) || (useqs && !h_us) || (uedges && !h_ue)) {
     drop();
     return sigax_fail(SIGAX_E_CAPACITY, "out of host memory");
   }
@@ -451,13 +505,16 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
     if (e == hipSuccess && placed) e = hipMemcpy(h_lay, d_lay, (size_t)placed * sizeof(sigax_placement), hipMemcpyDeviceToHost);
     if (e == hipSuccess && useqs && bases) e = hipMemcpy(h_us, d_us, (size_t)bases, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(h_rm, d_rm, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && cut && n_edges) e = hipMemcpy(h_ct, d_ct, (size_t)n_edges * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && ne) e = hipMemcpy(h_ue, d_ue, (size_t)ne * sizeof(sigax_edge), hipMemcpyDeviceToHost);
   }
   if (e != hipSuccess) {
     drop();
     return sigax_fail(SIGAX_E_DEVICE, "copying the unitigs: %s", hipGetErrorString(e));
   }
-  for (int k = 0; k < 12; ++k) status12[k] = status[k];
+  if (cut && n == 0 && n_edges) memset(h_ct, 0, (size_t)n_edges * 4);
+  for (int k = 0; k < n_status; ++k) status_out[k] = status[k];
+  if (cut) *cut = h_ct;
   *n_unitigs = nu;
   *seq_offs = h_so;
   *lay_offs = h_lo;
@@ -467,4 +524,134 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
   if (useqs) *useqs = h_us;
   if (uedges) *uedges = h_ue;
   return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                       const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
+                                       uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                       sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
+                                       uint64_t status12[12]) {
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, opts, nullptr, n_unitigs, seq_offs, lay_offs,
+                             uflags, layout, useqs, removed, nullptr, uedges, status12);
+}
+
+// ---- non-maximal overlap cutting ----
+extern "C" int sigax_unitigs_prune_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes) {
+  if (!bytes) return sigax_fail(SIGAX_E_ARG, "bad argument");
+  const int rc = unitig_limits(n_reads, n_edges);
+  if (rc != SIGAX_OK) return rc;
+  *bytes = prune_work(n_reads, n_edges, want_graph != 0, careful != 0).bytes;
+  return SIGAX_OK;
+}
+
+static int unitigs_prune_run(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                             const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts, void* d_seq_offs,
+                             void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, void* d_cut,
+                             sigax_edge* d_uedges, void* d_status16, void* d_work, uint64_t work_bytes, void* stream, bool paced) {
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  const int ro = prune_opts_ok(opts, n_reads);
+  if (ro != SIGAX_OK) return ro;
+  if (n_reads && n_edges && !d_cut) return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (n_reads && ((uintptr_t)d_cut & 3)) return sigax_fail(SIGAX_E_ARG, "d_cut must be 4-byte aligned");
+  const PruneWork w = prune_work(n_reads, n_edges, d_uedges != nullptr, opts->careful != 0);
+  if (n_reads && work_bytes < w.bytes)
+    return sigax_fail(SIGAX_E_ARG, "workspace of %llu bytes, %llu needed (sigax_unitigs_prune_workspace)", (u64)work_bytes, w.bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  const sigax_trim_opts topts = {opts->max_rounds, opts->min_branch_length, opts->min_branch_coverage, 0};
+  if (n_reads == 0 || opts->delta == 0) {  // no cut step: the trim call, cut all zero
+    const int rc = unitigs_trim_run(device, d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, &topts, d_seq_offs, d_lay_offs,
+                                    d_uflags, d_layout, d_useqs, d_removed, d_uedges, d_status16, d_work, work_bytes, stream, paced);
+    if (rc != SIGAX_OK) return rc;
+    if (d_status16) HIP_TRY(hipMemsetAsync((char*)d_status16 + 96, 0, 32, st));
+    if (n_reads && n_edges) HIP_TRY(hipMemsetAsync(d_cut, 0, (size_t)n_edges * 4, st));
+    return SIGAX_OK;
+  }
+  if (!d_lengths || !d_seqs || !d_offs || !d_seq_offs || !d_lay_offs || !d_uflags || !d_layout || !d_removed || !d_status16 || !d_work ||
+      (n_edges && !d_edges))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (((uintptr_t)d_edges | (uintptr_t)d_layout | (uintptr_t)d_useqs | (uintptr_t)d_uedges | (uintptr_t)d_work) & 15)
+    return sigax_fail(SIGAX_E_ARG, "d_edges, d_layout, d_useqs, d_uedges and d_work must be 16-byte aligned");
+  if (((uintptr_t)d_offs | (uintptr_t)d_seq_offs | (uintptr_t)d_lay_offs | (uintptr_t)d_status16) & 7)
+    return sigax_fail(SIGAX_E_ARG, "d_offs, d_seq_offs, d_lay_offs and d_status16 must be 8-byte aligned");
+  if ((uintptr_t)d_removed & 3) return sigax_fail(SIGAX_E_ARG, "d_removed must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(device));
+  UnitigPruneArgs a;
+  static_cast<UnitigArgs&>(a) = unitig_args(d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, d_seq_offs, d_lay_offs, d_uflags,
+                                            d_layout, d_useqs, d_status16, d_work);
+  char* base = (char*)d_work;
+  a.removed = (uint32_t*)d_removed;
+  a.trim = (u64*)(base + w.t.trim);
+  a.verdict = (uint32_t*)(base + w.t.verdict);
+  a.umap = (uint32_t*)(base + w.t.umap);
+  a.round = 0;
+  a.min_branch_length = opts->min_branch_length;
+  a.min_branch_coverage = opts->min_branch_coverage;
+  a.uedges = d_uedges;
+  a.eflag = (uint32_t*)(base + w.t.eflag);
+  a.escan = (u64*)(base + w.t.escan);
+  a.epartial = (u64*)(base + w.t.epartial);
+  a.cut = (uint32_t*)d_cut;
+  a.maxlen = nullptr;
+  a.maxself = (uint32_t*)(base + w.maxself);
+  a.uniq = (uint32_t*)(base + w.uniq);
+  a.keys = (u64*)(base + w.keys);
+  a.key_cap = w.key_cap;
+  a.prune = (u64*)(base + w.prune);
+  a.delta = opts->delta;
+  a.careful = opts->careful;
+  a.num_reads = opts->num_reads;
+  a.genome_size = opts->genome_size;
+  a.uniq_threshold = opts->uniq_threshold;
+  uint32_t* const maxlen = (uint32_t*)(base + w.maxlen);
+  HIP_TRY(hipMemsetAsync(d_removed, 0, (size_t)n_reads * 4, st));
+  if (n_edges) HIP_TRY(hipMemsetAsync(d_cut, 0, (size_t)n_edges * 4, st));
+  HIP_TRY(hipMemsetAsync(a.trim, 0, TRIM_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(a.prune, 0, PRUNE_WORDS * 8, st));
+  auto reset = [&]() -> hipError_t {
+    const hipError_t e = hipMemsetAsync(base + w.t.u.zero_from, 0, (size_t)w.t.u.zero_bytes, st);
+    return e != hipSuccess ? e : hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st);
+  };
+  for (uint32_t r = 1; r <= opts->max_rounds; ++r) {
+    a.round = r;
+    {  // the cut step
+      HIP_TRY(reset());
+      a.maxlen = maxlen;
+      launch_prune_cut_round(a, st);
+      a.maxlen = nullptr;
+    }
+    HIP_TRY(reset());  // the trim step, over what the cut step left
+    launch_prune_trim_round(a, st);
+    if (paced) {
+      u64 flag = 0;
+      HIP_TRY(hipMemcpyAsync(&flag, a.trim + TRIM_ROUND0 + r, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (flag == 0) break;
+    }
+  }
+  a.round = 0;  // the unitigs of what is left
+  HIP_TRY(reset());
+  launch_unitigs_prune(a, st);
+  launch_unitig_prune_lift(a, st);
+  HIP_TRY(hipGetLastError());
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_prune_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                          const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts,
+                                          void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                          void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status16, void* d_work,
+                                          uint64_t work_bytes, void* stream) {
+  return unitigs_prune_run(device, d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, opts, d_seq_offs, d_lay_offs, d_uflags,
+                           d_layout, d_useqs, d_removed, d_cut, d_uedges, d_status16, d_work, work_bytes, stream, false);
+}
+
+extern "C" int sigax_unitigs_prune_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                        const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_prune_opts* opts,
+                                        uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                        sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                                        uint64_t status16[16]) {
+  if (!opts) return sigax_fail(SIGAX_E_ARG, "NULL where the prune options are required");
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, opts, n_unitigs, seq_offs, lay_offs,
+                             uflags, layout, useqs, removed, cut, uedges, status16);
 }

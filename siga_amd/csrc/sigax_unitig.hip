@@ -33,6 +33,14 @@
 //   k_lift_flag / k_lift_write   one lane per record: a live record that is no link of the final graph is flagged, launch_scan
 //                 gives it its place, and it is written over unitig ids and unitig ends (one 16-byte load, one 16-byte store)
 // A round's launches leave at once when the round before it removed nothing (idle_round).
+// Non-maximal overlap cutting (sigax_unitigs_prune_*; tests/prune_cases.py::expected_prune): the kernels above as
+// <TRIM = 2> also skip the records with cut[i] != 0, k_uni_degree<2> takes the longest participant per read end (atomicMax), and
+//   k_prune_clear  the step's scratch emptied: the maxima and, careful mode, the table (a kernel: idle rounds write nothing)
+//   k_prune_unique one lane per read: a head scores its unitig from its reads and bases (double, one log pair per unitig)
+//   k_prune_keys  careful mode, one lane per record: the (read end, unitig at the other end) pairs of the participants within
+//                 delta of their end's maximum go into an open-addressing table; the longest self record per read end
+//   k_prune_cut   one lane per record: candidate from either side, held back or not, cut[i] = round
+// The table's probe loops are bounded by its capacity, which holds at least twice the keys that can go in.
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
 // consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
 // beyond the 64 descriptors, no MFMA.
@@ -81,14 +89,15 @@ __device__ __forceinline__ u64 wave_total(u64 v) {
   return v;
 }
 
-// TRIM: the kernels of sigax_unitigs_trim_*: reads with removed[r] != 0 are not there, nor are the records that touch one.
-// They take the longer argument block; TRIM = false is sigax_unitigs_device's code as it was, over the block it had.
-template <bool TRIM>
-using ArgsOf = std::conditional_t<TRIM, UnitigTrimArgs, UnitigArgs>;
+// TRIM = 1: the kernels of sigax_unitigs_trim_*: reads with removed[r] != 0 are not there, nor are the records that touch one.
+// They take the longer argument block; TRIM = 0 is sigax_unitigs_device's code as it was, over the block it had.  TRIM = 2: the
+// kernels of sigax_unitigs_prune_*, as 1 and without the records that were cut, over a block of their own again.
+template <int TRIM>
+using ArgsOf = std::conditional_t<TRIM == 2, UnitigPruneArgs, std::conditional_t<TRIM == 1, UnitigTrimArgs, UnitigArgs>>;
 // a trim round after one that removed nothing has nothing to do (as k_uni_init(second) when no cycle was cut)
-template <bool TRIM>
+template <int TRIM>
 __device__ __forceinline__ bool idle_round(const ArgsOf<TRIM>& A) {
-  if constexpr (TRIM) return A.round > 1u && A.trim[TRIM_ROUND0 + A.round - 1u] == 0ull;
+  if constexpr (TRIM != 0) return A.round > 1u && A.trim[TRIM_ROUND0 + A.round - 1u] == 0ull;
   return false;
 }
 // where this wave adds to trim counter c
@@ -102,13 +111,19 @@ __device__ __forceinline__ u64 trim_count(const UnitigTrimArgs& A, u32 c) {
   return v;
 }
 // both reads of a kept record alive
-template <bool TRIM>
+template <int TRIM>
 __device__ __forceinline__ bool live_pair(const ArgsOf<TRIM>& A, const RecClass& c) {
-  if constexpr (TRIM) return (A.removed[c.sq >> 1] | A.removed[c.st >> 1]) == 0u;
+  if constexpr (TRIM != 0) return (A.removed[c.sq >> 1] | A.removed[c.st >> 1]) == 0u;
   return true;
 }
+// record i was cut in an earlier round (i < n_edges)
+template <int TRIM>
+__device__ __forceinline__ bool was_cut(const ArgsOf<TRIM>& A, u64 i) {
+  if constexpr (TRIM == 2) return A.cut[i] != 0u;
+  return false;
+}
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
   if (idle_round<TRIM>(A)) return;
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -117,7 +132,8 @@ __global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
     const RecClass c = classify(reinterpret_cast<const uint4*>(A.edges)[i], A);
     bad = c.kind == 0u;
     low = c.kind == 1u;
-    if (c.kind == 2u && !live_pair<TRIM>(A, c)) {
+    if (was_cut<TRIM>(A, i)) {
+    } else if (c.kind == 2u && !live_pair<TRIM>(A, c)) {
       dropped = 1;
     } else if (c.kind == 2u) {
       if (c.contain) {  // both directions (src/bigraph.cpp:497-522): every end of both reads
@@ -128,6 +144,13 @@ __global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
       } else {
         atomicAdd(&A.deg[c.sq], 1u);
         atomicAdd(&A.deg[c.st], 1u);
+        if constexpr (TRIM == 2) {  // a participant of the cut step
+          if (A.maxlen) {
+            const u32 len = reinterpret_cast<const uint4*>(A.edges)[i].z;
+            atomicMax(&A.maxlen[c.sq], len);
+            atomicMax(&A.maxlen[c.st], len);
+          }
+        }
       }
     }
   }
@@ -136,13 +159,13 @@ __global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
     if (tb) atomicAdd(&A.counts[UNI_C_BAD], tb);
     if (tl) atomicAdd(&A.counts[UNI_C_LOW], tl);
   }
-  if constexpr (TRIM) {
+  if constexpr (TRIM != 0) {
     const u64 td = wave_total(dropped);
     if ((threadIdx.x & 63u) == 0u && td && A.round == 0u) atomicAdd(trim_slot(A, TRIM_C_DROPPED), td);
   }
 }
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_links(ArgsOf<TRIM> A) {
   if (idle_round<TRIM>(A)) return;
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -150,7 +173,7 @@ __global__ __launch_bounds__(256) void k_uni_links(ArgsOf<TRIM> A) {
   if (i < A.n_edges) {
     const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
     const RecClass c = classify(rec, A);
-    if (c.kind == 2u && !c.contain && !c.self && live_pair<TRIM>(A, c) && A.deg[c.sq] == 1u && A.deg[c.st] == 1u) {
+    if (c.kind == 2u && !c.contain && !c.self && !was_cut<TRIM>(A, i) && live_pair<TRIM>(A, c) && A.deg[c.sq] == 1u && A.deg[c.st] == 1u) {
       A.link[c.sq] = make_uint2(c.st, rec.z);
       A.link[c.st] = make_uint2(c.sq, rec.z);
       simple = 1;
@@ -164,7 +187,7 @@ __global__ __launch_bounds__(256) void k_uni_links(ArgsOf<TRIM> A) {
 // rk[s] = {successor or NIL, state reached so far, hops so far, smallest read id so far}; dist[s] = bases so far: a hop
 // into read y over an overlap of len adds L[y] - len.  second: the ranking after the cut, which has nothing to do when
 // nothing was cut.
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_init(ArgsOf<TRIM> A, uint4* __restrict__ rk, u64* __restrict__ dist, int second) {
   if (idle_round<TRIM>(A)) return;
   if (second && A.counts[UNI_C_CYCLES] == 0ull) return;
@@ -182,7 +205,7 @@ __global__ __launch_bounds__(256) void k_uni_init(ArgsOf<TRIM> A, uint4* __restr
   }
 }
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_jump(ArgsOf<TRIM> A, const uint4* __restrict__ in, const u64* __restrict__ din,
                                                   uint4* __restrict__ out, u64* __restrict__ dout, int second) {
   if (idle_round<TRIM>(A)) return;
@@ -200,7 +223,7 @@ __global__ __launch_bounds__(256) void k_uni_jump(ArgsOf<TRIM> A, const uint4* _
   dout[s] = d;
 }
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_cut(ArgsOf<TRIM> A, const uint4* __restrict__ rk) {
   if (idle_round<TRIM>(A)) return;
   const u64 m = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -226,13 +249,13 @@ __global__ __launch_bounds__(256) void k_uni_cut(ArgsOf<TRIM> A, const uint4* __
 // it is entered through B and placed forward)
 __device__ __forceinline__ u32 head_dir(const uint4 a0, const uint4 a1) { return (a0.y >> 1) <= (a1.y >> 1) ? 0u : 1u; }
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_heads(ArgsOf<TRIM> A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
   if (idle_round<TRIM>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   if (r >= A.n_reads) return;
   bool alive = true;
-  if constexpr (TRIM) alive = A.removed[r] == 0u;  // a removed read lies alone in the ranking: it heads nothing
+  if constexpr (TRIM != 0) alive = A.removed[r] == 0u;  // a removed read lies alone in the ranking: it heads nothing
   const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
   const u32 d = head_dir(a0, a1);
   const uint4 to = d ? a1 : a0, away = d ? a0 : a1;
@@ -250,14 +273,14 @@ __global__ __launch_bounds__(256) void k_uni_heads(ArgsOf<TRIM> A, const uint4* 
 }
 
 // ---- phase 6: placements ----
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_place(ArgsOf<TRIM> A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.n_reads;
   if (r >= n) return;
   const u64 *unum = A.scan, *layr = A.scan + (n + 1), *lo = A.scan + 2 * (n + 1), *hi = A.scan + 3 * (n + 1);
   bool alive = true;
-  if constexpr (TRIM) {  // a removed read has no placement and heads nothing
+  if constexpr (TRIM != 0) {  // a removed read has no placement and heads nothing
     alive = A.removed[r] == 0u;
     if (!alive) A.umap[r] = NIL;
   }
@@ -277,7 +300,7 @@ __global__ __launch_bounds__(256) void k_uni_place(ArgsOf<TRIM> A, const uint4* 
       A.dst[slot] = seq0 + off + skip;
       A.src[slot] = (d ? b0 + L - 1ull - skip : b0 + skip) | ((u64)d << 63);
     }
-    if constexpr (TRIM) A.umap[r] = ((u32)unum[h] << 1) | d;
+    if constexpr (TRIM != 0) A.umap[r] = ((u32)unum[h] << 1) | d;
     if (to.z == 0u && to.x == NIL) {  // the head writes its unitig's entries
       const u64 u = unum[r];
       if (u < n) {
@@ -294,7 +317,7 @@ __global__ __launch_bounds__(256) void k_uni_place(ArgsOf<TRIM> A, const uint4* 
       A.lay_offs[U] = layr[n];
     }
     A.dst[n] = bases;
-    if constexpr (TRIM) {  // the placements are those of the alive reads: k_uni_bases<true> stops after them
+    if constexpr (TRIM != 0) {  // the placements are those of the alive reads: k_uni_bases<1> stops after them
       if (layr[n] < n) A.dst[layr[n]] = bases;
     }
     const u64 cyc = A.counts[UNI_C_CYCLES], simple = A.counts[UNI_C_SIMPLE];
@@ -317,12 +340,12 @@ struct BaseSh {
   u64 src[4][64];
 };
 
-template <bool TRIM>
+template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_bases(ArgsOf<TRIM> A) {
   __shared__ BaseSh sh;
   const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   u64 n = A.n_reads;
-  if constexpr (TRIM) {  // the placements of the alive reads (k_uni_place<true> closed dst after them)
+  if constexpr (TRIM != 0) {  // the placements of the alive reads (k_uni_place<1> closed dst after them)
     const u64 placed = A.scan[(A.n_reads + 1) + A.n_reads];
     if (placed < n) n = placed;
   }
@@ -423,7 +446,7 @@ __global__ __launch_bounds__(256) void k_uni_bases(ArgsOf<TRIM> A) {
 // One lane per read.  A head judges its unitig: its left end is the end the head is entered through (nothing links there),
 // its right end the state the walk away from the head stops in; a ring's two ends each carry its closing record.
 __global__ __launch_bounds__(256) void k_trim_decide(UnitigTrimArgs A, const uint4* __restrict__ rk) {
-  if (idle_round<true>(A)) return;
+  if (idle_round<1>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.n_reads;
   u32 island = 0, dead_end = 0;
@@ -454,7 +477,7 @@ __global__ __launch_bounds__(256) void k_trim_decide(UnitigTrimArgs A, const uin
 
 // One lane per read: the verdict lies under its head, which the final rank entry names.
 __global__ __launch_bounds__(256) void k_trim_mark(UnitigTrimArgs A, const uint4* __restrict__ rk) {
-  if (idle_round<true>(A)) return;
+  if (idle_round<1>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.n_reads;
   u32 gone = 0;
@@ -475,16 +498,18 @@ __global__ __launch_bounds__(256) void k_trim_mark(UnitigTrimArgs A, const uint4
 
 // ---- the records that were not merged, over unitigs ----
 // lifted: kept, both reads alive, and not a link of the final graph (a ring's closing record was one and was cut: lifted)
-__device__ __forceinline__ bool lifted(const UnitigTrimArgs& A, const RecClass& c) {
-  if (c.kind != 2u || !live_pair<true>(A, c)) return false;
+template <int TRIM>
+__device__ __forceinline__ bool lifted(const ArgsOf<TRIM>& A, const RecClass& c, u64 i) {
+  if (c.kind != 2u || was_cut<TRIM>(A, i) || !live_pair<TRIM>(A, c)) return false;
   const bool simple = !c.contain && !c.self && A.deg[c.sq] == 1u && A.deg[c.st] == 1u;
   return !(simple && A.link[c.sq].x == c.st);
 }
 
-__global__ __launch_bounds__(256) void k_lift_flag(UnitigTrimArgs A) {
+template <int TRIM>
+__global__ __launch_bounds__(256) void k_lift_flag(ArgsOf<TRIM> A) {
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
   if (i >= A.n_edges) return;
-  A.eflag[i] = lifted(A, classify(reinterpret_cast<const uint4*>(A.edges)[i], A)) ? 1u : 0u;
+  A.eflag[i] = lifted<TRIM>(A, classify(reinterpret_cast<const uint4*>(A.edges)[i], A), i) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(256) void k_lift_write(UnitigTrimArgs A) {
@@ -513,10 +538,162 @@ __global__ void k_trim_status(UnitigTrimArgs A) {
   A.status[11] = A.uedges ? A.trim[TRIM_LIFTED] : 0ull;
 }
 
+// ---- non-maximal overlap cutting: one round's cut step (MaximumOverlapVisitor, src/bigraph_visitors.cpp:410-512) ----
+__device__ __forceinline__ u64* prune_slot(const UnitigPruneArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  return A.prune + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 prune_count(const UnitigPruneArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.prune[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+// the head of the unitig of state s (s < 2 n_reads), by the final rank entry; NIL where the entry names no read
+__device__ __forceinline__ u32 head_of(const UnitigPruneArgs& A, const uint4* __restrict__ rk, u32 s) {
+  const u64 r = s >> 1;
+  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+  const u32 h = (head_dir(a0, a1) ? a1 : a0).y >> 1;
+  return (u64)h < A.n_reads ? h : NIL;
+}
+
+// Before a cut step: the longest participant per read end back to 0 and, careful mode, the longest self record and the key table
+// back to empty.  A kernel and no memset, so that the rounds after one that changed nothing do not write the table again.
+__global__ __launch_bounds__(256) void k_prune_clear(UnitigPruneArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < 2 * A.n_reads) {
+    A.maxlen[i] = 0u;
+    if (A.careful) A.maxself[i] = 0u;
+  }
+  if (A.careful && i < A.key_cap) A.keys[i] = ~0ull;
+}
+
+// One lane per read.  A head scores its unitig: (N - K) (log(G - b) - log(G - 2 b)) - K log 2 in double, K its reads, b its
+// bases; log(0.001) stands for the second logarithm when b < G <= 2 b, as in the reference; b >= G: not unique.
+__global__ __launch_bounds__(256) void k_prune_unique(UnitigPruneArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 u = 0;
+  if (r < n) {
+    if (A.removed[r] == 0u && A.cnt[r] != 0u) {
+      const u64 K = A.cnt[n + 1 + r], b = (u64)A.cnt[2 * (n + 1) + r] | ((u64)A.cnt[3 * (n + 1) + r] << 32);
+      const u64 N = A.num_reads, G = A.genome_size;
+      if (b < G && K <= N) {
+        const u64 rest = G - b;  // G > 2 b  <=>  rest > b
+        const double second = rest > b ? log((double)(rest - b)) : log(0.001);
+        const double score = (double)(N - K) * (log((double)rest) - second) - (double)K * log(2.0);
+        u = score >= A.uniq_threshold ? 1u : 0u;
+      }
+    }
+    A.uniq[r] = u;
+  }
+  const u64 tu = wave_total(u);
+  if ((threadIdx.x & 63u) == 0u && tu && A.round == 1u) atomicAdd(prune_slot(A, PRUNE_C_UNIQUE), tu);
+}
+
+// a participant of the cut step: live, and no containment -> its two read ends and its length
+__device__ __forceinline__ bool participant(const UnitigPruneArgs& A, u64 i, u32& s, u32& t, u32& len) {
+  const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
+  const RecClass c = classify(rec, A);
+  s = c.sq;
+  t = c.st;
+  len = rec.z;
+  return c.kind == 2u && !c.contain && A.cut[i] == 0u && live_pair<2>(A, c);
+}
+__device__ __forceinline__ u64 key_hash(u64 k) {
+  k ^= k >> 33;
+  k *= 0xFF51AFD7ED558CCDull;
+  k ^= k >> 33;
+  k *= 0xC4CEB9FE1A85EC53ull;
+  return k ^ (k >> 33);
+}
+__device__ __forceinline__ void key_insert(const UnitigPruneArgs& A, u64 key) {
+  const u64 mask = A.key_cap - 1ull;
+  u64 at = key_hash(key) & mask;
+  for (u64 p = 0; p < A.key_cap; ++p, at = (at + 1ull) & mask) {  // (never more than key_cap probes; at most half the table fills)
+    const u64 was = atomicCAS(&A.keys[at], ~0ull, key);
+    if (was == ~0ull || was == key) return;
+  }
+}
+__device__ __forceinline__ bool key_there(const UnitigPruneArgs& A, u64 key) {
+  const u64 mask = A.key_cap - 1ull;
+  u64 at = key_hash(key) & mask;
+  for (u64 p = 0; p < A.key_cap; ++p, at = (at + 1ull) & mask) {
+    const u64 is = A.keys[at];
+    if (is == key) return true;
+    if (is == ~0ull) return false;
+  }
+  return false;
+}
+
+// Careful mode, one lane per record: what holds a candidate back.
+__global__ __launch_bounds__(256) void k_prune_keys(UnitigPruneArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n_edges) return;
+  u32 s, t, len;
+  if (!participant(A, i, s, t, len)) return;
+  const u32 hs = head_of(A, rk, s), ht = head_of(A, rk, t);
+  if (hs == NIL || ht == NIL) return;
+  if (hs == ht) {
+    atomicMax(&A.maxself[s], len);
+    atomicMax(&A.maxself[t], len);
+  }
+  const u32 ms = A.maxlen[s], mt = A.maxlen[t];
+  if ((ms > len ? ms - len : 0u) < A.delta) key_insert(A, ((u64)s << 32) | ht);
+  if ((mt > len ? mt - len : 0u) < A.delta) key_insert(A, ((u64)t << 32) | hs);
+}
+
+// One lane per record: cut iff a candidate from one of its two sides and not held back on that side.
+__global__ __launch_bounds__(256) void k_prune_cut(UnitigPruneArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 cut = 0;
+  u32 s, t, len;
+  if (i < A.n_edges && participant(A, i, s, t, len)) {
+    const u32 hs = head_of(A, rk, s), ht = head_of(A, rk, t);
+    if (hs != NIL && ht != NIL) {
+      const u32 ms = A.maxlen[s], mt = A.maxlen[t];
+      bool from_s = A.uniq[hs] != 0u && (ms > len ? ms - len : 0u) >= A.delta;
+      bool from_t = A.uniq[ht] != 0u && (mt > len ? mt - len : 0u) >= A.delta;
+      if (A.careful) {
+        if (hs == ht) {  // a self record of the unitig: held back where the longest at that end is one too
+          if (from_s && A.maxself[s] == ms) from_s = false;
+          if (from_t && A.maxself[t] == mt) from_t = false;
+        } else {  // held back where, seen from the other end, the unitig it comes from is among the longest
+          if (from_s && key_there(A, ((u64)t << 32) | hs)) from_s = false;
+          if (from_t && key_there(A, ((u64)s << 32) | ht)) from_t = false;
+        }
+      }
+      if (from_s || from_t) {
+        A.cut[i] = A.round;
+        cut = 1;
+      }
+    }
+  }
+  const u64 tc = wave_total(cut);
+  if ((threadIdx.x & 63u) == 0u && tc) {
+    atomicAdd(prune_slot(A, PRUNE_C_CUT), tc);
+    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+    A.prune[PRUNE_ROUND0 + A.round] = 1ull;
+  }
+}
+
+__global__ void k_prune_status(UnitigPruneArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.prune[PRUNE_ROUND0 + r] != 0ull;
+  A.status[12] = prune_count(A, PRUNE_C_CUT);
+  A.status[13] = rounds;
+  A.status[14] = prune_count(A, PRUNE_C_UNIQUE);
+  A.status[15] = 0ull;
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
-template <bool TRIM>
+template <int TRIM>
 unsigned launch_graph(const ArgsOf<TRIM>& a, hipStream_t st) {
   const u64 n = a.n_reads, ns = 2 * n;
   if (a.n_edges) {
@@ -535,7 +712,7 @@ unsigned launch_graph(const ArgsOf<TRIM>& a, hipStream_t st) {
   return rounds & 1;
 }
 
-template <bool TRIM>
+template <int TRIM>
 void launch_unitigs_t(const ArgsOf<TRIM>& a, hipStream_t st) {
   const u64 n = a.n_reads;
   const unsigned f = launch_graph<TRIM>(a, st);
@@ -555,23 +732,23 @@ unsigned unitig_rounds(unsigned long long n_reads) {
 }
 
 void launch_unitigs(const UnitigArgs& a, hipStream_t st) {
-  if (a.n_reads) launch_unitigs_t<false>(a, st);
+  if (a.n_reads) launch_unitigs_t<0>(a, st);
 }
 
 void launch_unitigs_trim(const UnitigTrimArgs& a, hipStream_t st) {
-  if (a.n_reads && a.removed) launch_unitigs_t<true>(a, st);
+  if (a.n_reads && a.removed) launch_unitigs_t<1>(a, st);
 }
 
 void launch_unitig_bases(const UnitigArgs& a, hipStream_t st) {
-  if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases<false>, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
+  if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases<0>, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
 }
 
 void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
   if (n == 0 || !a.removed || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
-  const unsigned f = launch_graph<true>(a, st);
+  const unsigned f = launch_graph<1>(a, st);
   const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<true>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_uni_heads<1>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
   hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
   hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
 }
@@ -579,9 +756,48 @@ void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st) {
 void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st) {
   if (a.n_reads == 0 || !a.removed) return;
   if (a.uedges && a.n_edges) {
-    hipLaunchKernelGGL(k_lift_flag, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_lift_flag<1>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
     launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
     hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
   }
   hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || !a.maxlen || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  const u64 lanes = a.careful && a.key_cap > 2 * n ? a.key_cap : 2 * n;
+  hipLaunchKernelGGL(k_prune_clear, dim3(blocks_of(lanes)), dim3(256), 0, st, a);
+  const unsigned f = launch_graph<2>(a, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_prune_unique, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  if (a.n_edges == 0) return;  // (unitigs are scored and counted all the same)
+  if (a.careful) hipLaunchKernelGGL(k_prune_keys, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_prune_cut, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin);
+}
+
+void launch_prune_trim_round(const UnitigPruneArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.maxlen || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  const unsigned f = launch_graph<2>(a, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+}
+
+void launch_unitigs_prune(const UnitigPruneArgs& a, hipStream_t st) {
+  if (a.n_reads && a.removed && !a.maxlen) launch_unitigs_t<2>(a, st);
+}
+
+void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  if (a.uedges && a.n_edges) {
+    hipLaunchKernelGGL(k_lift_flag<2>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
+    hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a));
+  }
+  hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, static_cast<const UnitigTrimArgs&>(a));
+  hipLaunchKernelGGL(k_prune_status, dim3(1), dim3(64), 0, st, a);
 }

@@ -192,7 +192,8 @@ class Locator {
 // `siga unitig`: the first step of the reference's `siga assemble`, Bigraph::simplify (src/bigraph.cpp:341-414), on the GPU: the
 // reads go through the overlap stages, their edge records stay records (no ASQG), and every unbranched chain of them becomes
 // one unitig (sigax_unitigs_host; the rules in include/sigax.h).  With setTrim / setGraph / setRemoved also the loop that follows
-// in assemble (TrimVisitor and simplify() in turn) and the graph between the unitigs (sigax_unitigs_trim_host).  One GPU.
+// in assemble (TrimVisitor and simplify() in turn) and the graph between the unitigs (sigax_unitigs_trim_host); with setMaxOverlap
+// also that loop's MaximumOverlapVisitor (sigax_unitigs_prune_host).  One GPU.
 class Unitigger {
  public:
   explicit Unitigger(bool irreducible = true, bool rc = true) : _irreducible(irreducible), _rc(rc), _unitigs(0), _bases(0), _merged(0), _cycles(0) {}
@@ -217,7 +218,24 @@ class Unitigger {
   void setGraph(const std::string& path) { _graph = path; }
   // one "name\tround" line per removed read, in read order
   void setRemoved(const std::string& path) { _removed = path; }
-  uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something
+  // Non-maximal overlap cutting in every round, before its trim step, as the default mode of the reference's `assemble` does it
+  // (MaximumOverlapVisitor, src/bigraph_visitors.cpp:410-512): at a unitig that scores as unique under (numReads, genomeSize,
+  // threshold; -N, -G, -T) every record shorter by `delta` (-d) or more than the longest of its read end is cut; `careful`
+  // (--max-overlap-carefully) keeps it where its other end knows no better one.  delta = 0, the default: none, and run() goes
+  // through the calls it went through without this.  numReads = 0: the reads of the file.  (sigax_unitigs_prune_host; the
+  // rules in include/sigax.h.)
+  void setMaxOverlap(size_t delta, bool careful, size_t numReads, size_t genomeSize, double threshold = 13.0) {
+    _delta = delta;
+    _careful = careful;
+    _numReads = numReads;
+    _genomeSize = genomeSize;
+    _uniqThreshold = threshold;
+  }
+  // one "query name\ttarget name\tlength\tround" line per cut record, in record order
+  void setCutEdges(const std::string& path) { _cutEdges = path; }
+  uint64_t recordsCut() const { return _recordsCut; }
+  uint64_t cutRounds() const { return _cutRounds; }    // rounds in which something was cut
+  uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something (with setMaxOverlap: or cut something)
   uint64_t islands() const { return _islands; }
   uint64_t deadEnds() const { return _deadEnds; }
   uint64_t readsRemoved() const { return _readsRemoved; }
@@ -233,8 +251,11 @@ class Unitigger {
   size_t _piece = 0;
   size_t _rounds = 0, _minBranchLength = 150;
   long _minBranchCoverage = -1;
-  std::string _graph, _removed;
-  uint64_t _trimRounds = 0, _islands = 0, _deadEnds = 0, _readsRemoved = 0;
+  std::string _graph, _removed, _cutEdges;
+  uint64_t _trimRounds = 0, _islands = 0, _deadEnds = 0, _readsRemoved = 0, _recordsCut = 0, _cutRounds = 0;
+  size_t _delta = 0, _numReads = 0, _genomeSize = 0;
+  bool _careful = false;
+  double _uniqThreshold = 13.0;
   std::string _error;
 };
 

@@ -536,6 +536,15 @@ static int unitig_help() {
          "                                       one VT line per unitig, one ED line per overlap that was not merged\n"
          "          --removed=FILE               write one line per removed read to FILE: read name, the round it went in\n"
          "\n"
+         "Maximal overlap parameters (as `siga assemble`; they need -x: the cutting runs in its rounds, before the trimming):\n"
+         "      -d, --max-overlap-delta=LEN      at a unitig that counts as unique, cut every overlap shorter by LEN or more than the\n"
+         "                                       longest at the same unitig end (default: 0, none)\n"
+         "          --max-overlap-carefully      ... but keep it where the unitig is among the longest seen from the overlap's other end\n"
+         "      -N, --num-reads=N                the number of reads in the data set (default: the reads in READSFILE)\n"
+         "      -G, --genome-size=LEN            the genome's length (required with -d)\n"
+         "      -T, --uniq-threshold=X           a unitig counts as unique from this score on (default: 13.0)\n"
+         "          --cut-edges=FILE             write one line per cut overlap to FILE: query name, target name, length, round\n"
+         "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
          "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
@@ -558,7 +567,7 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 }
 
 static int run_unitig(int argc, char** argv) {
-  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED };
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -566,19 +575,23 @@ static int run_unitig(int argc, char** argv) {
                                     {"cut-terminal", required_argument, nullptr, 'x'}, {"min-branch-length", required_argument, nullptr, 'n'},
                                     {"min-branch-coverage", required_argument, nullptr, 'C'}, {"graph", required_argument, nullptr, OPT_GRAPH},
                                     {"removed", required_argument, nullptr, OPT_REMOVED},
+                                    {"max-overlap-delta", required_argument, nullptr, 'd'}, {"max-overlap-carefully", no_argument, nullptr, OPT_CAREFULLY},
+                                    {"num-reads", required_argument, nullptr, 'N'},   {"genome-size", required_argument, nullptr, 'G'},
+                                    {"uniq-threshold", required_argument, nullptr, 'T'}, {"cut-edges", required_argument, nullptr, OPT_CUT_EDGES},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix, out, layout, graph, removed;
-  size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150;
+  std::string prefix, out, layout, graph, removed, cutEdges;
+  size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   long minBranchCoverage = -1;
-  bool exhaustive = false, norc = false, help = false;
+  double uniqThreshold = 13.0;
+  bool exhaustive = false, norc = false, help = false, carefully = false;
   int device = 0, c;
   std::vector<std::string> ini_store;
   std::vector<char*> ini_argv;
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:h", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:h", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
@@ -592,6 +605,20 @@ static int run_unitig(int argc, char** argv) {
         minBranchCoverage = (long)v;
         break;
       }
+      case 'd': if (!unitig_number(optarg, "-d, --max-overlap-delta", 0xFFFFFFFFull, &delta)) return 1; break;
+      case 'N': if (!unitig_number(optarg, "-N, --num-reads", ~0ull, &numReads)) return 1; break;
+      case 'G': if (!unitig_number(optarg, "-G, --genome-size", ~0ull, &genomeSize)) return 1; break;
+      case 'T': {
+        char* end = nullptr;
+        uniqThreshold = strtod(optarg, &end);
+        if (end == optarg || *end != '\0') {
+          fprintf(stderr, "siga unitig: -T, --uniq-threshold needs a number, got '%s'\n", optarg);
+          return 1;
+        }
+        break;
+      }
+      case OPT_CAREFULLY: carefully = true; break;
+      case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
       case OPT_GRAPH: graph = optarg; break;
       case OPT_REMOVED: removed = optarg; break;
@@ -603,6 +630,18 @@ static int run_unitig(int argc, char** argv) {
     }
   }
   if (help || argc - optind != 1) return unitig_help();
+  if (delta > 0 && cutTerminal == 0) {
+    fprintf(stderr, "siga unitig: -d, --max-overlap-delta needs -x, --cut-terminal: the cutting runs in its rounds\n");
+    return 1;
+  }
+  if (delta > 0 && genomeSize == 0) {
+    fprintf(stderr, "siga unitig: -d, --max-overlap-delta needs -G, --genome-size\n");
+    return 1;
+  }
+  if (delta == 0 && (carefully || !cutEdges.empty())) {
+    fprintf(stderr, "siga unitig: --max-overlap-carefully and --cut-edges need -d, --max-overlap-delta\n");
+    return 1;
+  }
   std::string input = argv[optind];
   if (prefix.empty()) prefix = sigah::Utils::stem(input);
   if (out.empty()) out = prefix + ".unitigs.fa";
@@ -615,6 +654,8 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setTrim(cutTerminal, minBranchLength, minBranchCoverage);
   unitigger.setGraph(graph);
   unitigger.setRemoved(removed);
+  unitigger.setMaxOverlap(delta, carefully, numReads, genomeSize, uniqThreshold);
+  unitigger.setCutEdges(cutEdges);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -624,6 +665,8 @@ static int run_unitig(int argc, char** argv) {
   if (cutTerminal)
     fprintf(stderr, "%llu trim rounds, %llu islands and %llu dead ends removed, %llu reads\n", (unsigned long long)unitigger.trimRounds(),
             (unsigned long long)unitigger.islands(), (unsigned long long)unitigger.deadEnds(), (unsigned long long)unitigger.readsRemoved());
+  if (delta)
+    fprintf(stderr, "%llu records cut in %llu rounds\n", (unsigned long long)unitigger.recordsCut(), (unsigned long long)unitigger.cutRounds());
   return 0;
 }
 

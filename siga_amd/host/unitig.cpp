@@ -18,6 +18,7 @@ struct Unitigs {
   char* useqs = nullptr;
   uint32_t* removed = nullptr;  // the two of sigax_unitigs_trim_host
   sigax_edge* uedges = nullptr;
+  uint32_t* cut = nullptr;  // sigax_unitigs_prune_host's
   Unitigs() = default;
   Unitigs(const Unitigs&) = delete;
   Unitigs& operator=(const Unitigs&) = delete;
@@ -29,6 +30,7 @@ struct Unitigs {
     sigax_free(useqs);
     sigax_free(removed);
     sigax_free(uedges);
+    sigax_free(cut);
   }
 };
 
@@ -82,7 +84,7 @@ static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t
 bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta, const std::string& layout,
                     size_t threads) {
   _error.clear();
-  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = 0;
+  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -112,11 +114,30 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  uint64_t status[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t status[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
-  if (trim) {
+  if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
+  if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
+  }
+  if (_delta > 0) {
+    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
+    sigax_prune_opts opts;
+    opts.max_rounds = (uint32_t)_rounds;
+    opts.min_branch_length = (uint32_t)_minBranchLength;
+    opts.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
+    opts.delta = (uint32_t)_delta;
+    opts.careful = _careful ? 1u : 0u;
+    opts.reserved = 0;
+    opts.num_reads = _numReads ? _numReads : n;
+    opts.genome_size = _genomeSize;
+    opts.uniq_threshold = _uniqThreshold;
+    if (sigax_unitigs_prune_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,
+                                 &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                 _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else if (trim) {
     sigax_trim_opts opts;
     opts.max_rounds = (uint32_t)_rounds;
     opts.min_branch_length = (uint32_t)_minBranchLength;
@@ -140,6 +161,8 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _islands = status[7];
   _deadEnds = status[8];
   _readsRemoved = status[9];
+  _recordsCut = status[12];
+  _cutRounds = status[13];
   // ">unitig-<n>[ KC:i:<reads>][ circular=<closing overlap>]": the coverage tag only above 1, as FastaVisitor writes it
   // (src/bigraph_visitors.cpp:248-257)
   FILE* out = fasta.empty() ? stdout : fopen(fasta.c_str(), "wb");
@@ -185,6 +208,31 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     ok = write_all(rf, t);
     if (fclose(rf) != 0) ok = false;
     if (!ok) return fail("Failed to write " + _removed);
+    t.clear();
+  }
+  if (!_cutEdges.empty()) {
+    FILE* cf = fopen(_cutEdges.c_str(), "wb");
+    if (!cf) return fail("Failed to create " + _cutEdges);
+    t.clear();
+    for (size_t i = 0; i < edges.size() && ok; ++i)
+      if (u.cut[i] && edges[i].query < n && edges[i].target < n) {
+        const std::string_view q = reads.name(edges[i].query), tg = reads.name(edges[i].target);
+        t.append(q.data(), q.size());
+        t += '\t';
+        t.append(tg.data(), tg.size());
+        t += '\t';
+        append_u64(t, edges[i].length);
+        t += '\t';
+        append_u64(t, u.cut[i]);
+        t += '\n';
+        if (t.size() >= ((size_t)1 << 20)) {
+          ok = write_all(cf, t);
+          t.clear();
+        }
+      }
+    if (ok) ok = write_all(cf, t);
+    if (fclose(cf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _cutEdges);
     t.clear();
   }
   if (layout.empty()) return true;

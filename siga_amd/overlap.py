@@ -184,6 +184,50 @@ def unitigs_trim(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch
     return out
 
 
+def unitigs_prune(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
+                  num_reads=None, genome_size=None, uniq_threshold=13.0, graph=True, bases=True, device=0):
+    """`unitigs_trim` with non-maximal overlap cutting in every round (sigax_unitigs_prune_host, the rules in include/sigax.h):
+    at a unitig that scores as unique under (num_reads N, genome_size G, uniq_threshold T) a record shorter by delta or more than
+    the longest of its read end is cut before the round's trim step; with careful it stays where, seen from its other end, the
+    unitig is among the longest.  delta = 0 is `unitigs_trim`.  num_reads=None: len(lengths).  -> the dict of `unitigs_trim` plus
+    cut u32[n_edges] (0, or the round a record was cut in); status u64[16]: as there with 6 = rounds that changed something,
+    then {records cut, rounds that cut, unique unitigs seen by the first cut step, 0}."""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(lengths)
+    if len(offs) != n + 1:
+        raise ValueError("offs must have len(lengths) + 1 entries")
+    if isinstance(seqs, np.ndarray):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+    else:
+        buf = bytes(seqs)
+    L = _lib.lib()
+    opts = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
+                          _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
+                          n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
+    nu = C.c_uint64()
+    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
+    status = np.zeros(16, dtype=np.uint64)
+    _check(L.sigax_unitigs_prune_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+                                      offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf),
+                                      C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct), C.byref(ue) if graph else None,
+                                      status.ctypes.data), "sigax_unitigs_prune_host")
+    try:
+        u = int(nu.value)
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
+               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
+        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
+    finally:
+        for p in (so, lo, uf, lay, us, rm, ct, ue):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
