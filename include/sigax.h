@@ -435,7 +435,8 @@ int  sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint64_t n_edg
 /* ---- `siga unitig -x -d`: non-maximal overlap cutting in the rounds (csrc/sigax_unitig.hip) ---------------------------------------
  * The second visitor of a round of the reference's default `assemble` loop (src/assembler.cpp:166-221): MaximumOverlapVisitor
  * (src/bigraph_visitors.cpp:410-512; -d, --max-overlap-carefully, -N, -G, -T) before TrimVisitor, each followed by simplify().
- * LoopRemoveVisitor, ChimericVisitor and the paired and linked-read visitors are not restated.  Everything not said here is as
+ * ChimericVisitor is the block after this one; LoopRemoveVisitor and the paired and linked-read visitors are not restated.
+ * Everything not said here is as
  * in the `siga unitig -x` block above: record classes, B/E ends, degrees, simple records, rings, orientation, numbering, the
  * trim verdict, lifted records.
  *
@@ -504,6 +505,78 @@ int  sigax_unitigs_prune_host(int device, const sigax_edge* edges, uint64_t n_ed
                               uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                               sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                               uint64_t status16[16]);
+/* ---- `siga unitig -x -l`: chimeric unitig removal in the rounds (csrc/sigax_unitig.hip) ------------------------------------------
+ * The last visitor of a round of the reference's default `assemble` loop: ChimericVisitor (src/bigraph_visitors.cpp:83-198,
+ * src/assembler.cpp:207-213; -l, -A, -a, -N, -G, -T), after MaximumOverlapVisitor and TrimVisitor, each followed by simplify().
+ * It removes the short, thinly covered vertex that bridges two places of the genome.  Everything not said here is as in the
+ * `-x` and `-d` blocks above: record classes, B/E ends, live records, degrees, unitigs, rings, the trim verdict, PARTICIPANTS
+ * (live records that are no containments), unique(U), lifted records.
+ *
+ * sigax_chimeric_opts: prune = the sigax_prune_opts of the block above; min_chimeric_length Lc (-l; 0 = no chimeric step),
+ * min_chimeric_coverage Ac (-A; 0xFFFFFFFF = no coverage test), chimeric_delta delta_c (-a), reserved2 = 0,
+ * chimeric_threshold Tc (-T as the chimeric visitor takes it).
+ *
+ * One round r = 1, 2, ...: CUT STEP (when delta > 0), TRIM STEP, CHIMERIC STEP (when Lc > 0).  Each step runs over the state the
+ * step before left and takes every decision from the state at its own start.  A round in which no step changed anything ends
+ * the loop and is not counted.
+ *
+ * The chimeric verdict.  For the unitigs of the state at the start of the step, sL and sR are the outward read ends of unitig
+ * U and dL, dR their degrees, as the trim block defines them; K(U) its reads, bases(U) its bases.  U is CHIMERIC iff
+ *   1. ENDS        dL == 1 and dR == 1, and the one live record at each of sL and sR is a participant.  p = the state at the
+ *                  other end of sL's record, q = that of sR's; P = U(p), Q = U(q).  (A ring's ends carry each other: 3 fails.)
+ *   2. SIZE        bases(U) <= Lc and, when Ac is given, (K(U) - 1) * max(Lc, 1) <= (max(Ac, 1) - 1) * bases(U) in u64: the
+ *                  cross-multiplied Point::avg of the trim verdict.
+ *   3. NEIGHBOURS  deg[p] >= 2 and deg[q] >= 2 (degrees as everywhere: containments count).
+ *   4. SUPPORT     good(p) or good(q).  good(p) iff unique(P) under Tc (the expression and the bases >= G rule of the -d block)
+ *                  and, over the OTHERS of p -- the participants that touch p and have their other end outside U -- either
+ *                  every one has min(bases(U(other)), 2^32 - 1) > bases(U) + delta_c (u64), or every one has K(U(other)) >
+ *                  K(U) + 3.  With no others both hold, as the reference's loops do.  (A unitig of 2^32 - 1 bases or more counts
+ *                  as one of 2^32 - 1: that decides only where bases(U) + delta_c reaches 2^32 - 1.)
+ * All reads of a chimeric unitig get removed[read] = r | SIGAX_REMOVED_CHIMERIC.  Only these entry points ever set that bit.
+ *
+ * Deviations from the reference:
+ *   which end of the neighbour  The reference asks prevVert->degrees(ED_SENSE) and nextVert->degrees(ED_ANTISENSE) and walks those
+ *       edge lists, whatever end the edge's twin leaves from.  For a neighbour joined on the other strand that is the wrong
+ *       end, and for a merged vertex which end is SENSE depends on the order of its hash map.  Here it is always the end the
+ *       record touches.  The two agree wherever neighbour and vertex lie on one strand.
+ *   coverage option  The reference's -A never reaches the visitor (assembler.cpp:56 reads `max-chimeric-coverage`, the option is
+ *       named `min-chimeric-coverage`), so its coverage test always passes.  Here Ac works; not given = no test.
+ *   default of -a  The reference's default of -1 makes seq.length() + _delta wrap to length - 1.  Here delta_c is a u32 added in
+ *       u64, default 0.
+ *   defaults of N and G  The reference's fallbacks for N = 0 and G = 0 are not restated: G is required, N defaults to the reads.
+ *   scores near Tc  A score within rounding of Tc may fall on either side: the device's log need not round as libm's does.
+ *
+ * status20 = 20 u64, written: 0-15 as status16, with 6 = rounds in which any step changed something, 9 = all removed reads, 7
+ * and 8 the trim steps' islands and dead ends only; 16 chimeric unitigs removed, 17 reads the chimeric steps removed, 18 rounds
+ * in which a chimeric step removed something, 19 = 0.
+ *
+ * sigax_unitigs_chimeric_device: sigax_unitigs_prune_device with these options and d_status20.  Asynchronous on `stream`,
+ * allocates nothing, never waits for the device; it enqueues max_rounds rounds, whose launches return at once after a round that
+ * changed nothing.  d_work = sigax_unitigs_chimeric_workspace(n_reads, n_edges, d_uedges != NULL, careful) bytes: the prune
+ * call's scratch and 72 bytes per read.  min_chimeric_length = 0 gives exactly the prune call's result, status 16-19 zero and no
+ * flag bit.  Refusals as for the prune call, and reserved2 != 0, min_chimeric_length > 0 with genome_size == 0 or with num_reads
+ * < n_reads: SIGAX_E_ARG.  Whatever the records hold, nothing outside the buffers is touched. */
+#define SIGAX_REMOVED_CHIMERIC 0x80000000u
+typedef struct sigax_chimeric_opts {
+  sigax_prune_opts prune;
+  uint32_t min_chimeric_length;    /* Lc; 0 = no chimeric step */
+  uint32_t min_chimeric_coverage;  /* Ac; SIGAX_TRIM_NO_COVERAGE = no test */
+  uint32_t chimeric_delta;
+  uint32_t reserved2;              /* = 0 */
+  double   chimeric_threshold;     /* Tc */
+} sigax_chimeric_opts;
+int  sigax_unitigs_chimeric_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_chimeric_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                   const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_chimeric_opts* opts,
+                                   void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                   void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status20, void* d_work,
+                                   uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_prune_host, with status20.  It stops after the first round that changed nothing. */
+int  sigax_unitigs_chimeric_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                 const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_chimeric_opts* opts,
+                                 uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                 sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                                 uint64_t status20[20]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

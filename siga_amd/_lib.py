@@ -29,6 +29,7 @@ SIGAX_LOCATE_OVER = 2
 SIGAX_PLACED_REV = 1
 SIGAX_UNITIG_CIRCULAR = 1
 SIGAX_TRIM_NO_COVERAGE = 0xFFFFFFFF
+SIGAX_REMOVED_CHIMERIC = 0x80000000
 TRIM_MAX_ROUNDS = 64
 
 
@@ -39,6 +40,12 @@ class TrimOpts(C.Structure):  # sigax_trim_opts
 class PruneOpts(C.Structure):  # sigax_prune_opts
     _fields_ = ([(n, C.c_uint32) for n in ("max_rounds", "min_branch_length", "min_branch_coverage", "delta", "careful", "reserved")] +
                 [("num_reads", C.c_uint64), ("genome_size", C.c_uint64), ("uniq_threshold", C.c_double)])
+
+
+class ChimericOpts(C.Structure):  # sigax_chimeric_opts
+    _fields_ = ([("prune", PruneOpts)] +
+                [(n, C.c_uint32) for n in ("min_chimeric_length", "min_chimeric_coverage", "chimeric_delta", "reserved2")] +
+                [("chimeric_threshold", C.c_double)])
 
 
 class Stats(C.Structure):
@@ -86,6 +93,7 @@ SYMBOLS = [
     "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
+    "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -186,6 +194,11 @@ def lib():
                                              u64, vp]
     L.sigax_unitigs_prune_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(PruneOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp,
                                            pvp, pvp, pvp, vp]
+    L.sigax_unitigs_chimeric_workspace.argtypes = [u64, u64, ci, ci, C.POINTER(u64)]
+    L.sigax_unitigs_chimeric_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(ChimericOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, u64, vp]
+    L.sigax_unitigs_chimeric_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(ChimericOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
+                                              pvp, pvp, pvp, pvp, vp]
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
     L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]

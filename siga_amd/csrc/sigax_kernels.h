@@ -341,6 +341,30 @@ void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st);
 void launch_prune_trim_round(const UnitigPruneArgs& a, hipStream_t st);
 void launch_unitigs_prune(const UnitigPruneArgs& a, hipStream_t st);
 void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st);
+// chimeric unitig removal (sigax_unitigs_chimeric_*): the prune block and what a round's chimeric step needs.  The existing
+// kernels take the prune block out of it (by value); only the kernels of the chimeric step see the rest.
+struct UnitigChimericArgs : UnitigPruneArgs {
+  uint32_t* nbr;                         // [2 n_reads], cleared by the step (all ones): at a read end of degree 1 whose record is a
+                                         // participant, the read end at that record's other side
+  unsigned long long* minb[2];           // 2 x [2 n_reads], cleared (all ones): per read end of degree >= 2 the smallest
+                                         // (min(bases(U(b)), 2^32 - 1) << 32 | head(b)) over its participants' other ends b; [1]: the
+                                         // smallest among those whose head is not [0]'s
+  unsigned long long* mink[2];           // the same over (K(U(b)) << 32 | head(b))
+  unsigned long long* chim;              // CHIM_WORDS u64, zeroed before round 1: the CHIM_C_* counters, slotted as the trim counters are,
+                                         // and at CHIM_ROUND0 + r whether round r's chimeric step removed something
+  unsigned long long* prune_aside;       // PRUNE_WORDS u64: where the scoring pass of a chimeric step counts (status[14] is the cut step's)
+  uint32_t min_chimeric_length, min_chimeric_coverage, chimeric_delta;
+  double chimeric_threshold;
+};
+enum { CHIM_C_UNITIGS = 0, CHIM_C_READS = 1, CHIM_COUNTERS = 2, CHIM_ROUND0 = CHIM_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+       CHIM_WORDS = CHIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
+static const uint32_t REMOVED_CHIMERIC = 0x80000000u;
+// one round's chimeric step (a.round >= 1, a.maxlen = NULL), after launch_prune_trim_round: the graph of the live records, every
+// unitig scored under chimeric_threshold, the neighbours and the two minima per read end, the verdict per unitig, removed[] marked
+// with REMOVED_CHIMERIC.  Leaves at once when the round before changed nothing.  The caller resets as for launch_trim_round; the
+// step clears nbr, minb and mink itself.  launch_chimeric_status: status[16 .. 19], after launch_unitig_prune_lift.
+void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st);
+void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st);
 
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);

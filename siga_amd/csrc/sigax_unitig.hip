@@ -40,6 +40,14 @@
 //   k_prune_keys  careful mode, one lane per record: the (read end, unitig at the other end) pairs of the participants within
 //                 delta of their end's maximum go into an open-addressing table; the longest self record per read end
 //   k_prune_cut   one lane per record: candidate from either side, held back or not, cut[i] = round
+// Chimeric unitig removal (sigax_unitigs_chimeric_*; tests/chimeric_cases.py::expected_chimeric): a third step of a
+// round, over the <TRIM = 2> kernels and k_prune_unique under the chimeric threshold, and
+//   k_chim_clear   the step's scratch emptied (a kernel: idle rounds write nothing)
+//   k_chim_minima  one lane per record, twice: an end of degree 1 learns the read end at its record's other side; an end of
+//                  degree >= 2 takes the smallest (bases, head) and (reads, head) over the unitigs its participants lead to
+//                  (64-bit atomicMin behind a plain compare), then the smallest among those not of the first one's unitig
+//   k_chim_decide  one lane per read: a head judges its unitig from its two end degrees, its neighbours' degrees, scores and minima
+//   k_chim_mark    one lane per read: removed[r] = round | 0x80000000 under a chimeric head
 // The table's probe loops are bounded by its capacity, which holds at least twice the keys that can go in.
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
 // consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
@@ -690,6 +698,143 @@ __global__ void k_prune_status(UnitigPruneArgs A) {
   A.status[15] = 0ull;
 }
 
+// ---- chimeric unitig removal: one round's chimeric step (ChimericVisitor, src/bigraph_visitors.cpp:83-198) ----
+__device__ __forceinline__ u64* chim_slot(const UnitigChimericArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  return A.chim + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 chim_count(const UnitigChimericArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.chim[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+// reads and bases of the unitig under head h (h < n_reads), as k_uni_heads left them
+__device__ __forceinline__ u64 unit_reads(const UnitigArgs& A, u32 h) { return A.cnt[A.n_reads + 1 + h]; }
+__device__ __forceinline__ u64 unit_bases(const UnitigArgs& A, u32 h) {
+  return (u64)A.cnt[2 * (A.n_reads + 1) + h] | ((u64)A.cnt[3 * (A.n_reads + 1) + h] << 32);
+}
+__device__ __forceinline__ u64 chim_pack(u64 v, u32 h) { return ((v < 0xFFFFFFFFull ? v : 0xFFFFFFFFull) << 32) | h; }
+// (the entry only ever falls: a stale read costs an atomic that changes nothing, never a missed minimum)
+__device__ __forceinline__ void chim_min(u64* at, u64 v) {
+  if (v < *at) atomicMin(at, v);
+}
+
+// Before a chimeric step: neighbours and minima back to empty.  A kernel, as k_prune_clear: idle rounds write nothing.
+__global__ __launch_bounds__(256) void k_chim_clear(UnitigChimericArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= 2 * A.n_reads) return;
+  A.nbr[i] = NIL;
+  A.minb[0][i] = ~0ull;
+  A.minb[1][i] = ~0ull;
+  A.mink[0][i] = ~0ull;
+  A.mink[1][i] = ~0ull;
+}
+
+// One lane per record, a participant in both directions a -> b.  second = 0: an end of degree 1 learns its neighbour (its one
+// record: a single writer), an end of degree >= 2 takes the minima over the unitigs at its records' other ends.  second = 1: the
+// minima among the records whose unitig is not the first minimum's.
+__global__ __launch_bounds__(256) void k_chim_minima(UnitigChimericArgs A, const uint4* __restrict__ rk, int second) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n_edges) return;
+  u32 s, t, len;
+  if (!participant(A, i, s, t, len)) return;
+  const u32 hs = head_of(A, rk, s), ht = head_of(A, rk, t);
+  if (hs == NIL || ht == NIL) return;
+  const u64 bs = chim_pack(unit_bases(A, hs), hs), bt = chim_pack(unit_bases(A, ht), ht);
+  const u64 ks = chim_pack(unit_reads(A, hs), hs), kt = chim_pack(unit_reads(A, ht), ht);
+  for (int dir = 0; dir < 2; ++dir) {
+    const u32 a = dir ? t : s, b = dir ? s : t, hb = dir ? hs : ht;
+    const u64 vb = dir ? bs : bt, vk = dir ? ks : kt;
+    const u32 da = A.deg[a];
+    if (!second) {
+      if (da == 1u) {
+        A.nbr[a] = b;
+      } else if (da >= 2u) {
+        chim_min(&A.minb[0][a], vb);
+        chim_min(&A.mink[0][a], vk);
+      }
+    } else if (da >= 2u) {
+      if ((u32)A.minb[0][a] != hb) chim_min(&A.minb[1][a], vb);
+      if ((u32)A.mink[0][a] != hb) chim_min(&A.mink[1][a], vk);
+    }
+  }
+}
+
+// good(p) for the unitig under head h with `bases` and K reads: U(p) unique under Tc (k_prune_unique left it), and every other
+// unitig at p longer than bases + delta_c, or every one with more than K + 3 reads.  The minimum over the others is the second
+// entry where the first names h itself.  All ones = no others: both hold.
+__device__ __forceinline__ bool chim_good(const UnitigChimericArgs& A, const uint4* __restrict__ rk, u32 p, u32 h, u64 bases, u64 K) {
+  const u32 hp = head_of(A, rk, p);
+  if (hp == NIL || A.uniq[hp] == 0u) return false;
+  u64 mb = A.minb[0][p], mk = A.mink[0][p];
+  if (mb != ~0ull && (u32)mb == h) mb = A.minb[1][p];
+  if (mk != ~0ull && (u32)mk == h) mk = A.mink[1][p];
+  const bool by_bases = mb == ~0ull || (mb >> 32) > bases + (u64)A.chimeric_delta;
+  const bool by_reads = mk == ~0ull || (mk >> 32) > K + 3ull;
+  return by_bases || by_reads;
+}
+
+// One lane per read.  A head judges its unitig, its ends found as k_trim_decide finds them.
+__global__ __launch_bounds__(256) void k_chim_decide(UnitigChimericArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 v = 0;
+  if (r < n) {
+    if (A.removed[r] == 0u && A.cnt[r] != 0u) {
+      const u64 K = unit_reads(A, (u32)r), bases = unit_bases(A, (u32)r);
+      const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+      const u32 d = head_dir(a0, a1);
+      const u32 sl = 2u * (u32)r + d, sr = (d ? a0 : a1).y;
+      const u64 L = A.min_chimeric_length, C = A.min_chimeric_coverage;
+      if ((u64)sr < 2 * n && A.deg[sl] == 1u && A.deg[sr] == 1u && bases <= L &&
+          (A.min_chimeric_coverage == TRIM_NO_COVERAGE || (K - 1ull) * (L ? L : 1ull) <= ((C ? C : 1ull) - 1ull) * bases)) {
+        const u32 p = A.nbr[sl], q = A.nbr[sr];
+        if ((u64)p < 2 * n && (u64)q < 2 * n && A.deg[p] >= 2u && A.deg[q] >= 2u &&
+            (chim_good(A, rk, p, (u32)r, bases, K) || chim_good(A, rk, q, (u32)r, bases, K)))
+          v = 1;
+      }
+    }
+    A.verdict[r] = v;
+  }
+  const u64 tv = wave_total(v);
+  if ((threadIdx.x & 63u) == 0u && tv) atomicAdd(chim_slot(A, CHIM_C_UNITIGS), tv);
+}
+
+// One lane per read, as k_trim_mark: the verdict lies under its head.
+__global__ __launch_bounds__(256) void k_chim_mark(UnitigChimericArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 gone = 0;
+  if (r < n && A.removed[r] == 0u) {
+    const u32 h = head_of(A, rk, 2u * (u32)r);
+    if (h != NIL && A.verdict[h] != 0u) {
+      A.removed[r] = A.round | REMOVED_CHIMERIC;
+      gone = 1;
+    }
+  }
+  const u64 tg = wave_total(gone);
+  if ((threadIdx.x & 63u) == 0u && tg) {
+    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
+    atomicAdd(chim_slot(A, CHIM_C_READS), tg);
+    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+    A.chim[CHIM_ROUND0 + A.round] = 1ull;
+  }
+}
+
+__global__ void k_chim_status(UnitigChimericArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.chim[CHIM_ROUND0 + r] != 0ull;
+  A.status[16] = chim_count(A, CHIM_C_UNITIGS);
+  A.status[17] = chim_count(A, CHIM_C_READS);
+  A.status[18] = rounds;
+  A.status[19] = 0ull;
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
@@ -800,4 +945,29 @@ void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st) {
   }
   hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, static_cast<const UnitigTrimArgs&>(a));
   hipLaunchKernelGGL(k_prune_status, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.maxlen || !a.nbr || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  hipLaunchKernelGGL(k_chim_clear, dim3(blocks_of(2 * n)), dim3(256), 0, st, a);
+  const UnitigPruneArgs& pa = a;
+  const unsigned f = launch_graph<2>(pa, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
+  UnitigPruneArgs score = pa;  // the cut step's scoring kernel, under the chimeric threshold, counting aside
+  score.uniq_threshold = a.chimeric_threshold;
+  score.prune = a.prune_aside;
+  hipLaunchKernelGGL(k_prune_unique, dim3(blocks_of(n)), dim3(256), 0, st, score);
+  if (a.n_edges) {
+    hipLaunchKernelGGL(k_chim_minima, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin, 0);
+    hipLaunchKernelGGL(k_chim_minima, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin, 1);
+  }
+  hipLaunchKernelGGL(k_chim_decide, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_chim_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+}
+
+void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  hipLaunchKernelGGL(k_chim_status, dim3(1), dim3(64), 0, st, a);
 }

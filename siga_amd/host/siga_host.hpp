@@ -193,7 +193,8 @@ class Locator {
 // reads go through the overlap stages, their edge records stay records (no ASQG), and every unbranched chain of them becomes
 // one unitig (sigax_unitigs_host; the rules in include/sigax.h).  With setTrim / setGraph / setRemoved also the loop that follows
 // in assemble (TrimVisitor and simplify() in turn) and the graph between the unitigs (sigax_unitigs_trim_host); with setMaxOverlap
-// also that loop's MaximumOverlapVisitor (sigax_unitigs_prune_host).  One GPU.
+// also that loop's MaximumOverlapVisitor (sigax_unitigs_prune_host); with setChimeric also its ChimericVisitor
+// (sigax_unitigs_chimeric_host).  One GPU.
 class Unitigger {
  public:
   explicit Unitigger(bool irreducible = true, bool rc = true) : _irreducible(irreducible), _rc(rc), _unitigs(0), _bases(0), _merged(0), _cycles(0) {}
@@ -233,6 +234,22 @@ class Unitigger {
   }
   // one "query name\ttarget name\tlength\tround" line per cut record, in record order
   void setCutEdges(const std::string& path) { _cutEdges = path; }
+  // Chimeric unitig removal as the last step of every round, as the default mode of the reference's `assemble` does it with -l
+  // (ChimericVisitor, src/bigraph_visitors.cpp:83-198): a unitig of at most minLength bases (-l; 0, the default: none, and run()
+  // goes through the calls it went through without this) and, with minCoverage >= 0 (-A; -1: no such test), of low coverage, that
+  // bridges two branched read ends, goes where a neighbour is unique under `threshold` (-T) and no other unitig there is as short
+  // (within `delta`, -a) or as thin.  Needs rounds and a genome size (setTrim, setMaxOverlap).  (sigax_unitigs_chimeric_host; the
+  // rules in include/sigax.h.)
+  void setChimeric(size_t minLength, long minCoverage = -1, size_t delta = 0, double threshold = 0.0) {
+    _chimLength = minLength;
+    _chimCoverage = minCoverage;
+    _chimDelta = delta;
+    _chimThreshold = threshold;
+  }
+  // one "name\tround" line per read a chimeric step removed, in read order
+  void setChimericOut(const std::string& path) { _chimericOut = path; }
+  uint64_t chimericUnitigs() const { return _chimUnitigs; }
+  uint64_t chimericReads() const { return _chimReads; }
   uint64_t recordsCut() const { return _recordsCut; }
   uint64_t cutRounds() const { return _cutRounds; }    // rounds in which something was cut
   uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something (with setMaxOverlap: or cut something)
@@ -256,6 +273,11 @@ class Unitigger {
   size_t _delta = 0, _numReads = 0, _genomeSize = 0;
   bool _careful = false;
   double _uniqThreshold = 13.0;
+  size_t _chimLength = 0, _chimDelta = 0;
+  long _chimCoverage = -1;
+  double _chimThreshold = 0.0;
+  std::string _chimericOut;
+  uint64_t _chimUnitigs = 0, _chimReads = 0;
   std::string _error;
 };
 

@@ -545,6 +545,15 @@ static int unitig_help() {
          "      -T, --uniq-threshold=X           a unitig counts as unique from this score on (default: 13.0)\n"
          "          --cut-edges=FILE             write one line per cut overlap to FILE: query name, target name, length, round\n"
          "\n"
+         "Chimeric parameters (as `siga assemble`; they need -x and -G: the removal is the last step of a round):\n"
+         "      -l, --min-chimeric-length=LEN    remove a unitig of at most LEN bases that bridges two branched unitig ends, one of\n"
+         "                                       them at a unique unitig whose other neighbours are all longer or deeper\n"
+         "                                       (default: 0, none)\n"
+         "      -A, --min-chimeric-coverage=N    ... and only if its coverage, (reads - 1) / bases, is at most (N - 1) / LEN\n"
+         "      -a, --max-chimeric-delta=LEN     the other neighbours must be longer by more than LEN bases (default: 0)\n"
+         "          --chimeric=FILE              write one line per read removed as chimeric to FILE: read name, the round it went in\n"
+         "      -T sets both thresholds; without it cutting takes 13.0 and the chimeric step 0.0\n"
+         "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
          "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
@@ -567,7 +576,7 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 }
 
 static int run_unitig(int argc, char** argv) {
-  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES };
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -578,12 +587,16 @@ static int run_unitig(int argc, char** argv) {
                                     {"max-overlap-delta", required_argument, nullptr, 'd'}, {"max-overlap-carefully", no_argument, nullptr, OPT_CAREFULLY},
                                     {"num-reads", required_argument, nullptr, 'N'},   {"genome-size", required_argument, nullptr, 'G'},
                                     {"uniq-threshold", required_argument, nullptr, 'T'}, {"cut-edges", required_argument, nullptr, OPT_CUT_EDGES},
+                                    {"min-chimeric-length", required_argument, nullptr, 'l'},
+                                    {"min-chimeric-coverage", required_argument, nullptr, 'A'},
+                                    {"max-chimeric-delta", required_argument, nullptr, 'a'}, {"chimeric", required_argument, nullptr, OPT_CHIMERIC},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix, out, layout, graph, removed, cutEdges;
+  std::string prefix, out, layout, graph, removed, cutEdges, chimericOut;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
-  long minBranchCoverage = -1;
-  double uniqThreshold = 13.0;
+  size_t chimLength = 0, chimDelta = 0;
+  long minBranchCoverage = -1, chimCoverage = -1;
+  double uniqThreshold = 13.0, chimThreshold = 0.0;  // (-T sets both: src/assembler.cpp:55-67)
   bool exhaustive = false, norc = false, help = false, carefully = false;
   int device = 0, c;
   std::vector<std::string> ini_store;
@@ -591,7 +604,7 @@ static int run_unitig(int argc, char** argv) {
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:h", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:l:A:a:h", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
@@ -615,8 +628,18 @@ static int run_unitig(int argc, char** argv) {
           fprintf(stderr, "siga unitig: -T, --uniq-threshold needs a number, got '%s'\n", optarg);
           return 1;
         }
+        chimThreshold = uniqThreshold;
         break;
       }
+      case 'l': if (!unitig_number(optarg, "-l, --min-chimeric-length", 0xFFFFFFFFull, &chimLength)) return 1; break;
+      case 'a': if (!unitig_number(optarg, "-a, --max-chimeric-delta", 0xFFFFFFFFull, &chimDelta)) return 1; break;
+      case 'A': {
+        size_t v = 0;
+        if (!unitig_number(optarg, "-A, --min-chimeric-coverage", 0xFFFFFFFEull, &v)) return 1;
+        chimCoverage = (long)v;
+        break;
+      }
+      case OPT_CHIMERIC: chimericOut = optarg; break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -642,6 +665,18 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: --max-overlap-carefully and --cut-edges need -d, --max-overlap-delta\n");
     return 1;
   }
+  if (chimLength > 0 && cutTerminal == 0) {
+    fprintf(stderr, "siga unitig: -l, --min-chimeric-length needs -x, --cut-terminal: the removal runs in its rounds\n");
+    return 1;
+  }
+  if (chimLength > 0 && genomeSize == 0) {
+    fprintf(stderr, "siga unitig: -l, --min-chimeric-length needs -G, --genome-size\n");
+    return 1;
+  }
+  if (chimLength == 0 && (chimCoverage >= 0 || chimDelta > 0 || !chimericOut.empty())) {
+    fprintf(stderr, "siga unitig: -A, -a and --chimeric need -l, --min-chimeric-length\n");
+    return 1;
+  }
   std::string input = argv[optind];
   if (prefix.empty()) prefix = sigah::Utils::stem(input);
   if (out.empty()) out = prefix + ".unitigs.fa";
@@ -651,6 +686,8 @@ static int run_unitig(int argc, char** argv) {
     return -1;
   }
   sigah::Unitigger unitigger(!exhaustive, !norc);
+  unitigger.setChimeric(chimLength, chimCoverage, chimDelta, chimThreshold);
+  unitigger.setChimericOut(chimericOut);
   unitigger.setTrim(cutTerminal, minBranchLength, minBranchCoverage);
   unitigger.setGraph(graph);
   unitigger.setRemoved(removed);
@@ -667,6 +704,9 @@ static int run_unitig(int argc, char** argv) {
             (unsigned long long)unitigger.islands(), (unsigned long long)unitigger.deadEnds(), (unsigned long long)unitigger.readsRemoved());
   if (delta)
     fprintf(stderr, "%llu records cut in %llu rounds\n", (unsigned long long)unitigger.recordsCut(), (unsigned long long)unitigger.cutRounds());
+  if (chimLength)
+    fprintf(stderr, "%llu chimeric unitigs removed, %llu reads\n", (unsigned long long)unitigger.chimericUnitigs(),
+            (unsigned long long)unitigger.chimericReads());
   return 0;
 }
 

@@ -84,7 +84,7 @@ static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t
 bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta, const std::string& layout,
                     size_t threads) {
   _error.clear();
-  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = 0;
+  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -114,14 +114,38 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  uint64_t status[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t status[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
+  if (!_chimericOut.empty() && _chimLength == 0) return fail("chimeric reads are only written with a min-chimeric length");
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
   if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
   }
-  if (_delta > 0) {
+  if (_chimLength > 0) {
+    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
+    if (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll)
+      return fail("chimeric length, delta or coverage out of range");
+    sigax_chimeric_opts opts;
+    opts.prune.max_rounds = (uint32_t)_rounds;
+    opts.prune.min_branch_length = (uint32_t)_minBranchLength;
+    opts.prune.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
+    opts.prune.delta = (uint32_t)_delta;
+    opts.prune.careful = _careful ? 1u : 0u;
+    opts.prune.reserved = 0;
+    opts.prune.num_reads = _numReads ? _numReads : n;
+    opts.prune.genome_size = _genomeSize;
+    opts.prune.uniq_threshold = _uniqThreshold;
+    opts.min_chimeric_length = (uint32_t)_chimLength;
+    opts.min_chimeric_coverage = _chimCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_chimCoverage;
+    opts.chimeric_delta = (uint32_t)_chimDelta;
+    opts.reserved2 = 0;
+    opts.chimeric_threshold = _chimThreshold;
+    if (sigax_unitigs_chimeric_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
+                                    (uint32_t)minOverlap, &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                    _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else if (_delta > 0) {
     if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
     sigax_prune_opts opts;
     opts.max_rounds = (uint32_t)_rounds;
@@ -163,6 +187,8 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _readsRemoved = status[9];
   _recordsCut = status[12];
   _cutRounds = status[13];
+  _chimUnitigs = status[16];
+  _chimReads = status[17];
   // ">unitig-<n>[ KC:i:<reads>][ circular=<closing overlap>]": the coverage tag only above 1, as FastaVisitor writes it
   // (src/bigraph_visitors.cpp:248-257)
   FILE* out = fasta.empty() ? stdout : fopen(fasta.c_str(), "wb");
@@ -202,12 +228,29 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
         const std::string_view name = reads.name(r);
         t.append(name.data(), name.size());
         t += '\t';
-        append_u64(t, u.removed[r]);
+        append_u64(t, u.removed[r] & ~SIGAX_REMOVED_CHIMERIC);
         t += '\n';
       }
     ok = write_all(rf, t);
     if (fclose(rf) != 0) ok = false;
     if (!ok) return fail("Failed to write " + _removed);
+    t.clear();
+  }
+  if (!_chimericOut.empty()) {
+    FILE* rf = fopen(_chimericOut.c_str(), "wb");
+    if (!rf) return fail("Failed to create " + _chimericOut);
+    t.clear();
+    for (size_t r = 0; r < n; ++r)
+      if (u.removed[r] & SIGAX_REMOVED_CHIMERIC) {
+        const std::string_view name = reads.name(r);
+        t.append(name.data(), name.size());
+        t += '\t';
+        append_u64(t, u.removed[r] & ~SIGAX_REMOVED_CHIMERIC);
+        t += '\n';
+      }
+    ok = write_all(rf, t);
+    if (fclose(rf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _chimericOut);
     t.clear();
   }
   if (!_cutEdges.empty()) {

@@ -228,6 +228,54 @@ def unitigs_prune(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branc
     return out
 
 
+def unitigs_chimeric(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
+                     num_reads=None, genome_size=None, uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None,
+                     chimeric_delta=0, chimeric_threshold=0.0, graph=True, bases=True, device=0):
+    """`unitigs_prune` with chimeric unitig removal as the last step of every round (sigax_unitigs_chimeric_host, the rules in
+    include/sigax.h): a unitig of at most min_chimeric_length bases (and, unless min_chimeric_coverage is None, of low coverage)
+    with one participant record at each end, both leading to branched read ends, goes where one of the two neighbours scores as
+    unique under chimeric_threshold and every other unitig at that end is longer by more than chimeric_delta, or holds more than
+    three reads more.  min_chimeric_length = 0 is `unitigs_prune`.  -> its dict; removed carries _lib.SIGAX_REMOVED_CHIMERIC on
+    the reads a chimeric step removed; status u64[20]: as there, then {chimeric unitigs, their reads, rounds with one, 0}."""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(lengths)
+    if len(offs) != n + 1:
+        raise ValueError("offs must have len(lengths) + 1 entries")
+    if isinstance(seqs, np.ndarray):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+    else:
+        buf = bytes(seqs)
+    L = _lib.lib()
+    prune = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
+                           _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
+                           n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
+    opts = _lib.ChimericOpts(prune, int(min_chimeric_length),
+                             _lib.SIGAX_TRIM_NO_COVERAGE if min_chimeric_coverage is None else int(min_chimeric_coverage), int(chimeric_delta), 0,
+                             float(chimeric_threshold))
+    nu = C.c_uint64()
+    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
+    status = np.zeros(20, dtype=np.uint64)
+    _check(L.sigax_unitigs_chimeric_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+                                         offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo),
+                                         C.byref(uf), C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct),
+                                         C.byref(ue) if graph else None, status.ctypes.data), "sigax_unitigs_chimeric_host")
+    try:
+        u = int(nu.value)
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
+               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
+        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
+    finally:
+        for p in (so, lo, uf, lay, us, rm, ct, ue):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
