@@ -9,11 +9,13 @@
 //
 // RCCL is bound at run time (dlopen): libsigax.so carries no link-time dependency on it, the one-GPU paths never touch it,
 // and a process that already holds an RCCL (PyTorch ships its own librccl.so) gets THAT one instead of a second copy.
+// SIGAX_RCCL_LIB=<path> binds the library at that path and looks nowhere else.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -45,19 +47,31 @@ bool rccl_load() {
   std::lock_guard<std::mutex> lock(g_rccl_mu);
   if (g_rccl.tried) return g_rccl.ok;
   g_rccl.tried = true;
-  // an RCCL this process has already (PyTorch's), else the ROCm one
+  // SIGAX_RCCL_LIB=<path>: exactly that library and nothing else (a site's own build; the tests' stand-in)
+  const char* forced = getenv("SIGAX_RCCL_LIB");
   void* h = nullptr;
-  if (dlsym(RTLD_DEFAULT, "ncclCommInitRank") != nullptr) h = RTLD_DEFAULT;
-  const char* names[] = {"librccl.so.1", "librccl.so"};
-  for (int pass = 0; pass < 2 && !h; ++pass)
-    for (const char* n : names) {
-      h = dlopen(n, RTLD_NOW | RTLD_GLOBAL | (pass == 0 ? RTLD_NOLOAD : 0));
-      if (h) break;
+  if (forced && *forced) {
+    h = dlopen(forced, RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+      const char* why = dlerror();
+      g_rccl.why = std::string("SIGAX_RCCL_LIB=") + forced + " cannot be loaded: " + (why ? why : "?");
+      return false;
     }
-  if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-  if (!h) {
-    g_rccl.why = std::string("librccl.so not found: ") + (dlerror() ? dlerror() : "?");
-    return false;
+  } else {
+    // an RCCL this process has already (PyTorch's), else the ROCm one
+    if (dlsym(RTLD_DEFAULT, "ncclCommInitRank") != nullptr) h = RTLD_DEFAULT;
+    const char* names[] = {"librccl.so.1", "librccl.so"};
+    for (int pass = 0; pass < 2 && !h; ++pass)
+      for (const char* n : names) {
+        h = dlopen(n, RTLD_NOW | RTLD_GLOBAL | (pass == 0 ? RTLD_NOLOAD : 0));
+        if (h) break;
+      }
+    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+      const char* why = dlerror();  // (once: the call clears the text it returns)
+      g_rccl.why = std::string("librccl.so not found: ") + (why ? why : "?");
+      return false;
+    }
   }
   g_rccl.h = h;
   auto sym = [&](const char* n) { return dlsym(h, n); };
@@ -72,7 +86,7 @@ bool rccl_load() {
   g_rccl.GetErrorString = (decltype(g_rccl.GetErrorString))sym("ncclGetErrorString");
   g_rccl.ok = g_rccl.GetUniqueId && g_rccl.CommInitRank && g_rccl.CommDestroy && g_rccl.AllGather && g_rccl.Send && g_rccl.Recv &&
               g_rccl.GroupStart && g_rccl.GroupEnd && g_rccl.GetErrorString;
-  if (!g_rccl.ok) g_rccl.why = "librccl.so lacks one of the nccl* entry points";
+  if (!g_rccl.ok) g_rccl.why = std::string(forced && *forced ? forced : "librccl.so") + " lacks one of the nccl* entry points";
   return g_rccl.ok;
 }
 }  // namespace
