@@ -577,6 +577,97 @@ int  sigax_unitigs_chimeric_host(int device, const sigax_edge* edges, uint64_t n
                                  uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                                  sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                  uint64_t status20[20]);
+/* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
+ * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
+ * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain
+ * and samples |distance(mate) - distance(read)| of every pair with both mates in one chain.  Those chains are the unitigs and
+ * that distance is sigax_placement.offset, so the visitor is one pass over the layout a unitig call left.  PairedReadVisitor
+ * (:669-969) searches the graph between mates under a node budget in hash-map order; its result depends on that order and it is
+ * not restated.  What a paired-end user still needs -- which unitig ends the pairs join -- is given as link records.
+ * DESIGN.md 9h; the serial restatement the tests hold this against is tests/pair_cases.py::expected_pairs.
+ *
+ * Input: the result of any of the four unitig calls (the number of unitigs, seq_offs, lay_offs, uflags, and layout with
+ * lay_offs[n_unitigs] placements: fewer than n_reads after trimming), lengths u32[n_reads], mate u32[n_reads] with
+ * SIGAX_NO_MATE = no mate, and sigax_pairs_opts.
+ *
+ * Pairs.  Read i is PAIRED iff j = mate[i] < n_reads, j != i and mate[j] == i; the pair is handled once, from its smaller id.
+ * A read with mate[i] != SIGAX_NO_MATE that is not paired counts as a malformed entry and is otherwise ignored.
+ *
+ * Placement.  Placement p of the layout belongs to unitig u, the largest u < n_unitigs with lay_offs[u] <= p as a bisection
+ * over lay_offs[0 .. n_unitigs] finds it (lo = 0, hi = n_unitigs; while hi - lo > 1: mid = (lo + hi) / 2, lo = mid if
+ * lay_offs[mid] <= p, else hi = mid; at most 32 steps).  Its read has left = offset, right = offset + length, rev = flags &
+ * SIGAX_PLACED_REV.  bases(u) = seq_offs[u+1] - seq_offs[u].  All arithmetic is modulo 2^64 (layouts of a unitig call never wrap).
+ *
+ * Every pair falls into exactly one class:
+ *   UNPLACED  a mate is not in the layout (a round removed it).
+ *   RING      both mates in one unitig flagged SIGAX_UNITIG_CIRCULAR.  Counted, never sampled: a distance on a ring is defined
+ *             modulo the ring only (the reference samples it from wherever its hash map enters the ring).
+ *   SAME      both mates in one unitig that is not circular.  d = |left(j) - left(i)| (the reference's sample, :604-614), span =
+ *             max(right) - min(left).  With a = the mate of smaller left (tie: smaller id) and b the other, the pair is INWARD iff
+ *             !rev(a) && rev(b), OUTWARD iff rev(a) && !rev(b), else TANDEM; every SAME pair is in exactly one of the three.  A
+ *             SAME pair with span >= 2^32 is also FAR: it is left out of all sums and of the histogram (every square fits 64
+ *             bits).  Every other SAME pair adds d to (n, sum d, sum d^2 in 128 bits); if it is of the library's orientation --
+ *             INWARD, with SIGAX_PAIRS_OUTWARD instead OUTWARD -- it also adds span to (n, sum span, sum span^2 in 128 bits) and
+ *             to hist[min(span >> hist_shift, hist_bins - 1)].
+ *   ACROSS    the mates lie in different unitigs.  A read faces the unitig end its mate is expected beyond: for an inward
+ *             library a forward read faces end E (1) with g = bases(u) - left and a reversed read end B (0) with g = right; with
+ *             SIGAX_PAIRS_OUTWARD a forward read faces B with g = right, a reversed read E with g = bases(u) - left.  s = g_i +
+ *             g_j is the span the pair would have if the two ends abutted.  If either unitig is circular the pair counts as a
+ *             dropped ring link; else if max_span != 0 && s > max_span it counts as over the span; else it joins the link with
+ *             key (a, b), a = 2 u + end of one mate and b that of the other, ordered a <= b (a == b cannot occur).
+ *
+ * Links: one sigax_pair_link per distinct key, ascending by (a, b); count pairs, min_span = the smallest s saturated at 2^32 - 1,
+ * sum_span = the sum of s.  No result depends on the order in which pairs are processed.
+ *
+ * Options: hist_bins 1 .. 8192 (SIGAX_PAIRS_MAX_BINS), hist_shift 0 .. 31, reserved = 0, flags other than SIGAX_PAIRS_OUTWARD refused.
+ *
+ * status24 = 24 u64, written (not added to): 0 reads with a mate entry, 1 malformed entries, 2 pairs, 3 UNPLACED, 4 SAME, 5
+ * INWARD, 6 OUTWARD, 7 TANDEM, 8 RING, 9 FAR, 10-13 {n, sum d, sum d^2 low, high}, 14-17 {n, sum span, sum span^2 low, high},
+ * 18 ACROSS, 19 ring links dropped, 20 over max_span, 21 pairs that went into links, 22 link records written, 23 = 0.
+ *
+ * Deviations from the reference:
+ *   strand flips    After a strand flip the reference's running distance adds the overhang of the read it enters, not of the
+ *       one it leaves (:585-592).  With reads of one length both are the left coordinate and d is the reference's sample; with
+ *       unequal lengths the reference mixes left-end and right-end coordinates.  Here d is always the difference of left ends.
+ *   edge reduction  The reference's edges() (:637-663) drops containment edges and parallel edges of equal label before it asks
+ *       for degrees; here the chains are the unitigs, where containments count in every degree.  The two agree on graphs without
+ *       containments and duplicate reads, that is after `siga rmdup`.
+ *   rings           See RING.
+ *   unitig call     The reference estimates on the graph as loaded; here on whichever unitig call the caller ran (max_rounds = 0:
+ *       the same graph).
+ *   span, the orientation classes, the histogram and the links are not in the reference.
+ *
+ * sigax_unitigs_pairs_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the
+ * device.  d_n_unitigs points at a u64 ON THE DEVICE -- entry 0 of the unitig call's status block -- so the call can be enqueued
+ * straight behind the unitig call; a value above n_reads is taken as n_reads, and lay_offs[n_unitigs] likewise.  d_seq_offs and
+ * d_lay_offs u64[n_reads + 1], d_uflags u32[n_reads], d_layout sigax_placement[n_reads] (the unitig call's buffers); d_hist
+ * u64[hist_bins], fully written; d_links room for n_reads / 2 records, of which status24[22] are written; d_work =
+ * sigax_unitigs_pairs_workspace bytes (some 38 bytes per read).  d_layout and d_work 16-byte aligned, d_n_unitigs, d_seq_offs,
+ * d_lay_offs, d_hist, d_links and d_status24 8-byte aligned, d_mate, d_lengths and d_uflags 4-byte aligned.  A NULL where a
+ * buffer is required, a misaligned buffer, a short workspace, bad options and n_reads >= 2^31: SIGAX_E_ARG.  n_reads = 0:
+ * SIGAX_OK, status and histogram zeros.  Whatever mate, layout and lay_offs hold -- a placement whose read is >= n_reads,
+ * lay_offs that do not ascend -- nothing outside the buffers is touched, and every loop has a bound the host knows.
+ * sigax_unitigs_pairs_workspace asks the device sort for the size of its scratch: a size query, it launches nothing. */
+#define SIGAX_NO_MATE        0xFFFFFFFFu
+#define SIGAX_PAIRS_OUTWARD  1u     /* the library's pairs point away from each other (mate-pair libraries) */
+#define SIGAX_PAIRS_MAX_BINS 8192u
+typedef struct sigax_pairs_opts { uint32_t flags, hist_bins, hist_shift, reserved; uint64_t max_span; } sigax_pairs_opts;
+typedef struct sigax_pair_link { uint32_t a, b, count, min_span; uint64_t sum_span; } sigax_pair_link; /* 24 bytes */
+int  sigax_unitigs_pairs_workspace(int device, uint64_t n_reads, uint64_t* bytes);
+int  sigax_unitigs_pairs_device(int device, const void* d_mate, const void* d_lengths, uint64_t n_reads, const void* d_n_unitigs,
+                                const void* d_seq_offs, const void* d_lay_offs, const void* d_uflags, const sigax_placement* d_layout,
+                                const sigax_pairs_opts* opts, void* d_hist, sigax_pair_link* d_links, void* d_status24, void* d_work,
+                                uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous.  seq_offs and lay_offs u64[n_unitigs + 1], uflags u32[n_unitigs], layout
+ * sigax_placement[lay_offs[n_unitigs]]; n_unitigs or lay_offs[n_unitigs] above n_reads: SIGAX_E_ARG.  *hist u64[hist_bins] and
+ * *links sigax_pair_link[status24[22]] are malloc'd; release with sigax_free.  status24 is filled. */
+int  sigax_unitigs_pairs_host(int device, const uint32_t* mate, const uint32_t* lengths, uint64_t n_reads, uint64_t n_unitigs,
+                              const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
+                              const sigax_pairs_opts* opts, uint64_t** hist, sigax_pair_link** links, uint64_t status24[24]);
+/* Host arithmetic only: insert_size = (uint64_t)(sum d / n) and delta = (uint64_t)sqrt(sum d^2 / n - (sum d / n)^2) in double, as
+ * the reference computes them (:622-631, the population moment); span_mean and span_sd likewise from entries 14-17, not
+ * truncated.  n = 0 gives zeros.  Any output may be NULL. */
+int  sigax_pairs_estimate(const uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, double* span_mean, double* span_sd);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -31,6 +31,15 @@ SIGAX_UNITIG_CIRCULAR = 1
 SIGAX_TRIM_NO_COVERAGE = 0xFFFFFFFF
 SIGAX_REMOVED_CHIMERIC = 0x80000000
 TRIM_MAX_ROUNDS = 64
+SIGAX_NO_MATE = 0xFFFFFFFF
+SIGAX_PAIRS_OUTWARD = 1
+SIGAX_PAIRS_MAX_BINS = 8192
+PAIR_LINK_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("count", "<u4"), ("min_span", "<u4"), ("sum_span", "<u8")])  # sigax_pair_link
+assert PAIR_LINK_DTYPE.itemsize == 24
+# the entries of sigax_unitigs_pairs_*'s status24, by name
+PAIRS_STATUS = ("mate_entries", "malformed", "pairs", "unplaced", "same", "inward", "outward", "tandem", "ring", "far", "d_n", "d_sum",
+                "d_sq_low", "d_sq_high", "span_n", "span_sum", "span_sq_low", "span_sq_high", "across", "ring_links_dropped", "over_max_span",
+                "linked_pairs", "link_records", "reserved")
 
 
 class TrimOpts(C.Structure):  # sigax_trim_opts
@@ -46,6 +55,10 @@ class ChimericOpts(C.Structure):  # sigax_chimeric_opts
     _fields_ = ([("prune", PruneOpts)] +
                 [(n, C.c_uint32) for n in ("min_chimeric_length", "min_chimeric_coverage", "chimeric_delta", "reserved2")] +
                 [("chimeric_threshold", C.c_double)])
+
+
+class PairsOpts(C.Structure):  # sigax_pairs_opts
+    _fields_ = [(n, C.c_uint32) for n in ("flags", "hist_bins", "hist_shift", "reserved")] + [("max_span", C.c_uint64)]
 
 
 class Stats(C.Structure):
@@ -94,6 +107,7 @@ SYMBOLS = [
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
     "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
+    "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -199,6 +213,10 @@ def lib():
                                                 vp, u64, vp]
     L.sigax_unitigs_chimeric_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(ChimericOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
                                               pvp, pvp, pvp, pvp, vp]
+    L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
+    L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
+    L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]
+    L.sigax_pairs_estimate.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
     L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]

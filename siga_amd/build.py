@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "lib", "libsigax.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["sigax_kernels.hip", "sigax_api.cpp", "sigax_index.cpp", "sigax_tables.cpp", "sigax_correct.cpp", "sigax_index_build.hip",
            "sigax_comm.cpp", "sigax_keys.hip", "sigax_match.hip", "sigax_match.cpp", "sigax_order.hip", "sigax_spectrum.hip", "sigax_spectrum.cpp",
-           "sigax_locate.hip", "sigax_locate.cpp", "sigax_unitig.hip", "sigax_unitig.cpp"]
+           "sigax_locate.hip", "sigax_locate.cpp", "sigax_unitig.hip", "sigax_unitig.cpp", "sigax_pairs.hip", "sigax_pairs.cpp"]
 HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", "sigax_rank.h", os.path.join(ROOT, "include", "sigax.h")]
 
 
@@ -41,8 +41,8 @@ HOST = os.path.join(HERE, "host")
 HOSTLIB = os.path.join(HERE, "lib", "libsiga_host.so")
 CLI = os.path.join(HERE, "lib", "siga")
 CXX = os.environ.get("CXX", "g++")
-HOST_SOURCES = ["reads.cpp", "strand_index.cpp", "out_file.cpp", "asqg_text.cpp", "overlap_builder.cpp", "correct_match.cpp", "locate.cpp", "kmer_spectrum.cpp", "unitig.cpp", "host_capi.cpp"]
-HOST_HEADERS = ["siga_host.hpp", "host_util.hpp", "reads.hpp", "out_file.hpp", "asqg_text.hpp", "sais.hpp", "line_deflate.hpp"]
+HOST_SOURCES = ["reads.cpp", "strand_index.cpp", "out_file.cpp", "asqg_text.cpp", "overlap_builder.cpp", "correct_match.cpp", "locate.cpp", "kmer_spectrum.cpp", "unitig.cpp", "pairs.cpp", "host_capi.cpp"]
+HOST_HEADERS = ["siga_host.hpp", "host_util.hpp", "reads.hpp", "out_file.hpp", "asqg_text.hpp", "sais.hpp", "line_deflate.hpp", "pairs.hpp"]
 
 
 def build_host(force=False, verbose=False):

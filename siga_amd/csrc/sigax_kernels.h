@@ -366,6 +366,41 @@ static const uint32_t REMOVED_CHIMERIC = 0x80000000u;
 void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st);
 void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st);
 
+// `siga unitig --pairs` (sigax_pairs.hip): mate-pair statistics and links over the layout a unitig call left.  Everything below
+// `status` is the caller's scratch (sigax_pairs.cpp lays it out).
+struct PairArgs {
+  const uint32_t* mate;                  // [n_reads]
+  const uint32_t* lengths;               // [n_reads]
+  unsigned long long n_reads;
+  const unsigned long long* n_unitigs;   // 1 u64 on the device: the unitig call's status[0]
+  const unsigned long long* seq_offs;    // [n_reads + 1]
+  const unsigned long long* lay_offs;    // [n_reads + 1]
+  const uint32_t* uflags;                // [n_reads]
+  const sigax_placement* layout;         // [n_reads]
+  uint32_t flags, hist_bins, hist_shift;
+  unsigned long long max_span;
+  unsigned long long* hist;              // [hist_bins], zeroed
+  sigax_pair_link* links;                // [cap]
+  unsigned long long* status;            // 24 u64, written
+  unsigned long long* where;             // [n_reads], zeroed: (unitig << 32) | (placement + 1) of a read, 0 = not placed
+  unsigned long long* cnt;               // PAIR_WORDS u64, zeroed: counter c = status entry c, slotted as the trim counters are; the
+                                         // appended link entries at PAIR_APPENDED
+  unsigned long long cap;                // n_reads / 2: the most pairs there can be
+  unsigned long long* keys[2];           // 2 x [cap]: [0] the appended link keys (a << 32) | b, all ones where empty; [1] sorted
+  unsigned long long* vals[2];           // 2 x [cap]: their s, as appended and as sorted
+  uint32_t* head;                        // [cap]: a sorted entry begins a run of equal keys
+  unsigned long long* scan;              // [cap + 1]: the heads before it
+  unsigned long long* partial;           // scan_partials_needed(cap) u64
+  unsigned long long* scan_total;        // 1 u64, zeroed: the records
+  void* sort_tmp;                        // pairs_sort_bytes(cap) bytes
+  unsigned long long sort_tmp_bytes;
+};
+enum { PAIR_COUNTERS = 22, PAIR_APPENDED = PAIR_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, PAIR_WORDS = PAIR_APPENDED + 8, PAIR_HIST_MAX = 8192,
+       PAIR_READS_PER_BLOCK = 1024 };
+// bytes of scratch the device sort of `cap` (key, value) entries asks for: a size query, launches nothing
+hipError_t pairs_sort_bytes(unsigned long long cap, unsigned long long* bytes);
+hipError_t launch_pairs(const PairArgs& a, hipStream_t st);
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

@@ -1,0 +1,148 @@
+// siga_amd/host/pairs.cpp -- `siga unitig --pairs`: mates by name, the pairs call over the unitigs, its two files.
+#include "pairs.hpp"
+
+#include <algorithm>
+#include <cstdio>
+
+#include "host_util.hpp"
+
+namespace sigah {
+
+std::vector<uint32_t> mates_by_name(const ReadStore& rs, const std::vector<uint32_t>& ranks) {
+  const size_t n = rs.size();
+  std::vector<uint32_t> mate(n, SIGAX_NO_MATE);
+  if (n == 0) return mate;
+  // one read per rank, and how many share it: the names in sorted order without comparing any twice
+  uint32_t top = 0;
+  for (size_t i = 0; i < n; ++i) top = std::max(top, ranks[i]);
+  std::vector<uint32_t> first((size_t)top + 1, SIGAX_NO_MATE), count((size_t)top + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    if (count[ranks[i]]++ == 0) first[ranks[i]] = (uint32_t)i;
+  }
+  std::vector<uint32_t> sorted;  // the ranks that occur, ascending: their names ascend
+  sorted.reserve((size_t)top + 1);
+  for (uint32_t r = 0; r <= top; ++r)
+    if (count[r]) sorted.push_back(r);
+  std::string want;
+  for (size_t i = 0; i < n; ++i) {
+    const std::string_view name = rs.name(i);
+    if (name.empty() || count[ranks[i]] != 1) continue;
+    char c = name.back();
+    switch (c) {
+      case 'A': c = 'B'; break;
+      case 'B': c = 'A'; break;
+      case '1': c = '2'; break;
+      case '2': c = '1'; break;
+      case 'f': c = 'r'; break;
+      case 'r': c = 'f'; break;
+      default: continue;
+    }
+    want.assign(name.data(), name.size());
+    want.back() = c;
+    const auto it = std::lower_bound(sorted.begin(), sorted.end(), std::string_view(want),
+                                     [&](uint32_t r, std::string_view w) { return rs.name(first[r]) < w; });
+    if (it != sorted.end() && rs.name(first[*it]) == std::string_view(want) && count[*it] == 1) mate[i] = first[*it];
+  }
+  return mate;
+}
+
+namespace {
+const char* const kStatusNames[24] = {"mate_entries", "malformed", "pairs", "unplaced", "same", "inward", "outward", "tandem",
+                                      "ring", "far", "d_n", "d_sum", "d_sq_low", "d_sq_high", "span_n", "span_sum",
+                                      "span_sq_low", "span_sq_high", "across", "ring_links_dropped", "over_max_span", "linked_pairs",
+                                      "link_records", "reserved"};
+
+bool write_file(const std::string& path, const std::string& t) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  bool ok = t.empty() || fwrite(t.data(), 1, t.size(), f) == t.size();
+  if (fclose(f) != 0) ok = false;
+  return ok;
+}
+
+void append_double(std::string& t, double v) {
+  char buf[40];
+  snprintf(buf, sizeof buf, "%.17g", v);
+  t += buf;
+}
+}  // namespace
+
+std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
+                      const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
+                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta) {
+  sigax_pairs_opts opts;
+  opts.flags = rq.outward ? SIGAX_PAIRS_OUTWARD : 0u;
+  opts.hist_bins = rq.bins;
+  opts.hist_shift = rq.shift;
+  opts.reserved = 0;
+  opts.max_span = rq.maxSpan;
+  uint64_t* hist = nullptr;
+  sigax_pair_link* links = nullptr;
+  if (sigax_unitigs_pairs_host(device, mate.data(), lengths.data(), mate.size(), n_unitigs, seq_offs, lay_offs, uflags, layout, &opts, &hist, &links,
+                               status24) != SIGAX_OK)
+    return std::string("pairs failed: ") + sigax_last_error();
+  double span_mean = 0, span_sd = 0;
+  sigax_pairs_estimate(status24, insert_size, delta, &span_mean, &span_sd);
+  // {"pairs": {<the 24 counts by name>, "insert_size", "delta", "span_mean", "span_sd", "hist_bins", "hist_shift", "histogram":
+  // [[bin, pairs], ...]}} and a newline; the histogram lists the non-empty bins in ascending order
+  std::string t = "{\"pairs\": {";
+  for (int k = 0; k < 24; ++k) {
+    t += '"';
+    t += kStatusNames[k];
+    t += "\": ";
+    append_u64(t, status24[k]);
+    t += ", ";
+  }
+  t += "\"insert_size\": ";
+  append_u64(t, *insert_size);
+  t += ", \"delta\": ";
+  append_u64(t, *delta);
+  t += ", \"span_mean\": ";
+  append_double(t, span_mean);
+  t += ", \"span_sd\": ";
+  append_double(t, span_sd);
+  t += ", \"hist_bins\": ";
+  append_u64(t, rq.bins);
+  t += ", \"hist_shift\": ";
+  append_u64(t, rq.shift);
+  t += ", \"histogram\": [";
+  bool any = false;
+  for (uint32_t b = 0; b < rq.bins; ++b)
+    if (hist[b]) {
+      if (any) t += ", ";
+      any = true;
+      t += '[';
+      append_u64(t, b);
+      t += ", ";
+      append_u64(t, hist[b]);
+      t += ']';
+    }
+  t += "]}}\n";
+  bool ok = write_file(rq.json, t);
+  std::string bad = ok ? "" : rq.json;
+  if (ok && !rq.links.empty()) {
+    // "LK\tunitig-<u>\t<B|E>\tunitig-<v>\t<B|E>\t<count>\t<min_span>\t<sum_span>", in record order
+    t.clear();
+    for (uint64_t i = 0; i < status24[22]; ++i) {
+      const sigax_pair_link& l = links[i];
+      t += "LK\tunitig-";
+      append_u64(t, l.a >> 1);
+      t += (l.a & 1u) ? "\tE\tunitig-" : "\tB\tunitig-";
+      append_u64(t, l.b >> 1);
+      t += (l.b & 1u) ? "\tE\t" : "\tB\t";
+      append_u64(t, l.count);
+      t += '\t';
+      append_u64(t, l.min_span);
+      t += '\t';
+      append_u64(t, l.sum_span);
+      t += '\n';
+    }
+    ok = write_file(rq.links, t);
+    if (!ok) bad = rq.links;
+  }
+  sigax_free(hist);
+  sigax_free(links);
+  return ok ? std::string() : "Failed to write " + bad;
+}
+
+}  // namespace sigah

@@ -1,0 +1,32 @@
+// siga_amd/host/pairs.hpp -- internal: the paired-end side of `siga unitig` (pairs.cpp).
+#ifndef SIGA_AMD_HOST_PAIRS_HPP_
+#define SIGA_AMD_HOST_PAIRS_HPP_
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "reads.hpp"
+#include "siga_host.hpp"
+
+namespace sigah {
+
+// The mate of every read by name, as PairEnd::id finds it (src/reads.cpp:19-41): the mate's name is the read's with its last
+// character swapped 1<->2, A<->B or f<->r.  SIGAX_NO_MATE where the name ends otherwise, the mate's name is absent, or either
+// of the two names occurs more than once.  `ranks` = name_ranks' (equal names, equal rank).
+std::vector<uint32_t> mates_by_name(const ReadStore& rs, const std::vector<uint32_t>& ranks);
+
+struct PairsRequest {
+  std::string json, links;  // files; links may be empty
+  uint64_t maxSpan = 0;
+  bool outward = false;
+  uint32_t bins = 1024, shift = 0;
+};
+// sigax_unitigs_pairs_host over a unitig call's result, then the two files.  -> "" or what went wrong
+std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
+                      const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
+                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta);
+
+}  // namespace sigah
+
+#endif

@@ -4,7 +4,7 @@
 // on the GPU), SuffixArray + BWT writers (src/suffix_array.cpp, src/bwt.cpp), OverlapBuilder
 // (src/overlap_builder.h:19-45), Utils::stem (src/utils.cpp:128-135).  One source file per object: reads.cpp (readers),
 // strand_index.cpp (index builders and writers), overlap_builder.cpp (FMIndex, OverlapBuilder), correct_match.cpp
-// (CorrectProcessor, Matcher), locate.cpp (Locator), kmer_spectrum.cpp (KmerSpectrum), unitig.cpp (Unitigger), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
+// (CorrectProcessor, Matcher), locate.cpp (Locator), kmer_spectrum.cpp (KmerSpectrum), unitig.cpp (Unitigger), pairs.cpp (its paired-end side), host_capi.cpp (the sigah_* C entry points); out_file.*, asqg_text.*, reads.hpp and
 // host_util.hpp are internal to the library.
 #ifndef SIGA_AMD_HOST_SIGA_HOST_HPP_
 #define SIGA_AMD_HOST_SIGA_HOST_HPP_
@@ -194,7 +194,8 @@ class Locator {
 // one unitig (sigax_unitigs_host; the rules in include/sigax.h).  With setTrim / setGraph / setRemoved also the loop that follows
 // in assemble (TrimVisitor and simplify() in turn) and the graph between the unitigs (sigax_unitigs_trim_host); with setMaxOverlap
 // also that loop's MaximumOverlapVisitor (sigax_unitigs_prune_host); with setChimeric also its ChimericVisitor
-// (sigax_unitigs_chimeric_host).  One GPU.
+// (sigax_unitigs_chimeric_host); with setPairs also the insert size estimate of its paired-end mode and the links between
+// unitig ends (sigax_unitigs_pairs_host).  One GPU.
 class Unitigger {
  public:
   explicit Unitigger(bool irreducible = true, bool rc = true) : _irreducible(irreducible), _rc(rc), _unitigs(0), _bases(0), _merged(0), _cycles(0) {}
@@ -248,6 +249,29 @@ class Unitigger {
   }
   // one "name\tround" line per read a chimeric step removed, in read order
   void setChimericOut(const std::string& path) { _chimericOut = path; }
+  // The paired-end side (sigax_unitigs_pairs_host; the rules in include/sigax.h): mates are found by name as PairEnd::id does
+  // (src/reads.cpp:19-41; the last character swaps 1<->2, A<->B, f<->r), every pair is looked up in the unitigs this run built,
+  // and `json` gets {"pairs": {the 24 counts by name, insert_size, delta, span_mean, span_sd, hist_bins, hist_shift, histogram
+  // [[bin, pairs], ...]}}: the estimate of the reference's InsertSizeEstimateVisitor (src/bigraph_visitors.cpp:517-663) and the
+  // spans of the pairs of the library's orientation (inward; `outward`: outward).  `links` not empty: one line
+  // "LK\tunitig-<u>\t<B|E>\tunitig-<v>\t<B|E>\t<count>\t<min_span>\t<sum_span>" per pair of unitig ends that pairs join, ascending;
+  // maxSpan > 0 leaves out the pairs whose span with the two ends abutting would exceed it.  json empty, the default: none, and
+  // every other output is the one without this call.
+  void setPairs(const std::string& json, const std::string& links = std::string(), uint64_t maxSpan = 0, bool outward = false,
+                size_t bins = 1024, size_t shift = 0) {
+    _pairsOut = json;
+    _linksOut = links;
+    _maxSpan = maxSpan;
+    _outward = outward;
+    _pairsBins = bins;
+    _pairsShift = shift;
+  }
+  uint64_t pairs() const { return _pairs; }
+  uint64_t pairsSame() const { return _pairsSame; }      // both mates in one unitig that is no ring
+  uint64_t pairsAcross() const { return _pairsAcross; }  // the mates in two unitigs
+  uint64_t pairLinks() const { return _pairLinks; }      // link records
+  uint64_t insertSize() const { return _insertSize; }
+  uint64_t insertDelta() const { return _insertDelta; }
   uint64_t chimericUnitigs() const { return _chimUnitigs; }
   uint64_t chimericReads() const { return _chimReads; }
   uint64_t recordsCut() const { return _recordsCut; }
@@ -278,6 +302,11 @@ class Unitigger {
   double _chimThreshold = 0.0;
   std::string _chimericOut;
   uint64_t _chimUnitigs = 0, _chimReads = 0;
+  std::string _pairsOut, _linksOut;
+  uint64_t _maxSpan = 0;
+  bool _outward = false;
+  size_t _pairsBins = 1024, _pairsShift = 0;
+  uint64_t _pairs = 0, _pairsSame = 0, _pairsAcross = 0, _pairLinks = 0, _insertSize = 0, _insertDelta = 0;
   std::string _error;
 };
 

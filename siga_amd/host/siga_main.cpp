@@ -554,6 +554,17 @@ static int unitig_help() {
          "          --chimeric=FILE              write one line per read removed as chimeric to FILE: read name, the round it went in\n"
          "      -T sets both thresholds; without it cutting takes 13.0 and the chimeric step 0.0\n"
          "\n"
+         "Paired-end parameters (mates by name: the last character swaps 1 and 2, A and B, f and r):\n"
+         "          --pairs=FILE                 look every pair up in the unitigs and write the statistics to FILE as JSON: the counts\n"
+         "                                       by class, the insert size estimate of `siga assemble --pe-mode=1`, the span histogram\n"
+         "          --links=FILE                 also write one line per pair of unitig ends that pairs join to FILE:\n"
+         "                                       LK, unitig, B or E, unitig, B or E, pairs, smallest span, sum of spans (needs --pairs)\n"
+         "          --max-span=LEN               leave out of the links a pair whose span with the two ends abutting exceeds LEN\n"
+         "                                       (default: 0, no limit)\n"
+         "          --outward                    the library's pairs point away from each other (default: towards each other)\n"
+         "          --pairs-bins=N               bins of the span histogram, 1 to 8192 (default: 1024); the last takes the rest\n"
+         "          --pairs-shift=S              a bin is 2^S bases wide, 0 to 31 (default: 0)\n"
+         "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
          "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
@@ -576,7 +587,8 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 }
 
 static int run_unitig(int argc, char** argv) {
-  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC };
+  enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC, OPT_PAIRS, OPT_LINKS,
+         OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -590,9 +602,15 @@ static int run_unitig(int argc, char** argv) {
                                     {"min-chimeric-length", required_argument, nullptr, 'l'},
                                     {"min-chimeric-coverage", required_argument, nullptr, 'A'},
                                     {"max-chimeric-delta", required_argument, nullptr, 'a'}, {"chimeric", required_argument, nullptr, OPT_CHIMERIC},
+                                    {"pairs", required_argument, nullptr, OPT_PAIRS}, {"links", required_argument, nullptr, OPT_LINKS},
+                                    {"max-span", required_argument, nullptr, OPT_MAX_SPAN}, {"outward", no_argument, nullptr, OPT_OUTWARD},
+                                    {"pairs-bins", required_argument, nullptr, OPT_PAIRS_BINS},
+                                    {"pairs-shift", required_argument, nullptr, OPT_PAIRS_SHIFT},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix, out, layout, graph, removed, cutEdges, chimericOut;
+  std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
+  size_t maxSpan = 0, pairsBins = 1024, pairsShift = 0;
+  bool outward = false, pairsTuned = false;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
   long minBranchCoverage = -1, chimCoverage = -1;
@@ -640,6 +658,12 @@ static int run_unitig(int argc, char** argv) {
         break;
       }
       case OPT_CHIMERIC: chimericOut = optarg; break;
+      case OPT_PAIRS: pairsOut = optarg; break;
+      case OPT_LINKS: linksOut = optarg; break;
+      case OPT_MAX_SPAN: if (!unitig_number(optarg, "--max-span", ~0ull, &maxSpan)) return 1; pairsTuned = true; break;
+      case OPT_OUTWARD: outward = pairsTuned = true; break;
+      case OPT_PAIRS_BINS: if (!unitig_number(optarg, "--pairs-bins", 8192, &pairsBins) || pairsBins == 0) return 1; pairsTuned = true; break;
+      case OPT_PAIRS_SHIFT: if (!unitig_number(optarg, "--pairs-shift", 31, &pairsShift)) return 1; pairsTuned = true; break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -677,6 +701,10 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: -A, -a and --chimeric need -l, --min-chimeric-length\n");
     return 1;
   }
+  if (pairsOut.empty() && (!linksOut.empty() || pairsTuned)) {
+    fprintf(stderr, "siga unitig: --links, --max-span, --outward, --pairs-bins and --pairs-shift need --pairs\n");
+    return 1;
+  }
   std::string input = argv[optind];
   if (prefix.empty()) prefix = sigah::Utils::stem(input);
   if (out.empty()) out = prefix + ".unitigs.fa";
@@ -693,6 +721,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setRemoved(removed);
   unitigger.setMaxOverlap(delta, carefully, numReads, genomeSize, uniqThreshold);
   unitigger.setCutEdges(cutEdges);
+  unitigger.setPairs(pairsOut, linksOut, maxSpan, outward, pairsBins, pairsShift);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -707,6 +736,10 @@ static int run_unitig(int argc, char** argv) {
   if (chimLength)
     fprintf(stderr, "%llu chimeric unitigs removed, %llu reads\n", (unsigned long long)unitigger.chimericUnitigs(),
             (unsigned long long)unitigger.chimericReads());
+  if (!pairsOut.empty())
+    fprintf(stderr, "%llu pairs, %llu in one unitig (insert size %llu, delta %llu), %llu across unitigs in %llu links\n",
+            (unsigned long long)unitigger.pairs(), (unsigned long long)unitigger.pairsSame(), (unsigned long long)unitigger.insertSize(),
+            (unsigned long long)unitigger.insertDelta(), (unsigned long long)unitigger.pairsAcross(), (unsigned long long)unitigger.pairLinks());
   return 0;
 }
 

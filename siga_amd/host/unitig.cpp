@@ -3,6 +3,7 @@
 
 #include "asqg_text.hpp"
 #include "host_util.hpp"
+#include "pairs.hpp"
 #include "reads.hpp"
 #include "siga_host.hpp"
 
@@ -84,7 +85,7 @@ static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t
 bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOverlap, const std::string& fasta, const std::string& layout,
                     size_t threads) {
   _error.clear();
-  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = 0;
+  _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = _pairs = _pairsSame = _pairsAcross = _pairLinks = _insertSize = _insertDelta = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -118,6 +119,8 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
   if (!_chimericOut.empty() && _chimLength == 0) return fail("chimeric reads are only written with a min-chimeric length");
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
+  if (_pairsOut.empty() && !_linksOut.empty()) return fail("links are only written with the pairs statistics");
+  if (!_pairsOut.empty() && (_pairsBins == 0 || _pairsBins > SIGAX_PAIRS_MAX_BINS || _pairsShift > 31)) return fail("pairs bins or shift out of range");
   if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
@@ -189,6 +192,23 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _cutRounds = status[13];
   _chimUnitigs = status[16];
   _chimReads = status[17];
+  if (!_pairsOut.empty()) {  // over the unitigs as they stand, whichever call built them; the other outputs do not depend on it
+    PairsRequest rq;
+    rq.json = _pairsOut;
+    rq.links = _linksOut;
+    rq.maxSpan = _maxSpan;
+    rq.outward = _outward;
+    rq.bins = (uint32_t)_pairsBins;
+    rq.shift = (uint32_t)_pairsShift;
+    uint64_t st24[24];
+    const std::string e = run_pairs(inf.device, mates_by_name(reads, ranks), lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
+                                    &_insertSize, &_insertDelta);
+    if (!e.empty()) return fail(e);
+    _pairs = st24[2];
+    _pairsSame = st24[4];
+    _pairsAcross = st24[18];
+    _pairLinks = st24[22];
+  }
   // ">unitig-<n>[ KC:i:<reads>][ circular=<closing overlap>]": the coverage tag only above 1, as FastaVisitor writes it
   // (src/bigraph_visitors.cpp:248-257)
   FILE* out = fasta.empty() ? stdout : fopen(fasta.c_str(), "wb");

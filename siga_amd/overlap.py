@@ -276,6 +276,71 @@ def unitigs_chimeric(edges, lengths, seqs, offs, min_overlap, max_rounds, min_br
     return out
 
 
+def mates_by_name(names):
+    """The mate of every read by name, as the reference's PairEnd::id finds it (src/reads.cpp:19-41): the mate's name is the
+    read's with its last character swapped 1<->2, A<->B or f<->r.  -> u32[n]; SIGAX_NO_MATE where the name ends otherwise, the
+    mate's name is absent, or either of the two names occurs more than once."""
+    swap = {"1": "2", "2": "1", "A": "B", "B": "A", "f": "r", "r": "f"}
+    ns = [n.decode("latin-1") if isinstance(n, (bytes, bytearray)) else str(n) for n in names]
+    seen = {}
+    for i, n in enumerate(ns):
+        seen[n] = i if n not in seen else -1  # -1: more than once
+    mate = np.full(len(ns), _lib.SIGAX_NO_MATE, dtype=np.uint32)
+    for i, n in enumerate(ns):
+        if n and n[-1] in swap and seen[n] == i:
+            j = seen.get(n[:-1] + swap[n[-1]], -1)
+            if j >= 0:
+                mate[i] = j
+    return mate
+
+
+def pairs_estimate(status):
+    """sigax_pairs_estimate over a status24 -> (insert_size, delta, span_mean, span_sd)."""
+    status = np.ascontiguousarray(status, dtype=np.uint64)
+    if len(status) != 24:
+        raise ValueError("status must have 24 entries")
+    ins, dl, sm, sd = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double()
+    _check(_lib.lib().sigax_pairs_estimate(status.ctypes.data, C.byref(ins), C.byref(dl), C.byref(sm), C.byref(sd)), "sigax_pairs_estimate")
+    return int(ins.value), int(dl.value), float(sm.value), float(sd.value)
+
+
+def unitigs_pairs(res, lengths, mate, hist_bins=1024, hist_shift=0, max_span=0, outward=False, device=0):
+    """Mate-pair statistics and the links between unitig ends (sigax_unitigs_pairs_host, the rules in include/sigax.h) over the
+    dict `res` any `unitigs*` call returned: lengths u32[n], mate u32[n] (`mates_by_name`; SIGAX_NO_MATE = none) -> dict(status
+    u64[24] (named by _lib.PAIRS_STATUS), hist u64[hist_bins] of span >> hist_shift over the same-unitig pairs of the library's
+    orientation, links PAIR_LINK_DTYPE records ascending by (a, b) with a = 2 * unitig + end (0 = B, 1 = E), insert_size,
+    delta, span_mean, span_sd)."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    mate = np.ascontiguousarray(mate, dtype=np.uint32)
+    n = len(lengths)
+    if len(mate) != n:
+        raise ValueError("mate must have len(lengths) entries")
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    lo = np.ascontiguousarray(res["lay_offs"], dtype=np.uint64)
+    uf = np.ascontiguousarray(res["uflags"], dtype=np.uint32)
+    lay = np.ascontiguousarray(res["layout"], dtype=PLACEMENT_DTYPE)
+    u = len(uf)
+    if len(so) != u + 1 or len(lo) != u + 1:
+        raise ValueError("seq_offs and lay_offs must have len(uflags) + 1 entries")
+    if len(lay) < int(lo[u]):
+        raise ValueError("layout shorter than lay_offs says")
+    L = _lib.lib()
+    opts = _lib.PairsOpts(_lib.SIGAX_PAIRS_OUTWARD if outward else 0, int(hist_bins), int(hist_shift), 0, int(max_span))
+    hp, lp = C.c_void_p(), C.c_void_p()
+    status = np.zeros(24, dtype=np.uint64)
+    _check(L.sigax_unitigs_pairs_host(device, mate.ctypes.data if n else None, lengths.ctypes.data if n else None, n, u, so.ctypes.data,
+                                      lo.ctypes.data, uf.ctypes.data if u else None, lay.ctypes.data if len(lay) else None, C.byref(opts),
+                                      C.byref(hp), C.byref(lp), status.ctypes.data), "sigax_unitigs_pairs_host")
+    try:
+        out = {"status": status, "hist": _copy_records(hp, int(hist_bins), np.dtype(np.uint64)),
+               "links": _copy_records(lp, int(status[22]), _lib.PAIR_LINK_DTYPE)}
+    finally:
+        L.sigax_free(hp)
+        L.sigax_free(lp)
+    out["insert_size"], out["delta"], out["span_mean"], out["span_sd"] = pairs_estimate(status)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
