@@ -668,6 +668,91 @@ int  sigax_unitigs_pairs_host(int device, const uint32_t* mate, const uint32_t* 
  * the reference computes them (:622-631, the population moment); span_mean and span_sd likewise from entries 14-17, not
  * truncated.  n = 0 gives zeros.  Any output may be NULL. */
 int  sigax_pairs_estimate(const uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, double* span_mean, double* span_sd);
+/* ---- `siga unitig --scaffold`: unitigs joined through the link records (csrc/sigax_scaffold.hip) ---------------------------------
+ * What consumes the link records of the block above.  The reference's own answer to paired ends, PairedReadVisitor
+ * (src/bigraph_visitors.cpp:669-969), walks the graph between mates in hash-map order and is not restated; nothing below is in
+ * the reference.  A scaffold is the unitig of the `siga unitig` block with unitig for read, unitig end for read end and a gap
+ * for an overlap: decide per link, take degrees per unitig end, rank the lists, cut rings, place the unitigs, write the bases.
+ * No result depends on the order of the links.  DESIGN.md 9i; the serial restatement the tests hold this against is
+ * tests/scaffold_cases.py::expected_scaffolds.
+ *
+ * Input: the result of a unitig call and of the pairs call that followed it: the number of unitigs nu, seq_offs, uflags and
+ * useqs of the unitig call; links, their number nl and status24 of the pairs call.  bases(u) = seq_offs[u+1] - seq_offs[u]
+ * (modulo 2^64; the tables of a unitig call never wrap).  sigax_scaffold_opts: flags, min_pairs, link_ratio, min_unitig_bases,
+ * insert_size, min_gap, max_gap.
+ *
+ * Options: flags other than SIGAX_SCAFFOLD_INSERT_FROM_STATUS refused.  With that flag insert_size = floor(status24[15] /
+ * status24[14]), taken on the device -- the mean span of the pairs of the library's orientation inside a unitig -- and 0 when
+ * status24[14] == 0; the insert_size field must then be 0.  1 <= min_gap <= max_gap < 2^31 and insert_size < 2^62; anything else
+ * is SIGAX_E_ARG.
+ *
+ * Link classes.  A link (a, b, count, min_span, sum_span) falls into the first class that applies:
+ *   MALFORMED  a >= 2 nu, b >= 2 nu, a >= b, or count == 0.
+ *   SELF       a >> 1 == b >> 1.
+ *   CIRCULAR   either unitig is flagged SIGAX_UNITIG_CIRCULAR.
+ *   SHORT      bases(u) < min_unitig_bases for either unitig.
+ *   THIN       count < min_pairs.
+ *   otherwise it is a CANDIDATE.
+ * best[e] = the largest count among the candidates at unitig end e.  A candidate is WEAK iff link_ratio > 0 and count *
+ * link_ratio <= best[a] or count * link_ratio <= best[b], in u64; the rest are STRONG.  deg[e] = the strong candidates at e (a key
+ * given twice counts twice).  A strong candidate is a JOIN iff deg[a] == 1 and deg[b] == 1, else it is AMBIGUOUS.
+ *
+ * The gap of a join: m = sum_span / count (u64 division).  If m >= insert_size the gap is min_gap, and the join counts as
+ * "estimate below min_gap".  Otherwise gap = min(max(insert_size - m, min_gap), max_gap); it counts as clamped if the upper
+ * clamp applied and as below min_gap if the lower one did.  Both counts run over all joins, a cycle's closing join included.
+ *
+ * Scaffolds are the connected components of the unitigs under joins; a circular unitig is always a scaffold of its own.  A path
+ * starts at its terminal unitig with the smaller id.  A unitig entered through B lies forward, one entered through E
+ * reverse-complemented (A<->T, C<->G, other bytes as they are); the first unitig is forward iff it is left through E, a single
+ * unitig is forward.  offset[0] = 0, offset[i+1] = offset[i] + bases(u_i) + gap(i, i+1); the scaffold has offset[last] +
+ * bases(u_last) bases: the unitigs' bases as placed and N in every gap.  A cycle starts at its smallest unitig id, forward, left
+ * through E; the join that would enter the start again is not merged: the scaffold's flag has bit 0 set and flags >> 1 is that
+ * join's gap.  Scaffolds are numbered by ascending id of their first unitig.
+ *
+ * Output: sc_offs u64[S + 1] the scaffolds' base offsets, sc_lay_offs u64[S + 1], sc_flags u32[S], sc_layout sigax_placement[nu]
+ * (read = the unitig id, flags bit 0 = SIGAX_PLACED_REV, offset within the scaffold), sseqs the bases.
+ * status16 = 16 u64, written (not added to): 0 scaffolds S, 1 scaffold bases (gaps included), 2 links read, 3 MALFORMED, 4 SELF,
+ * 5 CIRCULAR, 6 SHORT, 7 THIN, 8 WEAK, 9 AMBIGUOUS, 10 joins merged (a cycle's closing join is not counted), 11 cycles, 12 gap
+ * bases (the N of the scaffolds: the gaps of the merged joins), 13 joins with estimate below min_gap, 14 joins clamped at max_gap,
+ * 15 = 1 when status16[1] > sseqs_capacity: the bases were not written for lack of room.
+ *
+ * sigax_scaffold_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the
+ * device.  d_n_unitigs and d_n_links point at u64 ON THE DEVICE -- entry 0 of the unitig call's status block and status24[22] of
+ * the pairs call -- so the call can be enqueued straight behind sigax_unitigs_pairs_device; a count above its capacity
+ * (max_unitigs, max_links) is taken as the capacity.  d_seq_offs u64[max_unitigs + 1], d_uflags u32[max_unitigs], d_useqs
+ * useqs_bytes bytes: no byte at or beyond useqs_bytes is read.  d_links max_links records.  d_sc_offs and d_sc_lay_offs
+ * u64[max_unitigs + 1], d_sc_flags u32[max_unitigs], d_sc_layout sigax_placement[max_unitigs]; entries beyond S (nu for the
+ * layout) are not written.  d_sseqs sseqs_capacity bytes, or NULL with capacity 0 for the layout alone (d_useqs may then be
+ * NULL too); the bases are written only if status16[1] <= sseqs_capacity, else nothing is written to d_sseqs.  d_status24 may
+ * be NULL without SIGAX_SCAFFOLD_INSERT_FROM_STATUS; d_links and d_n_links may be NULL with max_links = 0.  d_work =
+ * sigax_scaffold_workspace bytes (204 bytes per unitig, none per link).  d_useqs, d_sseqs, d_sc_layout and d_work 16-byte
+ * aligned, d_uflags and d_sc_flags 4-byte aligned, every other buffer 8-byte aligned.  A NULL where a buffer is required, a
+ * misaligned buffer, a short workspace, bad options, max_unitigs >= 2^31, max_links >= 2^32, sseqs_capacity >= 2^43:
+ * SIGAX_E_ARG, with the offending argument named in sigax_last_error().  max_unitigs = 0: SIGAX_OK, status zeros, and
+ * d_sc_offs[0] = d_sc_lay_offs[0] = 0 where those two are given (all other buffers may be NULL).  Whatever the
+ * tables hold -- seq_offs that do not ascend, links beyond the unitigs -- nothing outside the buffers is touched and every loop
+ * has a bound the host knows: the rankings run ceil(log2 max_unitigs) + 1 rounds, twice; a bisection at most 32 steps. */
+#define SIGAX_SCAFFOLD_INSERT_FROM_STATUS 1u
+typedef struct sigax_scaffold_opts {
+  uint32_t flags, min_pairs, link_ratio, min_unitig_bases;
+  uint64_t insert_size;
+  uint32_t min_gap, max_gap;
+} sigax_scaffold_opts;
+int  sigax_scaffold_workspace(uint64_t max_unitigs, uint64_t max_links, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_scaffold_device(int device, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_uflags,
+                           const void* d_useqs, uint64_t useqs_bytes, const sigax_pair_link* d_links, const void* d_n_links,
+                           uint64_t max_links, const void* d_status24, const sigax_scaffold_opts* opts, void* d_sc_offs,
+                           void* d_sc_lay_offs, void* d_sc_flags, sigax_placement* d_sc_layout, void* d_sseqs, uint64_t sseqs_capacity,
+                           void* d_status16, void* d_work, uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous.  seq_offs u64[n_unitigs + 1], uflags u32[n_unitigs], useqs seq_offs[n_unitigs] bytes (NULL when
+ * sseqs is NULL), links n_links records, status24 NULL or the pairs call's (required with SIGAX_SCAFFOLD_INSERT_FROM_STATUS).
+ * It runs the layout, reads the total, then writes the bases into a buffer of exactly that size: status16[15] is 0.  *sc_offs and
+ * *sc_lay_offs u64[*n_scaffolds + 1], *sc_flags u32[*n_scaffolds], *sc_layout sigax_placement[n_unitigs], *sseqs status16[1] bytes
+ * (pass sseqs = NULL for the layout alone); all malloc'd, release with sigax_free. */
+int  sigax_scaffold_host(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint32_t* uflags, const char* useqs,
+                         const sigax_pair_link* links, uint64_t n_links, const uint64_t* status24, const sigax_scaffold_opts* opts,
+                         uint64_t* n_scaffolds, uint64_t** sc_offs, uint64_t** sc_lay_offs, uint32_t** sc_flags,
+                         sigax_placement** sc_layout, char** sseqs, uint64_t status16[16]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

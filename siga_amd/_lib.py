@@ -40,6 +40,10 @@ assert PAIR_LINK_DTYPE.itemsize == 24
 PAIRS_STATUS = ("mate_entries", "malformed", "pairs", "unplaced", "same", "inward", "outward", "tandem", "ring", "far", "d_n", "d_sum",
                 "d_sq_low", "d_sq_high", "span_n", "span_sum", "span_sq_low", "span_sq_high", "across", "ring_links_dropped", "over_max_span",
                 "linked_pairs", "link_records", "reserved")
+SIGAX_SCAFFOLD_INSERT_FROM_STATUS = 1
+# the entries of sigax_scaffold_*'s status16, by name
+SCAFFOLD_STATUS = ("scaffolds", "bases", "links", "malformed", "self", "circular", "short", "thin", "weak", "ambiguous", "joins", "cycles",
+                   "gap_bases", "below_min_gap", "clamped_at_max_gap", "bases_not_written")
 
 
 class TrimOpts(C.Structure):  # sigax_trim_opts
@@ -59,6 +63,11 @@ class ChimericOpts(C.Structure):  # sigax_chimeric_opts
 
 class PairsOpts(C.Structure):  # sigax_pairs_opts
     _fields_ = [(n, C.c_uint32) for n in ("flags", "hist_bins", "hist_shift", "reserved")] + [("max_span", C.c_uint64)]
+
+
+class ScaffoldOpts(C.Structure):  # sigax_scaffold_opts
+    _fields_ = ([(n, C.c_uint32) for n in ("flags", "min_pairs", "link_ratio", "min_unitig_bases")] + [("insert_size", C.c_uint64)] +
+                [(n, C.c_uint32) for n in ("min_gap", "max_gap")])
 
 
 class Stats(C.Structure):
@@ -108,6 +117,7 @@ SYMBOLS = [
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
     "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
+    "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -217,6 +227,11 @@ def lib():
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]
     L.sigax_pairs_estimate.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sigax_scaffold_workspace.argtypes = [u64, u64, C.POINTER(u64)]
+    L.sigax_scaffold_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, C.POINTER(ScaffoldOpts), vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
+    L.sigax_scaffold_host.argtypes = [ci, u64, vp, vp, vp, vp, u64, vp, C.POINTER(ScaffoldOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp, vp]
+    # (not in include/sigax.h: the measurement aid of tools/scaffold_bench.py, sigax_internal.h)
+    L.sigax_scaffold_bases_device.argtypes = L.sigax_scaffold_device.argtypes
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)
     L.sigax_unitigs_bases_device.argtypes = [ci, vp, vp, u64, u64, vp, vp, u64, vp]
     L.sigax_edges_order_workspace.argtypes = [u64, u64, C.POINTER(u64)]

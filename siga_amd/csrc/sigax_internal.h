@@ -67,6 +67,14 @@ struct HostGuard {
 extern "C" int sigax_unitigs_bases_device(int device, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint64_t n_edges, void* d_useqs,
                                           void* d_work, uint64_t work_bytes, void* stream);
 
+// Measurement aid of tools/scaffold_bench.py, exported but not part of include/sigax.h and not stable: the bases pass of
+// sigax_scaffold_device alone, over the scratch a call with the same arguments left in d_work.  Same argument checks.
+extern "C" int sigax_scaffold_bases_device(int device, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_uflags,
+                                           const void* d_useqs, uint64_t useqs_bytes, const sigax_pair_link* d_links, const void* d_n_links,
+                                           uint64_t max_links, const void* d_status24, const sigax_scaffold_opts* opts, void* d_sc_offs,
+                                           void* d_sc_lay_offs, void* d_sc_flags, sigax_placement* d_sc_layout, void* d_sseqs,
+                                           uint64_t sseqs_capacity, void* d_status16, void* d_work, uint64_t work_bytes, void* stream);
+
 #pragma GCC visibility push(hidden)
 
 // ------------------------------------------------------------------------------------------------------

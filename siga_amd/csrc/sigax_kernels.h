@@ -401,6 +401,47 @@ enum { PAIR_COUNTERS = 22, PAIR_APPENDED = PAIR_COUNTERS * TRIM_SLOTS * TRIM_STR
 hipError_t pairs_sort_bytes(unsigned long long cap, unsigned long long* bytes);
 hipError_t launch_pairs(const PairArgs& a, hipStream_t st);
 
+// `siga unitig --scaffold` (sigax_scaffold.hip): unitigs joined through the link records of the pairs call.  Everything below
+// `status` is the caller's scratch (sigax_scaffold.cpp lays it out).  nu = min(*n_unitigs, max_unitigs), nl likewise.
+struct ScaffoldArgs {
+  const unsigned long long* n_unitigs;   // on the device
+  const unsigned long long* n_links;     // on the device
+  unsigned long long max_unitigs, max_links;
+  const unsigned long long* seq_offs;    // [max_unitigs + 1]
+  const uint32_t* uflags;                // [max_unitigs]
+  const unsigned char* useqs;            // useqs_bytes bytes: nothing at or beyond them is read
+  unsigned long long useqs_bytes;
+  const sigax_pair_link* links;          // [max_links]
+  const unsigned long long* status24;    // of the pairs call
+  uint32_t flags, min_pairs, link_ratio, min_unitig_bases, min_gap, max_gap;
+  unsigned long long insert_size;
+  unsigned long long* sc_offs;           // [max_unitigs + 1]
+  unsigned long long* sc_lay_offs;       // [max_unitigs + 1]
+  uint32_t* sc_flags;                    // [max_unitigs]
+  sigax_placement* sc_layout;            // [max_unitigs]
+  unsigned char* sseqs;                  // sseqs_capacity bytes or NULL
+  unsigned long long sseqs_capacity;
+  unsigned long long* status;            // 16 u64, written
+  unsigned long long* cnt;               // SCAF_WORDS u64: counter c = status entry c, slotted as the trim counters are
+  uint32_t* best;                        // [2 max_unitigs]: the largest count among the candidates of a unitig end
+  uint32_t* deg;                         // [2 max_unitigs]: its strong candidates
+  uint2* link;                           // [2 max_unitigs]: {the unitig end its join leads to or NIL, the join's gap}
+  uint32_t* closing;                     // [max_unitigs]: a cycle's flag word under its smallest unitig
+  unsigned long long* rank[2];           // 2 x [2 max_unitigs] uint4
+  unsigned long long* dist[2];           // 2 x [2 max_unitigs]
+  uint32_t* hcnt;                        // 4 x [max_unitigs + 1]: per unitig {is a head, its scaffold's unitigs, bases low, high}
+  unsigned long long* scan;              // 4 x [max_unitigs + 1]: their prefix sums
+  unsigned long long* partial;           // scan_partials_needed(max_unitigs) u64
+  unsigned long long* scan_total;        // 1 u64
+  unsigned long long* pdst;              // [max_unitigs + 1]: where in sseqs placement i's unitig begins; [placements] = all bases
+  unsigned long long* psrc;              // [max_unitigs]: where in useqs it lies | reversed << 63
+  unsigned long long* plen;              // [max_unitigs]: its bases
+};
+// counters 2-14 are status entries; SCAF_C_CLOSING_GAPS sums the gaps of the joins that close cycles
+enum { SCAF_C_CLOSING_GAPS = 0, SCAF_COUNTERS = 16, SCAF_ANY_CUT = SCAF_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, SCAF_WORDS = SCAF_ANY_CUT + 8 };
+hipError_t launch_scaffold(const ScaffoldArgs& a, hipStream_t st);
+void launch_scaffold_bases(const ScaffoldArgs& a, hipStream_t st);  // the last phase alone, over what launch_scaffold left
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

@@ -1,4 +1,5 @@
-// siga_amd/host/pairs.cpp -- `siga unitig --pairs`: mates by name, the pairs call over the unitigs, its two files.
+// siga_amd/host/pairs.cpp -- `siga unitig --pairs`: mates by name, the pairs call over the unitigs, its two files; and
+// `--scaffold`: the scaffold call over the unitigs and the links, its two files.
 #include "pairs.hpp"
 
 #include <algorithm>
@@ -65,11 +66,78 @@ void append_double(std::string& t, double v) {
   snprintf(buf, sizeof buf, "%.17g", v);
   t += buf;
 }
+
+// sigax_scaffold_host, then ">scaffold-<n> unitigs=<k> gaps=<k - 1>[ circular=<closing gap>]" and the bases per scaffold, and
+// one line "scaffold-<n>\tunitig-<u>\t<+|->\t<offset>\t<gap before>" per placement (0 before a scaffold's first)
+std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint32_t* uflags, const char* useqs,
+                         const sigax_pair_link* links, uint64_t n_links, const uint64_t status24[24], const ScaffoldRequest& rq,
+                         uint64_t status16[16]) {
+  if (!rq.haveInsertSize && status24[14] == 0)
+    return "no pair of the library's orientation lies inside a unitig: there is no insert size to estimate the gaps from; give --insert-size";
+  sigax_scaffold_opts opts;
+  opts.flags = rq.haveInsertSize ? 0u : SIGAX_SCAFFOLD_INSERT_FROM_STATUS;
+  opts.min_pairs = rq.minPairs;
+  opts.link_ratio = rq.linkRatio;
+  opts.min_unitig_bases = rq.minUnitigBases;
+  opts.insert_size = rq.haveInsertSize ? rq.insertSize : 0;
+  opts.min_gap = rq.minGap;
+  opts.max_gap = rq.maxGap;
+  uint64_t ns = 0, *sc_offs = nullptr, *sc_lay = nullptr;
+  uint32_t* sc_flags = nullptr;
+  sigax_placement* lay = nullptr;
+  char* seqs = nullptr;
+  if (sigax_scaffold_host(device, n_unitigs, seq_offs, uflags, useqs, links, n_links, status24, &opts, &ns, &sc_offs, &sc_lay, &sc_flags, &lay, &seqs,
+                          status16) != SIGAX_OK)
+    return std::string("scaffold failed: ") + sigax_last_error();
+  std::string fa, lt;
+  for (uint64_t s = 0; s < ns; ++s) {
+    const uint64_t k = sc_lay[s + 1] - sc_lay[s];
+    fa += ">scaffold-";
+    append_u64(fa, s);
+    fa += " unitigs=";
+    append_u64(fa, k);
+    fa += " gaps=";
+    append_u64(fa, k ? k - 1 : 0);
+    if (sc_flags[s] & 1u) {
+      fa += " circular=";
+      append_u64(fa, sc_flags[s] >> 1);
+    }
+    fa += '\n';
+    fa.append(seqs + sc_offs[s], sc_offs[s + 1] - sc_offs[s]);
+    fa += '\n';
+    for (uint64_t p = sc_lay[s]; p < sc_lay[s + 1]; ++p) {
+      const sigax_placement& x = lay[p];
+      lt += "scaffold-";
+      append_u64(lt, s);
+      lt += "\tunitig-";
+      append_u64(lt, x.read);
+      lt += (x.flags & SIGAX_PLACED_REV) ? "\t-\t" : "\t+\t";
+      append_u64(lt, x.offset);
+      lt += '\t';
+      uint64_t gap = 0;
+      if (p > sc_lay[s]) {
+        const sigax_placement& b = lay[p - 1];
+        gap = x.offset - b.offset - (seq_offs[b.read + 1] - seq_offs[b.read]);
+      }
+      append_u64(lt, gap);
+      lt += '\n';
+    }
+  }
+  sigax_free(sc_offs);
+  sigax_free(sc_lay);
+  sigax_free(sc_flags);
+  sigax_free(lay);
+  sigax_free(seqs);
+  if (!write_file(rq.fasta, fa)) return "Failed to write " + rq.fasta;
+  if (!rq.layout.empty() && !write_file(rq.layout, lt)) return "Failed to write " + rq.layout;
+  return std::string();
+}
 }  // namespace
 
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
-                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta) {
+                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, const ScaffoldRequest* sc,
+                      const char* useqs, uint64_t status16[16]) {
   sigax_pairs_opts opts;
   opts.flags = rq.outward ? SIGAX_PAIRS_OUTWARD : 0u;
   opts.hist_bins = rq.bins;
@@ -140,9 +208,11 @@ std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::
     ok = write_file(rq.links, t);
     if (!ok) bad = rq.links;
   }
+  std::string e = ok ? std::string() : "Failed to write " + bad;
+  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16);
   sigax_free(hist);
   sigax_free(links);
-  return ok ? std::string() : "Failed to write " + bad;
+  return e;
 }
 
 }  // namespace sigah

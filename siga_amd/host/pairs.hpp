@@ -22,10 +22,18 @@ struct PairsRequest {
   bool outward = false;
   uint32_t bins = 1024, shift = 0;
 };
-// sigax_unitigs_pairs_host over a unitig call's result, then the two files.  -> "" or what went wrong
+struct ScaffoldRequest {
+  std::string fasta, layout;  // files; fasta empty: no scaffolds; layout may be empty
+  uint32_t minPairs = 2, linkRatio = 0, minUnitigBases = 0, minGap = 1, maxGap = 1000000;
+  bool haveInsertSize = false;  // else floor(sum span / n) of the pairs call
+  uint64_t insertSize = 0;
+};
+// sigax_unitigs_pairs_host over a unitig call's result, then the two files; with sc->fasta also sigax_scaffold_host over the
+// unitigs (useqs: their bases) and the links, then its two files and status16.  -> "" or what went wrong
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
-                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta);
+                      const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta,
+                      const ScaffoldRequest* sc = nullptr, const char* useqs = nullptr, uint64_t status16[16] = nullptr);
 
 }  // namespace sigah
 

@@ -266,6 +266,28 @@ class Unitigger {
     _pairsBins = bins;
     _pairsShift = shift;
   }
+  // Scaffolds (sigax_scaffold_host; the rules in include/sigax.h), behind the pairs call and over its links: `fasta` gets
+  // ">scaffold-<n> unitigs=<k> gaps=<k - 1>[ circular=<closing gap>]" and the bases, N in the gaps; `layout`, if not empty, one
+  // line "scaffold-<n>\tunitig-<u>\t<+|->\t<offset>\t<gap before>" per placement.  A link of at least minPairs pairs between
+  // unitigs of at least minUnitigBases bases that is the only strong one at both its ends joins them (linkRatio > 0: links with
+  // count * linkRatio <= the largest count at either end are set aside).  insertSize < 0: floor(sum span / n) of the pairs call,
+  // and a failure when no pair of the library's orientation lay inside a unitig.  fasta empty, the default: none, and every
+  // other output is the one without this call.  Needs setPairs.
+  void setScaffold(const std::string& fasta, const std::string& layout = std::string(), size_t minPairs = 2, size_t linkRatio = 0,
+                   size_t minUnitigBases = 0, long long insertSize = -1, size_t minGap = 1, size_t maxGap = 1000000) {
+    _scaffoldOut = fasta;
+    _scaffoldLayout = layout;
+    _scMinPairs = minPairs;
+    _scLinkRatio = linkRatio;
+    _scMinUnitigBases = minUnitigBases;
+    _scInsertSize = insertSize;
+    _scMinGap = minGap;
+    _scMaxGap = maxGap;
+  }
+  uint64_t scaffolds() const { return _scaffolds; }
+  uint64_t scaffoldJoins() const { return _scJoins; }          // joins merged
+  uint64_t scaffoldAmbiguous() const { return _scAmbiguous; }  // strong links that are not the only one at an end
+  uint64_t scaffoldGapBases() const { return _scGapBases; }
   uint64_t pairs() const { return _pairs; }
   uint64_t pairsSame() const { return _pairsSame; }      // both mates in one unitig that is no ring
   uint64_t pairsAcross() const { return _pairsAcross; }  // the mates in two unitigs
@@ -307,6 +329,10 @@ class Unitigger {
   bool _outward = false;
   size_t _pairsBins = 1024, _pairsShift = 0;
   uint64_t _pairs = 0, _pairsSame = 0, _pairsAcross = 0, _pairLinks = 0, _insertSize = 0, _insertDelta = 0;
+  std::string _scaffoldOut, _scaffoldLayout;
+  size_t _scMinPairs = 2, _scLinkRatio = 0, _scMinUnitigBases = 0, _scMinGap = 1, _scMaxGap = 1000000;
+  long long _scInsertSize = -1;
+  uint64_t _scaffolds = 0, _scJoins = 0, _scAmbiguous = 0, _scGapBases = 0;
   std::string _error;
 };
 

@@ -565,6 +565,19 @@ static int unitig_help() {
          "          --pairs-bins=N               bins of the span histogram, 1 to 8192 (default: 1024); the last takes the rest\n"
          "          --pairs-shift=S              a bin is 2^S bases wide, 0 to 31 (default: 0)\n"
          "\n"
+         "Scaffold parameters (they need --pairs: the scaffolds are built from its links):\n"
+         "          --scaffold=FILE              join the unitigs whose ends one link joins and no other, and write the scaffolds to FILE,\n"
+         "                                       N in the gaps: >scaffold-<n> unitigs=<k> gaps=<k - 1>, circular=<closing gap> for a ring\n"
+         "          --scaffold-layout=FILE       also write one line per unitig to FILE: scaffold, unitig, + or -, offset, gap before it\n"
+         "          --min-pairs=N                a link needs at least N pairs (default: 2)\n"
+         "          --link-ratio=R               set aside a link of C pairs where C * R is at most the largest count at one of its ends\n"
+         "                                       (default: 0, off)\n"
+         "          --min-scaffold-unitig=LEN    leave links at unitigs of fewer than LEN bases alone (default: 0)\n"
+         "          --insert-size=N              the span of a pair, from which a gap is estimated (default: the mean span of the pairs\n"
+         "                                       inside a unitig, sum / n rounded down)\n"
+         "          --min-gap=N                  a gap is at least N bases, also where the estimate is smaller or negative (default: 1)\n"
+         "          --max-gap=N                  ... and at most N bases (default: 1000000)\n"
+         "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
          "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
@@ -588,7 +601,8 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 
 static int run_unitig(int argc, char** argv) {
   enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC, OPT_PAIRS, OPT_LINKS,
-         OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT };
+         OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT, OPT_SCAFFOLD, OPT_SCAFFOLD_LAYOUT, OPT_MIN_PAIRS, OPT_LINK_RATIO,
+         OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -606,11 +620,20 @@ static int run_unitig(int argc, char** argv) {
                                     {"max-span", required_argument, nullptr, OPT_MAX_SPAN}, {"outward", no_argument, nullptr, OPT_OUTWARD},
                                     {"pairs-bins", required_argument, nullptr, OPT_PAIRS_BINS},
                                     {"pairs-shift", required_argument, nullptr, OPT_PAIRS_SHIFT},
+                                    {"scaffold", required_argument, nullptr, OPT_SCAFFOLD},
+                                    {"scaffold-layout", required_argument, nullptr, OPT_SCAFFOLD_LAYOUT},
+                                    {"min-pairs", required_argument, nullptr, OPT_MIN_PAIRS}, {"link-ratio", required_argument, nullptr, OPT_LINK_RATIO},
+                                    {"min-scaffold-unitig", required_argument, nullptr, OPT_MIN_SCAFFOLD_UNITIG},
+                                    {"insert-size", required_argument, nullptr, OPT_INSERT_SIZE},
+                                    {"min-gap", required_argument, nullptr, OPT_MIN_GAP}, {"max-gap", required_argument, nullptr, OPT_MAX_GAP},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
   size_t maxSpan = 0, pairsBins = 1024, pairsShift = 0;
   bool outward = false, pairsTuned = false;
+  std::string scaffoldOut, scaffoldLayout;
+  size_t minPairs = 2, linkRatio = 0, minScaffoldUnitig = 0, insertSize = 0, minGap = 1, maxGap = 1000000;
+  bool haveInsertSize = false, scaffoldTuned = false;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
   long minBranchCoverage = -1, chimCoverage = -1;
@@ -664,6 +687,14 @@ static int run_unitig(int argc, char** argv) {
       case OPT_OUTWARD: outward = pairsTuned = true; break;
       case OPT_PAIRS_BINS: if (!unitig_number(optarg, "--pairs-bins", 8192, &pairsBins) || pairsBins == 0) return 1; pairsTuned = true; break;
       case OPT_PAIRS_SHIFT: if (!unitig_number(optarg, "--pairs-shift", 31, &pairsShift)) return 1; pairsTuned = true; break;
+      case OPT_SCAFFOLD: scaffoldOut = optarg; break;
+      case OPT_SCAFFOLD_LAYOUT: scaffoldLayout = optarg; scaffoldTuned = true; break;
+      case OPT_MIN_PAIRS: if (!unitig_number(optarg, "--min-pairs", 0xFFFFFFFFull, &minPairs)) return 1; scaffoldTuned = true; break;
+      case OPT_LINK_RATIO: if (!unitig_number(optarg, "--link-ratio", 0xFFFFFFFFull, &linkRatio)) return 1; scaffoldTuned = true; break;
+      case OPT_MIN_SCAFFOLD_UNITIG: if (!unitig_number(optarg, "--min-scaffold-unitig", 0xFFFFFFFFull, &minScaffoldUnitig)) return 1; scaffoldTuned = true; break;
+      case OPT_INSERT_SIZE: if (!unitig_number(optarg, "--insert-size", (1ull << 62) - 1, &insertSize)) return 1; haveInsertSize = scaffoldTuned = true; break;
+      case OPT_MIN_GAP: if (!unitig_number(optarg, "--min-gap", 0x7FFFFFFFull, &minGap) || minGap == 0) return 1; scaffoldTuned = true; break;
+      case OPT_MAX_GAP: if (!unitig_number(optarg, "--max-gap", 0x7FFFFFFFull, &maxGap)) return 1; scaffoldTuned = true; break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -705,6 +736,18 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: --links, --max-span, --outward, --pairs-bins and --pairs-shift need --pairs\n");
     return 1;
   }
+  if (scaffoldOut.empty() && scaffoldTuned) {
+    fprintf(stderr, "siga unitig: --scaffold-layout, --min-pairs, --link-ratio, --min-scaffold-unitig, --insert-size, --min-gap and --max-gap need --scaffold\n");
+    return 1;
+  }
+  if (!scaffoldOut.empty() && pairsOut.empty()) {
+    fprintf(stderr, "siga unitig: --scaffold needs --pairs: the scaffolds are built from its links\n");
+    return 1;
+  }
+  if (maxGap < minGap) {
+    fprintf(stderr, "siga unitig: --max-gap %zu is below --min-gap %zu\n", maxGap, minGap);
+    return 1;
+  }
   std::string input = argv[optind];
   if (prefix.empty()) prefix = sigah::Utils::stem(input);
   if (out.empty()) out = prefix + ".unitigs.fa";
@@ -722,6 +765,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setMaxOverlap(delta, carefully, numReads, genomeSize, uniqThreshold);
   unitigger.setCutEdges(cutEdges);
   unitigger.setPairs(pairsOut, linksOut, maxSpan, outward, pairsBins, pairsShift);
+  unitigger.setScaffold(scaffoldOut, scaffoldLayout, minPairs, linkRatio, minScaffoldUnitig, haveInsertSize ? (long long)insertSize : -1, minGap, maxGap);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -740,6 +784,10 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "%llu pairs, %llu in one unitig (insert size %llu, delta %llu), %llu across unitigs in %llu links\n",
             (unsigned long long)unitigger.pairs(), (unsigned long long)unitigger.pairsSame(), (unsigned long long)unitigger.insertSize(),
             (unsigned long long)unitigger.insertDelta(), (unsigned long long)unitigger.pairsAcross(), (unsigned long long)unitigger.pairLinks());
+  if (!scaffoldOut.empty())
+    fprintf(stderr, "%llu scaffolds, %llu joins, %llu ambiguous links, %llu gap bases\n", (unsigned long long)unitigger.scaffolds(),
+            (unsigned long long)unitigger.scaffoldJoins(), (unsigned long long)unitigger.scaffoldAmbiguous(),
+            (unsigned long long)unitigger.scaffoldGapBases());
   return 0;
 }
 

@@ -86,6 +86,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
                     size_t threads) {
   _error.clear();
   _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = _pairs = _pairsSame = _pairsAcross = _pairLinks = _insertSize = _insertDelta = 0;
+  _scaffolds = _scJoins = _scAmbiguous = _scGapBases = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -121,6 +122,11 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
   if (_pairsOut.empty() && !_linksOut.empty()) return fail("links are only written with the pairs statistics");
   if (!_pairsOut.empty() && (_pairsBins == 0 || _pairsBins > SIGAX_PAIRS_MAX_BINS || _pairsShift > 31)) return fail("pairs bins or shift out of range");
+  if (_pairsOut.empty() && !_scaffoldOut.empty()) return fail("scaffolds are only built with the pairs statistics");
+  if (_scaffoldOut.empty() && !_scaffoldLayout.empty()) return fail("the scaffold layout is only written with the scaffolds");
+  if (!_scaffoldOut.empty() && (_scMinPairs > 0xFFFFFFFFull || _scLinkRatio > 0xFFFFFFFFull || _scMinUnitigBases > 0xFFFFFFFFull || _scMinGap < 1 ||
+                                _scMaxGap < _scMinGap || _scMaxGap >= (1ull << 31) || _scInsertSize >= (1ll << 62)))
+    return fail("scaffold options out of range");
   if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
@@ -200,10 +206,24 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     rq.outward = _outward;
     rq.bins = (uint32_t)_pairsBins;
     rq.shift = (uint32_t)_pairsShift;
-    uint64_t st24[24];
+    ScaffoldRequest sq;
+    sq.fasta = _scaffoldOut;
+    sq.layout = _scaffoldLayout;
+    sq.minPairs = (uint32_t)_scMinPairs;
+    sq.linkRatio = (uint32_t)_scLinkRatio;
+    sq.minUnitigBases = (uint32_t)_scMinUnitigBases;
+    sq.minGap = (uint32_t)_scMinGap;
+    sq.maxGap = (uint32_t)_scMaxGap;
+    sq.haveInsertSize = _scInsertSize >= 0;
+    sq.insertSize = _scInsertSize >= 0 ? (uint64_t)_scInsertSize : 0;
+    uint64_t st24[24], st16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const std::string e = run_pairs(inf.device, mates_by_name(reads, ranks), lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
-                                    &_insertSize, &_insertDelta);
+                                    &_insertSize, &_insertDelta, &sq, u.useqs, st16);
     if (!e.empty()) return fail(e);
+    _scaffolds = st16[0];
+    _scJoins = st16[10];
+    _scAmbiguous = st16[9];
+    _scGapBases = st16[12];
     _pairs = st24[2];
     _pairsSame = st24[4];
     _pairsAcross = st24[18];

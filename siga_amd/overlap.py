@@ -341,6 +341,61 @@ def unitigs_pairs(res, lengths, mate, hist_bins=1024, hist_shift=0, max_span=0, 
     return out
 
 
+def unitigs_scaffold(res, links, insert_size=None, status=None, min_pairs=2, link_ratio=0, min_unitig_bases=0, min_gap=1, max_gap=1000000,
+                     bases=True, device=0):
+    """Unitigs joined into scaffolds through the link records of `unitigs_pairs` (sigax_scaffold_host, the rules in
+    include/sigax.h): `res` is the dict any `unitigs*` call returned (seq_offs, uflags and, with bases, useqs), `links` and
+    `status` the links and status of `unitigs_pairs` over it.  insert_size=None takes floor(status[15] / status[14]), the mean
+    span of the library's pairs inside a unitig.  A link of at least min_pairs pairs between unitigs of at least
+    min_unitig_bases bases that is the only strong one at both its ends joins them; link_ratio > 0 sets aside the links with
+    count * link_ratio <= the largest count at either end.  -> dict(sc_offs u64[S + 1], sc_lay_offs u64[S + 1], sc_flags u32[S]
+    (bit 0: a cycle, flags >> 1 its closing gap), layout PLACEMENT_DTYPE[unitigs] (read = the unitig), seqs u8 (None without
+    bases: N in the gaps), status u64[16] named by _lib.SCAFFOLD_STATUS)."""
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    uf = np.ascontiguousarray(res["uflags"], dtype=np.uint32)
+    links = np.ascontiguousarray(links, dtype=_lib.PAIR_LINK_DTYPE)
+    u = len(uf)
+    if len(so) != u + 1:
+        raise ValueError("seq_offs must have len(uflags) + 1 entries")
+    us = None
+    if bases:
+        if res.get("useqs") is None:
+            raise ValueError("bases=True needs the unitig bases (res['useqs'])")
+        us = res["useqs"]
+        us = np.frombuffer(bytes(us), dtype=np.uint8) if isinstance(us, (bytes, bytearray)) else np.ascontiguousarray(us, dtype=np.uint8)
+        if len(us) < int(so[u]):
+            raise ValueError("useqs shorter than seq_offs says")
+    flags = 0
+    if insert_size is None:
+        if status is None:
+            raise ValueError("insert_size=None needs the status of unitigs_pairs")
+        flags = _lib.SIGAX_SCAFFOLD_INSERT_FROM_STATUS
+    st24 = None
+    if status is not None:
+        st24 = np.ascontiguousarray(status, dtype=np.uint64)
+        if len(st24) != 24:
+            raise ValueError("status must have 24 entries")
+    L = _lib.lib()
+    opts = _lib.ScaffoldOpts(flags, int(min_pairs), int(link_ratio), int(min_unitig_bases), 0 if insert_size is None else int(insert_size),
+                             int(min_gap), int(max_gap))
+    ns = C.c_uint64()
+    po, pl, pf, play, ps = (C.c_void_p() for _ in range(5))
+    st16 = np.zeros(16, dtype=np.uint64)
+    _check(L.sigax_scaffold_host(device, u, so.ctypes.data, uf.ctypes.data if u else None, us.ctypes.data if bases and len(us) else None,
+                                 links.ctypes.data if len(links) else None, len(links), None if st24 is None else st24.ctypes.data,
+                                 C.byref(opts), C.byref(ns), C.byref(po), C.byref(pl), C.byref(pf), C.byref(play),
+                                 C.byref(ps) if bases else None, st16.ctypes.data), "sigax_scaffold_host")
+    try:
+        s = int(ns.value)
+        out = {"sc_offs": _copy_records(po, s + 1, np.dtype(np.uint64)), "sc_lay_offs": _copy_records(pl, s + 1, np.dtype(np.uint64)),
+               "sc_flags": _copy_records(pf, s, np.dtype(np.uint32)), "layout": _copy_records(play, u, PLACEMENT_DTYPE), "status": st16}
+        out["seqs"] = _copy_records(ps, int(st16[1]), np.dtype(np.uint8)) if bases else None
+    finally:
+        for p in (po, pl, pf, play, ps):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
