@@ -577,6 +577,78 @@ int  sigax_unitigs_chimeric_host(int device, const sigax_edge* edges, uint64_t n
                                  uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                                  sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                  uint64_t status20[20]);
+/* ---- `siga unitig -x -b`: bubble popping in the rounds (csrc/sigax_unitig.hip) ----------------------------------------------------
+ * A bubble is two unitigs that leave the same unitig end and arrive at the same unitig end: a heterozygous SNP, a two-copy
+ * near-repeat, a recurring error.  Neither arm is a tip, both carry overlaps of full length, and the chimeric step leaves both or
+ * takes both.  The reference declares the step and never wrote it: SmoothingVisitor::visit returns false
+ * (src/bigraph_visitors.cpp:1021-1036).  So there is nothing to restate and nothing to deviate from; the rules below are this
+ * library's own, and no decision depends on record, read or hash-map order.  Everything not said here is as in the `-x`, `-d` and
+ * `-l` blocks above: live records, PARTICIPANTS, sL, sR, dL, dR, K(U), bases(U), and a state = 2 * read + end.  DESIGN.md 9j; the
+ * serial restatement the tests hold this against is tests/bubble_cases.py::expected_bubble.
+ *
+ * sigax_bubble_opts: chimeric = the sigax_chimeric_opts of the block above; max_bubble_span Lb (-b; 0 = no bubble step),
+ * max_divergence_permille D (--bubble-divergence; SIGAX_BUBBLE_NO_BASES = no bases test), reserved3 = 0.
+ *
+ * One round r = 1, 2, ...: CUT STEP (when delta > 0), TRIM STEP, BUBBLE STEP (when Lb > 0), CHIMERIC STEP (when Lc > 0).  The bubble
+ * step comes before the chimeric step on purpose: once the losing arm is gone the winner's neighbours are no longer branched, so
+ * the chimeric step cannot take the surviving arm in the same round.  Each step runs over the state the step before left and takes
+ * every decision from the state at its own start.  A round in which no step changed anything ends the loop and is not counted.
+ *
+ * The bubble verdict, for the unitigs of the state at the start of the step:
+ *   1. ARM    U is an arm iff it is no ring, dL == 1 and dR == 1, the one live record at each of sL and sR is a participant, and,
+ *             with p, q the states at the other ends of those records, U(p) != U, U(q) != U and p != q.  U(p) == U(q) is allowed:
+ *             the two ends of one unitig may carry a bubble.  key(U) = (lo, hi) = (min(p, q), max(p, q)); o_lo, o_hi are the
+ *             lengths of the records at those sides; span(U) = bases(U) - o_lo - o_hi as a signed 64-bit value.  An arm takes
+ *             part iff 1 <= span(U) <= Lb.
+ *   2. GROUP  The arms that take part and share (lo, hi, span) form a group.  A group of one does nothing.  In a group of two or
+ *             more the WINNER is the arm with the largest K, then the smallest id of its first read (the read its layout begins
+ *             with); every other arm of the group is a LOSER.
+ *   3. BASES  S(U) is the unitig's bases exactly as the final pass would write them for U.  A(U) = S(U) if U's left end is the
+ *             one joined to lo, otherwise its reverse complement, bytes complemented as the bases pass complements them (A <-> T,
+ *             C <-> G, every other byte itself).  mism(L, W) is the number of t in [0, span) with A(L)[o_lo(L) + t] !=
+ *             A(W)[o_lo(W) + t]; outside that window both arms equal the neighbours' bases, because overlaps are exact.  Loser L
+ *             is POPPED iff D == SIGAX_BUBBLE_NO_BASES, or mism * 1000 <= D * span in u64.  A loser that fails the test stays
+ *             and is counted.
+ *   4. MARK   All reads of a popped arm get removed[read] = r | SIGAX_REMOVED_BUBBLE.  Only these entry points ever set that bit.
+ *             A winner is never removed by this step.  An arm is in exactly one group.
+ * Out of scope: arms of different span (indel bubbles); bubbles whose arms are themselves branched (paths, not unitigs); a
+ * second candidate winner when the first fails the bases test.  Not held: inputs beyond 2^32 bases (nor are the prune and
+ * chimeric rounds).
+ *
+ * status24 = 24 u64, written: 0-19 as status20, with 6 = rounds in which any step changed something and 9 = all removed reads;
+ * 20 arms popped, 21 reads the bubble steps removed, 22 rounds in which a bubble step removed something, 23 losers kept because
+ * they failed the bases test, summed over the rounds that ran.
+ *
+ * sigax_unitigs_bubble_device: sigax_unitigs_chimeric_device with these options and d_status24.  Asynchronous on `stream`,
+ * allocates nothing, never waits for the device; it enqueues max_rounds rounds, whose kernels return at once after a round that
+ * changed nothing (the one prefix sum of a bubble step with a bases test has no such form; nothing reads its result then).  Every
+ * index is checked against its buffer; the comparison loop is bounded by Lb, the bisection over a unitig's placements by 32 steps,
+ * the group table's probes by its capacity.  d_work = sigax_unitigs_bubble_workspace(n_reads, n_edges, d_uedges != NULL, careful)
+ * bytes: the chimeric call's scratch, 60 bytes per read, 12 bytes per slot of the group table (the power of two >= max(16,
+ * 2 n_reads)), and 25 216 bytes of counters, each piece rounded up to 16 bytes.  max_bubble_span = 0 gives exactly the chimeric
+ * call's result, status 20-23 zero and no new flag bit.  The bubble step needs neither genome_size nor num_reads.  Refusals as
+ * for the chimeric call, and reserved3 != 0: SIGAX_E_ARG; d_seqs == NULL is refused with any n_reads > 0, so with a bases test
+ * too.  Whatever the records hold, nothing outside the buffers is touched. */
+#define SIGAX_REMOVED_BUBBLE 0x40000000u
+#define SIGAX_BUBBLE_NO_BASES 0xFFFFFFFFu
+typedef struct sigax_bubble_opts {
+  sigax_chimeric_opts chimeric;
+  uint32_t max_bubble_span;          /* Lb; 0 = no bubble step */
+  uint32_t max_divergence_permille;  /* D; SIGAX_BUBBLE_NO_BASES = no bases test */
+  uint32_t reserved3[2];             /* = 0 */
+} sigax_bubble_opts;
+int  sigax_unitigs_bubble_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_bubble_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                 const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts,
+                                 void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                 void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status24, void* d_work,
+                                 uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_chimeric_host, with status24.  It stops after the first round that changed nothing. */
+int  sigax_unitigs_bubble_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                               const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts,
+                               uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                               sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                               uint64_t status24[24]);
 /* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
  * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
  * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain

@@ -30,6 +30,8 @@ SIGAX_PLACED_REV = 1
 SIGAX_UNITIG_CIRCULAR = 1
 SIGAX_TRIM_NO_COVERAGE = 0xFFFFFFFF
 SIGAX_REMOVED_CHIMERIC = 0x80000000
+SIGAX_REMOVED_BUBBLE = 0x40000000
+SIGAX_BUBBLE_NO_BASES = 0xFFFFFFFF
 TRIM_MAX_ROUNDS = 64
 SIGAX_NO_MATE = 0xFFFFFFFF
 SIGAX_PAIRS_OUTWARD = 1
@@ -59,6 +61,11 @@ class ChimericOpts(C.Structure):  # sigax_chimeric_opts
     _fields_ = ([("prune", PruneOpts)] +
                 [(n, C.c_uint32) for n in ("min_chimeric_length", "min_chimeric_coverage", "chimeric_delta", "reserved2")] +
                 [("chimeric_threshold", C.c_double)])
+
+
+class BubbleOpts(C.Structure):  # sigax_bubble_opts
+    _fields_ = [("chimeric", ChimericOpts), ("max_bubble_span", C.c_uint32), ("max_divergence_permille", C.c_uint32),
+                ("reserved3", C.c_uint32 * 2)]
 
 
 class PairsOpts(C.Structure):  # sigax_pairs_opts
@@ -116,6 +123,7 @@ SYMBOLS = [
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
     "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
+    "sigax_unitigs_bubble_workspace", "sigax_unitigs_bubble_device", "sigax_unitigs_bubble_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
@@ -223,6 +231,11 @@ def lib():
                                                 vp, u64, vp]
     L.sigax_unitigs_chimeric_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(ChimericOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
                                               pvp, pvp, pvp, pvp, vp]
+    L.sigax_unitigs_bubble_workspace.argtypes = [u64, u64, ci, ci, C.POINTER(u64)]
+    L.sigax_unitigs_bubble_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(BubbleOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, u64, vp]
+    L.sigax_unitigs_bubble_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(BubbleOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
+                                            pvp, pvp, pvp, pvp, vp]
     L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]

@@ -365,6 +365,36 @@ static const uint32_t REMOVED_CHIMERIC = 0x80000000u;
 // step clears nbr, minb and mink itself.  launch_chimeric_status: status[16 .. 19], after launch_unitig_prune_lift.
 void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st);
 void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st);
+// bubble popping (sigax_unitigs_bubble_*): the chimeric block and what a round's bubble step needs.  The existing kernels take the
+// block they know out of it (by value); only the kernels of the bubble step see the rest.
+struct UnitigBubbleArgs : UnitigChimericArgs {
+  uint32_t* bnbr;                        // [2 n_reads], cleared by the step (all ones): at a read end of degree 1 whose record is a
+                                         // participant, the read end at that record's other side ...
+  uint32_t* blen;                        // [2 n_reads] ... and that record's length
+  uint4* arm;                            // [n_reads], under a head: {lo, hi, span, o_lo} of an arm that takes part
+  uint32_t* aside;                       // [n_reads], under a head: 1 = the unitig's left end is the one joined to lo
+  uint32_t* gslot;                       // [n_reads], under a head: the table slot of the arm's group, all ones = takes no part
+  uint32_t* table;                       // group_cap u32, cleared (all ones): the head of the arm that opened the group; open
+                                         // addressing over a hash of (lo, hi, span)
+  unsigned long long* best;              // group_cap u64, cleared (0): the largest (K << 32) | ~head over the group's arms
+  unsigned long long group_cap;          // a power of two >= 2 n_reads: at most n_reads groups go in
+  uint32_t* losers;                      // [n_reads]: the heads of the arms that wait for the bases test, as appended
+  uint4* where;                          // [n_reads]: the step's own layout, per placement {read | placed reversed << 31, its overlap with the
+                                         // read before it, low and high half of where in its unitig the bases it adds begin}
+  unsigned long long* bub;               // BUB_WORDS u64, zeroed before round 1: the BUB_C_* counters, slotted as the trim counters are;
+                                         // the appended losers at BUB_APPENDED; at BUB_ROUND0 + r whether round r's step removed something
+  uint32_t max_bubble_span, max_divergence_permille;
+};
+enum { BUB_C_POPPED = 0, BUB_C_READS = 1, BUB_C_KEPT = 2, BUB_COUNTERS = 3, BUB_APPENDED = BUB_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+       BUB_ROUND0 = BUB_APPENDED + 8, BUB_WORDS = BUB_ROUND0 + TRIM_MAX_ROUNDS + 8, BUB_COMPARE_WAVES = 8192 };
+static const uint32_t REMOVED_BUBBLE = 0x40000000u;
+static const uint32_t BUBBLE_NO_BASES = 0xFFFFFFFFu;
+// one round's bubble step (a.round >= 1, a.maxlen = NULL), after launch_prune_trim_round and before launch_chimeric_round: the graph of
+// the live records, the arms and their groups, a group's winner, the bases test of every other arm, removed[] marked with
+// REMOVED_BUBBLE.  Its kernels leave at once when the round before changed nothing.  The caller resets as for launch_trim_round; the
+// step clears its own scratch.  launch_bubble_status: status[20 .. 23], after launch_chimeric_status.
+void launch_bubble_round(const UnitigBubbleArgs& a, hipStream_t st);
+void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st);
 
 // `siga unitig --pairs` (sigax_pairs.hip): mate-pair statistics and links over the layout a unitig call left.  Everything below
 // `status` is the caller's scratch (sigax_pairs.cpp lays it out).

@@ -153,6 +153,36 @@ ChimericWork chimeric_work(u64 n, u64 n_edges, bool graph, bool careful) {
   return w;
 }
 
+// the bubble calls' scratch: the chimeric calls', then what a round's bubble step needs
+struct BubbleWork {
+  ChimericWork c;
+  u64 bub, bnbr, blen, arm, where, aside, gslot, losers, table, best, group_cap, bytes;
+};
+BubbleWork bubble_work(u64 n, u64 n_edges, bool graph, bool careful) {
+  BubbleWork w;
+  w.c = chimeric_work(n, n_edges, graph, careful);
+  u64 at = w.c.bytes;
+  auto take = [&](u64 bytes) {
+    const u64 here = at;
+    at += (bytes + 15) & ~15ull;
+    return here;
+  };
+  w.bub = take(BUB_WORDS * 8);
+  w.bnbr = take(2 * n * 4);
+  w.blen = take(2 * n * 4);
+  w.arm = take(n * 16);
+  w.where = take(n * 16);
+  w.aside = take(n * 4);
+  w.gslot = take(n * 4);
+  w.losers = take(n * 4);
+  w.group_cap = 16;
+  while (w.group_cap < 2 * n) w.group_cap <<= 1;
+  w.table = take(w.group_cap * 4);
+  w.best = take(w.group_cap * 8);
+  w.bytes = at;
+  return w;
+}
+
 int unitig_limits(u64 n_reads, u64 n_edges) {
   if (n_reads >= (1ull << 31)) return sigax_fail(SIGAX_E_ARG, "2^31 reads or more: a state names a read end in 32 bits");
   if (n_edges > (1ull << 32)) return sigax_fail(SIGAX_E_ARG, "more than 2^32 records");
@@ -185,6 +215,15 @@ int chimeric_opts_ok(const sigax_chimeric_opts* o, u64 n_reads) {
   if (o->reserved2 != 0) return sigax_fail(SIGAX_E_ARG, "sigax_chimeric_opts.reserved2 must be 0");
   if (o->min_chimeric_length > 0 && o->prune.genome_size == 0)
     return sigax_fail(SIGAX_E_ARG, "genome_size must be given with min_chimeric_length > 0");
+  return SIGAX_OK;
+}
+
+// the chimeric call's refusals with Lc = 0 where the bubble step alone runs: it needs neither G nor N
+int bubble_opts_ok(const sigax_bubble_opts* o, u64 n_reads) {
+  if (!o) return sigax_fail(SIGAX_E_ARG, "NULL where the bubble options are required");
+  const int rc = chimeric_opts_ok(&o->chimeric, n_reads);
+  if (rc != SIGAX_OK) return rc;
+  if (o->reserved3[0] != 0 || o->reserved3[1] != 0) return sigax_fail(SIGAX_E_ARG, "sigax_bubble_opts.reserved3 must be 0");
   return SIGAX_OK;
 }
 
@@ -439,15 +478,22 @@ static int unitigs_chimeric_run(int device, const sigax_edge* d_edges, uint64_t 
                                 void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, void* d_cut,
                                 sigax_edge* d_uedges, void* d_status20, void* d_work, uint64_t work_bytes, void* stream, bool paced);
 
-// The host form of the three calls.  The trim call passes opts, and NULL for popts, copts and cut; `status` then holds 12 counts.  The
+static int unitigs_bubble_run(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                              const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts, void* d_seq_offs,
+                              void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, void* d_cut,
+                              sigax_edge* d_uedges, void* d_status24, void* d_work, uint64_t work_bytes, void* stream, bool paced);
+
+// The host form of the four calls.  The bubble call passes bopts, &bopts->chimeric for copts, its prune for popts, and cut; `status`
+// then holds 24.  The trim call passes opts, and NULL for popts, copts and cut; `status` then holds 12 counts.  The
 // prune call passes popts and cut, and NULL for opts and copts; `status` then holds 16.  The chimeric call passes copts, &copts->prune
 // for popts, and cut; `status` then holds 20.
 static int unitigs_rounds_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
                                const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_trim_opts* opts,
-                               const sigax_prune_opts* popts, const sigax_chimeric_opts* copts, uint64_t* n_unitigs, uint64_t** seq_offs,
+                               const sigax_prune_opts* popts, const sigax_chimeric_opts* copts, const sigax_bubble_opts* bopts,
+                               uint64_t* n_unitigs, uint64_t** seq_offs,
                                uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs, uint32_t** removed,
                                uint32_t** cut, sigax_edge** uedges, uint64_t* status_out) {
-  const int n_status = copts ? 20 : popts ? 16 : 12;
+  const int n_status = bopts ? 24 : copts ? 20 : popts ? 16 : 12;
   if (!n_unitigs || !seq_offs || !lay_offs || !uflags || !layout || !removed || !status_out || (popts && !cut) ||
       (n_reads && (!lengths || !seqs || !offs)) || (n_edges && !edges))
     return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
@@ -463,7 +509,7 @@ static int unitigs_rounds_host(int device, const sigax_edge* edges, uint64_t n_e
   for (int k = 0; k < n_status; ++k) status_out[k] = 0;
   const int rl = unitig_limits(n_reads, n_edges);
   if (rl != SIGAX_OK) return rl;
-  const int ro = copts ? chimeric_opts_ok(copts, n_reads) : popts ? prune_opts_ok(popts, n_reads) : trim_opts_ok(opts);
+  const int ro = bopts ? bubble_opts_ok(bopts, n_reads) : copts ? chimeric_opts_ok(copts, n_reads) : popts ? prune_opts_ok(popts, n_reads) : trim_opts_ok(opts);
   if (ro != SIGAX_OK) return ro;
   const u64 n = n_reads;
   for (u64 i = 0; i < n; ++i)
@@ -475,13 +521,14 @@ static int unitigs_rounds_host(int device, const sigax_edge* edges, uint64_t n_e
     for (u64 i = 0; i <= n; ++i) rebased[i] = offs[i] - b0;
     offs = rebased.data();
   }
-  u64 status[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  u64 status[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   DevGuard g;
   void *d_edges = nullptr, *d_lengths = nullptr, *d_seqs = nullptr, *d_offs = nullptr, *d_so = nullptr, *d_lo = nullptr, *d_uf = nullptr,
        *d_lay = nullptr, *d_us = nullptr, *d_rm = nullptr, *d_ct = nullptr, *d_ue = nullptr, *d_status = nullptr, *d_work = nullptr;
   if (n) {
     HIP_TRY(hipSetDevice(device));
-    const u64 wb = copts   ? chimeric_work(n, n_edges, uedges != nullptr, popts->careful != 0).bytes
+    const u64 wb = bopts   ? bubble_work(n, n_edges, uedges != nullptr, popts->careful != 0).bytes
+                   : copts ? chimeric_work(n, n_edges, uedges != nullptr, popts->careful != 0).bytes
                    : popts ? prune_work(n, n_edges, uedges != nullptr, popts->careful != 0).bytes
                            : trim_work(n, n_edges, uedges != nullptr).bytes;
     if (popts) HIP_TRY(g.alloc(&d_ct, (size_t)n_edges * 4 + 16));
@@ -502,7 +549,10 @@ static int unitigs_rounds_host(int device, const sigax_edge* edges, uint64_t n_e
     HIP_TRY(hipMemcpy(d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice));
     if (nb) HIP_TRY(hipMemcpy(d_seqs, seqs + b0, (size_t)nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_offs, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    const int rc = copts ? unitigs_chimeric_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, copts, d_so,
+    const int rc = bopts ? unitigs_bubble_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, bopts, d_so,
+                                              d_lo, d_uf, (sigax_placement*)d_lay, d_us, d_rm, d_ct, (sigax_edge*)d_ue, d_status, d_work, wb,
+                                              nullptr, true)
+                   : copts ? unitigs_chimeric_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, copts, d_so,
                                                 d_lo, d_uf, (sigax_placement*)d_lay, d_us, d_rm, d_ct, (sigax_edge*)d_ue, d_status, d_work, wb,
                                                 nullptr, true)
                    : popts ? unitigs_prune_run(device, (const sigax_edge*)d_edges, n_edges, d_lengths, d_seqs, d_offs, n, min_overlap, popts, d_so,
@@ -574,8 +624,8 @@ extern "C" int sigax_unitigs_trim_host(int device, const sigax_edge* edges, uint
                                        uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                                        sigax_placement** layout, char** useqs, uint32_t** removed, sigax_edge** uedges,
                                        uint64_t status12[12]) {
-  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, opts, nullptr, nullptr, n_unitigs, seq_offs,
-                             lay_offs, uflags, layout, useqs, removed, nullptr, uedges, status12);
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, opts, nullptr, nullptr, nullptr, n_unitigs,
+                             seq_offs, lay_offs, uflags, layout, useqs, removed, nullptr, uedges, status12);
 }
 
 // ---- non-maximal overlap cutting ----
@@ -695,8 +745,8 @@ extern "C" int sigax_unitigs_prune_host(int device, const sigax_edge* edges, uin
                                         sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                         uint64_t status16[16]) {
   if (!opts) return sigax_fail(SIGAX_E_ARG, "NULL where the prune options are required");
-  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, opts, nullptr, n_unitigs, seq_offs,
-                             lay_offs, uflags, layout, useqs, removed, cut, uedges, status16);
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, opts, nullptr, nullptr, n_unitigs,
+                             seq_offs, lay_offs, uflags, layout, useqs, removed, cut, uedges, status16);
 }
 
 // ---- chimeric unitig removal ----
@@ -831,6 +881,163 @@ extern "C" int sigax_unitigs_chimeric_host(int device, const sigax_edge* edges, 
                                            sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                            uint64_t status20[20]) {
   if (!opts) return sigax_fail(SIGAX_E_ARG, "NULL where the chimeric options are required");
-  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, &opts->prune, opts, n_unitigs, seq_offs,
-                             lay_offs, uflags, layout, useqs, removed, cut, uedges, status20);
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, &opts->prune, opts, nullptr, n_unitigs,
+                             seq_offs, lay_offs, uflags, layout, useqs, removed, cut, uedges, status20);
+}
+
+// ---- bubble popping ----
+extern "C" int sigax_unitigs_bubble_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes) {
+  if (!bytes) return sigax_fail(SIGAX_E_ARG, "bad argument");
+  const int rc = unitig_limits(n_reads, n_edges);
+  if (rc != SIGAX_OK) return rc;
+  *bytes = bubble_work(n_reads, n_edges, want_graph != 0, careful != 0).bytes;
+  return SIGAX_OK;
+}
+
+static int unitigs_bubble_run(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                              const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts, void* d_seq_offs,
+                              void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs, void* d_removed, void* d_cut,
+                              sigax_edge* d_uedges, void* d_status24, void* d_work, uint64_t work_bytes, void* stream, bool paced) {
+  const int rl = unitig_limits(n_reads, n_edges);
+  if (rl != SIGAX_OK) return rl;
+  const int ro = bubble_opts_ok(opts, n_reads);
+  if (ro != SIGAX_OK) return ro;
+  const sigax_chimeric_opts* co = &opts->chimeric;
+  const sigax_prune_opts* po = &co->prune;
+  const BubbleWork w = bubble_work(n_reads, n_edges, d_uedges != nullptr, po->careful != 0);
+  if (n_reads && work_bytes < w.bytes)
+    return sigax_fail(SIGAX_E_ARG, "workspace of %llu bytes, %llu needed (sigax_unitigs_bubble_workspace)", (u64)work_bytes, w.bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  if (n_reads == 0 || opts->max_bubble_span == 0) {  // no bubble step: the chimeric call
+    const int rc = unitigs_chimeric_run(device, d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, co, d_seq_offs, d_lay_offs,
+                                        d_uflags, d_layout, d_useqs, d_removed, d_cut, d_uedges, d_status24, d_work, work_bytes, stream, paced);
+    if (rc != SIGAX_OK) return rc;
+    if (d_status24) HIP_TRY(hipMemsetAsync((char*)d_status24 + 160, 0, 32, st));
+    return SIGAX_OK;
+  }
+  if (!d_lengths || !d_seqs || !d_offs || !d_seq_offs || !d_lay_offs || !d_uflags || !d_layout || !d_removed || !d_status24 || !d_work ||
+      (n_edges && (!d_edges || !d_cut)))
+    return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
+  if (((uintptr_t)d_edges | (uintptr_t)d_layout | (uintptr_t)d_useqs | (uintptr_t)d_uedges | (uintptr_t)d_work) & 15)
+    return sigax_fail(SIGAX_E_ARG, "d_edges, d_layout, d_useqs, d_uedges and d_work must be 16-byte aligned");
+  if (((uintptr_t)d_offs | (uintptr_t)d_seq_offs | (uintptr_t)d_lay_offs | (uintptr_t)d_status24) & 7)
+    return sigax_fail(SIGAX_E_ARG, "d_offs, d_seq_offs, d_lay_offs and d_status24 must be 8-byte aligned");
+  if ((uintptr_t)d_removed & 3) return sigax_fail(SIGAX_E_ARG, "d_removed must be 4-byte aligned");
+  if ((uintptr_t)d_cut & 3) return sigax_fail(SIGAX_E_ARG, "d_cut must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(device));
+  UnitigBubbleArgs a;
+  static_cast<UnitigArgs&>(a) = unitig_args(d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, d_seq_offs, d_lay_offs, d_uflags,
+                                            d_layout, d_useqs, d_status24, d_work);
+  char* base = (char*)d_work;
+  const ChimericWork& cw = w.c;
+  const PruneWork& pw = cw.p;
+  a.removed = (uint32_t*)d_removed;
+  a.trim = (u64*)(base + pw.t.trim);
+  a.verdict = (uint32_t*)(base + pw.t.verdict);
+  a.umap = (uint32_t*)(base + pw.t.umap);
+  a.round = 0;
+  a.min_branch_length = po->min_branch_length;
+  a.min_branch_coverage = po->min_branch_coverage;
+  a.uedges = d_uedges;
+  a.eflag = (uint32_t*)(base + pw.t.eflag);
+  a.escan = (u64*)(base + pw.t.escan);
+  a.epartial = (u64*)(base + pw.t.epartial);
+  a.cut = (uint32_t*)d_cut;
+  a.maxlen = nullptr;
+  a.maxself = (uint32_t*)(base + pw.maxself);
+  a.uniq = (uint32_t*)(base + pw.uniq);
+  a.keys = (u64*)(base + pw.keys);
+  a.key_cap = pw.key_cap;
+  a.prune = (u64*)(base + pw.prune);
+  a.delta = po->delta;
+  a.careful = po->careful;
+  a.num_reads = po->num_reads;
+  a.genome_size = po->genome_size;
+  a.uniq_threshold = po->uniq_threshold;
+  a.nbr = (uint32_t*)(base + cw.nbr);
+  for (int k = 0; k < 2; ++k) {
+    a.minb[k] = (u64*)(base + cw.minb[k]);
+    a.mink[k] = (u64*)(base + cw.mink[k]);
+  }
+  a.chim = (u64*)(base + cw.chim);
+  a.prune_aside = (u64*)(base + cw.aside);
+  a.min_chimeric_length = co->min_chimeric_length;
+  a.min_chimeric_coverage = co->min_chimeric_coverage;
+  a.chimeric_delta = co->chimeric_delta;
+  a.chimeric_threshold = co->chimeric_threshold;
+  a.bnbr = (uint32_t*)(base + w.bnbr);
+  a.blen = (uint32_t*)(base + w.blen);
+  a.arm = (uint4*)(base + w.arm);
+  a.aside = (uint32_t*)(base + w.aside);
+  a.gslot = (uint32_t*)(base + w.gslot);
+  a.losers = (uint32_t*)(base + w.losers);
+  a.table = (uint32_t*)(base + w.table);
+  a.best = (u64*)(base + w.best);
+  a.group_cap = w.group_cap;
+  a.where = (uint4*)(base + w.where);
+  a.bub = (u64*)(base + w.bub);
+  a.max_bubble_span = opts->max_bubble_span;
+  a.max_divergence_permille = opts->max_divergence_permille;
+  uint32_t* const maxlen = (uint32_t*)(base + pw.maxlen);
+  HIP_TRY(hipMemsetAsync(d_removed, 0, (size_t)n_reads * 4, st));
+  if (n_edges) HIP_TRY(hipMemsetAsync(d_cut, 0, (size_t)n_edges * 4, st));
+  HIP_TRY(hipMemsetAsync(a.trim, 0, TRIM_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(a.prune, 0, PRUNE_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(a.chim, 0, CHIM_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(a.prune_aside, 0, PRUNE_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(a.bub, 0, BUB_WORDS * 8, st));
+  auto reset = [&]() -> hipError_t {
+    const hipError_t e = hipMemsetAsync(base + pw.t.u.zero_from, 0, (size_t)pw.t.u.zero_bytes, st);
+    return e != hipSuccess ? e : hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st);
+  };
+  for (uint32_t r = 1; r <= po->max_rounds; ++r) {
+    a.round = r;
+    if (po->delta > 0) {  // the cut step
+      HIP_TRY(reset());
+      a.maxlen = maxlen;
+      launch_prune_cut_round(a, st);
+      a.maxlen = nullptr;
+    }
+    HIP_TRY(reset());  // the trim step, over what the cut step left
+    launch_prune_trim_round(a, st);
+    HIP_TRY(reset());  // the bubble step, over what the trim step left
+    launch_bubble_round(a, st);
+    if (co->min_chimeric_length > 0) {
+      HIP_TRY(reset());  // the chimeric step, over what the bubble step left
+      launch_chimeric_round(a, st);
+    }
+    if (paced) {
+      u64 flag = 0;
+      HIP_TRY(hipMemcpyAsync(&flag, a.trim + TRIM_ROUND0 + r, 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (flag == 0) break;
+    }
+  }
+  a.round = 0;  // the unitigs of what is left
+  HIP_TRY(reset());
+  launch_unitigs_prune(a, st);
+  launch_unitig_prune_lift(a, st);
+  launch_chimeric_status(a, st);
+  launch_bubble_status(a, st);
+  HIP_TRY(hipGetLastError());
+  return SIGAX_OK;
+}
+
+extern "C" int sigax_unitigs_bubble_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                           const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts,
+                                           void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                           void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status24, void* d_work,
+                                           uint64_t work_bytes, void* stream) {
+  return unitigs_bubble_run(device, d_edges, n_edges, d_lengths, d_seqs, d_offs, n_reads, min_overlap, opts, d_seq_offs, d_lay_offs, d_uflags,
+                            d_layout, d_useqs, d_removed, d_cut, d_uedges, d_status24, d_work, work_bytes, stream, false);
+}
+
+extern "C" int sigax_unitigs_bubble_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                         const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts,
+                                         uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                         sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                                         uint64_t status24[24]) {
+  if (!opts) return sigax_fail(SIGAX_E_ARG, "NULL where the bubble options are required");
+  return unitigs_rounds_host(device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, nullptr, &opts->chimeric.prune, &opts->chimeric, opts,
+                             n_unitigs, seq_offs, lay_offs, uflags, layout, useqs, removed, cut, uedges, status24);
 }

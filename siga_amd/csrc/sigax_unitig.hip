@@ -48,7 +48,17 @@
 //                  (64-bit atomicMin behind a plain compare), then the smallest among those not of the first one's unitig
 //   k_chim_decide  one lane per read: a head judges its unitig from its two end degrees, its neighbours' degrees, scores and minima
 //   k_chim_mark    one lane per read: removed[r] = round | 0x80000000 under a chimeric head
-// The table's probe loops are bounded by its capacity, which holds at least twice the keys that can go in.
+// Bubble popping (sigax_unitigs_bubble_*; tests/bubble_cases.py::expected_bubble): a step between the trim and the
+// chimeric step of a round, over the <TRIM = 2> kernels, and
+//   k_bub_clear    the step's scratch emptied (a kernel: idle rounds write nothing)
+//   k_bub_ends     one lane per record: an end of degree 1 learns the read end at its record's other side and the record's length
+//   k_bub_place    one lane per read: the step's own layout, where in its unitig the bases a read adds begin (bases test only)
+//   k_bub_arms     one lane per read: a head judges whether its unitig is an arm that takes part, and with which (lo, hi, span)
+//   k_bub_group    one lane per read: an arm finds its group's slot in an open-addressing table and offers (K << 32) | ~head
+//   k_bub_losers   one lane per read: an arm that is not its group's maximum is popped (no bases test) or appended to a list
+//   k_bub_compare  one wave per appended loser: lanes stride over the window, each base found by bisecting the placements
+//   k_bub_mark     one lane per read: removed[r] = round | 0x40000000 under a popped head
+// The tables' probe loops are bounded by their capacity, which holds at least twice the keys that can go in.
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
 // consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
 // beyond the 64 descriptors, no MFMA.
@@ -835,6 +845,246 @@ __global__ void k_chim_status(UnitigChimericArgs A) {
   A.status[19] = 0ull;
 }
 
+// ---- bubble popping: one round's bubble step (the reference declares SmoothingVisitor and leaves it empty: the rules are sigax.h's) ----
+__device__ __forceinline__ u64* bub_slot(const UnitigBubbleArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  return A.bub + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 bub_count(const UnitigBubbleArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.bub[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+
+// Before a bubble step: neighbours, group table and maxima back to empty, no loser appended.  A kernel, as k_prune_clear.
+__global__ __launch_bounds__(256) void k_bub_clear(UnitigBubbleArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < 2 * A.n_reads) {
+    A.bnbr[i] = NIL;
+    A.blen[i] = 0u;
+  }
+  if (i < A.group_cap) {
+    A.table[i] = NIL;
+    A.best[i] = 0ull;
+  }
+  if (i == 0) A.bub[BUB_APPENDED] = 0ull;
+}
+
+// One lane per record, a participant in both directions a -> b: an end of degree 1 learns its neighbour and its record's length (its
+// one record: a single writer).
+__global__ __launch_bounds__(256) void k_bub_ends(UnitigBubbleArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.n_edges) return;
+  u32 s, t, len;
+  if (!participant(A, i, s, t, len)) return;
+  if (A.deg[s] == 1u) {
+    A.bnbr[s] = t;
+    A.blen[s] = len;
+  }
+  if (A.deg[t] == 1u) {
+    A.bnbr[t] = s;
+    A.blen[t] = len;
+  }
+}
+
+// One lane per read, as k_uni_place finds its slot: {read | reversed << 31, the overlap with the read before it, where in the unitig
+// the bases it adds begin}.  Those begins ascend along a unitig: k_bub_compare bisects on them.
+__global__ __launch_bounds__(256) void k_bub_place(UnitigBubbleArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  if (r >= n || A.removed[r] != 0u) return;
+  const u64* layr = A.scan + (n + 1);
+  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+  const u32 d = head_dir(a0, a1);
+  const uint4 to = d ? a1 : a0;
+  const u64 h = to.y >> 1;
+  if (h >= n) return;
+  const u64 slot = layr[h] + to.z;
+  if (slot >= n) return;
+  const uint2 lk = A.link[2 * r + d];
+  const u32 skip = lk.x == NIL ? 0u : lk.y;
+  const u64 from = dist[2 * r + d] + skip;
+  A.where[slot] = make_uint4((u32)r | (d << 31), skip, (u32)from, (u32)(from >> 32));
+}
+
+// One lane per read.  A head judges whether its unitig is an arm that takes part, its ends found as k_chim_decide finds them.
+__global__ __launch_bounds__(256) void k_bub_arms(UnitigBubbleArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  if (r >= n) return;
+  uint4 arm = make_uint4(0u, 0u, 0u, 0u);
+  u32 side = 0;
+  if (A.removed[r] == 0u && A.cnt[r] != 0u && A.closing[r] == 0u) {  // a head, and no ring
+    const u64 bases = unit_bases(A, (u32)r);
+    const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+    const u32 d = head_dir(a0, a1);
+    const u32 sl = 2u * (u32)r + d, sr = (d ? a0 : a1).y;
+    if ((u64)sr < 2 * n && A.deg[sl] == 1u && A.deg[sr] == 1u) {
+      const u32 p = A.bnbr[sl], q = A.bnbr[sr];
+      if ((u64)p < 2 * n && (u64)q < 2 * n && p != q && head_of(A, rk, p) != (u32)r && head_of(A, rk, q) != (u32)r) {
+        side = p < q;
+        const u32 o_lo = side ? A.blen[sl] : A.blen[sr], o_hi = side ? A.blen[sr] : A.blen[sl];
+        const u64 ends = (u64)o_lo + o_hi;
+        if (bases > ends && bases - ends <= (u64)A.max_bubble_span) arm = make_uint4(side ? p : q, side ? q : p, (u32)(bases - ends), o_lo);
+      }
+    }
+  }
+  A.arm[r] = arm;
+  A.aside[r] = side;
+  A.gslot[r] = NIL;
+}
+
+// One lane per read.  An arm that takes part finds the slot of its group -- the first free one on the probe path of (lo, hi, span), or
+// the one an arm of that key opened -- and offers (K << 32) | ~head to the group's maximum.  arm[] is the kernel before's: stable.
+__global__ __launch_bounds__(256) void k_bub_group(UnitigBubbleArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (r >= A.n_reads) return;
+  const uint4 arm = A.arm[r];
+  if (arm.z == 0u) return;
+  const u64 mask = A.group_cap - 1ull;
+  u64 at = key_hash((((u64)arm.x << 32) | arm.y) ^ key_hash(arm.z)) & mask;
+  for (u64 p = 0; p < A.group_cap; ++p, at = (at + 1ull) & mask) {  // (never more than group_cap probes; at most half the table fills)
+    const u32 was = atomicCAS(&A.table[at], NIL, (u32)r);
+    bool mine = was == NIL || was == (u32)r;
+    if (!mine && (u64)was < A.n_reads) {
+      const uint4 o = A.arm[was];
+      mine = o.x == arm.x && o.y == arm.y && o.z == arm.z;
+    }
+    if (mine) {
+      A.gslot[r] = (u32)at;
+      atomicMax(&A.best[at], (unit_reads(A, (u32)r) << 32) | (u64)(~(u32)r));
+      return;
+    }
+  }
+}
+
+// One lane per read.  An arm that is not its group's maximum is a loser: without a bases test it is popped here, with one it is
+// appended to the list k_bub_compare walks (a wave's losers behind one add).
+__global__ __launch_bounds__(256) void k_bub_losers(UnitigBubbleArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  const u32 lane = threadIdx.x & 63u;
+  bool loser = false;
+  if (r < n) {
+    const u32 g = A.gslot[r];
+    if ((u64)g < A.group_cap) loser = (u32)(~A.best[g]) != (u32)r;
+  }
+  const bool no_bases = A.max_divergence_permille == BUBBLE_NO_BASES;
+  if (r < n) A.verdict[r] = loser && no_bases ? 1u : 0u;
+  const u64 losers = __ballot(loser);
+  if (!losers) return;
+  if (no_bases) {
+    if (lane == 0u) atomicAdd(bub_slot(A, BUB_C_POPPED), (u64)__popcll(losers));
+    return;
+  }
+  u64 base = 0;
+  if (lane == 0u) base = atomicAdd(A.bub + BUB_APPENDED, (u64)__popcll(losers));
+  base = __shfl(base, 0, 64);
+  const u64 at = base + (u64)__popcll(losers & ((1ull << lane) - 1ull));
+  if (loser && at < n) A.losers[at] = (u32)r;
+}
+
+// base o_lo + t of A(U), U the arm under head h: S(U) is read through the placements k_bub_place left, as the final pass would write
+// it; an arm entered through its right end is read from its far end, complemented.
+__device__ __forceinline__ u32 arm_base(const UnitigBubbleArgs& A, u32 h, const uint4 arm, u32 side, u64 t, u64 src_end) {
+  const u64 n = A.n_reads, bases = unit_bases(A, h), K = unit_reads(A, h), first = A.scan[(n + 1) + h];
+  const u64 in = (u64)arm.w + t;
+  if (in >= bases || K == 0ull || first >= n) return 'N';  // (no consistent state comes here)
+  const u64 x = side ? in : bases - 1ull - in;
+  u64 a = 0, b = K < n - first ? K : n - first;  // the last placement that begins at or before x
+  for (int step = 0; step < 32 && b - a > 1ull; ++step) {
+    const u64 m = (a + b) >> 1;
+    const uint4 e = A.where[first + m];
+    if (((u64)e.z | ((u64)e.w << 32)) <= x) a = m;
+    else b = m;
+  }
+  const uint4 e = A.where[first + a];
+  const u64 r = e.x & 0x7FFFFFFFu, from = (u64)e.z | ((u64)e.w << 32);
+  const u32 rev = e.x >> 31;
+  if (r >= n || from < e.y || x < from - e.y) return 'N';
+  const u64 j = x - (from - e.y), L = A.lengths[r];
+  if (j >= L) return 'N';
+  const u64 at = A.offs[r] + (rev ? L - 1ull - j : j);
+  if (at >= src_end) return 'N';
+  u32 c = A.seqs[at];
+  if (rev) c = comp_byte(c);
+  return side ? c : comp_byte(c);
+}
+
+// One wave per appended loser, the grid's W waves striding over the list (at most n_reads / W + 1 turns); lanes stride over the window (at most
+// Lb / 64 + 1 turns).  Popped iff mism * 1000 <= D * span.
+__global__ __launch_bounds__(256) void k_bub_compare(UnitigBubbleArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 n = A.n_reads;
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, waves = gridDim.x * 4u;
+  u64 appended = A.bub[BUB_APPENDED];
+  if (appended > n) appended = n;
+  const u64 src_end = A.offs[n];
+  u64 popped = 0, kept = 0;
+  for (u64 i = wave; i < appended; i += waves) {
+    const u32 h = A.losers[i];
+    if ((u64)h >= n) continue;
+    const u32 g = A.gslot[h];
+    if ((u64)g >= A.group_cap) continue;
+    const u32 w = (u32)(~A.best[g]);
+    if ((u64)w >= n) continue;
+    const uint4 al = A.arm[h], aw = A.arm[w];
+    const u32 sl = A.aside[h], sw = A.aside[w];
+    const u64 span = al.z < A.max_bubble_span ? al.z : A.max_bubble_span;
+    u64 mism = 0;
+    for (u64 t = lane; t < span; t += 64) mism += arm_base(A, h, al, sl, t, src_end) != arm_base(A, w, aw, sw, t, src_end);
+    mism = wave_total(mism);
+    if (mism * 1000ull <= (u64)A.max_divergence_permille * span) {
+      if (lane == 0u) A.verdict[h] = 1u;
+      ++popped;
+    } else {
+      ++kept;
+    }
+  }
+  if (lane == 0u) {
+    if (popped) atomicAdd(bub_slot(A, BUB_C_POPPED), popped);
+    if (kept) atomicAdd(bub_slot(A, BUB_C_KEPT), kept);
+  }
+}
+
+// One lane per read, as k_chim_mark: the verdict lies under its head.
+__global__ __launch_bounds__(256) void k_bub_mark(UnitigBubbleArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 gone = 0;
+  if (r < n && A.removed[r] == 0u) {
+    const u32 h = head_of(A, rk, 2u * (u32)r);
+    if (h != NIL && A.verdict[h] != 0u) {
+      A.removed[r] = A.round | REMOVED_BUBBLE;
+      gone = 1;
+    }
+  }
+  const u64 tg = wave_total(gone);
+  if ((threadIdx.x & 63u) == 0u && tg) {
+    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
+    atomicAdd(bub_slot(A, BUB_C_READS), tg);
+    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+    A.bub[BUB_ROUND0 + A.round] = 1ull;
+  }
+}
+
+__global__ void k_bub_status(UnitigBubbleArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.bub[BUB_ROUND0 + r] != 0ull;
+  A.status[20] = bub_count(A, BUB_C_POPPED);
+  A.status[21] = bub_count(A, BUB_C_READS);
+  A.status[22] = rounds;
+  A.status[23] = bub_count(A, BUB_C_KEPT);
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
@@ -970,4 +1220,33 @@ void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st) {
 void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st) {
   if (a.n_reads == 0 || !a.removed) return;
   hipLaunchKernelGGL(k_chim_status, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_bubble_round(const UnitigBubbleArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.maxlen || !a.bnbr || !a.where || a.max_bubble_span == 0u || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  hipLaunchKernelGGL(k_bub_clear, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
+  const UnitigPruneArgs& pa = a;
+  const unsigned f = launch_graph<2>(pa, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
+  if (a.n_edges) hipLaunchKernelGGL(k_bub_ends, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+  const bool bases_test = a.max_divergence_permille != BUBBLE_NO_BASES;
+  if (bases_test) {  // where each unitig's placements begin (the scan has no idle form: after an idle round nothing reads its result)
+    launch_scan(a.cnt + (n + 1), n, a.partial, a.scan + (n + 1), a.scan_total, st);
+    hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  }
+  hipLaunchKernelGGL(k_bub_arms, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_bub_group, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_bub_losers, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  if (bases_test) {
+    const u32 waves = (u32)(n < BUB_COMPARE_WAVES ? n : BUB_COMPARE_WAVES);
+    hipLaunchKernelGGL(k_bub_compare, dim3((waves + 3u) / 4u), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_bub_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+}
+
+void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  hipLaunchKernelGGL(k_bub_status, dim3(1), dim3(64), 0, st, a);
 }

@@ -52,6 +52,10 @@ def lib():
                                                  C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
                                                  C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
                                                  C.c_char_p, C.c_void_p, C.c_char_p, C.c_uint64]
+        L.sigah_unitig_bubble_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                               C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
+                                               C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
+                                               C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_uint64]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -148,7 +152,7 @@ def locate_files(paths, prefix, rc=True, max_hits=1000, max_len=None, device=0, 
 def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreducible=True, rc=True, device=0, piece_reads=0, cut_terminal=0,
                 min_branch_length=150, min_branch_coverage=None, graph=None, removed=None, max_overlap_delta=0, max_overlap_carefully=False,
                 num_reads=None, genome_size=None, uniq_threshold=13.0, cut_edges=None, min_chimeric_length=0, min_chimeric_coverage=None,
-                max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None):
+                max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None, max_bubble_span=0, bubble_divergence=50, bubbles=None):
     """`siga unitig`: FMIndex::load + Unitigger::run; the FASTA goes to the file `out`, or to stdout, the placements to the file
     `layout` when one is named.  piece_reads: reads per overlap call (0: 2^20); the result does not depend on it.
     cut_terminal (-x), min_branch_length (-n), min_branch_coverage (-C, None: no coverage test): tip trimming, 0 rounds = none;
@@ -159,8 +163,25 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
     lines.  With a delta the dict also holds records_cut and cut_rounds.
     min_chimeric_length (-l; 0: none), min_chimeric_coverage (-A, None: no coverage test), max_chimeric_delta (-a),
     chimeric_threshold (-T as the chimeric step takes it): chimeric unitig removal as the last step of a round; chimeric: the file
-    of "name<TAB>round" lines of the reads it removed.  With a length the dict also holds chimeric_unitigs and chimeric_reads."""
+    of "name<TAB>round" lines of the reads it removed.  With a length the dict also holds chimeric_unitigs and chimeric_reads.
+    max_bubble_span (-b; 0: none), bubble_divergence (--bubble-divergence, per mille; None: --no-bubble-bases): bubble popping between
+    the trim and the chimeric step of a round; bubbles: the file of "name<TAB>round" lines of the reads it removed.  With a span the
+    dict also holds bubbles_popped, bubble_reads and bubbles_kept."""
     err = C.create_string_buffer(512)
+    if max_bubble_span:
+        status = np.zeros(15, dtype=np.uint64)
+        if lib().sigah_unitig_bubble_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,
+                                          (out or "").encode(), (layout or "").encode(), piece_reads, int(cut_terminal), int(min_branch_length),
+                                          -1 if min_branch_coverage is None else int(min_branch_coverage), (graph or "").encode(),
+                                          (removed or "").encode(), int(max_overlap_delta), int(max_overlap_carefully), int(num_reads or 0),
+                                          int(genome_size or 0), float(uniq_threshold), (cut_edges or "").encode(), int(min_chimeric_length),
+                                          -1 if min_chimeric_coverage is None else int(min_chimeric_coverage), int(max_chimeric_delta),
+                                          float(chimeric_threshold), (chimeric or "").encode(), int(max_bubble_span),
+                                          -1 if bubble_divergence is None else int(bubble_divergence), (bubbles or "").encode(),
+                                          status.ctypes.data, err, 512) != 0:
+            raise RuntimeError("siga unitig failed: " + err.value.decode())
+        return dict(zip(("unitigs", "bases", "merged", "circular", "rounds", "islands", "dead_ends", "reads_removed", "records_cut", "cut_rounds",
+                         "chimeric_unitigs", "chimeric_reads", "bubbles_popped", "bubble_reads", "bubbles_kept"), (int(x) for x in status)))
     if min_chimeric_length:
         status = np.zeros(12, dtype=np.uint64)
         if lib().sigah_unitig_chimeric_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,

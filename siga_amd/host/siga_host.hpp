@@ -249,6 +249,17 @@ class Unitigger {
   }
   // one "name\tround" line per read a chimeric step removed, in read order
   void setChimericOut(const std::string& path) { _chimericOut = path; }
+  // Bubble popping between the trim and the chimeric step of every round (the reference declares SmoothingVisitor and leaves it
+  // empty; the rules are include/sigax.h's): of the unitigs that join the same two read ends and hold the same number of bases
+  // between them, at most maxSpan (-b; 0, the default: none, and run() goes through the calls it went through without this), the
+  // one with the most reads stays; another goes where its bases differ from the winner's in at most `divergence` per mille of
+  // that window (--bubble-divergence; -1: no bases test).  Needs rounds (setTrim).  (sigax_unitigs_bubble_host.)
+  void setBubble(size_t maxSpan, long divergence = 50) {
+    _bubbleSpan = maxSpan;
+    _bubbleDivergence = divergence;
+  }
+  // one "name\tround" line per read a bubble step removed, in read order
+  void setBubbleOut(const std::string& path) { _bubbleOut = path; }
   // The paired-end side (sigax_unitigs_pairs_host; the rules in include/sigax.h): mates are found by name as PairEnd::id does
   // (src/reads.cpp:19-41; the last character swaps 1<->2, A<->B, f<->r), every pair is looked up in the unitigs this run built,
   // and `json` gets {"pairs": {the 24 counts by name, insert_size, delta, span_mean, span_sd, hist_bins, hist_shift, histogram
@@ -296,6 +307,9 @@ class Unitigger {
   uint64_t insertDelta() const { return _insertDelta; }
   uint64_t chimericUnitigs() const { return _chimUnitigs; }
   uint64_t chimericReads() const { return _chimReads; }
+  uint64_t bubblesPopped() const { return _bubPopped; }  // arms popped
+  uint64_t bubbleReads() const { return _bubReads; }
+  uint64_t bubblesKept() const { return _bubKept; }      // losers kept because they failed the bases test, over the rounds
   uint64_t recordsCut() const { return _recordsCut; }
   uint64_t cutRounds() const { return _cutRounds; }    // rounds in which something was cut
   uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something (with setMaxOverlap: or cut something)
@@ -324,6 +338,10 @@ class Unitigger {
   double _chimThreshold = 0.0;
   std::string _chimericOut;
   uint64_t _chimUnitigs = 0, _chimReads = 0;
+  size_t _bubbleSpan = 0;
+  long _bubbleDivergence = 50;
+  std::string _bubbleOut;
+  uint64_t _bubPopped = 0, _bubReads = 0, _bubKept = 0;
   std::string _pairsOut, _linksOut;
   uint64_t _maxSpan = 0;
   bool _outward = false;

@@ -554,6 +554,14 @@ static int unitig_help() {
          "          --chimeric=FILE              write one line per read removed as chimeric to FILE: read name, the round it went in\n"
          "      -T sets both thresholds; without it cutting takes 13.0 and the chimeric step 0.0\n"
          "\n"
+         "Bubble parameters (they need -x: the step runs in its rounds, after the trimming and before the chimeric step):\n"
+         "      -b, --max-bubble-span=LEN        of the unitigs that join the same two unitig ends and hold the same number of bases, at\n"
+         "                                       most LEN, between them, keep the one with the most reads (default: 0, none)\n"
+         "          --bubble-divergence=PERMILLE ... and remove another only if its bases differ from the kept one's in at most\n"
+         "                                       PERMILLE per mille of those bases (default: 50)\n"
+         "          --no-bubble-bases            ... whatever its bases\n"
+         "          --bubbles=FILE               write one line per read removed as a bubble arm to FILE: read name, the round it went in\n"
+         "\n"
          "Paired-end parameters (mates by name: the last character swaps 1 and 2, A and B, f and r):\n"
          "          --pairs=FILE                 look every pair up in the unitigs and write the statistics to FILE as JSON: the counts\n"
          "                                       by class, the insert size estimate of `siga assemble --pe-mode=1`, the span histogram\n"
@@ -602,7 +610,7 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 static int run_unitig(int argc, char** argv) {
   enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC, OPT_PAIRS, OPT_LINKS,
          OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT, OPT_SCAFFOLD, OPT_SCAFFOLD_LAYOUT, OPT_MIN_PAIRS, OPT_LINK_RATIO,
-         OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP };
+         OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -616,6 +624,9 @@ static int run_unitig(int argc, char** argv) {
                                     {"min-chimeric-length", required_argument, nullptr, 'l'},
                                     {"min-chimeric-coverage", required_argument, nullptr, 'A'},
                                     {"max-chimeric-delta", required_argument, nullptr, 'a'}, {"chimeric", required_argument, nullptr, OPT_CHIMERIC},
+                                    {"max-bubble-span", required_argument, nullptr, 'b'},
+                                    {"bubble-divergence", required_argument, nullptr, OPT_BUBBLE_DIVERGENCE},
+                                    {"no-bubble-bases", no_argument, nullptr, OPT_NO_BUBBLE_BASES}, {"bubbles", required_argument, nullptr, OPT_BUBBLES},
                                     {"pairs", required_argument, nullptr, OPT_PAIRS}, {"links", required_argument, nullptr, OPT_LINKS},
                                     {"max-span", required_argument, nullptr, OPT_MAX_SPAN}, {"outward", no_argument, nullptr, OPT_OUTWARD},
                                     {"pairs-bins", required_argument, nullptr, OPT_PAIRS_BINS},
@@ -636,6 +647,9 @@ static int run_unitig(int argc, char** argv) {
   bool haveInsertSize = false, scaffoldTuned = false;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
+  size_t bubbleSpan = 0, bubbleDivergence = 50;
+  bool noBubbleBases = false, bubbleTuned = false;
+  std::string bubblesOut;
   long minBranchCoverage = -1, chimCoverage = -1;
   double uniqThreshold = 13.0, chimThreshold = 0.0;  // (-T sets both: src/assembler.cpp:55-67)
   bool exhaustive = false, norc = false, help = false, carefully = false;
@@ -645,7 +659,7 @@ static int run_unitig(int argc, char** argv) {
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:l:A:a:h", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:l:A:a:b:h", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
@@ -681,6 +695,10 @@ static int run_unitig(int argc, char** argv) {
         break;
       }
       case OPT_CHIMERIC: chimericOut = optarg; break;
+      case 'b': if (!unitig_number(optarg, "-b, --max-bubble-span", 0xFFFFFFFFull, &bubbleSpan)) return 1; break;
+      case OPT_BUBBLE_DIVERGENCE: if (!unitig_number(optarg, "--bubble-divergence", 0xFFFFFFFEull, &bubbleDivergence)) return 1; bubbleTuned = true; break;
+      case OPT_NO_BUBBLE_BASES: noBubbleBases = bubbleTuned = true; break;
+      case OPT_BUBBLES: bubblesOut = optarg; break;
       case OPT_PAIRS: pairsOut = optarg; break;
       case OPT_LINKS: linksOut = optarg; break;
       case OPT_MAX_SPAN: if (!unitig_number(optarg, "--max-span", ~0ull, &maxSpan)) return 1; pairsTuned = true; break;
@@ -732,6 +750,14 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: -A, -a and --chimeric need -l, --min-chimeric-length\n");
     return 1;
   }
+  if (bubbleSpan > 0 && cutTerminal == 0) {
+    fprintf(stderr, "siga unitig: -b, --max-bubble-span needs -x, --cut-terminal: the step runs in its rounds\n");
+    return 1;
+  }
+  if (bubbleSpan == 0 && (bubbleTuned || !bubblesOut.empty())) {
+    fprintf(stderr, "siga unitig: --bubble-divergence, --no-bubble-bases and --bubbles need -b, --max-bubble-span\n");
+    return 1;
+  }
   if (pairsOut.empty() && (!linksOut.empty() || pairsTuned)) {
     fprintf(stderr, "siga unitig: --links, --max-span, --outward, --pairs-bins and --pairs-shift need --pairs\n");
     return 1;
@@ -759,6 +785,8 @@ static int run_unitig(int argc, char** argv) {
   sigah::Unitigger unitigger(!exhaustive, !norc);
   unitigger.setChimeric(chimLength, chimCoverage, chimDelta, chimThreshold);
   unitigger.setChimericOut(chimericOut);
+  unitigger.setBubble(bubbleSpan, noBubbleBases ? -1 : (long)bubbleDivergence);
+  unitigger.setBubbleOut(bubblesOut);
   unitigger.setTrim(cutTerminal, minBranchLength, minBranchCoverage);
   unitigger.setGraph(graph);
   unitigger.setRemoved(removed);
@@ -780,6 +808,9 @@ static int run_unitig(int argc, char** argv) {
   if (chimLength)
     fprintf(stderr, "%llu chimeric unitigs removed, %llu reads\n", (unsigned long long)unitigger.chimericUnitigs(),
             (unsigned long long)unitigger.chimericReads());
+  if (bubbleSpan)
+    fprintf(stderr, "%llu bubble arms popped, %llu reads, %llu kept on divergence\n", (unsigned long long)unitigger.bubblesPopped(),
+            (unsigned long long)unitigger.bubbleReads(), (unsigned long long)unitigger.bubblesKept());
   if (!pairsOut.empty())
     fprintf(stderr, "%llu pairs, %llu in one unitig (insert size %llu, delta %llu), %llu across unitigs in %llu links\n",
             (unsigned long long)unitigger.pairs(), (unsigned long long)unitigger.pairsSame(), (unsigned long long)unitigger.insertSize(),

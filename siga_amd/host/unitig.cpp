@@ -116,9 +116,10 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  uint64_t status[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t status[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
   if (!_chimericOut.empty() && _chimLength == 0) return fail("chimeric reads are only written with a min-chimeric length");
+  if (!_bubbleOut.empty() && _bubbleSpan == 0) return fail("bubble reads are only written with a max-bubble span");
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
   if (_pairsOut.empty() && !_linksOut.empty()) return fail("links are only written with the pairs statistics");
   if (!_pairsOut.empty() && (_pairsBins == 0 || _pairsBins > SIGAX_PAIRS_MAX_BINS || _pairsShift > 31)) return fail("pairs bins or shift out of range");
@@ -131,7 +132,35 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
   }
-  if (_chimLength > 0) {
+  if (_bubbleSpan > 0) {
+    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
+    if (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll)
+      return fail("chimeric length, delta or coverage out of range");
+    if (_bubbleSpan > 0xFFFFFFFFull || _bubbleDivergence >= (long)0xFFFFFFFFll) return fail("bubble span or divergence out of range");
+    sigax_bubble_opts opts;
+    sigax_prune_opts& po = opts.chimeric.prune;
+    po.max_rounds = (uint32_t)_rounds;
+    po.min_branch_length = (uint32_t)_minBranchLength;
+    po.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
+    po.delta = (uint32_t)_delta;
+    po.careful = _careful ? 1u : 0u;
+    po.reserved = 0;
+    po.num_reads = _numReads ? _numReads : n;
+    po.genome_size = _genomeSize;
+    po.uniq_threshold = _uniqThreshold;
+    opts.chimeric.min_chimeric_length = (uint32_t)_chimLength;
+    opts.chimeric.min_chimeric_coverage = _chimCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_chimCoverage;
+    opts.chimeric.chimeric_delta = (uint32_t)_chimDelta;
+    opts.chimeric.reserved2 = 0;
+    opts.chimeric.chimeric_threshold = _chimThreshold;
+    opts.max_bubble_span = (uint32_t)_bubbleSpan;
+    opts.max_divergence_permille = _bubbleDivergence < 0 ? SIGAX_BUBBLE_NO_BASES : (uint32_t)_bubbleDivergence;
+    opts.reserved3[0] = opts.reserved3[1] = 0;
+    if (sigax_unitigs_bubble_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
+                                  (uint32_t)minOverlap, &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                  _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else if (_chimLength > 0) {
     if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
     if (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll)
       return fail("chimeric length, delta or coverage out of range");
@@ -198,6 +227,9 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _cutRounds = status[13];
   _chimUnitigs = status[16];
   _chimReads = status[17];
+  _bubPopped = status[20];
+  _bubReads = status[21];
+  _bubKept = status[23];
   if (!_pairsOut.empty()) {  // over the unitigs as they stand, whichever call built them; the other outputs do not depend on it
     PairsRequest rq;
     rq.json = _pairsOut;
@@ -268,7 +300,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
         const std::string_view name = reads.name(r);
         t.append(name.data(), name.size());
         t += '\t';
-        append_u64(t, u.removed[r] & ~SIGAX_REMOVED_CHIMERIC);
+        append_u64(t, u.removed[r] & ~(SIGAX_REMOVED_CHIMERIC | SIGAX_REMOVED_BUBBLE));
         t += '\n';
       }
     ok = write_all(rf, t);
@@ -291,6 +323,23 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     ok = write_all(rf, t);
     if (fclose(rf) != 0) ok = false;
     if (!ok) return fail("Failed to write " + _chimericOut);
+    t.clear();
+  }
+  if (!_bubbleOut.empty()) {
+    FILE* rf = fopen(_bubbleOut.c_str(), "wb");
+    if (!rf) return fail("Failed to create " + _bubbleOut);
+    t.clear();
+    for (size_t r = 0; r < n; ++r)
+      if (u.removed[r] & SIGAX_REMOVED_BUBBLE) {
+        const std::string_view name = reads.name(r);
+        t.append(name.data(), name.size());
+        t += '\t';
+        append_u64(t, u.removed[r] & ~SIGAX_REMOVED_BUBBLE);
+        t += '\n';
+      }
+    ok = write_all(rf, t);
+    if (fclose(rf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _bubbleOut);
     t.clear();
   }
   if (!_cutEdges.empty()) {

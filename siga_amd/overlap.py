@@ -276,6 +276,56 @@ def unitigs_chimeric(edges, lengths, seqs, offs, min_overlap, max_rounds, min_br
     return out
 
 
+def unitigs_bubble(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
+                   num_reads=None, genome_size=None, uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None,
+                   chimeric_delta=0, chimeric_threshold=0.0, max_bubble_span=0, bubble_divergence=50, graph=True, bases=True, device=0):
+    """`unitigs_chimeric` with bubble popping between the trim and the chimeric step of every round (sigax_unitigs_bubble_host, the
+    rules in include/sigax.h): of the unitigs that join the same two read ends through one participant record at each end and hold
+    the same number of bases between them, at most max_bubble_span, the one with the most reads (then the smallest first read) stays;
+    another goes where its bases differ from the winner's in at most bubble_divergence per mille of that window (None: no bases
+    test).  max_bubble_span = 0 is `unitigs_chimeric`.  -> its dict; removed carries _lib.SIGAX_REMOVED_BUBBLE on the reads a bubble
+    step removed; status u64[24]: as there, then {arms popped, their reads, rounds with one, losers kept on divergence}."""
+    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(lengths)
+    if len(offs) != n + 1:
+        raise ValueError("offs must have len(lengths) + 1 entries")
+    if isinstance(seqs, np.ndarray):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+    else:
+        buf = bytes(seqs)
+    L = _lib.lib()
+    prune = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
+                           _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
+                           n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
+    chim = _lib.ChimericOpts(prune, int(min_chimeric_length),
+                             _lib.SIGAX_TRIM_NO_COVERAGE if min_chimeric_coverage is None else int(min_chimeric_coverage), int(chimeric_delta), 0,
+                             float(chimeric_threshold))
+    opts = _lib.BubbleOpts(chim, int(max_bubble_span), _lib.SIGAX_BUBBLE_NO_BASES if bubble_divergence is None else int(bubble_divergence),
+                           (C.c_uint32 * 2)(0, 0))
+    nu = C.c_uint64()
+    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
+    status = np.zeros(24, dtype=np.uint64)
+    _check(L.sigax_unitigs_bubble_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+                                       offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo),
+                                       C.byref(uf), C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct),
+                                       C.byref(ue) if graph else None, status.ctypes.data), "sigax_unitigs_bubble_host")
+    try:
+        u = int(nu.value)
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
+               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
+        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
+    finally:
+        for p in (so, lo, uf, lay, us, rm, ct, ue):
+            L.sigax_free(p)
+    return out
+
+
 def mates_by_name(names):
     """The mate of every read by name, as the reference's PairEnd::id finds it (src/reads.cpp:19-41): the mate's name is the
     read's with its last character swapped 1<->2, A<->B or f<->r.  -> u32[n]; SIGAX_NO_MATE where the name ends otherwise, the
