@@ -860,17 +860,27 @@ int  sigax_locality_keys(int device, const void* d_seqs, const void* d_offs, uin
 /* How many sub-batches a run is cut into (0 = automatic).  With more than one, sub-batch i's filter/extract kernels run on
  * an internal stream beside sub-batch i+1's block finder (the first is VALU-bound, the second memory-request-bound). */
 int  sigax_batch_set_subbatches(sigax_batch*, uint32_t n);
-/* Enqueue the whole path: find -> filter/extract -> order -> edges.  Asynchronous.  The kernels run on three internal
+/* Enqueue the whole path: find -> filter/extract -> block offsets -> ordered blocks, or with SIGAX_EDGES the edge records.
+ * Asynchronous.  The kernels run on three internal
  * streams owned by the index (finder, filter/extract, tail) and ordered against `stream`: work already on `stream` is
  * waited for, and `stream` waits for the run's last kernel.  Several batch objects of one index may be in flight at
  * once (each with its own `stream`): their finder launches queue behind each other, so batch k+1's finder starts beside
- * batch k's filter/extract tail.  A batch object must be finished before it is run again. */
+ * batch k's filter/extract tail.  A batch object must be finished before it is run again.
+ * A run with SIGAX_EDGES makes its edge records straight from the blocks as filter/extract left them and does NOT put the
+ * 80-byte blocks in order: block_offs, the substring flags and the edge records are its outputs, and the ordered blocks
+ * are made the first time they are asked for (sigax_batch_device_outputs with d_blocks, sigax_batch_download).  A run
+ * without SIGAX_EDGES orders its blocks in the run, as they are its result. */
 int  sigax_batch_run(sigax_batch*, uint32_t read_base, uint32_t min_overlap, uint32_t flags, void* stream);
 /* Wait for the stream, check arena overflow flags (growing arenas and re-running if needed), fill stats. */
 int  sigax_batch_finish(sigax_batch*, void* stream, sigax_stats* stats);
-/* Device pointers of the finished batch's outputs (valid until the next run on this batch). */
+/* Device pointers of the finished batch's outputs (valid until the next run on this batch).  Any of the four may be NULL.
+ * After a run with SIGAX_EDGES a non-NULL d_blocks makes the call order the blocks first: one copy kernel on the index's tail
+ * stream, which the call waits for -- the other three pointers cost nothing.  The first such call after a run (this one or
+ * sigax_batch_download) does the copy; later ones return the same pointer at once.  Every sigax_batch_run, and every repeat
+ * of the run inside sigax_batch_finish, starts over. */
 int  sigax_batch_device_outputs(sigax_batch*, const sigax_block** d_blocks, const uint64_t** d_block_offs,
                                 const uint8_t** d_substring, const sigax_edge** d_edges);
+/* Everything to the host (malloc'd; release with sigax_result_free); orders the blocks as sigax_batch_device_outputs does. */
 int  sigax_batch_download(sigax_batch*, sigax_result* out);
 /* Only what the ASQG writer needs (OverlapPostProcess + Hit2OverlapConverter, src/overlap_builder.cpp:291-375): the
  * substring flags (n_reads bytes, caller's buffer, may be NULL) and the edge records (malloc'd; release with sigax_free). */
@@ -881,7 +891,8 @@ int  sigax_batch_size_hint(sigax_index*, uint32_t max_read_len, uint32_t min_ove
                            uint32_t* max_reads);
 /* Device time of the kernels of the last finished run, measured with HIP events on the streams they were launched on,
  * summed over the run's sub-batch launches: ms[0] find, ms[1] filter/extract (32- and 64-lane launches),
- * ms[2] filter/extract (general), ms[3] order, ms[4] edges.  *n_sub = finder launches of the run (sub-batches, times
+ * ms[2] filter/extract (general), ms[3] block scan + edge stage pass (without SIGAX_EDGES: block scan + ordered copy),
+ * ms[4] edge scan + emit pass (without SIGAX_EDGES: 0).  *n_sub = finder launches of the run (sub-batches, times
  * two when the finder runs once per strand's two-step table); the other kernels run once per sub-batch. */
 int  sigax_batch_kernel_ms(sigax_batch*, float ms[5], uint32_t* n_sub);
 

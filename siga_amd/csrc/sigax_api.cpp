@@ -47,7 +47,7 @@ static int ensure(DevBuf* b, size_t bytes) {
   return SIGAX_OK;
 }
 
-enum { EV_START = 0, EV_FX_DONE, EV_ORDER, EV_EDGES, EV_ORD0, EV_ORD1, EV_COUNT };
+enum { EV_START = 0, EV_FX_DONE, EV_ORDER, EV_EDGES, EV_ORD0, EV_ORD1, EV_BLOCKS, EV_COUNT };
 // per sub-batch: find begin/end on the find stream, fast begin/end and general end on the filter/extract stream
 enum { SV_F0 = 0, SV_F1, SV_X0, SV_X1, SV_G1, SV_COUNT };
 
@@ -101,6 +101,7 @@ struct sigax_batch {
   sigax_stats last;
   u64 last_total_blocks, last_total_edges;
   bool finished;
+  bool blocks_ordered;  // outb holds the last enqueued run's ordered blocks (order_blocks)
 };
 
 // every device buffer a batch object owns
@@ -144,7 +145,7 @@ extern "C" int sigax_batch_create(sigax_index* ix, uint32_t max_reads, uint64_t 
   b->read_base = b->minov = b->flags = 0;
   b->d_ids = nullptr;
   b->ids_n = 0;
-  b->ran = b->finished = false;
+  b->ran = b->finished = b->blocks_ordered = false;
   b->cap = 0;
   b->cap_floor = 0;
   b->pool_cap = 0;
@@ -528,9 +529,33 @@ static int fx_sub(sigax_batch* b, unsigned i, uint32_t rb, uint32_t re, unsigned
   return SIGAX_OK;
 }
 
-// The short tail (scan, ordered scatter, edge records) runs on its own high-priority stream: queued behind the
+static OrderArgs order_args(sigax_batch* b) {
+  sigax_index* ix = b->ix;
+  OrderArgs oa;
+  oa.fin = (const sigax_block*)b->fin.p;
+  oa.item_base = (const u64*)b->item_base.p;
+  oa.fin_cnt = (const uint32_t*)b->fin_cnt.p;
+  oa.n_items = 2 * (u64)b->n_reads;
+  oa.fin_cap = b->fin_cap;
+  oa.offs2 = (const u64*)b->offs2.p;
+  oa.out = (sigax_block*)b->outb.p;
+  oa.out_cap = b->fin_cap;
+  oa.arena = b->arena.p;
+  oa.cap = b->cap;
+  oa.wide = ix->wide ? 1u : 0u;
+  oa.read_ids = b->d_ids;
+  oa.n_index_reads = (uint32_t)std::min<u64>(ix->n_strings, 0xFFFFFFFFull);
+  oa.bad_ids = nullptr;
+  return oa;
+}
+
+// The short tail (scans, ordered scatter or edge records) runs on its own high-priority stream: queued behind the
 // long kernels of the next batch on an ordinary stream it took ten times its own duration and held up the
 // batch's completion, i.e. the moment the caller can submit this batch object again.
+//   without SIGAX_EDGES: scan of fin_cnt (which also writes block_offs), ordered copy of the blocks: three launches
+//   with SIGAX_EDGES:    scan of fin_cnt, stage, scan of edge_cnt, emit: six launches.  No consumer of the edge records
+//     reads the ordered blocks, so they are not made here: order_blocks() makes them when they are asked for.  The staged
+//     records live in outb's allocation (fin_cap records of 16 bytes in room for fin_cap blocks of 80).
 static int tail(sigax_batch* b, bool edges, hipStream_t st) {
   sigax_index* ix = b->ix;
   const uint32_t n = b->n_reads;
@@ -539,42 +564,29 @@ static int tail(sigax_batch* b, bool edges, hipStream_t st) {
   hipStream_t ts = ix->s_tail;
   HIP_TRY(hipStreamWaitEvent(ts, b->ev[EV_FX_DONE], 0));
 
-  launch_scan((const uint32_t*)b->fin_cnt.p, 2 * (u64)n, (u64*)b->partial.p, (u64*)b->offs2.p, dstat + DS_TOTAL_BLOCKS, ts);
-  launch_pick_read_offsets((const u64*)b->offs2.p, n, (u64*)b->block_offs.p, ts);
-  OrderArgs oa;
-  oa.fin = (const sigax_block*)b->fin.p;
-  oa.item_base = (const u64*)b->item_base.p;
-  oa.fin_cnt = (const uint32_t*)b->fin_cnt.p;
-  oa.n_items = 2 * (u64)n;
-  oa.fin_cap = b->fin_cap;
-  oa.offs2 = (const u64*)b->offs2.p;
-  oa.out = (sigax_block*)b->outb.p;
-  oa.out_cap = b->fin_cap;
-  oa.arena = b->arena.p;
-  oa.cap = b->cap;
-  oa.wide = ix->wide ? 1u : 0u;
-  oa.item_edges = edges ? (uint32_t*)b->edge_cnt.p : nullptr;
-  oa.read_base = b->read_base;
-  oa.read_ids = b->d_ids;
-  oa.n_index_reads = (uint32_t)std::min<u64>(ix->n_strings, 0xFFFFFFFFull);
-  oa.bad_ids = dstat + DS_BAD_IDS;
-  oa.sai = ix->d_sai[0];
-  oa.rsai = ix->d_sai[1];
-  oa.n_sai = ix->n_sai;
-  oa.read_len = ix->d_read_len;
-  oa.name_rank = ix->d_name_rank;
-  launch_order_scatter(oa, ts);
-  HIP_TRY(hipEventRecord(b->ev[EV_ORDER], ts));
-
-  if (edges) {
-    EdgeArgs ea;
-    ea.blocks = (const sigax_block*)b->outb.p;
-    ea.blocks_cap = b->fin_cap;
+  launch_scan((const uint32_t*)b->fin_cnt.p, 2 * (u64)n, (u64*)b->partial.p, (u64*)b->offs2.p, dstat + DS_TOTAL_BLOCKS, ts, (u64*)b->block_offs.p);
+  EdgeArgs ea;
+  if (!edges) {
+    OrderArgs oa = order_args(b);
+    oa.bad_ids = dstat + DS_BAD_IDS;
+    launch_order_scatter(oa, ts);
+  } else {
+    ea.fin = (const sigax_block*)b->fin.p;
+    ea.item_base = (const u64*)b->item_base.p;
+    ea.fin_cap = b->fin_cap;
+    ea.arena = b->arena.p;
+    ea.cap = b->cap;
+    ea.wide = ix->wide ? 1u : 0u;
     ea.offs2 = (const u64*)b->offs2.p;
     ea.fin_cnt = (const uint32_t*)b->fin_cnt.p;
     ea.n_items = 2 * (u64)n;
+    ea.stage = b->outb.p;
+    ea.stage_cap = b->fin_cap;
+    ea.item_edges = (uint32_t*)b->edge_cnt.p;
     ea.read_base = b->read_base;
     ea.read_ids = b->d_ids;
+    ea.n_index_reads = (uint32_t)std::min<u64>(ix->n_strings, 0xFFFFFFFFull);
+    ea.bad_ids = dstat + DS_BAD_IDS;
     ea.sai = ix->d_sai[0];
     ea.rsai = ix->d_sai[1];
     ea.n_sai = ix->n_sai;
@@ -583,8 +595,14 @@ static int tail(sigax_batch* b, bool edges, hipStream_t st) {
     ea.edge_offs = (const u64*)b->edge_offs.p;
     ea.edges = (sigax_edge*)b->edges.p;
     ea.edge_cap = b->edge_cap;
+    launch_edges_stage(ea, ts);
+  }
+  b->blocks_ordered = !edges;
+  HIP_TRY(hipEventRecord(b->ev[EV_ORDER], ts));
+
+  if (edges) {
     launch_scan((const uint32_t*)b->edge_cnt.p, 2 * (u64)n, (u64*)b->partial.p, (u64*)b->edge_offs.p, dstat + DS_TOTAL_EDGES, ts);
-    launch_edges_fill(ea, ts);
+    launch_edges_emit(ea, ts);
   }
   HIP_TRY(hipEventRecord(b->ev[EV_EDGES], ts));
   HIP_TRY(hipStreamWaitEvent(st, b->ev[EV_EDGES], 0));
@@ -592,10 +610,29 @@ static int tail(sigax_batch* b, bool edges, hipStream_t st) {
   return SIGAX_OK;
 }
 
+// The ordered blocks of a finished run with SIGAX_EDGES, made when they are first asked for: fin, item_base, offs2 and the
+// candidate arena stay as the run left them until the batch's next run.  The copy goes to the tail stream under the index's
+// enqueue mutex, like every launch sequence on the shared streams, and is waited for.
+static int order_blocks(sigax_batch* b) {
+  if (b->blocks_ordered) return SIGAX_OK;
+  sigax_index* ix = b->ix;
+  HIP_TRY(hipSetDevice(ix->device));
+  {
+    std::lock_guard<std::mutex> lock(*ix->enqueue_mu);
+    launch_order_scatter(order_args(b), ix->s_tail);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev[EV_BLOCKS], ix->s_tail));
+  }
+  HIP_TRY(hipEventSynchronize(b->ev[EV_BLOCKS]));
+  b->blocks_ordered = true;
+  return SIGAX_OK;
+}
+
 static int enqueue(sigax_batch* b, hipStream_t st) {
   sigax_index* ix = b->ix;
   if (ix->fwd_only) return sigax_fail(SIGAX_E_STATE, "the index was opened without its reverse strand: overlap runs need <prefix>.rbwt too");
   std::lock_guard<std::mutex> lock(*ix->enqueue_mu);  // one batch's launch sequence at a time on the shared streams
+  b->blocks_ordered = false;  // outb is about to be rewritten (tail)
   publish_tables(ix);
   publish_deep(ix);
   // a whole pass over the indexed reads has been asked for before this run: the index is being reused
@@ -780,7 +817,11 @@ extern "C" int sigax_batch_finish(sigax_batch* b, void* stream, sigax_stats* sta
 extern "C" int sigax_batch_device_outputs(sigax_batch* b, const sigax_block** d_blocks, const uint64_t** d_block_offs,
                                           const uint8_t** d_substring, const sigax_edge** d_edges) {
   if (!b || !b->finished) return sigax_fail(SIGAX_E_STATE, "batch not finished");
-  if (d_blocks) *d_blocks = (const sigax_block*)b->outb.p;
+  if (d_blocks) {
+    int rc = order_blocks(b);
+    if (rc != SIGAX_OK) return rc;
+    *d_blocks = (const sigax_block*)b->outb.p;
+  }
   if (d_block_offs) *d_block_offs = (const uint64_t*)b->block_offs.p;
   if (d_substring) *d_substring = (const uint8_t*)b->substring.p;
   if (d_edges) *d_edges = (const sigax_edge*)b->edges.p;
@@ -801,6 +842,8 @@ extern "C" int sigax_batch_download(sigax_batch* b, sigax_result* out) {
   if (!b->finished) return sigax_fail(SIGAX_E_STATE, "batch not finished");
   HIP_TRY(hipSetDevice(b->ix->device));
   memset(out, 0, sizeof(*out));
+  int rc = order_blocks(b);
+  if (rc != SIGAX_OK) return rc;
   uint32_t n = b->n_reads;
   out->n_reads = n;
   out->stats = b->last;

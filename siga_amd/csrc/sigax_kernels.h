@@ -120,8 +120,26 @@ struct OrderArgs {
   unsigned long long out_cap;
   const void* arena;   // candidate records: a block whose `reserved` has bit 63 set carries (chain, slot) there instead
   uint32_t cap, wide;  // of its raw intervals, length and flags, which the scatter then takes from the candidate record
-  // edge records are counted on the way (per item), unless item_edges is NULL
-  uint32_t* item_edges;  // [n_items]
+  // the batch's reads in the index's read table, when they carry ids (see EdgeArgs): an id >= n_index_reads is counted in
+  // *bad_ids unless that is NULL (a run with edge records counts them in its stage pass)
+  const uint32_t* read_ids;
+  uint32_t n_index_reads;
+  unsigned long long* bad_ids;
+};
+
+// the two edge passes (k_edges_stage, k_edges_emit) with the scan of item_edges into edge_offs between them
+struct EdgeArgs {
+  const sigax_block* fin;                // unordered final blocks, as the filter/extract kernels left them
+  const unsigned long long* item_base;   // [n_items] where an item's blocks start in `fin`
+  unsigned long long fin_cap;
+  const void* arena;                     // candidate records (length and flags of the lane-group kernels' blocks)
+  uint32_t cap, wide;
+  const unsigned long long* offs2;       // [n_items+1] ordered index of each (read, side) item's first block
+  const uint32_t* fin_cnt;               // [n_items] its blocks
+  unsigned long long n_items;
+  void* stage;                           // [stage_cap] 16-byte records by ordered block index
+  unsigned long long stage_cap;
+  uint32_t* item_edges;                  // [n_items] records per item (written by the stage pass)
   uint32_t read_base;
   // the batch's reads in the index's read table: read_base + i, or read_ids[i] (a rank's share of a key-range sharding:
   // any subset in any order); an id >= n_index_reads makes no edge and is counted in *bad_ids
@@ -133,22 +151,7 @@ struct OrderArgs {
   unsigned long long n_sai;
   const uint32_t* read_len;
   const uint32_t* name_rank;
-};
-
-struct EdgeArgs {
-  const sigax_block* blocks;             // ordered output
-  unsigned long long blocks_cap;
-  const unsigned long long* offs2;       // [n_items+1] first block of each (read, side) item
-  const uint32_t* fin_cnt;               // [n_items] its blocks
-  unsigned long long n_items;
-  uint32_t read_base;
-  const uint32_t* read_ids;  // as in OrderArgs (items of out-of-range ids have no records: k_order_scatter counted none)
-  const uint32_t* sai;
-  const uint32_t* rsai;
-  unsigned long long n_sai;
-  const uint32_t* read_len;
-  const uint32_t* name_rank;
-  const unsigned long long* edge_offs;   // [n_items+1] scan of the per-item counts of k_order_scatter
+  const unsigned long long* edge_offs;   // [n_items+1] scan of item_edges
   sigax_edge* edges;
   unsigned long long edge_cap;
 };
@@ -499,8 +502,10 @@ void launch_filter_extract(const FxArgs& a, bool wide, unsigned grid, hipStream_
 // qhint: items the four queues held last time (per sub-batch; ~0 = unknown), or NULL
 void launch_filter_extract_fast(const FxArgs& a, bool wide, unsigned grid32, unsigned grid64, const unsigned long long* qhint, hipStream_t st);
 unsigned long long fast_pool_entries_per_wave();
+// offs[0..n] = exclusive scan of cnt[0..n), *total_out = offs[n]; partial: scan_partials_needed(n) u64 of scratch.
+// even_out (n even), or NULL: even_out[i] = offs[2i] for i <= n / 2
 void launch_scan(const uint32_t* cnt, unsigned long long n, unsigned long long* partial, unsigned long long* offs,
-                 unsigned long long* total_out, hipStream_t st);
+                 unsigned long long* total_out, hipStream_t st, unsigned long long* even_out = nullptr);
 unsigned long long scan_partials_needed(unsigned long long n);
 // Two-step table of one strand (fm_layout.h): gran2 = (n/64+1) x 32 u32; cnt = 20 x (n/64+1) u32, offs = (n/64+2) u64,
 // partial = scan_partials_needed(n/64+1) u64, total = 1 u64 of scratch.
@@ -521,9 +526,8 @@ void launch_xmap(const uint32_t* sai_y, const uint32_t* sai_x, uint32_t* isai_tm
 void launch_order_scatter(const OrderArgs& a, hipStream_t st);
 unsigned long long fast_fin_chunk();
 unsigned long long cand_bytes(bool wide);
-void launch_pick_read_offsets(const unsigned long long* offs2, unsigned long long n_reads, unsigned long long* block_offs,
-                              hipStream_t st);
-void launch_edges_fill(const EdgeArgs& a, hipStream_t st);
+void launch_edges_stage(const EdgeArgs& a, hipStream_t st);
+void launch_edges_emit(const EdgeArgs& a, hipStream_t st);
 // sigax_index_build.hip: locality order of a batch's reads (a permutation inside each of the nsub slot ranges bounds[0..nsub]),
 // queued on `st` without a host wait.  keys = n u32 of scratch, vals = n u32 = the order once the stream gets there
 // (*result = vals), tmp = sigax_order_reads_tmp_bytes(nsub) bytes for the class counters.

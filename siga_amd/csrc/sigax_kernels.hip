@@ -3374,27 +3374,55 @@ struct GFx {
 // the half's slots, output beyond its share) are queued for the next launch (launch_filter_extract_fast), the last of
 // which queues what it cannot finish for the general kernel.
 // Which (read, side) items of the sub-batch have more blocks than a 32-lane group holds?  They skip the 32-lane launches:
-// queued here for the 64-lane one, one atomic per wave of 64 items.  Same count as GFx::body(): the find's blocks plus the
-// containment copies of the list's two chains.
+// queued here for the 64-lane one.  Same count as GFx::body(): the find's blocks plus the containment copies of the list's
+// two chains.  A fixed grid of workgroups loops over the range, collects its wide items in LDS and appends them with one
+// atomic per flush: one atomic per wave that holds a wide item -- about every second wave at 30x -- serialised on the
+// queue's counter at 6-16 ns each, and this launch is the first link of every filter/extract chain.  The queue's order
+// is whatever the flushes make it; no result depends on it.
+#define FX_ROUTE_BUF 1024
+#define FX_ROUTE_GRID 512
 __global__ __launch_bounds__(256) void k_fx_route(FxArgs A) {
+  __shared__ u32 buf[FX_ROUTE_BUF];
+  __shared__ u32 nbuf;
+  __shared__ u64 qbase;
   const u64 first = 2ull * A.read_begin, last = 2ull * A.read_end;
-  const u64 item = first + (u64)blockIdx.x * 256 + threadIdx.x;
-  bool wide = false;
-  if (item < last) {
-    const u32 r = (u32)(item >> 1), sd = (u32)(item & 1);
-    const uint4 c4 = reinterpret_cast<const uint4*>(A.chain_cnt)[r];
-    const u32 nA = (sd == 0 ? c4.x : c4.y) & SIGAX_CC_COUNT_MASK, nB = (sd == 0 ? c4.w : c4.z) & SIGAX_CC_COUNT_MASK;
-    const u32 nc = ((c4.x & SIGAX_CC_CONTAIN) ? 1u : 0u) + ((c4.y & SIGAX_CC_CONTAIN) ? 1u : 0u) + ((c4.z & SIGAX_CC_CONTAIN) ? 1u : 0u) +
-                   ((c4.w & SIGAX_CC_CONTAIN) ? 1u : 0u);
-    wide = nA + nB + nc > 32u;
-  }
-  const u64 m = __ballot(wide);
-  if (!m) return;
   const u32 lane = threadIdx.x & 63u;
-  u64 b = 0;
-  if (lane == 0) b = atomicAdd(A.q_wide_n, (u64)__popcll(m));
-  b = readlane64(b, 0);
-  if (wide) A.q_wide[b + (u32)__popcll(m & ((1ull << lane) - 1ull))] = (u32)item;
+  if (threadIdx.x == 0) nbuf = 0;
+  __syncthreads();
+  auto flush = [&]() {  // called by the whole workgroup, behind a barrier
+    const u32 n = nbuf;
+    if (n == 0) return;
+    if (threadIdx.x == 0) qbase = atomicAdd(A.q_wide_n, (u64)n);
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < n; i += 256) A.q_wide[qbase + i] = buf[i];
+    __syncthreads();
+    if (threadIdx.x == 0) nbuf = 0;
+    __syncthreads();
+  };
+  for (u64 t0 = first + (u64)blockIdx.x * 256; t0 < last; t0 += (u64)gridDim.x * 256) {
+    const u64 item = t0 + threadIdx.x;
+    bool wide = false;
+    if (item < last) {
+      const u32 r = (u32)(item >> 1), sd = (u32)(item & 1);
+      const uint4 c4 = reinterpret_cast<const uint4*>(A.chain_cnt)[r];
+      const u32 nA = (sd == 0 ? c4.x : c4.y) & SIGAX_CC_COUNT_MASK, nB = (sd == 0 ? c4.w : c4.z) & SIGAX_CC_COUNT_MASK;
+      const u32 nc = ((c4.x & SIGAX_CC_CONTAIN) ? 1u : 0u) + ((c4.y & SIGAX_CC_CONTAIN) ? 1u : 0u) + ((c4.z & SIGAX_CC_CONTAIN) ? 1u : 0u) +
+                     ((c4.w & SIGAX_CC_CONTAIN) ? 1u : 0u);
+      wide = nA + nB + nc > 32u;
+    }
+    const u64 m = __ballot(wide);
+    if (m) {
+      u32 b = 0;
+      if (lane == 0) b = atomicAdd(&nbuf, (u32)__popcll(m));  // (on LDS)
+      b = (u32)readlane64((u64)b, 0);
+      if (wide) buf[b + (u32)__popcll(m & ((1ull << lane) - 1ull))] = (u32)item;
+    }
+    __syncthreads();
+    const u32 held = nbuf;
+    __syncthreads();  // every wave has read the count before any wave adds the next tile's items to it
+    if (held > FX_ROUTE_BUF - 256) flush();  // room for one more tile of 256 items
+  }
+  flush();
 }
 
 #ifndef SIGAX_FX_LEAN_WAVES
@@ -3893,7 +3921,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LMAX <= 512
 }
 
 // -------------------------------------------------------------------------------------------------------
-// exclusive scan of u32 counts into u64 offsets (three small kernels), ordered scatter of the final blocks
+// exclusive scan of u32 counts into u64 offsets (two small kernels), ordered scatter of the final blocks
 // -------------------------------------------------------------------------------------------------------
 #define SCAN_ITEMS 2048  // per workgroup of 256 threads
 
@@ -3925,20 +3953,14 @@ __global__ __launch_bounds__(256) void k_scan_partials(const u32* cnt, u64 n, u6
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void k_scan_top(u64* partial, u64 nparts, u64* total_out) {
-  u64 carry = 0;
-  for (u64 base = 0; base < nparts; base += 256) {
-    u64 i = base + threadIdx.x;
-    u64 v = i < nparts ? partial[i] : 0;
-    u64 tot;
-    u64 ex = block_exclusive_scan(v, &tot);
-    if (i < nparts) partial[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ __launch_bounds__(256) void k_scan_apply(const u32* cnt, u64 n, const u64* partial, u64* offs) {
+// Each workgroup sums the totals of the workgroups before it itself (at most a few thousand u64 values, from L2) instead
+// of waiting for a one-workgroup launch that scanned them.  even_out (or NULL): even_out[i] = offs[2i], i <= n / 2 -- the
+// per-read offsets of a per-(read, side) scan (n even).
+__global__ __launch_bounds__(256) void k_scan_apply(const u32* cnt, u64 n, const u64* partial, u64* offs, u64* total_out, u64* even_out) {
+  u64 before = 0;
+  for (u64 i = threadIdx.x; i < blockIdx.x; i += 256) before += partial[i];
+  u64 carry;
+  block_exclusive_scan(before, &carry);
   u64 base = (u64)blockIdx.x * SCAN_ITEMS + (u64)threadIdx.x * 8;
   u64 v[8], s = 0;
   for (int k = 0; k < 8; ++k) {
@@ -3946,18 +3968,19 @@ __global__ __launch_bounds__(256) void k_scan_apply(const u32* cnt, u64 n, const
     s += v[k];
   }
   u64 tot;
-  u64 ex = block_exclusive_scan(s, &tot) + partial[blockIdx.x];
+  u64 ex = block_exclusive_scan(s, &tot) + carry;
   for (int k = 0; k < 8; ++k) {
-    if (base + k < n) offs[base + k] = ex;
+    if (base + k < n) {
+      offs[base + k] = ex;
+      if (even_out != nullptr && !(k & 1)) even_out[(base + k) >> 1] = ex;  // base is a multiple of 8
+    }
     ex += v[k];
   }
-  if (base <= n && n < base + 8) offs[n] = ex;  // the thread owning position n writes the grand total
-}
-
-// block_offs[r] = offs2[2r]: per-read offsets from the per-(read, side) scan
-__global__ __launch_bounds__(256) void k_pick_read_offsets(const u64* offs2, u64 n_reads, u64* block_offs) {
-  u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (i <= n_reads) block_offs[i] = offs2[2 * i];
+  if (base <= n && n < base + 8) {  // the thread owning position n writes the grand total
+    offs[n] = ex;
+    *total_out = ex;
+    if (even_out != nullptr) even_out[n >> 1] = ex;
+  }
 }
 
 // one lane per (read, side) item: copy its blocks from the unordered arena to their place in the ordered output; blocks
@@ -3970,21 +3993,70 @@ __device__ __forceinline__ void order_fill_from_cand(const OrderArgs& A, u64 ite
   v3 = make_ulonglong2((u64)b.r1lo, (u64)b.r1lo + b.sz - 1);
   v4 = make_ulonglong2((u64)b.len | ((u64)b.af << 32), 0ull);
 }
-// Hit2OverlapConverter::convert's test for one (query, target) pair (src/overlap_builder.cpp:358,365)
-__device__ __forceinline__ bool edge_kept(const uint32_t* name_rank, const uint32_t* read_len, u32 q, u32 t, u32 len, u32 af) {
-  u32 nq = name_rank[q], nt = name_rank[t];
+// Hit2OverlapConverter::convert's test for one (query, target) pair (src/overlap_builder.cpp:358,365); nq, lq: the query's
+// name rank and length, which an item loads once for all its targets
+__device__ __forceinline__ bool edge_kept(const uint32_t* name_rank, const uint32_t* read_len, u32 nq, u32 lq, u32 t, u32 len, u32 af) {
+  u32 nt = name_rank[t];
   if (nq == nt) return false;                       // query.name != target.name (:358)
-  bool contained = (len == read_len[q]) || (len == read_len[t]);  // Match::isContainment (coord.h:150-152)
+  bool contained = (len == lq) || (len == read_len[t]);  // Match::isContainment (coord.h:150-152)
   if (nq < nt || (contained && (af & 1u))) return false;              // dedup rule (:365)
   return true;
 }
-// While a block is on its way to its place, its edge records are counted (the block and its .sai range are in registers;
-// the item knows its read): the item's total goes to item_edges, whose scan gives k_edges_fill the item's place in the
-// edge list.  Round 2 counted per block in a pass of its own that found each block's read by binary search.
+// The ordered copy: what a run without edge records ends with, and what a run with them does only when somebody asks for
+// its blocks (sigax_batch_download, sigax_batch_device_outputs with d_blocks).  bad_ids (or NULL): out-of-range read ids
+// are counted here in a run without edge records.
 __global__ __launch_bounds__(256) void k_order_scatter(OrderArgs A) {
   u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
   if (w >= A.n_items) return;
   u32 cnt = A.fin_cnt[w];
+  if (A.read_ids != nullptr && A.bad_ids != nullptr && A.read_ids[w >> 1] >= A.n_index_reads) atomicAdd(A.bad_ids, 1ull);
+  if (!cnt) return;
+  u64 srcb = A.item_base[w], dstb = A.offs2[w];
+  for (u32 i = 0; i < cnt; ++i) {
+    if (srcb + i >= A.fin_cap || dstb + i >= A.out_cap) break;  // only after an overflow, whose results the host discards
+    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + srcb + i);
+    ulonglong2* d = reinterpret_cast<ulonglong2*>(A.out + dstb + i);
+    ulonglong2 v0 = s[0], v1 = s[1], v4 = s[4];
+    ulonglong2 v2, v3;
+    if (v4.y >> 63) {
+      if (A.wide) order_fill_from_cand<true>(A, w, (u32)v4.y, v2, v3, v4);
+      else order_fill_from_cand<false>(A, w, (u32)v4.y, v2, v3, v4);
+    } else {
+      v2 = s[2]; v3 = s[3];
+    }
+    d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4;
+  }
+}
+
+// -------------------------------------------------------------------------------------------------------
+// edges: Hit2OverlapConverter::convert (overlap_builder.cpp:345-375) in two passes with the scan of the per-item counts
+// between them, one lane per (read, side) item: its blocks are consecutive in the ordered output, its records consecutive
+// in the edge list (hits order = the ED order at -t 1).  The ordered blocks themselves are not needed for it.
+//   stage: reads each block where filter/extract left it (fin + item_base) -- its capped0 range, and length and flags from
+//          the block or, for a lane-group block, from the half of its candidate record that holds them --, tests the
+//          block's one target and leaves a 16-byte record at the block's ORDERED index (neighbouring items write
+//          neighbouring records): the final sigax_edge, or EDGE_ST_DROPPED; a block whose range holds several targets
+//          (duplicates, repeats, exhaustive mode) is counted by walking it and left as EDGE_ST_WALK
+//   emit:  copies the staged records that were kept to their places and walks the EDGE_ST_WALK blocks again, from fin
+// `af` of a record holds the three AlignFlags bits, so the two markers are no record's af.
+// -------------------------------------------------------------------------------------------------------
+static_assert(sizeof(sigax_edge) == 16, "a staged record is a sigax_edge");
+#define EDGE_ST_DROPPED 0xFFFFFFFFu
+#define EDGE_ST_WALK 0xFFFFFFFEu
+
+// length | af << 32 of the block at fin[at]; v4 = its last 16 bytes
+__device__ __forceinline__ u64 edge_len_af(const EdgeArgs& A, u64 item, const ulonglong2& v4) {
+  if (!(v4.y >> 63)) return v4.x;
+  const u64 rec = (item >> 1) * 4 * A.cap + ((u32)v4.y & 0x3FFFFFFFu);
+  if (A.wide) return reinterpret_cast<const ulonglong2*>(reinterpret_cast<const Cand<true>*>(A.arena) + rec)[3].x;
+  const uint4 h = reinterpret_cast<const uint4*>(reinterpret_cast<const Cand<false>*>(A.arena) + rec)[1];
+  return (u64)h.z | ((u64)h.w << 32);
+}
+
+__global__ __launch_bounds__(256) void k_edges_stage(EdgeArgs A) {
+  const u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (w >= A.n_items) return;
+  const u32 cnt = A.fin_cnt[w];
   u32 kept = 0;
   u32 q = A.read_base + (u32)(w >> 1);
   bool known = true;  // the read is one of the index's
@@ -3993,59 +4065,71 @@ __global__ __launch_bounds__(256) void k_order_scatter(OrderArgs A) {
     known = q < A.n_index_reads;
     if (!known) atomicAdd(A.bad_ids, 1ull);
   }
-  if (cnt) {
-    u64 srcb = A.item_base[w], dstb = A.offs2[w];
+  if (cnt && known) {
+    const u64 srcb = A.item_base[w], dstb = A.offs2[w];
+    const u32 nq = A.name_rank[q], lq = A.read_len[q];
+    uint4* stage = reinterpret_cast<uint4*>(A.stage);
     for (u32 i = 0; i < cnt; ++i) {
-      if (srcb + i >= A.fin_cap || dstb + i >= A.out_cap) break;  // only after an overflow, whose results the host discards
+      if (srcb + i >= A.fin_cap || dstb + i >= A.stage_cap) break;  // only after an overflow, whose results the host discards
       const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + srcb + i);
-      ulonglong2* d = reinterpret_cast<ulonglong2*>(A.out + dstb + i);
-      ulonglong2 v0 = s[0], v1 = s[1], v4 = s[4];
-      ulonglong2 v2, v3;
-      if (v4.y >> 63) {
-        if (A.wide) order_fill_from_cand<true>(A, w, (u32)v4.y, v2, v3, v4);
-        else order_fill_from_cand<false>(A, w, (u32)v4.y, v2, v3, v4);
-      } else {
-        v2 = s[2]; v3 = s[3];
-      }
-      d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4;
-      if (A.item_edges != nullptr && known) {
-        const u32 len = (u32)v4.x, af = (u32)(v4.x >> 32);
-        const u32* sa = (af & 2u) ? A.rsai : A.sai;
+      const ulonglong2 v0 = s[0], v4 = s[4];
+      const u64 la = edge_len_af(A, w, v4);
+      const u32 len = (u32)la, af = (u32)(la >> 32);
+      const u32* sa = (af & 2u) ? A.rsai : A.sai;
+      uint4 rec = make_uint4(q, 0u, len, EDGE_ST_DROPPED);
+      if (v0.x == v0.y) {
+        if (v0.x < A.n_sai) {
+          rec.y = sa[v0.x];
+          if (edge_kept(A.name_rank, A.read_len, nq, lq, rec.y, len, af)) {
+            rec.w = af;
+            ++kept;
+          }
+        }
+      } else if (v0.x < v0.y) {
+        rec.w = EDGE_ST_WALK;
         for (u64 j = v0.x; j <= v0.y && j < A.n_sai; ++j)
-          if (edge_kept(A.name_rank, A.read_len, q, sa[j], len, af)) ++kept;
+          if (edge_kept(A.name_rank, A.read_len, nq, lq, sa[j], len, af)) ++kept;
       }
+      stage[dstb + i] = rec;
     }
   }
-  if (A.item_edges != nullptr) A.item_edges[w] = kept;
+  A.item_edges[w] = kept;
 }
 
-// -------------------------------------------------------------------------------------------------------
-// edges: Hit2OverlapConverter::convert (overlap_builder.cpp:345-375), one lane per (read, side) item: its blocks are
-// consecutive in the ordered output, its records consecutive in the edge list (hits order = the ED order at -t 1)
-// -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_edges_fill(EdgeArgs A) {
+__global__ __launch_bounds__(256) void k_edges_emit(EdgeArgs A) {
   const u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
   if (w >= A.n_items) return;
   const u32 cnt = A.fin_cnt[w];
   if (!cnt) return;
   u64 e = A.edge_offs[w];
-  if (A.edge_offs[w + 1] == e) return;  // no record from this item (most items: the self-containment blocks)
+  const u64 e_end = A.edge_offs[w + 1];
+  if (e_end == e) return;  // no record from this item (most items: the self-containment blocks)
   const u64 first = A.offs2[w];
-  const u32 q = A.read_ids != nullptr ? A.read_ids[w >> 1] : A.read_base + (u32)(w >> 1);
-  for (u32 i = 0; i < cnt; ++i) {
-    if (first + i >= A.blocks_cap) return;  // only after an overflow, whose results the host discards
-    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.blocks + first + i);
+  const uint4* stage = reinterpret_cast<const uint4*>(A.stage);
+  uint4* edges = reinterpret_cast<uint4*>(A.edges);  // sigax_edge = (query, target, length, af)
+  for (u32 i = 0; i < cnt && e < e_end; ++i) {
+    if (first + i >= A.stage_cap) return;  // only after an overflow, whose results the host discards
+    const uint4 rec = stage[first + i];
+    if (rec.w == EDGE_ST_DROPPED) continue;
+    if (rec.w != EDGE_ST_WALK) {
+      if (e < A.edge_cap) edges[e] = rec;
+      ++e;
+      continue;
+    }
+    const u64 at = A.item_base[w] + i;
+    if (at >= A.fin_cap) return;
+    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + at);
     const ulonglong2 v0 = s[0], v4 = s[4];
-    const u32 len = (u32)v4.x, af = (u32)(v4.x >> 32);
+    const u64 la = edge_len_af(A, w, v4);
+    const u32 len = (u32)la, af = (u32)(la >> 32);
     const u32* sa = (af & 2u) ? A.rsai : A.sai;
+    // (not rec.x: after an overflow the staged record may be a stale one)
+    const u32 q = A.read_ids != nullptr ? A.read_ids[w >> 1] : A.read_base + (u32)(w >> 1);
+    const u32 nq = A.name_rank[q], lq = A.read_len[q];
     for (u64 j = v0.x; j <= v0.y && j < A.n_sai; ++j) {
       const u32 t = sa[j];
-      if (edge_kept(A.name_rank, A.read_len, q, t, len, af)) {
-        if (e < A.edge_cap) {
-          sigax_edge rec;
-          rec.query = q; rec.target = t; rec.length = len; rec.af = af;
-          A.edges[e] = rec;
-        }
+      if (edge_kept(A.name_rank, A.read_len, nq, lq, t, len, af)) {
+        if (e < A.edge_cap) edges[e] = make_uint4(q, t, len, af);
         ++e;
       }
     }
@@ -4202,7 +4286,7 @@ static void launch_fx_stages(const FxArgs& a, unsigned grid32, unsigned grid64, 
     FxArgs x = a;
     x.q_wide = q[1];
     x.q_wide_n = qn[1];
-    hipLaunchKernelGGL(k_fx_route, dim3(nblk(2ull * (a.read_end - a.read_begin), 256)), dim3(256), 0, st, x);
+    hipLaunchKernelGGL(k_fx_route, dim3(std::min(nblk(2ull * (a.read_end - a.read_begin), 256), (unsigned)FX_ROUTE_GRID)), dim3(256), 0, st, x);
   };
   if (!lean) {
     stage(k_filter_extract_fast<WIDE, 32, 0>, grid32, -1, 2, -1);
@@ -4256,12 +4340,11 @@ void launch_filter_extract(const FxArgs& a, bool wide, unsigned grid, hipStream_
   else hipLaunchKernelGGL(k_filter_extract<false>, dim3(grid), dim3(256), 0, st, a);
 }
 
-void launch_scan(const u32* cnt, u64 n, u64* partial, u64* offs, u64* total_out, hipStream_t st) {
-  // offs has n+1 entries; offs[n] = total
+void launch_scan(const u32* cnt, u64 n, u64* partial, u64* offs, u64* total_out, hipStream_t st, u64* even_out) {
+  // offs has n+1 entries; offs[n] = total.  Two launches: per-workgroup totals, then the scan itself (k_scan_apply)
   unsigned g = nblk(n + 1, SCAN_ITEMS);
   hipLaunchKernelGGL(k_scan_partials, dim3(g), dim3(256), 0, st, cnt, n, partial);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, st, partial, (u64)g, total_out);
-  hipLaunchKernelGGL(k_scan_apply, dim3(g), dim3(256), 0, st, cnt, n, (const u64*)partial, offs);
+  hipLaunchKernelGGL(k_scan_apply, dim3(g), dim3(256), 0, st, cnt, n, (const u64*)partial, offs, total_out, even_out);
 }
 
 void launch_build2(const FmStrand& s, bool wide, u32* gran2, u64* super2, u32* cnt, u64* offs, u64* partial, u64* total, hipStream_t st) {
@@ -4294,16 +4377,17 @@ void launch_xmap(const u32* sai_y, const u32* sai_x, u32* isai_tmp, const u32* s
 
 u64 scan_partials_needed(u64 n) { return (n + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1; }
 
-void launch_pick_read_offsets(const u64* offs2, u64 n_reads, u64* block_offs, hipStream_t st) {
-  hipLaunchKernelGGL(k_pick_read_offsets, dim3(nblk(n_reads + 1, 256)), dim3(256), 0, st, offs2, n_reads, block_offs);
-}
-
 void launch_order_scatter(const OrderArgs& a, hipStream_t st) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(k_order_scatter, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
 }
 
-void launch_edges_fill(const EdgeArgs& a, hipStream_t st) {
+void launch_edges_stage(const EdgeArgs& a, hipStream_t st) {
   if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_edges_fill, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_edges_stage, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
+}
+
+void launch_edges_emit(const EdgeArgs& a, hipStream_t st) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(k_edges_emit, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
 }
