@@ -825,6 +825,115 @@ int  sigax_scaffold_host(int device, uint64_t n_unitigs, const uint64_t* seq_off
                          const sigax_pair_link* links, uint64_t n_links, const uint64_t* status24, const sigax_scaffold_opts* opts,
                          uint64_t* n_scaffolds, uint64_t** sc_offs, uint64_t** sc_lay_offs, uint32_t** sc_flags,
                          sigax_placement** sc_layout, char** sseqs, uint64_t status16[16]);
+/* ---- `siga unitig --scaffold --gapfill`: scaffold gaps closed by k-mer walks over the reads' index (csrc/sigax_gapfill.hip) -----
+ * Every join of a scaffold is a run of N whose length is an estimate from insert sizes.  The FM-index of the reads knows every
+ * k-mer of the sample, the ones that bridge a unitig end included: unitigs end where the overlap graph forks or runs dry, and a
+ * walk over k-mers shorter than the minimum overlap often does neither there.  The reference has no gap filler (the paired
+ * visitor that would walk between mates depends on hash-map order, see the `--pairs` block), so the rules below are this
+ * library's own.  DESIGN.md 9k; the serial restatement the tests hold this against is tests/gapfill_cases.py::expected_gapfill.
+ *
+ * Input: an open index (the forward strand is enough, and it is the only one read: no result depends on which tables the
+ * index holds); seq_offs and useqs of a unitig call, nu unitigs; the result of the scaffold call that followed: S, sc_lay_offs
+ * and sc_layout (sc_flags is not read); sigax_gapfill_opts {flags = 0, k, min_count, slack, max_fill, reserved = 0}.
+ * Preconditions: 8 <= k <= 128, min_count >= 1, slack < 2^31, max_fill < 2^31; anything else is SIGAX_E_ARG.
+ *
+ * count(w) = occ(w) + occ(revcomp(w)) on the forward index: exactly sigax_match_* with SIGAX_RC, so a reverse-palindromic w
+ * counts twice.  Bytes outside upper-case ACGT rank as '$', so no k-mer reaches across a read's end.
+ *
+ * Placements.  P = sc_lay_offs[S] (0 when S = 0).  Placement p < P belongs to scaffold s(p), the largest s < S with
+ * sc_lay_offs[s] <= p as a bisection finds it (lo = 0, hi = S; while hi - lo > 1: mid = (lo + hi) / 2, lo = mid if
+ * sc_lay_offs[mid] <= p, else hi = mid; at most 32 steps).  Its unitig is u = sc_layout[p].read.  The placement is BAD iff
+ * u >= nu, seq_offs[u+1] < seq_offs[u] or seq_offs[u+1] > useqs_bytes (no scaffold call makes one); bases(p) = seq_offs[u+1] -
+ * seq_offs[u], and 0 for a bad placement.  All arithmetic is modulo 2^64.
+ *
+ * Gaps.  A gap is a pair of consecutive placements (p, p+1), p+1 < P, with s(p) == s(p+1).  The closing join of a circular
+ * scaffold is no pair of placements: it is not a gap and stays as it is.  L = the bases of placement p's unitig as placed:
+ * reverse-complemented with SIGAX_PLACED_REV (A<->T, C<->G), other bytes as they are; R = the same for p+1.  G = offset[p+1] -
+ * offset[p] - bases(p), in u64.  Gaps are numbered in placement order, which is scaffold order, then placement order.
+ *
+ * Class of a gap: the first of these that applies.
+ *   MALFORMED     placement p or p+1 is bad.
+ *   SHORT         bases(L) < k or bases(R) < k.
+ *   NON_ACGT      the last k bytes of L or the first k bytes of R hold a byte outside ACGT.
+ *   FAR           G > max_fill.
+ *   NO_ROOM       the walk scratch is too small.  A gap that comes this far needs G + slack bytes of it; its bytes begin where
+ *                 the bytes of the gaps before it that came this far end, and it is NO_ROOM iff its own end lies beyond
+ *                 max_walk_bases.  It stays as laid.
+ *   otherwise     the outcome of the walks below.
+ *
+ * Walk(src, dst, limit).  Start with w = src.  For t = 1 .. limit: cand = {b in A, C, G, T : count(w[1:] + b) >= min_count}.
+ * |cand| = 0 gives DEAD_END; |cand| >= 2 gives BRANCH; otherwise append b, set w = w[1:] + b, and if w == dst the walk has
+ * REACHED at t and stops.  No reach after `limit` steps gives TOO_LONG.  limit = k + G + slack.
+ * A walk that REACHED at step t: t < k gives OVERLAP (the unitigs overlap by k - t bases by this walk).  Otherwise f = t - k;
+ * f + slack < G gives OFF_ESTIMATE; otherwise FILLED with the first f appended bases.  f = 0 is a legal fill.
+ * The forward walk is Walk(last k of L, first k of R).  If and only if its outcome is DEAD_END, BRANCH or TOO_LONG the reverse
+ * walk runs: Walk(revcomp(first k of R), revcomp(last k of L)); its fill is reverse-complemented.  The gap is FILLED if either
+ * walk filled it -- forward wins, and the direction is recorded -- otherwise its class is the forward walk's outcome.
+ *
+ * Output: the scaffold tables again, every filled gap's N replaced by its fill and every other gap left as laid: sc_offs'
+ * u64[S + 1], sc_layout' (the placements with their new offsets), sseqs' (N wherever neither a unitig nor a fill lies); sc_lay_offs
+ * and sc_flags do not change and are not rewritten.  With D(p) = the sum of (fill - G) over the filled gaps before placement p:
+ * offset'[p] = offset[p] + D(p) - D(h), h = sc_lay_offs[s(p)] taken as P when above it; scaffold s has offset'[last] + bases(last)
+ * bases over its last placement, 0 without one.  One sigax_gap per gap in gap order: scaffold, left and right (unitig ids), laid
+ * (G, saturated at 2^32 - 1), fill (bases; 0 unless FILLED), cls, fwd and rev (the two walks' outcomes: a class code, or
+ * SIGAX_GAP_NOT_RUN), dir (0 forward, 1 reverse; 0 unless FILLED), offset (where the gap starts in its new scaffold).
+ * status24 = 24 u64, written (not added to): 0 gaps; 1 + c gaps of class c for the eleven SIGAX_GAP_* codes (1 FILLED .. 11
+ * MALFORMED); 12 filled forward, 13 filled in reverse, 14 fill bases, 15 N bases left in gaps, 16 scaffold bases of the new
+ * tables, 17 extension steps made, 18 k-mer lookups made (8 per step), 19 rank-table sectors asked for (a diagnostic: the only
+ * entry that depends on the index's tables), 20 = 1 when status[16] > sseqs_capacity: the bases were not written for lack of
+ * room, 21 = 1 when any gap is NO_ROOM, 22 scaffolds S, 23 = 0.  No other result depends on scheduling or on the tables.
+ *
+ * sigax_gapfill_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the
+ * device.  d_n_unitigs and d_n_scaffolds point at u64 ON THE DEVICE -- entry 0 of the unitig call's and of the scaffold call's
+ * status block -- so the call can be enqueued straight behind sigax_scaffold_device; a count above max_unitigs is taken as
+ * max_unitigs, and sc_lay_offs[S] likewise.  d_seq_offs and d_sc_lay_offs u64[max_unitigs + 1], d_sc_layout
+ * sigax_placement[max_unitigs], d_useqs useqs_bytes bytes: no byte at or beyond them is read.  d_sc_offs u64[max_unitigs + 1],
+ * d_sc_layout_out sigax_placement[max_unitigs], d_gaps sigax_gap[max_unitigs]; entries beyond S, P and the gaps are not
+ * written.  d_sseqs sseqs_capacity bytes, or NULL with capacity 0; the bases are written only if status24[16] <=
+ * sseqs_capacity.  d_work = sigax_gapfill_workspace(max_unitigs, max_walk_bases) bytes (244 per unitig, and the walk
+ * scratch).  d_useqs, d_sseqs, d_sc_layout, d_sc_layout_out, d_gaps and d_work 16-byte aligned, every other buffer 8-byte
+ * aligned; d_sc_layout_out must not overlap d_sc_layout.  A NULL where a buffer is required, a misaligned buffer, a short
+ * workspace, bad options, max_unitigs >= 2^31, max_walk_bases or sseqs_capacity >= 2^43: SIGAX_E_ARG with the argument named
+ * in sigax_last_error().  max_unitigs = 0: SIGAX_OK, status zeros, d_sc_offs[0] = 0 where given.  Whatever the tables hold --
+ * offsets that do not ascend, unitig ids beyond the tables, a layout that claims more bases than useqs has -- nothing outside
+ * the buffers is touched, and every loop has a bound the host knows: a bisection 32 steps, a walk k + max_fill + slack steps of
+ * k symbols, at most two walks per gap. */
+#define SIGAX_GAP_FILLED       0u
+#define SIGAX_GAP_SHORT        1u
+#define SIGAX_GAP_NON_ACGT     2u
+#define SIGAX_GAP_FAR          3u
+#define SIGAX_GAP_NO_ROOM      4u
+#define SIGAX_GAP_DEAD_END     5u
+#define SIGAX_GAP_BRANCH       6u
+#define SIGAX_GAP_TOO_LONG     7u
+#define SIGAX_GAP_OVERLAP      8u
+#define SIGAX_GAP_OFF_ESTIMATE 9u
+#define SIGAX_GAP_MALFORMED    10u
+#define SIGAX_GAP_NOT_RUN      255u   /* sigax_gap.fwd / .rev: the walk was not made */
+#define SIGAX_GAPFILL_AUTO     0xFFFFFFFFFFFFFFFFull  /* sigax_gapfill_host: size the walk scratch from the layout */
+typedef struct sigax_gapfill_opts { uint32_t flags, k, min_count, slack, max_fill, reserved; } sigax_gapfill_opts;
+typedef struct sigax_gap {
+  uint32_t scaffold, left, right, laid;
+  uint32_t fill;
+  uint8_t  cls, fwd, rev, dir;
+  uint64_t offset;
+} sigax_gap; /* 32 bytes */
+int  sigax_gapfill_workspace(uint64_t max_unitigs, uint64_t max_walk_bases, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_gapfill_device(sigax_index*, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_useqs,
+                          uint64_t useqs_bytes, const void* d_n_scaffolds, const void* d_sc_lay_offs, const sigax_placement* d_sc_layout,
+                          const sigax_gapfill_opts* opts, void* d_sc_offs, sigax_placement* d_sc_layout_out, void* d_sseqs,
+                          uint64_t sseqs_capacity, sigax_gap* d_gaps, void* d_status24, void* d_work, uint64_t work_bytes,
+                          uint64_t max_walk_bases, void* stream);
+/* Host buffers, synchronous.  seq_offs u64[n_unitigs + 1], useqs seq_offs[n_unitigs] bytes, sc_lay_offs u64[n_scaffolds + 1],
+ * sc_layout sigax_placement[sc_lay_offs[n_scaffolds]]; n_scaffolds or sc_lay_offs[n_scaffolds] above n_unitigs: SIGAX_E_ARG.
+ * max_walk_bases = SIGAX_GAPFILL_AUTO sizes the walk scratch from the layout, so that no gap is NO_ROOM.  It runs the walks
+ * and the layout, reads the total, then writes the bases into a buffer of exactly that size: status24[20] is 0.  *sc_offs
+ * u64[n_scaffolds + 1], *sc_layout_out sigax_placement[placements], *sseqs status24[16] bytes (pass sseqs = NULL for the tables
+ * alone), *gaps sigax_gap[*n_gaps]; all malloc'd, release with sigax_free. */
+int  sigax_gapfill_host(sigax_index*, uint64_t n_unitigs, const uint64_t* seq_offs, const char* useqs, uint64_t n_scaffolds,
+                        const uint64_t* sc_lay_offs, const sigax_placement* sc_layout, const sigax_gapfill_opts* opts,
+                        uint64_t max_walk_bases, uint64_t** sc_offs, sigax_placement** sc_layout_out, char** sseqs, sigax_gap** gaps,
+                        uint64_t* n_gaps, uint64_t status24[24]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

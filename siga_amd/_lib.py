@@ -46,6 +46,17 @@ SIGAX_SCAFFOLD_INSERT_FROM_STATUS = 1
 # the entries of sigax_scaffold_*'s status16, by name
 SCAFFOLD_STATUS = ("scaffolds", "bases", "links", "malformed", "self", "circular", "short", "thin", "weak", "ambiguous", "joins", "cycles",
                    "gap_bases", "below_min_gap", "clamped_at_max_gap", "bases_not_written")
+# sigax_gapfill_*: the classes of a gap (sigax_gap.cls, .fwd, .rev), the record and the entries of status24, by name
+GAP_CLASSES = ("FILLED", "SHORT", "NON_ACGT", "FAR", "NO_ROOM", "DEAD_END", "BRANCH", "TOO_LONG", "OVERLAP", "OFF_ESTIMATE", "MALFORMED")
+SIGAX_GAP_NOT_RUN = 255
+SIGAX_GAPFILL_AUTO = 0xFFFFFFFFFFFFFFFF
+GAP_DTYPE = np.dtype([("scaffold", "<u4"), ("left", "<u4"), ("right", "<u4"), ("laid", "<u4"), ("fill", "<u4"), ("cls", "u1"), ("fwd", "u1"),
+                      ("rev", "u1"), ("dir", "u1"), ("offset", "<u8")])  # sigax_gap
+assert GAP_DTYPE.itemsize == 32
+GAPFILL_STATUS = ("gaps",) + tuple(c.lower() for c in GAP_CLASSES) + (
+    "filled_forward", "filled_reverse", "fill_bases", "n_bases_left", "bases", "steps", "lookups", "sectors", "bases_not_written",
+    "walk_scratch_too_small", "scaffolds", "reserved")
+assert len(GAPFILL_STATUS) == 24
 
 
 class TrimOpts(C.Structure):  # sigax_trim_opts
@@ -75,6 +86,10 @@ class PairsOpts(C.Structure):  # sigax_pairs_opts
 class ScaffoldOpts(C.Structure):  # sigax_scaffold_opts
     _fields_ = ([(n, C.c_uint32) for n in ("flags", "min_pairs", "link_ratio", "min_unitig_bases")] + [("insert_size", C.c_uint64)] +
                 [(n, C.c_uint32) for n in ("min_gap", "max_gap")])
+
+
+class GapfillOpts(C.Structure):  # sigax_gapfill_opts
+    _fields_ = [(n, C.c_uint32) for n in ("flags", "k", "min_count", "slack", "max_fill", "reserved")]
 
 
 class Stats(C.Structure):
@@ -126,6 +141,7 @@ SYMBOLS = [
     "sigax_unitigs_bubble_workspace", "sigax_unitigs_bubble_device", "sigax_unitigs_bubble_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
+    "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -243,6 +259,9 @@ def lib():
     L.sigax_scaffold_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_scaffold_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, C.POINTER(ScaffoldOpts), vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
     L.sigax_scaffold_host.argtypes = [ci, u64, vp, vp, vp, vp, u64, vp, C.POINTER(ScaffoldOpts), C.POINTER(u64), pvp, pvp, pvp, pvp, pvp, vp]
+    L.sigax_gapfill_workspace.argtypes = [u64, u64, C.POINTER(u64)]
+    L.sigax_gapfill_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, C.POINTER(GapfillOpts), vp, vp, vp, u64, vp, vp, vp, u64, u64, vp]
+    L.sigax_gapfill_host.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(GapfillOpts), u64, pvp, pvp, pvp, pvp, C.POINTER(u64), vp]
     # (not in include/sigax.h: the measurement aid of tools/scaffold_bench.py, sigax_internal.h)
     L.sigax_scaffold_bases_device.argtypes = L.sigax_scaffold_device.argtypes
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)

@@ -475,6 +475,58 @@ enum { SCAF_C_CLOSING_GAPS = 0, SCAF_COUNTERS = 16, SCAF_ANY_CUT = SCAF_COUNTERS
 hipError_t launch_scaffold(const ScaffoldArgs& a, hipStream_t st);
 void launch_scaffold_bases(const ScaffoldArgs& a, hipStream_t st);  // the last phase alone, over what launch_scaffold left
 
+// `siga unitig --scaffold --gapfill` (sigax_gapfill.hip): scaffold gaps closed by k-mer walks on the forward strand.  Everything
+// below `status` is the caller's scratch (sigax_gapfill.cpp lays it out).  n = max_unitigs; nu, S and P are clamped to it.
+struct GapfillArgs {
+  FmStrand fwd;
+  const unsigned long long* n_unitigs;   // on the device
+  const unsigned long long* n_scaffolds; // on the device
+  unsigned long long max_unitigs;
+  const unsigned long long* seq_offs;    // [n + 1]
+  const unsigned char* useqs;            // useqs_bytes bytes: nothing at or beyond them is read
+  unsigned long long useqs_bytes;
+  const unsigned long long* sc_lay_offs; // [n + 1]
+  const sigax_placement* sc_layout;      // [n]
+  uint32_t k, min_count, slack, max_fill;
+  unsigned long long* sc_offs;           // [n + 1], written
+  sigax_placement* sc_layout_out;        // [n], written
+  unsigned char* sseqs;                  // sseqs_capacity bytes or NULL
+  unsigned long long sseqs_capacity;
+  sigax_gap* gaps;                       // [n], written
+  unsigned long long* status;            // 24 u64, written
+  unsigned long long* cnt;               // GAP_WORDS u64, zeroed: the GAP_C_* counters and the walk kernel's chain counter
+  uint32_t* sof;                         // [n]: the scaffold of a placement
+  uint32_t* isgap;                       // [n]: placement p and p + 1 are a gap ...
+  uint32_t* need;                        // [n]: ... the bytes of walk scratch it needs (0: it is not walked)
+  uint32_t* fillc;                       // [n]: its fill when filled, else 0 ...
+  uint32_t* remc;                        // [n]: ... and the N that the fill replaces
+  uint32_t* lenlo;                       // [n]: the new bases of scaffold s, low and ...
+  uint32_t* lenhi;                       // [n]: ... high half
+  unsigned long long* gnum;              // [n + 1]: scans of the six, in that order
+  unsigned long long* soff;
+  unsigned long long* fsum;
+  unsigned long long* rsum;
+  unsigned long long* slo;
+  unsigned long long* shi;
+  unsigned long long* partial;           // scan_partials_needed(n) u64
+  unsigned long long* scan_total;        // 1 u64
+  uint2* gres;                           // [n]: {class | fwd << 8 | rev << 16 | dir << 24, fill}; class GAP_WALK before the walks
+  unsigned long long* gap_g;             // [n]: G
+  unsigned long long* win;               // [16 n]: per placement four windows of four words, 2 bits a base, base i at bit 2 i:
+                                         // the forward walk's start and goal, the reverse walk's start and goal
+  unsigned long long* pdst;              // [n + 1]: where in sseqs placement p's unitig begins; [P] = all bases
+  unsigned long long* psrc;              // [n]: where in useqs it lies | reversed << 63
+  unsigned long long* plen;              // [n]: its bases (0 for a bad placement)
+  unsigned char* walk;                   // max_walk_bases bytes: the bases a walk appends, as appended
+  unsigned long long max_walk_bases;
+};
+// counters 0 .. 10 are the classes; GAP_CHAIN is the persistent kernel's chain counter
+enum { GAP_C_FWD = 11, GAP_C_REV = 12, GAP_C_FILL = 13, GAP_C_NLEFT = 14, GAP_C_STEPS = 15, GAP_C_SECTORS = 16, GAP_C_GAPS = 17, GAP_CHAIN = 24,
+       GAP_WORDS = 32 };
+static const uint32_t GAP_WALK = 0xFFu, GAP_NONE = 0xFEu;  // gres classes before the walks: to be walked, no gap here
+hipError_t launch_gapfill(const GapfillArgs& a, bool wide, int n_cu, hipStream_t st);
+void launch_gapfill_bases(const GapfillArgs& a, hipStream_t st);  // the last phase alone, over what launch_gapfill left
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

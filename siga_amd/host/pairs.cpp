@@ -67,11 +67,18 @@ void append_double(std::string& t, double v) {
   t += buf;
 }
 
+const char* const kGapClasses[11] = {"FILLED", "SHORT", "NON_ACGT", "FAR", "NO_ROOM", "DEAD_END", "BRANCH", "TOO_LONG", "OVERLAP", "OFF_ESTIMATE",
+                                     "MALFORMED"};
+const char* gap_class(uint32_t c) { return c < 11 ? kGapClasses[c] : "NOT_RUN"; }
+
 // sigax_scaffold_host, then ">scaffold-<n> unitigs=<k> gaps=<k - 1>[ circular=<closing gap>]" and the bases per scaffold, and
-// one line "scaffold-<n>\tunitig-<u>\t<+|->\t<offset>\t<gap before>" per placement (0 before a scaffold's first)
+// one line "scaffold-<n>\tunitig-<u>\t<+|->\t<offset>\t<gap before>" per placement (0 before a scaffold's first).  With
+// rq.index the gaps are filled first (sigax_gapfill_host): the bases, the offsets and the gaps before are the new ones, every
+// header ends in " filled=<gaps filled>", and rq.gaps gets one line per gap:
+// "GP\tscaffold-<n>\tunitig-<left>\tunitig-<right>\t<laid>\t<class>\t<forward walk>\t<reverse walk>\t<+|->\t<fill>\t<offset>"
 std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint32_t* uflags, const char* useqs,
                          const sigax_pair_link* links, uint64_t n_links, const uint64_t status24[24], const ScaffoldRequest& rq,
-                         uint64_t status16[16]) {
+                         uint64_t status16[16], uint64_t gap24[24]) {
   if (!rq.haveInsertSize && status24[14] == 0)
     return "no pair of the library's orientation lies inside a unitig: there is no insert size to estimate the gaps from; give --insert-size";
   sigax_scaffold_opts opts;
@@ -89,7 +96,57 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
   if (sigax_scaffold_host(device, n_unitigs, seq_offs, uflags, useqs, links, n_links, status24, &opts, &ns, &sc_offs, &sc_lay, &sc_flags, &lay, &seqs,
                           status16) != SIGAX_OK)
     return std::string("scaffold failed: ") + sigax_last_error();
-  std::string fa, lt;
+  std::string fa, lt, gt;
+  std::vector<uint64_t> filled;
+  if (rq.index) {
+    sigax_gapfill_opts go = {0u, rq.gapKmer, rq.gapMinCount, rq.gapSlack, rq.gapMaxFill, 0u};
+    uint64_t *offs2 = nullptr, ng = 0, st[24];
+    sigax_placement* lay2 = nullptr;
+    char* seqs2 = nullptr;
+    sigax_gap* gaps = nullptr;
+    if (sigax_gapfill_host(rq.index, n_unitigs, seq_offs, useqs, ns, sc_lay, lay, &go, SIGAX_GAPFILL_AUTO, &offs2, &lay2, &seqs2, &gaps, &ng, st) !=
+        SIGAX_OK) {
+      sigax_free(sc_offs);
+      sigax_free(sc_lay);
+      sigax_free(sc_flags);
+      sigax_free(lay);
+      sigax_free(seqs);
+      return std::string("gap filling failed: ") + sigax_last_error();
+    }
+    sigax_free(sc_offs);
+    sigax_free(lay);
+    sigax_free(seqs);
+    sc_offs = offs2;
+    lay = lay2;
+    seqs = seqs2;
+    filled.assign(ns, 0);
+    for (uint64_t g = 0; g < ng; ++g) {
+      const sigax_gap& x = gaps[g];
+      if (x.cls == SIGAX_GAP_FILLED && x.scaffold < ns) ++filled[x.scaffold];
+      gt += "GP\tscaffold-";
+      append_u64(gt, x.scaffold);
+      gt += "\tunitig-";
+      append_u64(gt, x.left);
+      gt += "\tunitig-";
+      append_u64(gt, x.right);
+      gt += '\t';
+      append_u64(gt, x.laid);
+      gt += '\t';
+      gt += gap_class(x.cls);
+      gt += '\t';
+      gt += gap_class(x.fwd);
+      gt += '\t';
+      gt += gap_class(x.rev);
+      gt += x.dir ? "\t-\t" : "\t+\t";
+      append_u64(gt, x.fill);
+      gt += '\t';
+      append_u64(gt, x.offset);
+      gt += '\n';
+    }
+    sigax_free(gaps);
+    if (gap24)
+      for (int k = 0; k < 24; ++k) gap24[k] = st[k];
+  }
   for (uint64_t s = 0; s < ns; ++s) {
     const uint64_t k = sc_lay[s + 1] - sc_lay[s];
     fa += ">scaffold-";
@@ -101,6 +158,10 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
     if (sc_flags[s] & 1u) {
       fa += " circular=";
       append_u64(fa, sc_flags[s] >> 1);
+    }
+    if (rq.index) {
+      fa += " filled=";
+      append_u64(fa, filled[s]);
     }
     fa += '\n';
     fa.append(seqs + sc_offs[s], sc_offs[s + 1] - sc_offs[s]);
@@ -130,6 +191,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
   sigax_free(seqs);
   if (!write_file(rq.fasta, fa)) return "Failed to write " + rq.fasta;
   if (!rq.layout.empty() && !write_file(rq.layout, lt)) return "Failed to write " + rq.layout;
+  if (rq.index && !rq.gaps.empty() && !write_file(rq.gaps, gt)) return "Failed to write " + rq.gaps;
   return std::string();
 }
 }  // namespace
@@ -137,7 +199,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
                       const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, const ScaffoldRequest* sc,
-                      const char* useqs, uint64_t status16[16]) {
+                      const char* useqs, uint64_t status16[16], uint64_t gap24[24]) {
   sigax_pairs_opts opts;
   opts.flags = rq.outward ? SIGAX_PAIRS_OUTWARD : 0u;
   opts.hist_bins = rq.bins;
@@ -209,7 +271,7 @@ std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::
     if (!ok) bad = rq.links;
   }
   std::string e = ok ? std::string() : "Failed to write " + bad;
-  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16);
+  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16, gap24);
   sigax_free(hist);
   sigax_free(links);
   return e;

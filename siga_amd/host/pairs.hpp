@@ -27,13 +27,19 @@ struct ScaffoldRequest {
   uint32_t minPairs = 2, linkRatio = 0, minUnitigBases = 0, minGap = 1, maxGap = 1000000;
   bool haveInsertSize = false;  // else floor(sum span / n) of the pairs call
   uint64_t insertSize = 0;
+  // gap filling behind the scaffold call (sigax_gapfill_host): index NULL = none; gaps may be empty
+  sigax_index* index = nullptr;
+  uint32_t gapKmer = 31, gapMinCount = 3, gapSlack = 100, gapMaxFill = 10000;
+  std::string gaps;
 };
 // sigax_unitigs_pairs_host over a unitig call's result, then the two files; with sc->fasta also sigax_scaffold_host over the
-// unitigs (useqs: their bases) and the links, then its two files and status16.  -> "" or what went wrong
+// unitigs (useqs: their bases) and the links, then its two files and status16; with sc->index also sigax_gapfill_host over the
+// scaffolds before they are written, sc->gaps and gap24.  -> "" or what went wrong
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
                       const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta,
-                      const ScaffoldRequest* sc = nullptr, const char* useqs = nullptr, uint64_t status16[16] = nullptr);
+                      const ScaffoldRequest* sc = nullptr, const char* useqs = nullptr, uint64_t status16[16] = nullptr,
+                      uint64_t gap24[24] = nullptr);
 
 }  // namespace sigah
 

@@ -295,6 +295,22 @@ class Unitigger {
     _scMinGap = minGap;
     _scMaxGap = maxGap;
   }
+  // Gap filling (sigax_gapfill_host; the rules in include/sigax.h), behind the scaffold call and over the index the run already
+  // holds: every gap whose k-mer walk arrives gets its bases instead of N before the scaffolds are written, every FASTA header
+  // ends in " filled=<n>", the layout gives the new offsets and gaps, and `gaps`, if not empty, gets one GP line per gap.  Off by
+  // default: every output is then the one without this call.  Needs setScaffold.
+  void setGapfill(bool on, size_t kmer = 31, size_t minCount = 3, size_t slack = 100, size_t maxFill = 10000, const std::string& gaps = std::string()) {
+    _gapfill = on;
+    _gapKmer = kmer;
+    _gapMinCount = minCount;
+    _gapSlack = slack;
+    _gapMaxFill = maxFill;
+    _gapsOut = gaps;
+  }
+  uint64_t gaps() const { return _gaps; }
+  uint64_t gapsFilled() const { return _gapsFilled; }
+  uint64_t gapFillBases() const { return _gapFillBases; }
+  uint64_t gapBasesLeft() const { return _gapBasesLeft; }
   uint64_t scaffolds() const { return _scaffolds; }
   uint64_t scaffoldJoins() const { return _scJoins; }          // joins merged
   uint64_t scaffoldAmbiguous() const { return _scAmbiguous; }  // strong links that are not the only one at an end
@@ -351,6 +367,10 @@ class Unitigger {
   size_t _scMinPairs = 2, _scLinkRatio = 0, _scMinUnitigBases = 0, _scMinGap = 1, _scMaxGap = 1000000;
   long long _scInsertSize = -1;
   uint64_t _scaffolds = 0, _scJoins = 0, _scAmbiguous = 0, _scGapBases = 0;
+  bool _gapfill = false;
+  size_t _gapKmer = 31, _gapMinCount = 3, _gapSlack = 100, _gapMaxFill = 10000;
+  std::string _gapsOut;
+  uint64_t _gaps = 0, _gapsFilled = 0, _gapFillBases = 0, _gapBasesLeft = 0;
   std::string _error;
 };
 

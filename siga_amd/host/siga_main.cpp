@@ -586,6 +586,18 @@ static int unitig_help() {
          "          --min-gap=N                  a gap is at least N bases, also where the estimate is smaller or negative (default: 1)\n"
          "          --max-gap=N                  ... and at most N bases (default: 1000000)\n"
          "\n"
+         "Gap filling parameters (they need --scaffold):\n"
+         "          --gapfill                    walk from each unitig's last k-mer over the k-mers of the reads towards the next unitig's\n"
+         "                                       first, and back where that walk forks or ends; a gap a walk closes gets its bases for\n"
+         "                                       its N, every header gains filled=<gaps filled>, and the layout gives the new offsets\n"
+         "          --gap-kmer=K                 the walks' k, 8 to 128 (default: 31)\n"
+         "          --gap-min-count=N            a k-mer counts when it occurs N times in the reads, either strand (default: 3)\n"
+         "          --gap-slack=N                a walk may arrive N bases before or after the gap's estimate (default: 100)\n"
+         "          --gap-max-fill=N             leave gaps estimated above N bases alone (default: 10000)\n"
+         "          --gaps=FILE                  also write one line per gap to FILE: GP, scaffold, the two unitigs, the bases laid, the\n"
+         "                                       gap's class, the two walks' outcomes, + or - for the walk that filled it, the fill, the\n"
+         "                                       offset at which the gap starts\n"
+         "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
          "Headers: >unitig-<n> KC:i:<reads> (the tag only for more than one read), circular=<closing overlap> for a ring.\n"
@@ -610,7 +622,8 @@ static bool unitig_number(const char* arg, const char* option, unsigned long lon
 static int run_unitig(int argc, char** argv) {
   enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC, OPT_PAIRS, OPT_LINKS,
          OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT, OPT_SCAFFOLD, OPT_SCAFFOLD_LAYOUT, OPT_MIN_PAIRS, OPT_LINK_RATIO,
-         OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES };
+         OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
+         OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -637,6 +650,10 @@ static int run_unitig(int argc, char** argv) {
                                     {"min-scaffold-unitig", required_argument, nullptr, OPT_MIN_SCAFFOLD_UNITIG},
                                     {"insert-size", required_argument, nullptr, OPT_INSERT_SIZE},
                                     {"min-gap", required_argument, nullptr, OPT_MIN_GAP}, {"max-gap", required_argument, nullptr, OPT_MAX_GAP},
+                                    {"gapfill", no_argument, nullptr, OPT_GAPFILL}, {"gap-kmer", required_argument, nullptr, OPT_GAP_KMER},
+                                    {"gap-min-count", required_argument, nullptr, OPT_GAP_MIN_COUNT},
+                                    {"gap-slack", required_argument, nullptr, OPT_GAP_SLACK},
+                                    {"gap-max-fill", required_argument, nullptr, OPT_GAP_MAX_FILL}, {"gaps", required_argument, nullptr, OPT_GAPS},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
@@ -645,6 +662,9 @@ static int run_unitig(int argc, char** argv) {
   std::string scaffoldOut, scaffoldLayout;
   size_t minPairs = 2, linkRatio = 0, minScaffoldUnitig = 0, insertSize = 0, minGap = 1, maxGap = 1000000;
   bool haveInsertSize = false, scaffoldTuned = false;
+  bool gapfill = false, gapTuned = false;
+  size_t gapKmer = 31, gapMinCount = 3, gapSlack = 100, gapMaxFill = 10000;
+  std::string gapsOut;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
   size_t bubbleSpan = 0, bubbleDivergence = 50;
@@ -713,6 +733,12 @@ static int run_unitig(int argc, char** argv) {
       case OPT_INSERT_SIZE: if (!unitig_number(optarg, "--insert-size", (1ull << 62) - 1, &insertSize)) return 1; haveInsertSize = scaffoldTuned = true; break;
       case OPT_MIN_GAP: if (!unitig_number(optarg, "--min-gap", 0x7FFFFFFFull, &minGap) || minGap == 0) return 1; scaffoldTuned = true; break;
       case OPT_MAX_GAP: if (!unitig_number(optarg, "--max-gap", 0x7FFFFFFFull, &maxGap)) return 1; scaffoldTuned = true; break;
+      case OPT_GAPFILL: gapfill = true; break;
+      case OPT_GAP_KMER: if (!unitig_number(optarg, "--gap-kmer", 128, &gapKmer) || gapKmer < 8) return 1; gapTuned = true; break;
+      case OPT_GAP_MIN_COUNT: if (!unitig_number(optarg, "--gap-min-count", 0xFFFFFFFFull, &gapMinCount) || gapMinCount == 0) return 1; gapTuned = true; break;
+      case OPT_GAP_SLACK: if (!unitig_number(optarg, "--gap-slack", 0x7FFFFFFFull, &gapSlack)) return 1; gapTuned = true; break;
+      case OPT_GAP_MAX_FILL: if (!unitig_number(optarg, "--gap-max-fill", 0x7FFFFFFFull, &gapMaxFill)) return 1; gapTuned = true; break;
+      case OPT_GAPS: gapsOut = optarg; gapTuned = true; break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -770,6 +796,14 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: --scaffold needs --pairs: the scaffolds are built from its links\n");
     return 1;
   }
+  if (!gapfill && gapTuned) {
+    fprintf(stderr, "siga unitig: --gap-kmer, --gap-min-count, --gap-slack, --gap-max-fill and --gaps need --gapfill\n");
+    return 1;
+  }
+  if (gapfill && scaffoldOut.empty()) {
+    fprintf(stderr, "siga unitig: --gapfill needs --scaffold: it fills the gaps of the scaffolds\n");
+    return 1;
+  }
   if (maxGap < minGap) {
     fprintf(stderr, "siga unitig: --max-gap %zu is below --min-gap %zu\n", maxGap, minGap);
     return 1;
@@ -794,6 +828,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setCutEdges(cutEdges);
   unitigger.setPairs(pairsOut, linksOut, maxSpan, outward, pairsBins, pairsShift);
   unitigger.setScaffold(scaffoldOut, scaffoldLayout, minPairs, linkRatio, minScaffoldUnitig, haveInsertSize ? (long long)insertSize : -1, minGap, maxGap);
+  unitigger.setGapfill(gapfill, gapKmer, gapMinCount, gapSlack, gapMaxFill, gapsOut);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -819,6 +854,9 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "%llu scaffolds, %llu joins, %llu ambiguous links, %llu gap bases\n", (unsigned long long)unitigger.scaffolds(),
             (unsigned long long)unitigger.scaffoldJoins(), (unsigned long long)unitigger.scaffoldAmbiguous(),
             (unsigned long long)unitigger.scaffoldGapBases());
+  if (gapfill)
+    fprintf(stderr, "%llu gaps, %llu filled with %llu bases, %llu N left\n", (unsigned long long)unitigger.gaps(), (unsigned long long)unitigger.gapsFilled(),
+            (unsigned long long)unitigger.gapFillBases(), (unsigned long long)unitigger.gapBasesLeft());
   return 0;
 }
 

@@ -87,6 +87,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _error.clear();
   _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = _pairs = _pairsSame = _pairsAcross = _pairLinks = _insertSize = _insertDelta = 0;
   _scaffolds = _scJoins = _scAmbiguous = _scGapBases = 0;
+  _gaps = _gapsFilled = _gapFillBases = _gapBasesLeft = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -128,6 +129,10 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   if (!_scaffoldOut.empty() && (_scMinPairs > 0xFFFFFFFFull || _scLinkRatio > 0xFFFFFFFFull || _scMinUnitigBases > 0xFFFFFFFFull || _scMinGap < 1 ||
                                 _scMaxGap < _scMinGap || _scMaxGap >= (1ull << 31) || _scInsertSize >= (1ll << 62)))
     return fail("scaffold options out of range");
+  if (_gapfill && _scaffoldOut.empty()) return fail("gaps are only filled in scaffolds");
+  if (_gapfill && (_gapKmer < 8 || _gapKmer > 128 || _gapMinCount < 1 || _gapMinCount > 0xFFFFFFFFull || _gapSlack >= (1ull << 31) ||
+                   _gapMaxFill >= (1ull << 31)))
+    return fail("gap filling options out of range");
   if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
@@ -248,10 +253,23 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sq.maxGap = (uint32_t)_scMaxGap;
     sq.haveInsertSize = _scInsertSize >= 0;
     sq.insertSize = _scInsertSize >= 0 ? (uint64_t)_scInsertSize : 0;
+    if (_gapfill) {  // over the index this run has open
+      sq.index = index.handle();
+      sq.gapKmer = (uint32_t)_gapKmer;
+      sq.gapMinCount = (uint32_t)_gapMinCount;
+      sq.gapSlack = (uint32_t)_gapSlack;
+      sq.gapMaxFill = (uint32_t)_gapMaxFill;
+      sq.gaps = _gapsOut;
+    }
     uint64_t st24[24], st16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t gp24[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const std::string e = run_pairs(inf.device, mates_by_name(reads, ranks), lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
-                                    &_insertSize, &_insertDelta, &sq, u.useqs, st16);
+                                    &_insertSize, &_insertDelta, &sq, u.useqs, st16, gp24);
     if (!e.empty()) return fail(e);
+    _gaps = gp24[0];
+    _gapsFilled = gp24[1];
+    _gapFillBases = gp24[14];
+    _gapBasesLeft = gp24[15];
     _scaffolds = st16[0];
     _scJoins = st16[10];
     _scAmbiguous = st16[9];

@@ -446,6 +446,48 @@ def unitigs_scaffold(res, links, insert_size=None, status=None, min_pairs=2, lin
     return out
 
 
+def scaffolds_gapfill(pair, res, scaf, k=31, min_count=3, slack=100, max_fill=10000, max_walk_bases=None, bases=True):
+    """The gaps of `unitigs_scaffold`'s scaffolds closed by k-mer walks over the reads' index (sigax_gapfill_host, the rules in
+    include/sigax.h): `pair` is the FMIndexPair of the reads (the forward strand is enough), `res` the dict of the unitig call
+    (seq_offs, useqs), `scaf` the dict `unitigs_scaffold` returned over it.  A gap is filled when the walk from the left unitig's
+    last k-mer, taking the one next base that at least min_count reads (either strand) support, arrives at the right unitig's first
+    k-mer within slack bases of the laid gap -- or the walk back from the right unitig does; gaps laid wider than max_fill are not
+    tried.  max_walk_bases=None sizes the walk scratch so that every gap has room.  -> the dict shape of `unitigs_scaffold`
+    (sc_lay_offs and sc_flags as they came in, status u64[24] named by _lib.GAPFILL_STATUS) plus gaps, one _lib.GAP_DTYPE record
+    per gap in scaffold order: its class (_lib.GAP_CLASSES), the two walks' outcomes, the fill and where it starts."""
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    u = len(so) - 1
+    if res.get("useqs") is None:
+        raise ValueError("the walks start from the unitig bases (res['useqs'])")
+    us = res["useqs"]
+    us = np.frombuffer(bytes(us), dtype=np.uint8) if isinstance(us, (bytes, bytearray)) else np.ascontiguousarray(us, dtype=np.uint8)
+    if len(us) < int(so[u]):
+        raise ValueError("useqs shorter than seq_offs says")
+    slo = np.ascontiguousarray(scaf["sc_lay_offs"], dtype=np.uint64)
+    lay = np.ascontiguousarray(scaf["layout"], dtype=PLACEMENT_DTYPE)
+    s = len(slo) - 1
+    if s < 0 or len(lay) < int(slo[s]):
+        raise ValueError("layout shorter than sc_lay_offs says")
+    L = _lib.lib()
+    opts = _lib.GapfillOpts(0, int(k), int(min_count), int(slack), int(max_fill), 0)
+    po, play, ps, pg = (C.c_void_p() for _ in range(4))
+    ng = C.c_uint64()
+    st = np.zeros(24, dtype=np.uint64)
+    _check(L.sigax_gapfill_host(pair.handle, u, so.ctypes.data, us.ctypes.data if len(us) else None, s, slo.ctypes.data,
+                                lay.ctypes.data if len(lay) else None, C.byref(opts),
+                                _lib.SIGAX_GAPFILL_AUTO if max_walk_bases is None else int(max_walk_bases), C.byref(po), C.byref(play),
+                                C.byref(ps) if bases else None, C.byref(pg), C.byref(ng), st.ctypes.data), "sigax_gapfill_host")
+    try:
+        out = {"sc_offs": _copy_records(po, s + 1, np.dtype(np.uint64)), "sc_lay_offs": slo.copy(),
+               "sc_flags": np.array(scaf["sc_flags"], dtype=np.uint32), "layout": _copy_records(play, int(slo[s]) if u else 0, PLACEMENT_DTYPE),
+               "status": st, "gaps": _copy_records(pg, int(ng.value), _lib.GAP_DTYPE)}
+        out["seqs"] = _copy_records(ps, int(st[16]), np.dtype(np.uint8)) if bases else None
+    finally:
+        for p in (po, play, ps, pg):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
