@@ -934,6 +934,107 @@ int  sigax_gapfill_host(sigax_index*, uint64_t n_unitigs, const uint64_t* seq_of
                         const uint64_t* sc_lay_offs, const sigax_placement* sc_layout, const sigax_gapfill_opts* opts,
                         uint64_t max_walk_bases, uint64_t** sc_offs, sigax_placement** sc_layout_out, char** sseqs, sigax_gap** gaps,
                         uint64_t* n_gaps, uint64_t status24[24]);
+/* ---- `siga unitig --scaffold --join-overlaps`: overlapping scaffold neighbours written as one sequence (csrc/sigax_join.hip) ------
+ * Two unitigs that end at a fork of the overlap graph usually share the overlap that forked.  The scaffolder estimates a negative
+ * gap there, clamps it to min_gap and lays N between two sequences that run into each other; a k-mer walk cannot close such a
+ * gap, because its goal lies behind its start.  This pass looks for the overlap itself: where exactly one length v makes the
+ * left neighbour's last v bases the right neighbour's first v, and the reads support the sequence across the junction, the N and
+ * one copy of the overlap go.  The reference has no such step; the rules are this library's own.  DESIGN.md 9l; the serial
+ * restatement the tests hold this against is tests/join_cases.py::expected_join.
+ *
+ * Input: an open index (the forward strand is enough, and it is the only one read: no result depends on which tables the
+ * index holds); nu and seq_offs of a unitig call, read for unitig lengths only; S, sc_offs, sc_lay_offs, sc_layout and sseqs
+ * (sseqs_bytes bytes) of a scaffold or gapfill call; sigax_join_opts {flags = 0, min_overlap, max_overlap, slack, k, min_count,
+ * reserved = 0}.  Preconditions: 8 <= min_overlap <= max_overlap <= 4096, slack < 2^31, 8 <= k <= 128, min_count >= 1; anything
+ * else is SIGAX_E_ARG.  All arithmetic is modulo 2^64 unless it says otherwise.
+ *
+ * Placements, P and the scaffold s(p) of placement p (the 32-step bisection) are the gapfill block's.  u = sc_layout[p].read,
+ * len(s) = sc_offs[s+1] - sc_offs[s].  Placement p is BAD iff u >= nu; seq_offs[u+1] < seq_offs[u]; sc_offs[s+1] < sc_offs[s];
+ * sc_offs[s+1] > sseqs_bytes; or offset[p] + bases(p) > len(s) without wrapping, that is offset[p] > len(s) or bases(p) > len(s) -
+ * offset[p].  bases(p) = seq_offs[u+1] - seq_offs[u], and 0 for a bad placement.  The bases of a placement are read from the
+ * input sseqs as placed: X(p) = sseqs[sc_offs[s] + offset[p] .. + bases(p)).  No orientation is handled, useqs is not read,
+ * and a fill that gapfill wrote stays.
+ *
+ * Gaps are the gapfill block's: consecutive placements (p, p+1) of one scaffold, numbered in placement order; a ring's closing
+ * join is no gap.  G = offset[p+1] - offset[p] - bases(p) in u64, L = X(p), R = X(p+1).
+ *
+ * Class of a gap: the first of these that applies.
+ *   MALFORMED    placement p or p+1 is bad.
+ *   CLOSED       G = 0.
+ *   FAR          G > slack.  This covers the wrapped G of neighbours that already overlap, so a second call over the output of a
+ *                first joins nothing.
+ *   CLOSED       one of the gap's G bytes sseqs[sc_offs[s] + offset[p] + bases(p) .. + G) is not 'N': a fill.  (At most slack
+ *                bytes are read.)
+ *   SHORT        hi < lo, where lo = min_overlap and hi = min(max_overlap, |L| - 1, |R| - 1), an empty L or R giving hi < lo.
+ *   otherwise    the outcome of the match.
+ *
+ * Match.  match(v) holds iff the last v bytes of L equal the first v bytes of R byte for byte and every one of them is upper-case
+ * A, C, G or T.  M = {v in [lo, hi] : match(v)}.  |M| = 0 gives NONE; |M| >= 2 gives AMBIGUOUS (tandem repeats and homopolymer
+ * ends: the laid estimate is a clamp and cannot choose).  With one v the join is tested for read support over J = L ++ R[v:]:
+ * the windows across the junction are the k-byte windows of J that lie neither wholly in L nor wholly in R, those that start
+ * at s in [|L| - k + 1, |L| - v - 1] clipped to [0, |J| - k] -- none when v >= k - 1, since every k-mer of J is then in L or
+ * in R.  count(w) is the gapfill block's, occ(w) + occ(revcomp(w)); a window with a byte outside ACGT counts 0.  A window with
+ * count < min_count gives UNSUPPORTED, otherwise the gap is JOINED.
+ *
+ * Output.  For a JOINED gap the G bytes of N and the first v bytes of R go.  With E(p) = the sum of G + v over the joined gaps
+ * (q, q+1), q < p, and h = sc_lay_offs[s(p)] taken as P when above it: offset'[p] = offset[p] - (E(p) - E(h)).  Scaffold s has
+ * len(s) - (E(e) - E(h)) bases, e = sc_lay_offs[s+1] clamped likewise, and len(s) when e <= h.  The new bases are a compaction
+ * of the input sseqs: per joined gap the old bytes [offset[p+1] - G, offset[p+1] + v) of its scaffold are deleted, out[x] =
+ * in[x + the bytes deleted before x].  Where joins chain so closely that v1 + v2 > |R1| this is still well defined, since
+ * deleted bytes equal kept ones.  sc_lay_offs and sc_flags are not rewritten.  One 32-byte sigax_join per gap in gap order:
+ * scaffold, left and right (unitig ids), laid (G, saturated at 2^32 - 1), overlap (v; 0 unless JOINED or UNSUPPORTED), cls,
+ * matches (|M|, saturated at 255), windows (those the support test had, max(0, k - v - 1) after the clip, whether or not an
+ * early one failed; 0 unless JOINED or UNSUPPORTED), offset (offset'[p+1] of a JOINED gap, else offset'[p] + bases(p)).
+ * status16 = 16 u64, written (not added to): 0 gaps; 1 + c gaps of class c for the eight SIGAX_JOIN_* codes (1 JOINED .. 8
+ * MALFORMED); 9 overlap bases removed; 10 N removed; 11 scaffold bases of the new tables; 12 candidate overlaps tested, hi - lo +
+ * 1 over the gaps that came to the match; 13 junction windows, as in the records; 14 = 1 when status[11] > sseqs_capacity: the
+ * bases were not written for lack of room; 15 scaffolds S.  No result depends on scheduling or on the index's tables.
+ *
+ * sigax_join_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the device.
+ * d_n_unitigs and d_n_scaffolds point at u64 ON THE DEVICE, so the call can be enqueued straight behind sigax_scaffold_device
+ * or sigax_gapfill_device; a count above max_unitigs is taken as max_unitigs, and sc_lay_offs[S] likewise.  d_seq_offs,
+ * d_sc_offs and d_sc_lay_offs u64[max_unitigs + 1], d_sc_layout sigax_placement[max_unitigs], d_sseqs sseqs_bytes bytes: no
+ * byte at or beyond them is read.  d_sc_offs_out u64[max_unitigs + 1], d_sc_layout_out sigax_placement[max_unitigs], d_joins
+ * sigax_join[max_unitigs]; entries beyond S, P and the gaps are not written.  d_sseqs_out sseqs_capacity bytes, or NULL with
+ * capacity 0; the bases are written only if status16[11] <= sseqs_capacity.  d_work = sigax_join_workspace(max_unitigs) bytes
+ * (116 per unitig).  d_sseqs, d_sseqs_out, d_sc_layout, d_sc_layout_out, d_joins and d_work 16-byte aligned, every other buffer
+ * 8-byte aligned; d_sc_offs_out, d_sc_layout_out and d_sseqs_out must not overlap d_sc_offs, d_sc_layout and d_sseqs.  A NULL
+ * where a buffer is required, a misaligned or overlapping buffer, a short workspace, bad options, max_unitigs >= 2^31,
+ * sseqs_bytes or sseqs_capacity >= 2^43: SIGAX_E_ARG with the argument named in sigax_last_error().  max_unitigs = 0: SIGAX_OK,
+ * status zeros, d_sc_offs_out[0] = 0 where given.  Whatever the tables hold, nothing outside the buffers is touched, and every
+ * loop has a bound the host knows: a bisection 32 steps, the fill test slack bytes, the match max_overlap candidates of
+ * max_overlap bases, the support test k - 2 windows of k symbols. */
+#define SIGAX_JOIN_JOINED      0u
+#define SIGAX_JOIN_CLOSED      1u
+#define SIGAX_JOIN_FAR         2u
+#define SIGAX_JOIN_SHORT       3u
+#define SIGAX_JOIN_NONE        4u
+#define SIGAX_JOIN_AMBIGUOUS   5u
+#define SIGAX_JOIN_UNSUPPORTED 6u
+#define SIGAX_JOIN_MALFORMED   7u
+typedef struct sigax_join_opts { uint32_t flags, min_overlap, max_overlap, slack, k, min_count, reserved; } sigax_join_opts;
+typedef struct sigax_join {
+  uint32_t scaffold, left, right, laid;
+  uint32_t overlap;
+  uint8_t  cls, matches;
+  uint16_t windows;
+  uint64_t offset;
+} sigax_join; /* 32 bytes */
+int  sigax_join_workspace(uint64_t max_unitigs, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_join_device(sigax_index*, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_n_scaffolds,
+                       const void* d_sc_offs, const void* d_sc_lay_offs, const sigax_placement* d_sc_layout, const void* d_sseqs,
+                       uint64_t sseqs_bytes, const sigax_join_opts* opts, void* d_sc_offs_out, sigax_placement* d_sc_layout_out,
+                       void* d_sseqs_out, uint64_t sseqs_capacity, sigax_join* d_joins, void* d_status16, void* d_work, uint64_t work_bytes,
+                       void* stream);
+/* Host buffers, synchronous.  seq_offs u64[n_unitigs + 1], sc_offs and sc_lay_offs u64[n_scaffolds + 1], sc_layout
+ * sigax_placement[sc_lay_offs[n_scaffolds]], sseqs sc_offs[n_scaffolds] bytes; n_scaffolds or sc_lay_offs[n_scaffolds] above
+ * n_unitigs: SIGAX_E_ARG.  It runs the tables, reads the total, then writes the bases into a buffer of exactly that size:
+ * status16[14] is 0.  *sc_offs_out u64[n_scaffolds + 1], *sc_layout_out sigax_placement[placements], *sseqs_out status16[11]
+ * bytes (pass sseqs_out = NULL for the tables alone), *joins sigax_join[*n_joins]; all malloc'd, release with sigax_free. */
+int  sigax_join_host(sigax_index*, uint64_t n_unitigs, const uint64_t* seq_offs, uint64_t n_scaffolds, const uint64_t* sc_offs,
+                     const uint64_t* sc_lay_offs, const sigax_placement* sc_layout, const char* sseqs, const sigax_join_opts* opts,
+                     uint64_t** sc_offs_out, sigax_placement** sc_layout_out, char** sseqs_out, sigax_join** joins, uint64_t* n_joins,
+                     uint64_t status16[16]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -57,6 +57,14 @@ GAPFILL_STATUS = ("gaps",) + tuple(c.lower() for c in GAP_CLASSES) + (
     "filled_forward", "filled_reverse", "fill_bases", "n_bases_left", "bases", "steps", "lookups", "sectors", "bases_not_written",
     "walk_scratch_too_small", "scaffolds", "reserved")
 assert len(GAPFILL_STATUS) == 24
+# sigax_join_*: the classes of a gap (sigax_join.cls), the record and the entries of status16, by name
+JOIN_CLASSES = ("JOINED", "CLOSED", "FAR", "SHORT", "NONE", "AMBIGUOUS", "UNSUPPORTED", "MALFORMED")
+JOIN_DTYPE = np.dtype([("scaffold", "<u4"), ("left", "<u4"), ("right", "<u4"), ("laid", "<u4"), ("overlap", "<u4"), ("cls", "u1"), ("matches", "u1"),
+                       ("windows", "<u2"), ("offset", "<u8")])  # sigax_join
+assert JOIN_DTYPE.itemsize == 32
+JOIN_STATUS = ("gaps",) + tuple(c.lower() for c in JOIN_CLASSES) + (
+    "overlap_bases_removed", "n_bases_removed", "bases", "candidates", "windows", "bases_not_written", "scaffolds")
+assert len(JOIN_STATUS) == 16
 
 
 class TrimOpts(C.Structure):  # sigax_trim_opts
@@ -90,6 +98,10 @@ class ScaffoldOpts(C.Structure):  # sigax_scaffold_opts
 
 class GapfillOpts(C.Structure):  # sigax_gapfill_opts
     _fields_ = [(n, C.c_uint32) for n in ("flags", "k", "min_count", "slack", "max_fill", "reserved")]
+
+
+class JoinOpts(C.Structure):  # sigax_join_opts
+    _fields_ = [(n, C.c_uint32) for n in ("flags", "min_overlap", "max_overlap", "slack", "k", "min_count", "reserved")]
 
 
 class Stats(C.Structure):
@@ -142,6 +154,7 @@ SYMBOLS = [
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
+    "sigax_join_workspace", "sigax_join_device", "sigax_join_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -262,6 +275,9 @@ def lib():
     L.sigax_gapfill_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_gapfill_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, C.POINTER(GapfillOpts), vp, vp, vp, u64, vp, vp, vp, u64, u64, vp]
     L.sigax_gapfill_host.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(GapfillOpts), u64, pvp, pvp, pvp, pvp, C.POINTER(u64), vp]
+    L.sigax_join_workspace.argtypes = [u64, C.POINTER(u64)]
+    L.sigax_join_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(JoinOpts), vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    L.sigax_join_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(JoinOpts), pvp, pvp, pvp, pvp, C.POINTER(u64), vp]
     # (not in include/sigax.h: the measurement aid of tools/scaffold_bench.py, sigax_internal.h)
     L.sigax_scaffold_bases_device.argtypes = L.sigax_scaffold_device.argtypes
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)

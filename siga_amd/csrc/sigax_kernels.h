@@ -527,6 +527,54 @@ static const uint32_t GAP_WALK = 0xFFu, GAP_NONE = 0xFEu;  // gres classes befor
 hipError_t launch_gapfill(const GapfillArgs& a, bool wide, int n_cu, hipStream_t st);
 void launch_gapfill_bases(const GapfillArgs& a, hipStream_t st);  // the last phase alone, over what launch_gapfill left
 
+// `siga unitig --scaffold --join-overlaps` (sigax_join.hip): scaffold neighbours that overlap written as one sequence.  Everything
+// below `status` is the caller's scratch (sigax_join.cpp lays it out).  n = max_unitigs; nu, S and P are clamped to it.
+struct JoinArgs {
+  FmStrand fwd;
+  const unsigned long long* n_unitigs;   // on the device
+  const unsigned long long* n_scaffolds; // on the device
+  unsigned long long max_unitigs;
+  const unsigned long long* seq_offs;    // [n + 1]
+  const unsigned long long* sc_offs_in;  // [n + 1]
+  const unsigned long long* sc_lay_offs; // [n + 1]
+  const sigax_placement* sc_layout;      // [n]
+  const unsigned char* sseqs_in;         // sseqs_bytes bytes: nothing at or beyond them is read
+  unsigned long long sseqs_bytes;
+  uint32_t min_overlap, max_overlap, slack, k, min_count;
+  unsigned long long* sc_offs;           // [n + 1], written
+  sigax_placement* sc_layout_out;        // [n], written
+  unsigned char* sseqs;                  // sseqs_capacity bytes or NULL
+  unsigned long long sseqs_capacity;
+  sigax_join* joins;                     // [n], written
+  unsigned long long* status;            // 16 u64, written
+  unsigned long long* cnt;               // JOIN_WORDS u64, zeroed: the JOIN_C_* counters
+  uint32_t* sof;                         // [n]: the scaffold of a placement
+  uint32_t* isgap;                       // [n]: placement p and p + 1 are a gap ...
+  uint32_t* open;                        // [n]: ... that comes to the match
+  uint32_t* rem;                         // [n]: G + v of a joined gap, else 0
+  uint32_t* lenlo;                       // [n]: the new bases of scaffold s, low and ...
+  uint32_t* lenhi;                       // [n]: ... high half
+  unsigned long long* gnum;              // [n + 1]: scans of isgap, open, rem, lenlo, lenhi
+  unsigned long long* onum;
+  unsigned long long* esum;
+  unsigned long long* slo;
+  unsigned long long* shi;
+  unsigned long long* partial;           // scan_partials_needed(n) u64
+  unsigned long long* scan_total;        // 1 u64
+  uint32_t* list;                        // [n]: the placements whose gap comes to the match, in order
+  uint4* gres;                           // [n]: {class | matches << 8 | windows << 16, v, G saturated, hi}; class JOIN_OPEN before the match,
+                                         // JOIN_UNIQUE between the match and the support test
+  unsigned long long* plen;              // [n]: bases(p) (0 for a bad placement)
+  unsigned long long* psrc;              // [n]: where in sseqs_in X(p) begins
+  unsigned long long* pkey;              // [n + 1]: the output byte from which placement p's shift holds; [P] = all bases
+  unsigned long long* pshift;            // [n]: output byte x of that stretch is input byte x + pshift[p] (modulo 2^64)
+};
+// counters 0 .. 7 are the classes
+enum { JOIN_C_GAPS = 8, JOIN_C_OVERLAP = 9, JOIN_C_N = 10, JOIN_C_CAND = 11, JOIN_C_WINDOWS = 12, JOIN_WORDS = 16 };
+static const uint32_t JOIN_OPEN = 0xFFu, JOIN_NO_GAP = 0xFEu, JOIN_UNIQUE = 0xFDu;
+hipError_t launch_join(const JoinArgs& a, bool wide, int n_cu, hipStream_t st);
+void launch_join_bases(const JoinArgs& a, hipStream_t st);  // the last phase alone, over what launch_join left
+
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);
 void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, uint32_t k, unsigned long long n,

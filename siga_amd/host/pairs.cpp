@@ -70,15 +70,20 @@ void append_double(std::string& t, double v) {
 const char* const kGapClasses[11] = {"FILLED", "SHORT", "NON_ACGT", "FAR", "NO_ROOM", "DEAD_END", "BRANCH", "TOO_LONG", "OVERLAP", "OFF_ESTIMATE",
                                      "MALFORMED"};
 const char* gap_class(uint32_t c) { return c < 11 ? kGapClasses[c] : "NOT_RUN"; }
+const char* const kJoinClasses[8] = {"JOINED", "CLOSED", "FAR", "SHORT", "NONE", "AMBIGUOUS", "UNSUPPORTED", "MALFORMED"};
 
 // sigax_scaffold_host, then ">scaffold-<n> unitigs=<k> gaps=<k - 1>[ circular=<closing gap>]" and the bases per scaffold, and
 // one line "scaffold-<n>\tunitig-<u>\t<+|->\t<offset>\t<gap before>" per placement (0 before a scaffold's first).  With
 // rq.index the gaps are filled first (sigax_gapfill_host): the bases, the offsets and the gaps before are the new ones, every
 // header ends in " filled=<gaps filled>", and rq.gaps gets one line per gap:
 // "GP\tscaffold-<n>\tunitig-<left>\tunitig-<right>\t<laid>\t<class>\t<forward walk>\t<reverse walk>\t<+|->\t<fill>\t<offset>"
+// (the offsets of the gapfill call's tables).  With rq.joinIndex overlapping neighbours are then joined (sigax_join_host): the
+// bases and the offsets are the new ones, the gap before is signed, -<overlap> for a joined pair, every header ends in
+// " joined=<gaps joined>", and rq.joins gets one line per gap:
+// "JN\tscaffold-<n>\tunitig-<left>\tunitig-<right>\t<laid>\t<class>\t<overlap>\t<matches>\t<windows>\t<offset>"
 std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint32_t* uflags, const char* useqs,
                          const sigax_pair_link* links, uint64_t n_links, const uint64_t status24[24], const ScaffoldRequest& rq,
-                         uint64_t status16[16], uint64_t gap24[24]) {
+                         uint64_t status16[16], uint64_t gap24[24], uint64_t join16[16]) {
   if (!rq.haveInsertSize && status24[14] == 0)
     return "no pair of the library's orientation lies inside a unitig: there is no insert size to estimate the gaps from; give --insert-size";
   sigax_scaffold_opts opts;
@@ -96,8 +101,8 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
   if (sigax_scaffold_host(device, n_unitigs, seq_offs, uflags, useqs, links, n_links, status24, &opts, &ns, &sc_offs, &sc_lay, &sc_flags, &lay, &seqs,
                           status16) != SIGAX_OK)
     return std::string("scaffold failed: ") + sigax_last_error();
-  std::string fa, lt, gt;
-  std::vector<uint64_t> filled;
+  std::string fa, lt, gt, jt;
+  std::vector<uint64_t> filled, joined;
   if (rq.index) {
     sigax_gapfill_opts go = {0u, rq.gapKmer, rq.gapMinCount, rq.gapSlack, rq.gapMaxFill, 0u};
     uint64_t *offs2 = nullptr, ng = 0, st[24];
@@ -147,6 +152,54 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
     if (gap24)
       for (int k = 0; k < 24; ++k) gap24[k] = st[k];
   }
+  if (rq.joinIndex) {
+    sigax_join_opts jo = {0u, rq.joinMinOverlap, rq.joinMaxOverlap, rq.joinSlack, rq.joinKmer, rq.joinMinCount, 0u};
+    uint64_t *offs2 = nullptr, nj = 0, st[16];
+    sigax_placement* lay2 = nullptr;
+    char* seqs2 = nullptr;
+    sigax_join* recs = nullptr;
+    if (sigax_join_host(rq.joinIndex, n_unitigs, seq_offs, ns, sc_offs, sc_lay, lay, seqs, &jo, &offs2, &lay2, &seqs2, &recs, &nj, st) != SIGAX_OK) {
+      sigax_free(sc_offs);
+      sigax_free(sc_lay);
+      sigax_free(sc_flags);
+      sigax_free(lay);
+      sigax_free(seqs);
+      return std::string("joining overlaps failed: ") + sigax_last_error();
+    }
+    sigax_free(sc_offs);
+    sigax_free(lay);
+    sigax_free(seqs);
+    sc_offs = offs2;
+    lay = lay2;
+    seqs = seqs2;
+    joined.assign(ns, 0);
+    for (uint64_t g = 0; g < nj; ++g) {
+      const sigax_join& x = recs[g];
+      if (x.cls == SIGAX_JOIN_JOINED && x.scaffold < ns) ++joined[x.scaffold];
+      jt += "JN\tscaffold-";
+      append_u64(jt, x.scaffold);
+      jt += "\tunitig-";
+      append_u64(jt, x.left);
+      jt += "\tunitig-";
+      append_u64(jt, x.right);
+      jt += '\t';
+      append_u64(jt, x.laid);
+      jt += '\t';
+      jt += x.cls < 8 ? kJoinClasses[x.cls] : "?";
+      jt += '\t';
+      append_u64(jt, x.overlap);
+      jt += '\t';
+      append_u64(jt, x.matches);
+      jt += '\t';
+      append_u64(jt, x.windows);
+      jt += '\t';
+      append_u64(jt, x.offset);
+      jt += '\n';
+    }
+    sigax_free(recs);
+    if (join16)
+      for (int k = 0; k < 16; ++k) join16[k] = st[k];
+  }
   for (uint64_t s = 0; s < ns; ++s) {
     const uint64_t k = sc_lay[s + 1] - sc_lay[s];
     fa += ">scaffold-";
@@ -162,6 +215,10 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
     if (rq.index) {
       fa += " filled=";
       append_u64(fa, filled[s]);
+    }
+    if (rq.joinIndex) {
+      fa += " joined=";
+      append_u64(fa, joined[s]);
     }
     fa += '\n';
     fa.append(seqs + sc_offs[s], sc_offs[s + 1] - sc_offs[s]);
@@ -180,6 +237,10 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
         const sigax_placement& b = lay[p - 1];
         gap = x.offset - b.offset - (seq_offs[b.read + 1] - seq_offs[b.read]);
       }
+      if (rq.joinIndex && (int64_t)gap < 0) {  // neighbours that were joined: the overlap, signed
+        lt += '-';
+        gap = 0 - gap;
+      }
       append_u64(lt, gap);
       lt += '\n';
     }
@@ -192,6 +253,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
   if (!write_file(rq.fasta, fa)) return "Failed to write " + rq.fasta;
   if (!rq.layout.empty() && !write_file(rq.layout, lt)) return "Failed to write " + rq.layout;
   if (rq.index && !rq.gaps.empty() && !write_file(rq.gaps, gt)) return "Failed to write " + rq.gaps;
+  if (rq.joinIndex && !rq.joins.empty() && !write_file(rq.joins, jt)) return "Failed to write " + rq.joins;
   return std::string();
 }
 }  // namespace
@@ -199,7 +261,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
                       const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, const ScaffoldRequest* sc,
-                      const char* useqs, uint64_t status16[16], uint64_t gap24[24]) {
+                      const char* useqs, uint64_t status16[16], uint64_t gap24[24], uint64_t join16[16]) {
   sigax_pairs_opts opts;
   opts.flags = rq.outward ? SIGAX_PAIRS_OUTWARD : 0u;
   opts.hist_bins = rq.bins;
@@ -271,7 +333,7 @@ std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::
     if (!ok) bad = rq.links;
   }
   std::string e = ok ? std::string() : "Failed to write " + bad;
-  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16, gap24);
+  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16, gap24, join16);
   sigax_free(hist);
   sigax_free(links);
   return e;

@@ -307,6 +307,24 @@ class Unitigger {
     _gapMaxFill = maxFill;
     _gapsOut = gaps;
   }
+  // Overlapping neighbours joined (sigax_join_host; the rules in include/sigax.h), behind the scaffold call or, with gap filling,
+  // behind that: two neighbours whose ends overlap by exactly one length in minOverlap .. maxOverlap, with at most `slack` N
+  // between them and every k-mer across the junction seen minCount times, are written as one sequence; every FASTA header ends
+  // in " joined=<n>", the layout's gap before is signed, and `joins`, if not empty, gets one JN line per gap.  Off by default.
+  void setJoinOverlaps(bool on, size_t minOverlap = 16, size_t maxOverlap = 1000, size_t slack = 100, size_t kmer = 31, size_t minCount = 3,
+                       const std::string& joins = std::string()) {
+    _join = on;
+    _joinMinOverlap = minOverlap;
+    _joinMaxOverlap = maxOverlap;
+    _joinSlack = slack;
+    _joinKmer = kmer;
+    _joinMinCount = minCount;
+    _joinsOut = joins;
+  }
+  uint64_t joinGaps() const { return _joinGaps; }
+  uint64_t joinsMade() const { return _joinsMade; }
+  uint64_t joinOverlapBases() const { return _joinOverlapBases; }
+  uint64_t joinNRemoved() const { return _joinNRemoved; }
   uint64_t gaps() const { return _gaps; }
   uint64_t gapsFilled() const { return _gapsFilled; }
   uint64_t gapFillBases() const { return _gapFillBases; }
@@ -371,6 +389,10 @@ class Unitigger {
   size_t _gapKmer = 31, _gapMinCount = 3, _gapSlack = 100, _gapMaxFill = 10000;
   std::string _gapsOut;
   uint64_t _gaps = 0, _gapsFilled = 0, _gapFillBases = 0, _gapBasesLeft = 0;
+  bool _join = false;
+  size_t _joinMinOverlap = 16, _joinMaxOverlap = 1000, _joinSlack = 100, _joinKmer = 31, _joinMinCount = 3;
+  std::string _joinsOut;
+  uint64_t _joinGaps = 0, _joinsMade = 0, _joinOverlapBases = 0, _joinNRemoved = 0;
   std::string _error;
 };
 

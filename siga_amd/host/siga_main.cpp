@@ -596,7 +596,22 @@ static int unitig_help() {
          "          --gap-max-fill=N             leave gaps estimated above N bases alone (default: 10000)\n"
          "          --gaps=FILE                  also write one line per gap to FILE: GP, scaffold, the two unitigs, the bases laid, the\n"
          "                                       gap's class, the two walks' outcomes, + or - for the walk that filled it, the fill, the\n"
-         "                                       offset at which the gap starts\n"
+         "                                       offset at which the gap starts; with --join-overlaps the offsets are still those of\n"
+         "                                       the gap filling, before any join\n"
+         "\n"
+         "Overlap joining parameters (they need --scaffold):\n"
+         "          --join-overlaps              after the scaffolds are laid, and after --gapfill if given: where the last v bases of a\n"
+         "                                       unitig are the first v of the next for exactly one v, and the reads support the sequence\n"
+         "                                       across the junction, drop the N between them and one copy of the overlap; every header\n"
+         "                                       gains joined=<gaps joined>, and the layout's gap before becomes signed, -v for a joined pair\n"
+         "          --join-min-overlap=N         the shortest overlap looked for, 8 to 4096 (default: 16)\n"
+         "          --join-max-overlap=N         the longest, up to 4096 (default: 1000)\n"
+         "          --join-slack=N               leave gaps of more than N bases alone (default: 100)\n"
+         "          --join-kmer=K                the k of the support test, 8 to 128 (default: 31)\n"
+         "          --join-min-count=N           every k-mer across a junction must occur N times in the reads, either strand (default: 3)\n"
+         "          --joins=FILE                 also write one line per gap to FILE: JN, scaffold, the two unitigs, the bases laid, the\n"
+         "                                       gap's class, the overlap, the overlaps that matched, the junction k-mers looked up, the\n"
+         "                                       offset at which the right unitig or the gap now starts\n"
          "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
@@ -623,7 +638,8 @@ static int run_unitig(int argc, char** argv) {
   enum { OPT_NO_RC = 1, OPT_DEVICE, OPT_LAYOUT, OPT_EXHAUSTIVE, OPT_GRAPH, OPT_REMOVED, OPT_CAREFULLY, OPT_CUT_EDGES, OPT_CHIMERIC, OPT_PAIRS, OPT_LINKS,
          OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT, OPT_SCAFFOLD, OPT_SCAFFOLD_LAYOUT, OPT_MIN_PAIRS, OPT_LINK_RATIO,
          OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
-         OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS };
+         OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
+         OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -654,6 +670,10 @@ static int run_unitig(int argc, char** argv) {
                                     {"gap-min-count", required_argument, nullptr, OPT_GAP_MIN_COUNT},
                                     {"gap-slack", required_argument, nullptr, OPT_GAP_SLACK},
                                     {"gap-max-fill", required_argument, nullptr, OPT_GAP_MAX_FILL}, {"gaps", required_argument, nullptr, OPT_GAPS},
+                                    {"join-overlaps", no_argument, nullptr, OPT_JOIN}, {"join-min-overlap", required_argument, nullptr, OPT_JOIN_MIN_OVERLAP},
+                                    {"join-max-overlap", required_argument, nullptr, OPT_JOIN_MAX_OVERLAP},
+                                    {"join-slack", required_argument, nullptr, OPT_JOIN_SLACK}, {"join-kmer", required_argument, nullptr, OPT_JOIN_KMER},
+                                    {"join-min-count", required_argument, nullptr, OPT_JOIN_MIN_COUNT}, {"joins", required_argument, nullptr, OPT_JOINS},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
@@ -665,6 +685,9 @@ static int run_unitig(int argc, char** argv) {
   bool gapfill = false, gapTuned = false;
   size_t gapKmer = 31, gapMinCount = 3, gapSlack = 100, gapMaxFill = 10000;
   std::string gapsOut;
+  bool joinOverlaps = false, joinTuned = false;
+  size_t joinMinOverlap = 16, joinMaxOverlap = 1000, joinSlack = 100, joinKmer = 31, joinMinCount = 3;
+  std::string joinsOut;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
   size_t bubbleSpan = 0, bubbleDivergence = 50;
@@ -739,6 +762,13 @@ static int run_unitig(int argc, char** argv) {
       case OPT_GAP_SLACK: if (!unitig_number(optarg, "--gap-slack", 0x7FFFFFFFull, &gapSlack)) return 1; gapTuned = true; break;
       case OPT_GAP_MAX_FILL: if (!unitig_number(optarg, "--gap-max-fill", 0x7FFFFFFFull, &gapMaxFill)) return 1; gapTuned = true; break;
       case OPT_GAPS: gapsOut = optarg; gapTuned = true; break;
+      case OPT_JOIN: joinOverlaps = true; break;
+      case OPT_JOIN_MIN_OVERLAP: if (!unitig_number(optarg, "--join-min-overlap", 4096, &joinMinOverlap) || joinMinOverlap < 8) return 1; joinTuned = true; break;
+      case OPT_JOIN_MAX_OVERLAP: if (!unitig_number(optarg, "--join-max-overlap", 4096, &joinMaxOverlap) || joinMaxOverlap < 8) return 1; joinTuned = true; break;
+      case OPT_JOIN_SLACK: if (!unitig_number(optarg, "--join-slack", 0x7FFFFFFFull, &joinSlack)) return 1; joinTuned = true; break;
+      case OPT_JOIN_KMER: if (!unitig_number(optarg, "--join-kmer", 128, &joinKmer) || joinKmer < 8) return 1; joinTuned = true; break;
+      case OPT_JOIN_MIN_COUNT: if (!unitig_number(optarg, "--join-min-count", 0xFFFFFFFFull, &joinMinCount) || joinMinCount == 0) return 1; joinTuned = true; break;
+      case OPT_JOINS: joinsOut = optarg; joinTuned = true; break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -804,6 +834,18 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: --gapfill needs --scaffold: it fills the gaps of the scaffolds\n");
     return 1;
   }
+  if (!joinOverlaps && joinTuned) {
+    fprintf(stderr, "siga unitig: --join-min-overlap, --join-max-overlap, --join-slack, --join-kmer, --join-min-count and --joins need --join-overlaps\n");
+    return 1;
+  }
+  if (joinOverlaps && scaffoldOut.empty()) {
+    fprintf(stderr, "siga unitig: --join-overlaps needs --scaffold: it joins the neighbours of the scaffolds\n");
+    return 1;
+  }
+  if (joinOverlaps && joinMaxOverlap < joinMinOverlap) {
+    fprintf(stderr, "siga unitig: --join-max-overlap %zu is below --join-min-overlap %zu\n", joinMaxOverlap, joinMinOverlap);
+    return 1;
+  }
   if (maxGap < minGap) {
     fprintf(stderr, "siga unitig: --max-gap %zu is below --min-gap %zu\n", maxGap, minGap);
     return 1;
@@ -829,6 +871,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setPairs(pairsOut, linksOut, maxSpan, outward, pairsBins, pairsShift);
   unitigger.setScaffold(scaffoldOut, scaffoldLayout, minPairs, linkRatio, minScaffoldUnitig, haveInsertSize ? (long long)insertSize : -1, minGap, maxGap);
   unitigger.setGapfill(gapfill, gapKmer, gapMinCount, gapSlack, gapMaxFill, gapsOut);
+  unitigger.setJoinOverlaps(joinOverlaps, joinMinOverlap, joinMaxOverlap, joinSlack, joinKmer, joinMinCount, joinsOut);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -857,6 +900,9 @@ static int run_unitig(int argc, char** argv) {
   if (gapfill)
     fprintf(stderr, "%llu gaps, %llu filled with %llu bases, %llu N left\n", (unsigned long long)unitigger.gaps(), (unsigned long long)unitigger.gapsFilled(),
             (unsigned long long)unitigger.gapFillBases(), (unsigned long long)unitigger.gapBasesLeft());
+  if (joinOverlaps)
+    fprintf(stderr, "%llu gaps looked at, %llu joined over %llu overlap bases, %llu N removed\n", (unsigned long long)unitigger.joinGaps(),
+            (unsigned long long)unitigger.joinsMade(), (unsigned long long)unitigger.joinOverlapBases(), (unsigned long long)unitigger.joinNRemoved());
   return 0;
 }
 

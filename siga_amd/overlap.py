@@ -488,6 +488,48 @@ def scaffolds_gapfill(pair, res, scaf, k=31, min_count=3, slack=100, max_fill=10
     return out
 
 
+def scaffolds_join(pair, res, scaf, min_overlap=16, max_overlap=1000, slack=100, k=31, min_count=3, bases=True):
+    """Neighbours of a scaffold that overlap written as one sequence (sigax_join_host, the rules in include/sigax.h): `pair` is
+    the FMIndexPair of the reads (the forward strand is enough), `res` the dict of the unitig call (seq_offs, for the unitigs'
+    lengths), `scaf` the dict `unitigs_scaffold` or `scaffolds_gapfill` returned over it, with its bases.  A gap of at most slack
+    N is joined when exactly one length v in min_overlap .. max_overlap makes the left neighbour's last v bases the right
+    neighbour's first v and every k-mer across the junction occurs min_count times in the reads (either strand); the N and one
+    copy of the overlap then go.  -> the dict shape of `unitigs_scaffold` (sc_lay_offs and sc_flags as they came in, status
+    u64[16] named by _lib.JOIN_STATUS) plus joins, one _lib.JOIN_DTYPE record per gap in scaffold order: its class
+    (_lib.JOIN_CLASSES), the overlap, how many lengths matched, the junction windows looked up and where the gap lies now."""
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    u = len(so) - 1
+    sco = np.ascontiguousarray(scaf["sc_offs"], dtype=np.uint64)
+    slo = np.ascontiguousarray(scaf["sc_lay_offs"], dtype=np.uint64)
+    lay = np.ascontiguousarray(scaf["layout"], dtype=PLACEMENT_DTYPE)
+    s = len(slo) - 1
+    if s < 0 or len(sco) != s + 1 or len(lay) < int(slo[s]):
+        raise ValueError("sc_offs, sc_lay_offs and layout do not fit each other")
+    if scaf.get("seqs") is None:
+        raise ValueError("the overlaps are looked for in the scaffold bases (scaf['seqs'])")
+    sq = scaf["seqs"]
+    sq = np.frombuffer(bytes(sq), dtype=np.uint8) if isinstance(sq, (bytes, bytearray)) else np.ascontiguousarray(sq, dtype=np.uint8)
+    if len(sq) < int(sco[s]):
+        raise ValueError("seqs shorter than sc_offs says")
+    L = _lib.lib()
+    opts = _lib.JoinOpts(0, int(min_overlap), int(max_overlap), int(slack), int(k), int(min_count), 0)
+    po, play, ps, pj = (C.c_void_p() for _ in range(4))
+    nj = C.c_uint64()
+    st = np.zeros(16, dtype=np.uint64)
+    _check(L.sigax_join_host(pair.handle, u, so.ctypes.data, s, sco.ctypes.data, slo.ctypes.data, lay.ctypes.data if len(lay) else None,
+                             sq.ctypes.data if len(sq) else None, C.byref(opts), C.byref(po), C.byref(play), C.byref(ps) if bases else None,
+                             C.byref(pj), C.byref(nj), st.ctypes.data), "sigax_join_host")
+    try:
+        out = {"sc_offs": _copy_records(po, s + 1, np.dtype(np.uint64)), "sc_lay_offs": slo.copy(),
+               "sc_flags": np.array(scaf["sc_flags"], dtype=np.uint32), "layout": _copy_records(play, int(slo[s]) if u else 0, PLACEMENT_DTYPE),
+               "status": st, "joins": _copy_records(pj, int(nj.value), _lib.JOIN_DTYPE)}
+        out["seqs"] = _copy_records(ps, int(st[11]), np.dtype(np.uint8)) if bases else None
+    finally:
+        for p in (po, play, ps, pj):
+            L.sigax_free(p)
+    return out
+
+
 class ShardedResult(tuple):
     """What OverlapBuilder.overlap_sharded returns: the pair (edges, substring), which also answers to those two names as
     the result of `overlap` does -- `format_asqg` takes it as it is."""
