@@ -427,6 +427,19 @@ def many_gaps(count, k=15):
     return case("gaps_%d" % count, k, g, tuple(tile(g, k, seed=count)), [pieces, tail], {"slack": 10})
 
 
+@functools.lru_cache(maxsize=None)
+def long_fill(k):
+    """two gaps of 5000 true bases laid as 4950 (max_fill 10000, slack 100): the first filled forward; at the second a fork of
+    min_count reads at the forward start, so that only the reverse walk fills it.  A walk writes, and the bases pass copies, a fill
+    over hundreds of 16-byte pieces"""
+    n, f = 2 * k + 40, 5000
+    a0 = 200
+    g = genome(k, 9, a0 + 3 * n + 2 * f + 400)
+    b1, b2 = a0 + n + f, a0 + 2 * n + 2 * f
+    reads = tuple(tile(g, k, seed=50 + k, step=10) + fork_reads(g, k, b1 + n, 3, seed=k))
+    return case("long_fill", k, g, reads, [[(a0, a0 + n, False, f - 50), (b1, b1 + n, True, f - 50), (b2, b2 + n, False, None)]], seed=k)
+
+
 def random_case(seed):
     rng = random.Random(seed)
     k = rng.choice(KS)
@@ -464,6 +477,7 @@ def random_case(seed):
 def all_cases():
     out = [c for k in KS for c in hand_built(k)]
     out += [many_gaps(70, 15), many_gaps(300, 15), many_gaps(70, 31)]
+    out += [long_fill(31), long_fill(128)]
     out += [random_case(s) for s in range(100)]
     return out
 

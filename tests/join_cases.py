@@ -327,19 +327,96 @@ def hand_built(k):
 
 
 @functools.lru_cache(maxsize=None)
-def many_gaps(count, k=15):
+def many_gaps(count, k=15, step=4, depth=3, min_count=3, hole_under=None):
     """`count` gaps in one scaffold and a second scaffold behind it: pieces of 20 .. 60 bases, overlaps of 8 .. 19, now and then a
-    true gap"""
+    true gap.  step, depth: the tiling; min_count: the support asked for; hole_under = i: no read holds the last base of piece i,
+    which every window across the junction of gap i holds.  The pieces and the genome do not depend on the four"""
     rng = random.Random(count)
     at, pieces = 50, []
     for i in range(count + 1):
         ln = 20 + rng.randrange(41)
-        step = -rng.randrange(8, 20) if rng.random() < 0.8 else rng.randrange(0, 6)
-        pieces.append((at, at + ln, rng.random() < 0.5, max(1, step + rng.randrange(0, 4)) if i < count else None))
-        at += ln + step
+        over = -rng.randrange(8, 20) if rng.random() < 0.8 else rng.randrange(0, 6)
+        pieces.append((at, at + ln, rng.random() < 0.5, max(1, over + rng.randrange(0, 4)) if i < count else None))
+        at += ln + over
     g = genome(k, 200 + count, at + 400)
     tail = two(at + 100, 50, 17, 50)[0]
-    return case("gaps_%d" % count, k, g, tuple(tile(g, k, seed=count)), [pieces, tail], {"min_overlap": 8, "slack": 10})
+    drop = None if hole_under is None else pieces[hole_under][1] - 1
+    opts = {"min_overlap": 8, "slack": 10}
+    if min_count != 3:
+        opts["min_count"] = min_count
+    return case("gaps_%d" % count, k, g, tuple(tile(g, k, seed=count, step=step, depth=depth, drop=drop)), [pieces, tail], opts)
+
+
+MATCH_CLASSES = ("JOINED", "NONE", "AMBIGUOUS", "UNSUPPORTED")
+
+
+def came_to_the_match(exp):
+    """the gap numbers of expected_join's dict that came to the match, in the order k_join_list gives them to the match waves"""
+    return [i for i, j in enumerate(exp["joins"]) if CLASSES[j[5]] in MATCH_CLASSES]
+
+
+@functools.lru_cache(maxsize=None)
+def beyond_the_grid(n_cu):
+    """more open gaps than the 16 * n_cu one-wave workgroups of the match and support launches, sparsely tiled, with a hole in the
+    reads under one junction more than 100 open gaps beyond the grid -> (case, its expected result, the gap over the hole)"""
+    grid = 16 * n_cu
+    count = grid + 300
+    kw = dict(step=30, depth=1, min_count=1)
+    exp = case_expected(many_gaps(count, 15, **kw))
+    opened = came_to_the_match(exp)
+    assert len(opened) > grid + 100
+    at = next(i for i in opened[grid + 100:] if exp["joins"][i][5] == C["JOINED"] and exp["joins"][i][7] > 0 and i < count)
+    c = many_gaps(count, 15, hole_under=at, **kw)
+    return c, case_expected(c), at
+
+
+# ---- the match at its limits: ranges of up to 4096 candidates, every LDS word, |M| beyond 255 -----------------------------------------
+@functools.lru_cache(maxsize=None)
+def long_overlaps(k=31):
+    """overlaps of thousands of bases over a genome of 30 kb, sparsely tiled (min_count 1; with v >= k - 1 there are no junction
+    windows, so the reads hardly matter): hi = 4096 by both lengths and by max_overlap, v at, just above and far below hi, v either
+    side of 2048 (where a lane of k_join_match begins to pack a second word), 66 words, a byte outside ACGT deep in a long range,
+    |M| beyond 255 and a tandem repeat whose M has stride 3 over ten turns of the wave"""
+    g = genome(k, 77, 30000)
+    reads = tuple(tile(g, k, seed=1000 + k, step=20, depth=1))
+    key = "long_k%d" % k
+    out = []
+
+    def add(name, scaffolds, opts=None, gen=None, rd=None, **kw):
+        o = dict({"max_overlap": 4096, "min_count": 1}, **(opts or {}))
+        c = case(name, k, g if gen is None else gen, reads if rd is None else rd, scaffolds, o, reads_key=key if rd is None else "%s_k%d" % (name, k),
+                 seed=len(out) + 7 * k, **kw)
+        out.append(c)
+        return c
+
+    a0 = 500
+    add("hi_4096_by_both_lengths", two(a0, 4097, 4096, 4097), v=4096)
+    add("hi_66_words", two(a0, 2200, 2100, 2200), {"max_overlap": 2112}, v=2100)
+    add("last_word_partly_filled", two(a0, 4097, 4095, 4200), v=4095)
+    add("hi_by_max_overlap", two(a0, 6000, 4096, 6000), v=4096)
+    add("v_just_above_hi", two(a0, 6000, 4097, 6000), v=None)
+    for v in (2049, 2048, 2047):
+        add("v_%d" % v, two(a0, 5000, v, 6000), v=v)
+    add("v_in_the_middle", two(a0, 4097, 3000, 4097), v=3000)
+    # a byte outside ACGT at the same place in both copies of the overlap, 3000 bases before L's end and at R's base 3000: the
+    # two ends still agree byte for byte (and both pack to T's code), so only the run of ACGT, found in a far word, keeps v = 4096
+    # from matching.  L's overlap base i lies at 1 + i of the scaffold, R's at 4097 + 5 + i
+    i = 4096 - 3000
+    patch(patch(add("n_far_in_the_tail", two(a0, 4097, 4096, 4097), v=None), 0, 1 + i, b"N"), 0, 4102 + i, b"N")
+    c = add("lower_case_far_in_the_head", two(a0, 4097, 4096, 4097), v=None)
+    low = c["scaf"]["seqs"][4102 + 3000:4103 + 3000].lower()
+    patch(patch(c, 0, 1 + 3000, low), 0, 4102 + 3000, low)
+    # L ends and R begins with 600 bases of one letter: every v in 16 .. 600 matches
+    x = a0 + 700
+    other = lambda b: bytes([next(c for c in b"CGT" if c != b)])
+    gh = g[:x - 1] + other(g[x - 1]) + b"A" * 600 + other(g[x + 600]) + g[x + 601:]
+    rd = tuple(tile(gh, k, seed=1001 + k, step=20, depth=1))
+    add("matches_saturate", [[(a0, x + 600, False, 6), (x, x + 600 + 150, False, None)]], gen=gh, rd=rd, clean=False, matches=255, v=None)
+    # (ACG) x 500: L ends 600 bases into it, R begins 600 bases before its end, so v = 18, 21 .. 600 match and no other
+    gt = g[:x - 1] + (b"T" if g[x - 1:x] != b"T" else b"A") + b"ACG" * 500 + (b"T" if g[x + 1500:x + 1501] != b"T" else b"C") + g[x + 1501:]
+    rd = tuple(tile(gt, k, seed=1002 + k, step=20, depth=1))
+    add("long_tandem_repeat", [[(a0, x + 600, False, 6), (x + 900, x + 1500 + 150, False, None)]], gen=gt, rd=rd, clean=False, matches=195, v=None)
+    return out
 
 
 # ---- random cases: ten read sets, ten cases over each ---------------------------------------------------------------------------------
@@ -416,6 +493,7 @@ def random_case(seed):
 def all_cases():
     out = [c for k in KS for c in hand_built(k)]
     out += [many_gaps(70, 15), many_gaps(300, 15)]
+    out += long_overlaps(31)
     out += [random_case(s) for s in range(100)]
     return out
 

@@ -94,3 +94,13 @@ def test_count_is_the_oracles_occurrences_on_both_strands():
             assert gc.kmer_count(reads, k, w) == idx.occurrences(w) + idx.occurrences(gc.revcomp(w)), (k, w)
             pal += w == gc.revcomp(w)
         assert pal or k % 2
+
+
+@pytest.mark.parametrize("k", [31, 128])
+def test_long_fill(k):
+    c = gc.long_fill(k)
+    exp = gc.case_expected(c)
+    assert c["opts"]["max_fill"] == 10000 and c["opts"]["slack"] == 100
+    assert [g[3:9] for g in exp["gaps"]] == [(4950, 5000, FILLED, FILLED, gc.NOT_RUN, 0), (4950, 5000, FILLED, BRANCH, FILLED, 1)]
+    assert [exp["fills"][i] for i in (0, 1)] == c["truth"] and all(len(t) == 5000 for t in c["truth"])
+    assert c["scaf"]["layout"][1][1] & gc.REV  # the piece between the two fills lies reversed

@@ -202,6 +202,14 @@ def test_random_cases(block):
     _run_cases([gc.random_case(s) for s in range(20 * block, 20 * block + 20)])
 
 
+@pytest.mark.parametrize("k", [31, 128])
+def test_long_fill(k):
+    """fills of 5000 bases, one by the forward and one by the reverse walk: every byte of them is compared (_same)"""
+    c = gc.long_fill(k)
+    _run_cases([c])
+    assert [g[4:6] + g[8:9] for g in gc.case_expected(c)["gaps"]] == [(5000, gc.C["FILLED"], 0), (5000, gc.C["FILLED"], 1)]
+
+
 # ---- other forms of the index, in child processes ----
 def _child(env_extra, ids):
     env = dict(os.environ, **env_extra)

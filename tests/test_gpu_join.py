@@ -142,13 +142,17 @@ def _device(ix, c, what, capacity="exact", nu_dev=None, ns_dev=None, seqs_bytes=
     return exp, got
 
 
-def _host(ix, c, what):
+def _host_call(ix, c):
     import siga_amd
-    exp = jc.case_expected(c)
     o = c["opts"]
     scaf = dict(c["scaf"], layout=np.array([tuple(p) for p in c["scaf"]["layout"]], dtype=siga_amd._lib.PLACEMENT_DTYPE))
-    got = siga_amd.scaffolds_join(ix, c["res"], scaf, min_overlap=o["min_overlap"], max_overlap=o["max_overlap"], slack=o["slack"], k=o["k"],
-                                  min_count=o["min_count"])
+    return siga_amd.scaffolds_join(ix, c["res"], scaf, min_overlap=o["min_overlap"], max_overlap=o["max_overlap"], slack=o["slack"], k=o["k"],
+                                   min_count=o["min_count"])
+
+
+def _host(ix, c, what):
+    exp = jc.case_expected(c)
+    got = _host_call(ix, c)
     _same(got, exp, what + ", host")
     assert got["sc_lay_offs"].tolist() == c["scaf"]["sc_lay_offs"] and got["sc_flags"].tolist() == c["scaf"]["sc_flags"]
     return exp, got
@@ -193,6 +197,38 @@ def test_random_cases(block):
     _run_cases([jc.random_case(s) for s in range(20 * block, 20 * block + 20)], again=True)
 
 
+LIMITS = ("hi_4096_by_both_lengths", "hi_66_words")
+
+
+@pytest.mark.parametrize("part", ["limits", "rest"])
+def test_long_overlaps(part):
+    """k_join_match with up to 4096 candidates a gap: all 129 LDS words, lanes that pack two and three words, hi clipped by
+    max_overlap, |M| beyond 255 (tests/join_cases.py::long_overlaps)"""
+    _run_cases([c for c in jc.long_overlaps(31) if (c["kind"] in LIMITS) == (part == "limits")], again=True)
+
+
+def test_more_open_gaps_than_the_match_grid():
+    """16 * n_cu + 300 gaps: the one-wave workgroups of k_join_match and k_join_support take a second gap, the one over the hole
+    in the reads among them"""
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    c, exp, hole = jc.beyond_the_grid(n_cu)
+    opened = jc.came_to_the_match(exp)
+    print("n_cu", n_cu, "gaps", exp["status"][0], "came to the match", len(opened), "windows", exp["status"][13], "hole under gap", hole)
+    assert exp["status"][0] == 16 * n_cu + 301 and len(opened) > 16 * n_cu and exp["status"][13] > 0
+    assert exp["joins"][hole][5] == jc.C["UNSUPPORTED"] and opened.index(hole) >= 16 * n_cu
+    total = exp["status"][11]
+    for both in (False, True):
+        ix = _open(c["reads"], both)
+        try:
+            what = "%s, %s index" % (c["name"], "two-strand" if both else "forward-only")
+            got = _device(ix, c, what, capacity=total, compare=False)[1]
+            _same(got, exp, what + ", device")
+            if both:
+                _same(_host_call(ix, c), exp, what + ", host")
+        finally:
+            ix.close()
+
+
 # ---- other forms of the index, in child processes ----
 def _child(env_extra, ids):
     env = dict(os.environ, **env_extra)
@@ -201,7 +237,7 @@ def _child(env_extra, ids):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 
-SUBSET = ["test_hand_built[15]", "test_hand_built[64]", "test_random_cases[0]"]
+SUBSET = ["test_hand_built[15]", "test_hand_built[64]", "test_random_cases[0]", "test_long_overlaps[limits]"]
 
 
 def test_without_two_step_tables():

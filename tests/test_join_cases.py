@@ -128,3 +128,54 @@ def test_matches_and_windows_against_a_brute_force_count():
                                if not (s + k <= len(L)) and not (s >= len(L) - v))
             checked += 1
     assert checked > 300
+
+
+def test_long_overlaps_show_what_they_are_named_for():
+    cases = jc.long_overlaps(31)
+    by = {c["kind"]: (c, jc.case_expected(c)) for c in cases}
+    for c, exp in by.values():
+        (j,) = exp["joins"]
+        if c["v"] is not None:
+            assert (jc.CLASSES[j[5]], j[4], j[6], j[7]) == ("JOINED", c["v"], 1, 0), (c["name"], j)
+    hi = lambda kind: by[kind][1]["status"][12] + by[kind][0]["opts"]["min_overlap"] - 1
+    assert hi("hi_4096_by_both_lengths") == hi("hi_by_max_overlap") == hi("last_word_partly_filled") == 4096
+    assert hi("hi_66_words") == 2112 and (2112 + 31) // 32 == 66
+    for kind in ("v_just_above_hi", "n_far_in_the_tail", "lower_case_far_in_the_head"):
+        assert (jc.CLASSES[by[kind][1]["joins"][0][5]], hi(kind)) == ("NONE", 4096), kind
+    # without the odd byte, in both copies of the overlap, the two patched cases are the first one; with it the two ends still
+    # agree byte for byte at v = 4096 -- and a packing that gives the odd byte T's code sees T there in both -- so that nothing
+    # but the run of ACGT makes the class NONE
+    first = by["hi_4096_by_both_lengths"][0]["scaf"]["seqs"]
+    for kind, i, what in (("n_far_in_the_tail", 4096 - 3000, b"N"), ("lower_case_far_in_the_head", 3000, None)):
+        s = by[kind][0]["scaf"]["seqs"]
+        L, R = s[:4097], s[4102:4102 + 4097]
+        odd = what or first[4102 + i:4103 + i].lower()
+        assert L[1 + i:2 + i] == R[i:i + 1] == odd and not jc.ACGT.issuperset(odd)
+        assert L[1:] == R[:4096] and L[1:].replace(odd, b"T") == R[:4096].replace(odd, b"T")
+        assert s[:1 + i] + first[1 + i:2 + i] + s[2 + i:4102 + i] + first[4102 + i:4103 + i] + s[4103 + i:] == first
+        assert jc.matches_of(L.replace(odd, b"T"), R.replace(odd, b"T"), 16, 4096) == [4096]
+    # the saturation: more than 255 lengths match, the record says 255
+    for kind, want in (("matches_saturate", list(range(16, 601))), ("long_tandem_repeat", list(range(18, 601, 3)))):
+        c, exp = by[kind]
+        sc, so, lay = c["scaf"], c["res"]["seq_offs"], c["scaf"]["layout"]
+        L, R = (sc["seqs"][p[2]:p[2] + so[p[0] + 1] - so[p[0]]] for p in lay)
+        assert jc.matches_of(L, R, 16, min(4096, len(L) - 1, len(R) - 1)) == want
+        assert exp["joins"][0][5:7] == (jc.C["AMBIGUOUS"], min(len(want), 255)) and exp["joins"][0][6] == c["matches"]
+    assert by["matches_saturate"][1]["joins"][0][6] == 255
+
+
+def test_many_gaps_options_leave_the_pieces_alone():
+    a, b = jc.many_gaps(300), jc.many_gaps(300, 15, step=30, depth=1, min_count=1, hole_under=200)
+    assert a["res"] == b["res"] and a["scaf"] == b["scaf"] and a["genome"] == b["genome"]
+    assert a["opts"]["min_count"] == 3 and b["opts"]["min_count"] == 1 and len(b["reads"]) < len(a["reads"]) // 10
+
+
+def test_more_open_gaps_than_the_match_grid():
+    """16 workgroups a compute unit, 256 compute units on an MI355X (tests/test_gpu_join.py takes the device's own count)"""
+    n_cu = 256
+    c, exp, hole = jc.beyond_the_grid(n_cu)
+    opened = jc.came_to_the_match(exp)
+    print(exp["status"], len(opened), hole)
+    assert exp["status"][0] == 16 * n_cu + 301 and len(opened) > 16 * n_cu
+    assert exp["status"][13] > 0 and sum(1 for i in opened[16 * n_cu:] if exp["joins"][i][7]) > 0  # windows beyond the grid, too
+    assert exp["joins"][hole][5] == jc.C["UNSUPPORTED"] and opened.index(hole) >= 16 * n_cu
