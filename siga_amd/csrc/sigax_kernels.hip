@@ -3222,6 +3222,7 @@ struct GFx {
     for (int k = 0; k < 4; ++k) ntop += pop(__ballot(mine[k] && e[k].len == topLen));
     for (u32 guard = 0; guard < (1u << 20); ++guard) {
       bool odd = false, anyEnd = false;  // a block outside the simple case; a top-level block followed by '$'
+      bool oddTop = false;
       u32 cq[4];
       P newlo[4];
       bool x0[4];
@@ -3234,6 +3235,7 @@ struct GFx {
         const u64 g0 = p0 >> 7;
         if (!(p1 > p0 && ((p1 - 1) >> 7) == g0 && p1 <= ix.n)) {
           odd = true;
+          if (e[k].len == topLen) oddTop = true;  // a top-level block that is not tested for '$' here
           continue;
         }
         const uint4* q = ix.g + g0 * 4;
@@ -3271,6 +3273,9 @@ struct GFx {
       }
       sec_add(nm);
       if (__ballot(anyEnd)) {
+        // a top-level block whose range lies across granules may hold a '$' as well (two reads that end together, one of
+        // them duplicated): taking it for the "substring read" error would drop it, so the general kernel decides
+        if (__ballot(oddTop)) return false;
         // the top-level blocks have ended (:747-766): they are blocks 0 .. ntop-1; the first one without '$' is the
         // "substring read found" error and ends the emission
         u32 fb = ntop;

@@ -27,6 +27,7 @@ def named_reads(name):
     if name in ("toy", "mid"):
         return mr.survey_reads(*GOLDEN[name]["gen"])
     if name == "deep":   # 160x coverage: about 110 blocks per (read, side), beyond one wave's 64 lanes
+        # (items of exactly 16, 32, 64 and 256 blocks and their neighbours: tests/fx_width_cases.py)
         return mr.survey_reads(2500, 100, 4000, 21)
     if name == "tiny":   # 400 x 60 bp from 2 kb, 12x
         return mr.survey_reads(2000, 60, 400, 99)
