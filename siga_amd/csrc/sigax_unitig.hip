@@ -1118,6 +1118,33 @@ void launch_unitigs_t(const ArgsOf<TRIM>& a, hipStream_t st) {
   hipLaunchKernelGGL(k_uni_place<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, fdist);
   if (a.useqs) hipLaunchKernelGGL(k_uni_bases<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a);
 }
+
+// a round's trim step: TRIM = 1 over the trim block, TRIM = 2 over the records that are not cut (never with a.maxlen set: that is a cut step)
+template <int TRIM>
+void launch_trim_round_t(const ArgsOf<TRIM>& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  if constexpr (TRIM == 2)
+    if (a.maxlen) return;
+  const unsigned f = launch_graph<TRIM>(a, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+}
+
+// the lifted records and status[6 .. 11]; TRIM = 2: without the cut records, and status[12 .. 15]
+template <int TRIM>
+void launch_lift_t(const ArgsOf<TRIM>& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  if (a.uedges && a.n_edges) {
+    hipLaunchKernelGGL(k_lift_flag<TRIM>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
+    launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
+    hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a));
+  }
+  hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, static_cast<const UnitigTrimArgs&>(a));
+  if constexpr (TRIM == 2) hipLaunchKernelGGL(k_prune_status, dim3(1), dim3(64), 0, st, a);
+}
 }  // namespace
 
 unsigned unitig_rounds(unsigned long long n_reads) {
@@ -1138,25 +1165,9 @@ void launch_unitig_bases(const UnitigArgs& a, hipStream_t st) {
   if (a.n_reads && a.useqs) hipLaunchKernelGGL(k_uni_bases<0>, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a);
 }
 
-void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st) {
-  const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
-  const unsigned f = launch_graph<1>(a, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<1>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
-  hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
-  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
-}
+void launch_trim_round(const UnitigTrimArgs& a, hipStream_t st) { launch_trim_round_t<1>(a, st); }
 
-void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed) return;
-  if (a.uedges && a.n_edges) {
-    hipLaunchKernelGGL(k_lift_flag<1>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
-    launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
-    hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
-  }
-  hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, a);
-}
+void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st) { launch_lift_t<1>(a, st); }
 
 void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
@@ -1172,30 +1183,13 @@ void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_prune_cut, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin);
 }
 
-void launch_prune_trim_round(const UnitigPruneArgs& a, hipStream_t st) {
-  const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.maxlen || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
-  const unsigned f = launch_graph<2>(a, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
-  hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
-  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
-}
+void launch_prune_trim_round(const UnitigPruneArgs& a, hipStream_t st) { launch_trim_round_t<2>(a, st); }
 
 void launch_unitigs_prune(const UnitigPruneArgs& a, hipStream_t st) {
   if (a.n_reads && a.removed && !a.maxlen) launch_unitigs_t<2>(a, st);
 }
 
-void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed) return;
-  if (a.uedges && a.n_edges) {
-    hipLaunchKernelGGL(k_lift_flag<2>, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
-    launch_scan(a.eflag, a.n_edges, a.epartial, a.escan, a.trim + TRIM_LIFTED, st);
-    hipLaunchKernelGGL(k_lift_write, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a));
-  }
-  hipLaunchKernelGGL(k_trim_status, dim3(1), dim3(64), 0, st, static_cast<const UnitigTrimArgs&>(a));
-  hipLaunchKernelGGL(k_prune_status, dim3(1), dim3(64), 0, st, a);
-}
+void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st) { launch_lift_t<2>(a, st); }
 
 void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;

@@ -142,82 +142,52 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
   }
-  if (_bubbleSpan > 0) {
-    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
-    if (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll)
-      return fail("chimeric length, delta or coverage out of range");
-    if (_bubbleSpan > 0xFFFFFFFFull || _bubbleDivergence >= (long)0xFFFFFFFFll) return fail("bubble span or divergence out of range");
-    sigax_bubble_opts opts;
-    sigax_prune_opts& po = opts.chimeric.prune;
-    po.max_rounds = (uint32_t)_rounds;
-    po.min_branch_length = (uint32_t)_minBranchLength;
-    po.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
-    po.delta = (uint32_t)_delta;
-    po.careful = _careful ? 1u : 0u;
-    po.reserved = 0;
-    po.num_reads = _numReads ? _numReads : n;
-    po.genome_size = _genomeSize;
-    po.uniq_threshold = _uniqThreshold;
-    opts.chimeric.min_chimeric_length = (uint32_t)_chimLength;
-    opts.chimeric.min_chimeric_coverage = _chimCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_chimCoverage;
-    opts.chimeric.chimeric_delta = (uint32_t)_chimDelta;
-    opts.chimeric.reserved2 = 0;
-    opts.chimeric.chimeric_threshold = _chimThreshold;
-    opts.max_bubble_span = (uint32_t)_bubbleSpan;
-    opts.max_divergence_permille = _bubbleDivergence < 0 ? SIGAX_BUBBLE_NO_BASES : (uint32_t)_bubbleDivergence;
-    opts.reserved3[0] = opts.reserved3[1] = 0;
+  // the steps asked for: each call is the one before it with one more step in its rounds, and more scratch
+  const int level = _bubbleSpan > 0 ? 4 : _chimLength > 0 ? 3 : _delta > 0 ? 2 : trim ? 1 : 0;
+  if (level >= 2 && _delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
+  if (level >= 3 && (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll))
+    return fail("chimeric length, delta or coverage out of range");
+  if (level >= 4 && (_bubbleSpan > 0xFFFFFFFFull || _bubbleDivergence >= (long)0xFFFFFFFFll)) return fail("bubble span or divergence out of range");
+  sigax_bubble_opts opts;
+  sigax_chimeric_opts& co = opts.chimeric;
+  sigax_prune_opts& po = co.prune;
+  po.max_rounds = (uint32_t)_rounds;
+  po.min_branch_length = (uint32_t)_minBranchLength;
+  po.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
+  po.delta = (uint32_t)_delta;
+  po.careful = _careful ? 1u : 0u;
+  po.reserved = 0;
+  po.num_reads = _numReads ? _numReads : n;
+  po.genome_size = _genomeSize;
+  po.uniq_threshold = _uniqThreshold;
+  co.min_chimeric_length = (uint32_t)_chimLength;
+  co.min_chimeric_coverage = _chimCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_chimCoverage;
+  co.chimeric_delta = (uint32_t)_chimDelta;
+  co.reserved2 = 0;
+  co.chimeric_threshold = _chimThreshold;
+  opts.max_bubble_span = (uint32_t)_bubbleSpan;
+  opts.max_divergence_permille = _bubbleDivergence < 0 ? SIGAX_BUBBLE_NO_BASES : (uint32_t)_bubbleDivergence;
+  opts.reserved3[0] = opts.reserved3[1] = 0;
+  sigax_edge** const uedges = _graph.empty() ? nullptr : &u.uedges;
+  if (level == 4) {
     if (sigax_unitigs_bubble_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
                                   (uint32_t)minOverlap, &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
-                                  _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+                                  uedges, status) != SIGAX_OK)
       return fail(std::string("unitig failed: ") + sigax_last_error());
-  } else if (_chimLength > 0) {
-    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
-    if (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll)
-      return fail("chimeric length, delta or coverage out of range");
-    sigax_chimeric_opts opts;
-    opts.prune.max_rounds = (uint32_t)_rounds;
-    opts.prune.min_branch_length = (uint32_t)_minBranchLength;
-    opts.prune.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
-    opts.prune.delta = (uint32_t)_delta;
-    opts.prune.careful = _careful ? 1u : 0u;
-    opts.prune.reserved = 0;
-    opts.prune.num_reads = _numReads ? _numReads : n;
-    opts.prune.genome_size = _genomeSize;
-    opts.prune.uniq_threshold = _uniqThreshold;
-    opts.min_chimeric_length = (uint32_t)_chimLength;
-    opts.min_chimeric_coverage = _chimCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_chimCoverage;
-    opts.chimeric_delta = (uint32_t)_chimDelta;
-    opts.reserved2 = 0;
-    opts.chimeric_threshold = _chimThreshold;
+  } else if (level == 3) {
     if (sigax_unitigs_chimeric_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
-                                    (uint32_t)minOverlap, &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
-                                    _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+                                    (uint32_t)minOverlap, &co, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                    uedges, status) != SIGAX_OK)
       return fail(std::string("unitig failed: ") + sigax_last_error());
-  } else if (_delta > 0) {
-    if (_delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
-    sigax_prune_opts opts;
-    opts.max_rounds = (uint32_t)_rounds;
-    opts.min_branch_length = (uint32_t)_minBranchLength;
-    opts.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
-    opts.delta = (uint32_t)_delta;
-    opts.careful = _careful ? 1u : 0u;
-    opts.reserved = 0;
-    opts.num_reads = _numReads ? _numReads : n;
-    opts.genome_size = _genomeSize;
-    opts.uniq_threshold = _uniqThreshold;
+  } else if (level == 2) {
     if (sigax_unitigs_prune_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,
-                                 &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
-                                 _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+                                 &po, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut, uedges,
+                                 status) != SIGAX_OK)
       return fail(std::string("unitig failed: ") + sigax_last_error());
-  } else if (trim) {
-    sigax_trim_opts opts;
-    opts.max_rounds = (uint32_t)_rounds;
-    opts.min_branch_length = (uint32_t)_minBranchLength;
-    opts.min_branch_coverage = _minBranchCoverage < 0 ? SIGAX_TRIM_NO_COVERAGE : (uint32_t)_minBranchCoverage;
-    opts.reserved = 0;
+  } else if (level == 1) {
+    const sigax_trim_opts to = {po.max_rounds, po.min_branch_length, po.min_branch_coverage, 0};
     if (sigax_unitigs_trim_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,
-                                &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed,
-                                _graph.empty() ? nullptr : &u.uedges, status) != SIGAX_OK)
+                                &to, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, uedges, status) != SIGAX_OK)
       return fail(std::string("unitig failed: ") + sigax_last_error());
   } else {
     if (sigax_unitigs_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n, (uint32_t)minOverlap,

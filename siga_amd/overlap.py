@@ -104,13 +104,8 @@ def _copy_records(ptr, n, dtype):
     return out
 
 
-def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
-    """Unbranched chains of overlaps compacted (sigax_unitigs_host, the rules in include/sigax.h): `edges` EDGE_DTYPE records
-    of an overlap run, reads as lengths u32[n], bases `seqs` (bytes or uint8 array) and offs u64[n+1] by read id -> dict(
-    seq_offs u64[U+1], lay_offs u64[U+1], uflags u32[U], layout PLACEMENT_DTYPE[n], useqs uint8 array (None with
-    bases=False), status u64[6]).  Unitig u is useqs[seq_offs[u]:seq_offs[u+1]], its reads layout[lay_offs[u]:lay_offs[u+1]];
-    uflags & SIGAX_UNITIG_CIRCULAR marks a cycle, uflags >> 1 is its closing overlap.  status = {unitigs, unitig bases,
-    records ignored as malformed, records below min_overlap, simple records merged, cycles}.  Needs no index."""
+def _unitig_arrays(edges, lengths, seqs, offs):
+    """The read set and records of a `unitigs*` call as the library takes them -> (edges, lengths, bases buffer, offs, n)."""
     edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
     lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
     offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -119,13 +114,24 @@ def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
         raise ValueError("offs must have len(lengths) + 1 entries")
     if isinstance(seqs, np.ndarray):
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
+        buf = (C.c_char_p(seqs.ctypes.data) if seqs.size else b""), seqs  # (the array is kept alive with its pointer)
     else:
-        buf = bytes(seqs)
+        buf = bytes(seqs), None
+    return edges, lengths, buf, offs, n
+
+
+def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
+    """Unbranched chains of overlaps compacted (sigax_unitigs_host, the rules in include/sigax.h): `edges` EDGE_DTYPE records
+    of an overlap run, reads as lengths u32[n], bases `seqs` (bytes or uint8 array) and offs u64[n+1] by read id -> dict(
+    seq_offs u64[U+1], lay_offs u64[U+1], uflags u32[U], layout PLACEMENT_DTYPE[n], useqs uint8 array (None with
+    bases=False), status u64[6]).  Unitig u is useqs[seq_offs[u]:seq_offs[u+1]], its reads layout[lay_offs[u]:lay_offs[u+1]];
+    uflags & SIGAX_UNITIG_CIRCULAR marks a cycle, uflags >> 1 is its closing overlap.  status = {unitigs, unitig bases,
+    records ignored as malformed, records below min_overlap, simple records merged, cycles}.  Needs no index."""
+    edges, lengths, buf, offs, n = _unitig_arrays(edges, lengths, seqs, offs)
     L = _lib.lib()
     nu = C.c_uint64()
     so, lo, uf, lay, us = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    _check(L.sigax_unitigs_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
+    _check(L.sigax_unitigs_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf[0],
                                 offs.ctypes.data, n, int(min_overlap), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf), C.byref(lay),
                                 C.byref(us) if bases else None), "sigax_unitigs_host")
     try:
@@ -141,6 +147,55 @@ def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
     return out
 
 
+def _rounds_opts(level, n, max_rounds, min_branch_length, min_branch_coverage, delta=0, careful=False, num_reads=None, genome_size=None,
+                 uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None, chimeric_delta=0, chimeric_threshold=0.0,
+                 max_bubble_span=0, bubble_divergence=50):
+    """The options object of the rounds call `level` ("trim", "prune", "chimeric" or "bubble") over n reads."""
+    none = _lib.SIGAX_TRIM_NO_COVERAGE
+    branch = (int(max_rounds), int(min_branch_length), none if min_branch_coverage is None else int(min_branch_coverage))
+    if level == "trim":
+        return _lib.TrimOpts(*branch, 0)
+    opts = _lib.PruneOpts(*branch, int(delta), int(careful), 0, n if num_reads is None else int(num_reads),
+                          0 if genome_size is None else int(genome_size), float(uniq_threshold))
+    if level == "prune":
+        return opts
+    opts = _lib.ChimericOpts(opts, int(min_chimeric_length), none if min_chimeric_coverage is None else int(min_chimeric_coverage),
+                             int(chimeric_delta), 0, float(chimeric_threshold))
+    if level == "chimeric":
+        return opts
+    return _lib.BubbleOpts(opts, int(max_bubble_span), _lib.SIGAX_BUBBLE_NO_BASES if bubble_divergence is None else int(bubble_divergence),
+                           (C.c_uint32 * 2)(0, 0))
+
+
+def _unitigs_rounds(level, n_status, with_cut, edges, lengths, seqs, offs, min_overlap, graph, bases, device, **opt):
+    """One rounds call through its host entry point sigax_unitigs_<level>_host: the arrays prepared, the options built from
+    `opt`, the call, and its outputs copied into a dict (status u64[n_status]; cut only for a call that has one)."""
+    edges, lengths, buf, offs, n = _unitig_arrays(edges, lengths, seqs, offs)
+    L = _lib.lib()
+    name = "sigax_unitigs_%s_host" % level
+    opts = _rounds_opts(level, n, **opt)
+    nu = C.c_uint64()
+    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
+    status = np.zeros(n_status, dtype=np.uint64)
+    _check(getattr(L, name)(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf[0],
+                            offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf),
+                            C.byref(lay), C.byref(us) if bases else None, C.byref(rm), *([C.byref(ct)] if with_cut else []),
+                            C.byref(ue) if graph else None, status.ctypes.data), name)
+    try:
+        u = int(nu.value)
+        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
+               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32))}
+        if with_cut:
+            out["cut"] = _copy_records(ct, len(edges), np.dtype(np.uint32))
+        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
+        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
+        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
+    finally:
+        for p in (so, lo, uf, lay, us, rm, ct, ue):
+            L.sigax_free(p)
+    return out
+
+
 def unitigs_trim(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, graph=True, bases=True,
                  device=0):
     """`unitigs` after tip trimming, with the graph between the unitigs (sigax_unitigs_trim_host, the rules in include/sigax.h):
@@ -150,38 +205,8 @@ def unitigs_trim(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch
     that were not merged, over unitig ids and unitig ends; None with graph=False) and status u64[12]: the six counts of
     `unitigs`, then {rounds that removed something, islands, dead ends, reads removed, kept records dropped with a removed
     read, lifted records}.  max_rounds = 0 is `unitigs` itself."""
-    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-    offs = np.ascontiguousarray(offs, dtype=np.uint64)
-    n = len(lengths)
-    if len(offs) != n + 1:
-        raise ValueError("offs must have len(lengths) + 1 entries")
-    if isinstance(seqs, np.ndarray):
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
-    else:
-        buf = bytes(seqs)
-    L = _lib.lib()
-    opts = _lib.TrimOpts(int(max_rounds), int(min_branch_length),
-                         _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), 0)
-    nu = C.c_uint64()
-    so, lo, uf, lay, us, rm, ue = (C.c_void_p() for _ in range(7))
-    status = np.zeros(12, dtype=np.uint64)
-    _check(L.sigax_unitigs_trim_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
-                                     offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf),
-                                     C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ue) if graph else None,
-                                     status.ctypes.data), "sigax_unitigs_trim_host")
-    try:
-        u = int(nu.value)
-        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
-               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32))}
-        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
-        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
-        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
-    finally:
-        for p in (so, lo, uf, lay, us, rm, ue):
-            L.sigax_free(p)
-    return out
+    return _unitigs_rounds("trim", 12, False, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage)
 
 
 def unitigs_prune(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
@@ -192,40 +217,9 @@ def unitigs_prune(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branc
     unitig is among the longest.  delta = 0 is `unitigs_trim`.  num_reads=None: len(lengths).  -> the dict of `unitigs_trim` plus
     cut u32[n_edges] (0, or the round a record was cut in); status u64[16]: as there with 6 = rounds that changed something,
     then {records cut, rounds that cut, unique unitigs seen by the first cut step, 0}."""
-    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-    offs = np.ascontiguousarray(offs, dtype=np.uint64)
-    n = len(lengths)
-    if len(offs) != n + 1:
-        raise ValueError("offs must have len(lengths) + 1 entries")
-    if isinstance(seqs, np.ndarray):
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
-    else:
-        buf = bytes(seqs)
-    L = _lib.lib()
-    opts = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
-                          _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
-                          n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
-    nu = C.c_uint64()
-    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
-    status = np.zeros(16, dtype=np.uint64)
-    _check(L.sigax_unitigs_prune_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
-                                      offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo), C.byref(uf),
-                                      C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct), C.byref(ue) if graph else None,
-                                      status.ctypes.data), "sigax_unitigs_prune_host")
-    try:
-        u = int(nu.value)
-        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
-               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
-               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
-        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
-        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
-        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
-    finally:
-        for p in (so, lo, uf, lay, us, rm, ct, ue):
-            L.sigax_free(p)
-    return out
+    return _unitigs_rounds("prune", 16, True, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage, delta=delta, careful=careful,
+                           num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold)
 
 
 def unitigs_chimeric(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
@@ -237,43 +231,10 @@ def unitigs_chimeric(edges, lengths, seqs, offs, min_overlap, max_rounds, min_br
     unique under chimeric_threshold and every other unitig at that end is longer by more than chimeric_delta, or holds more than
     three reads more.  min_chimeric_length = 0 is `unitigs_prune`.  -> its dict; removed carries _lib.SIGAX_REMOVED_CHIMERIC on
     the reads a chimeric step removed; status u64[20]: as there, then {chimeric unitigs, their reads, rounds with one, 0}."""
-    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-    offs = np.ascontiguousarray(offs, dtype=np.uint64)
-    n = len(lengths)
-    if len(offs) != n + 1:
-        raise ValueError("offs must have len(lengths) + 1 entries")
-    if isinstance(seqs, np.ndarray):
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
-    else:
-        buf = bytes(seqs)
-    L = _lib.lib()
-    prune = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
-                           _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
-                           n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
-    opts = _lib.ChimericOpts(prune, int(min_chimeric_length),
-                             _lib.SIGAX_TRIM_NO_COVERAGE if min_chimeric_coverage is None else int(min_chimeric_coverage), int(chimeric_delta), 0,
-                             float(chimeric_threshold))
-    nu = C.c_uint64()
-    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
-    status = np.zeros(20, dtype=np.uint64)
-    _check(L.sigax_unitigs_chimeric_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
-                                         offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo),
-                                         C.byref(uf), C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct),
-                                         C.byref(ue) if graph else None, status.ctypes.data), "sigax_unitigs_chimeric_host")
-    try:
-        u = int(nu.value)
-        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
-               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
-               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
-        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
-        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
-        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
-    finally:
-        for p in (so, lo, uf, lay, us, rm, ct, ue):
-            L.sigax_free(p)
-    return out
+    return _unitigs_rounds("chimeric", 20, True, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage, delta=delta, careful=careful,
+                           num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
+                           min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold)
 
 
 def unitigs_bubble(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
@@ -285,45 +246,11 @@ def unitigs_bubble(edges, lengths, seqs, offs, min_overlap, max_rounds, min_bran
     another goes where its bases differ from the winner's in at most bubble_divergence per mille of that window (None: no bases
     test).  max_bubble_span = 0 is `unitigs_chimeric`.  -> its dict; removed carries _lib.SIGAX_REMOVED_BUBBLE on the reads a bubble
     step removed; status u64[24]: as there, then {arms popped, their reads, rounds with one, losers kept on divergence}."""
-    edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-    offs = np.ascontiguousarray(offs, dtype=np.uint64)
-    n = len(lengths)
-    if len(offs) != n + 1:
-        raise ValueError("offs must have len(lengths) + 1 entries")
-    if isinstance(seqs, np.ndarray):
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        buf = C.c_char_p(seqs.ctypes.data) if seqs.size else b""
-    else:
-        buf = bytes(seqs)
-    L = _lib.lib()
-    prune = _lib.PruneOpts(int(max_rounds), int(min_branch_length),
-                           _lib.SIGAX_TRIM_NO_COVERAGE if min_branch_coverage is None else int(min_branch_coverage), int(delta), int(careful), 0,
-                           n if num_reads is None else int(num_reads), 0 if genome_size is None else int(genome_size), float(uniq_threshold))
-    chim = _lib.ChimericOpts(prune, int(min_chimeric_length),
-                             _lib.SIGAX_TRIM_NO_COVERAGE if min_chimeric_coverage is None else int(min_chimeric_coverage), int(chimeric_delta), 0,
-                             float(chimeric_threshold))
-    opts = _lib.BubbleOpts(chim, int(max_bubble_span), _lib.SIGAX_BUBBLE_NO_BASES if bubble_divergence is None else int(bubble_divergence),
-                           (C.c_uint32 * 2)(0, 0))
-    nu = C.c_uint64()
-    so, lo, uf, lay, us, rm, ct, ue = (C.c_void_p() for _ in range(8))
-    status = np.zeros(24, dtype=np.uint64)
-    _check(L.sigax_unitigs_bubble_host(device, edges.ctypes.data if len(edges) else None, len(edges), lengths.ctypes.data if n else None, buf,
-                                       offs.ctypes.data, n, int(min_overlap), C.byref(opts), C.byref(nu), C.byref(so), C.byref(lo),
-                                       C.byref(uf), C.byref(lay), C.byref(us) if bases else None, C.byref(rm), C.byref(ct),
-                                       C.byref(ue) if graph else None, status.ctypes.data), "sigax_unitigs_bubble_host")
-    try:
-        u = int(nu.value)
-        out = {"seq_offs": _copy_records(so, u + 1, np.dtype(np.uint64)), "lay_offs": _copy_records(lo, u + 1, np.dtype(np.uint64)),
-               "uflags": _copy_records(uf, u, np.dtype(np.uint32)), "status": status, "removed": _copy_records(rm, n, np.dtype(np.uint32)),
-               "cut": _copy_records(ct, len(edges), np.dtype(np.uint32))}
-        out["layout"] = _copy_records(lay, int(out["lay_offs"][-1]), PLACEMENT_DTYPE)
-        out["useqs"] = _copy_records(us, int(out["seq_offs"][-1]), np.dtype(np.uint8)) if bases else None
-        out["uedges"] = _copy_records(ue, int(status[11]), EDGE_DTYPE) if graph else None
-    finally:
-        for p in (so, lo, uf, lay, us, rm, ct, ue):
-            L.sigax_free(p)
-    return out
+    return _unitigs_rounds("bubble", 24, True, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage, delta=delta, careful=careful,
+                           num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
+                           min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold,
+                           max_bubble_span=max_bubble_span, bubble_divergence=bubble_divergence)
 
 
 def mates_by_name(names):

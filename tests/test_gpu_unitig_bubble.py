@@ -61,19 +61,28 @@ def _host(case, max_rounds=None, **kw):
 CANARY = 64
 
 
-def _opts(case, max_rounds=None):
+N_STATUS = {"trim": 12, "prune": 16, "chimeric": 20, "bubble": 24}
+
+
+def _opts(case, max_rounds=None, level="bubble"):
     from siga_amd import _lib
     n = len(case["reads"])
-    prune = _lib.PruneOpts(case["x"] if max_rounds is None else max_rounds, case["L"],
-                           _lib.SIGAX_TRIM_NO_COVERAGE if case["C"] is None else case["C"], case["delta"], int(case["careful"]), 0,
-                           n if case["N"] is None else case["N"], case["G"] or 0, case["T"])
+    x, cov = case["x"] if max_rounds is None else max_rounds, _lib.SIGAX_TRIM_NO_COVERAGE if case["C"] is None else case["C"]
+    if level == "trim":
+        return _lib.TrimOpts(x, case["L"], cov, 0)
+    prune = _lib.PruneOpts(x, case["L"], cov, case["delta"], int(case["careful"]), 0, n if case["N"] is None else case["N"], case["G"] or 0, case["T"])
+    if level == "prune":
+        return prune
     chim = _lib.ChimericOpts(prune, case["Lc"], _lib.SIGAX_TRIM_NO_COVERAGE if case["Ac"] is None else case["Ac"], case["delta_c"], 0, case["Tc"])
+    if level == "chimeric":
+        return chim
     return _lib.BubbleOpts(chim, case["Lb"], _lib.SIGAX_BUBBLE_NO_BASES if case["D"] is None else case["D"], (C.c_uint32 * 2)(0, 0))
 
 
-def _device_call(case, max_rounds=None, layout_only=False, graph=True):
-    """sigax_unitigs_bubble_device over torch buffers, each output buffer of exactly its size plus CANARY bytes of 0xEE -> (dict like
-    the wrapper's, what lies beyond the bytes the call had to write)"""
+def _device_call(case, max_rounds=None, layout_only=False, graph=True, level="bubble"):
+    """sigax_unitigs_bubble_device (or the device form of a lower `level`, over that call's scratch and status block) over torch buffers,
+    each output buffer of exactly its size plus CANARY bytes of 0xEE -> (dict like the wrapper's, what lies beyond the bytes the call had
+    to write)"""
     from siga_amd import _lib
     L = _lib.lib()
     edges, lengths, seqs, offs = uc.arrays(case)
@@ -88,22 +97,23 @@ def _device_call(case, max_rounds=None, layout_only=False, graph=True):
         return torch.full((nbytes + CANARY,), 0xEE, dtype=torch.uint8, device=dev)
 
     wb = C.c_uint64()
-    assert L.sigax_unitigs_bubble_workspace(n, ne, int(graph), int(case["careful"]), C.byref(wb)) == 0
+    ns = N_STATUS[level]
+    assert getattr(L, "sigax_unitigs_%s_workspace" % level)(n, ne, int(graph), *([] if level == "trim" else [int(case["careful"])]), C.byref(wb)) == 0
     d_edges, d_len, d_seqs, d_offs = up(edges), up(lengths), up(seqs), up(offs)
     sizes = {"seq_offs": 8 * (n + 1), "lay_offs": 8 * (n + 1), "uflags": 4 * n, "layout": 16 * n, "useqs": nb, "removed": 4 * n, "cut": 4 * ne,
-             "uedges": 16 * ne, "status": 192, "work": wb.value}
+             "uedges": 16 * ne, "status": 8 * ns, "work": wb.value}
     d = {k: out(v) for k, v in sizes.items()}
-    opts = _opts(case, max_rounds)
+    opts = _opts(case, max_rounds, level)
     torch.cuda.synchronize()
-    rc = L.sigax_unitigs_bubble_device(0, d_edges.data_ptr(), ne, d_len.data_ptr(), d_seqs.data_ptr(), d_offs.data_ptr(), n, case["m"],
-                                       C.byref(opts), d["seq_offs"].data_ptr(), d["lay_offs"].data_ptr(), d["uflags"].data_ptr(),
-                                       d["layout"].data_ptr(), None if layout_only else d["useqs"].data_ptr(), d["removed"].data_ptr(),
-                                       d["cut"].data_ptr(), d["uedges"].data_ptr() if graph else None, d["status"].data_ptr(),
-                                       d["work"].data_ptr(), wb.value, None)
+    rc = getattr(L, "sigax_unitigs_%s_device" % level)(
+        0, d_edges.data_ptr(), ne, d_len.data_ptr(), d_seqs.data_ptr(), d_offs.data_ptr(), n, case["m"], C.byref(opts), d["seq_offs"].data_ptr(),
+        d["lay_offs"].data_ptr(), d["uflags"].data_ptr(), d["layout"].data_ptr(), None if layout_only else d["useqs"].data_ptr(),
+        d["removed"].data_ptr(), *([] if level == "trim" else [d["cut"].data_ptr()]), d["uedges"].data_ptr() if graph else None,
+        d["status"].data_ptr(), d["work"].data_ptr(), wb.value, None)
     assert rc == 0, _lib.last_error()
     torch.cuda.synchronize()
     h = {k: v.cpu().numpy() for k, v in d.items()}
-    status = h["status"][:192].view(np.uint64)
+    status = h["status"][:8 * ns].view(np.uint64)
     u, placed, lifted = int(status[0]), n - int(status[9]), int(status[11])
     assert u <= n and lifted <= ne and int(status[1]) <= nb
     res = {"status": status, "seq_offs": h["seq_offs"][:8 * (u + 1)].view(np.uint64), "lay_offs": h["lay_offs"][:8 * (u + 1)].view(np.uint64),
@@ -221,6 +231,58 @@ def test_lb_0_lc_0_and_delta_0_is_unitigs_trim(case):
     got = _host(bc.with_bubble_keys(case, Lb=0))
     _identical(got, want, 12)
     assert not got["cut"].any() and len(got["cut"]) == len(edges)
+
+
+# ---- a call whose upper steps are off runs as the lower call: the ladder through the device forms ----
+def _ladder(case, upper, lower):
+    """the device form `upper` with its own steps off (the keys of `case` say which) against the device form `lower`: every output byte,
+    the counts beyond the lower call's zero, cut all zero where the lower call has none, every canary"""
+    got, gtails = _device_call(case, level=upper)
+    want, wtails = _device_call(case, level=lower)
+    _untouched(gtails, "%s as %s" % (upper, lower))
+    _untouched(wtails, lower)
+    k = N_STATUS[lower]
+    print(upper, "as", lower, "status", got["status"].tolist(), "expected", want["status"].tolist())
+    assert got["status"][:k].tolist() == want["status"].tolist() and got["status"][k:].tolist() == [0] * (N_STATUS[upper] - k)
+    for key in ("removed", "layout", "seq_offs", "lay_offs", "uflags", "useqs", "uedges"):
+        assert got[key].tobytes() == want[key].tobytes(), key
+    if lower == "trim":
+        assert len(got["cut"]) == len(case["edges"]) and not got["cut"].any()
+    else:
+        assert got["cut"].tobytes() == want["cut"].tobytes()
+    return want
+
+
+@pytest.mark.parametrize("upper", ["bubble", "chimeric", "prune"])
+def test_device_ladder_down_to_trim(upper):
+    case = bc.with_bubble_keys(tc.case_named("cascade"), Lb=0)
+    assert case["Lb"] == 0 and case["Lc"] == 0 and case["delta"] == 0 and len(case["reads"]) <= 60
+    want = _ladder(case, upper, "trim")
+    assert want["status"].tolist() == tc.expected_of("cascade")["status"] and want["status"][6] == 3  # (the rounds did run)
+
+
+def test_device_ladder_bubble_to_chimeric():
+    case = bc.with_bubble_keys(cc.case_named("second_round"), Lb=0)
+    assert case["Lc"] > 0
+    want = _ladder(case, "bubble", "chimeric")
+    assert want["status"].tolist() == cc.expected_of("second_round")["status"] and want["status"][16] > 0
+
+
+def test_device_ladder_chimeric_to_prune():
+    case = bc.with_bubble_keys(pc.case_named("cascade"), Lb=0)
+    assert case["Lc"] == 0 and case["delta"] > 0 and len(case["reads"]) <= 40
+    want = _ladder(case, "chimeric", "prune")
+    assert want["status"].tolist() == pc.expected_of("cascade")["status"] and want["status"][12] > 0
+
+
+def test_last_round_slot():
+    """max_rounds = 64, the most there are: the host form stops after the first idle round, the device form enqueues all 64"""
+    case, exp = bc.case_named("second_round"), bc.expected_of("second_round", 64)
+    assert exp["status"][6] == 2 and exp["status"][20] == 1
+    _same(_host(case, 64), exp, "second_round, host, 64 rounds")
+    res, tails = _device_call(case, 64)
+    _same(res, exp, "second_round, device, 64 rounds")
+    _untouched(tails, "second_round, 64 rounds")
 
 
 @pytest.mark.parametrize("name", ["two_arms", "chains_flipped", "second_round", "three_arms"])

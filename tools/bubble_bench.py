@@ -8,9 +8,11 @@ a `timeout` of its own; a step is not started when the one before it failed:
             median of --steps calls after --warmup: sigax_unitigs_chimeric_device and sigax_unitigs_bubble_device with the same
             options at 1 and 10 rounds, the bubble call with the bases test (--divergence per mille) and without; N = the reads,
             G = --genome, T = 13, Tc = 0, L = Lc = 150, no coverage tests, no cut step, no graph
-            with --ab-lib: also sigax_unitigs_device, _trim_device, _prune_device and _chimeric_device through that library (the
-            parent commit's build) and through this one, over the same buffers, in the order parent, this, this, parent, parent,
-            this; and the chimeric call of the table above is the parent's
+            with --ab-lib: also sigax_unitigs_device, _trim_device, _prune_device, _chimeric_device and _bubble_device (10 rounds,
+            with the bases test) through that library (the parent commit's build) and through this one, over the same buffers, in
+            the order parent, this, this, parent, parent, this; in the same runs the wall-clock time of sigax_unitigs_trim_host and
+            sigax_unitigs_bubble_host over host copies of the same arrays, three calls each (allocation and copies included: reported,
+            no yardstick); and the chimeric call of the table above is the parent's
 Reports per call the time and the counts, the reads the bubble steps removed per round (from removed[]), and derives what a bubble
 step costs: the difference to the chimeric call per enqueued round.  Arms and groups are not counted on the device: status24 holds
 arms popped and losers kept.  One JSON document on stdout (and in --out; the A/B in --ab-out).  Needs a GPU; nothing but this
@@ -25,6 +27,7 @@ import os
 import subprocess
 import sys
 import tempfile
+import time
 
 import numpy as np
 
@@ -108,7 +111,8 @@ def step_measure(args):
                 ms.append(float(t.value))
         return spread(ms)
 
-    OLD = ("sigax_unitigs_device", "sigax_unitigs_trim_device", "sigax_unitigs_prune_device", "sigax_unitigs_chimeric_device")
+    OLD = ("sigax_unitigs_device", "sigax_unitigs_trim_device", "sigax_unitigs_prune_device", "sigax_unitigs_chimeric_device",
+           "sigax_unitigs_bubble_device", "sigax_unitigs_trim_host", "sigax_unitigs_bubble_host", "sigax_free")
     P = None
     if args.ab_lib:
         P = C.CDLL(args.ab_lib)
@@ -178,6 +182,24 @@ def step_measure(args):
             topts = _lib.TrimOpts(10, args.min_branch_length, _lib.SIGAX_TRIM_NO_COVERAGE, 0)
             popts = _lib.PruneOpts(10, args.min_branch_length, _lib.SIGAX_TRIM_NO_COVERAGE, 10, 0, 0, n, args.genome, 13.0)
             copts = _lib.ChimericOpts(popts, args.min_chimeric_length, _lib.SIGAX_TRIM_NO_COVERAGE, 0, 0, 0.0)
+            bopts = _lib.BubbleOpts(copts, args.max_bubble_span, args.divergence, (C.c_uint32 * 2)(0, 0))
+            h_edges = np.zeros(ne, dtype=_lib.EDGE_DTYPE)
+            if ne:
+                assert hip.hipMemcpy(h_edges.ctypes.data, d_edges, 16 * ne, 2) == 0
+
+            def timed_host(X, call, calls=3):
+                """wall clock of a host form, its arrays handed back after the clock has stopped"""
+                ms = []
+                for _ in range(calls):
+                    nu, o, st = C.c_uint64(), [C.c_void_p() for _ in range(7)], np.zeros(24, dtype=np.uint64)
+                    t0 = time.perf_counter()
+                    rc = call(nu, o, st)
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                    assert rc == 0, _lib.last_error()
+                    for q in o:
+                        X.sigax_free(q)
+                return spread(ms)
+
             runs = []
             for order, tree in enumerate(("parent", "this", "this", "parent", "parent", "this"), 1):
                 X = P if tree == "parent" else L
@@ -194,16 +216,28 @@ def step_measure(args):
                                                                                                  args.min_overlap, C.byref(copts), d_so, d_lo, d_uf,
                                                                                                  d_lay, d_us, d_rm, d_ct, None, d_stat, d_work,
                                                                                                  wb.value, stream))
+                run["bubble_device_10_rounds"] = timed(lambda: X.sigax_unitigs_bubble_device(0, d_edges, ne, d_len, d_seqs, d_offs, n,
+                                                                                             args.min_overlap, C.byref(bopts), d_so, d_lo, d_uf,
+                                                                                             d_lay, d_us, d_rm, d_ct, None, d_stat, d_work,
+                                                                                             wb.value, stream))
+                run["trim_host_10_rounds"] = timed_host(X, lambda nu, o, st: X.sigax_unitigs_trim_host(
+                    0, h_edges.ctypes.data, ne, lengths.ctypes.data, C.c_char_p(flat.ctypes.data), offs.ctypes.data, n, args.min_overlap,
+                    C.byref(topts), C.byref(nu), *[C.byref(q) for q in o[:6]], None, st.ctypes.data))
+                run["bubble_host_10_rounds"] = timed_host(X, lambda nu, o, st: X.sigax_unitigs_bubble_host(
+                    0, h_edges.ctypes.data, ne, lengths.ctypes.data, C.c_char_p(flat.ctypes.data), offs.ctypes.data, n, args.min_overlap,
+                    C.byref(bopts), C.byref(nu), *[C.byref(q) for q in o[:7]], None, st.ctypes.data))
                 runs.append(run)
             summary = {}
-            for call in ("unitigs_device", "trim_device_10_rounds", "prune_device_10_rounds", "chimeric_device_10_rounds"):
+            for call in ("unitigs_device", "trim_device_10_rounds", "prune_device_10_rounds", "chimeric_device_10_rounds", "bubble_device_10_rounds",
+                         "trim_host_10_rounds", "bubble_host_10_rounds"):
                 mean = {tree: float(np.mean([r[call]["median_ms"] for r in runs if r["tree"] == tree])) for tree in ("parent", "this")}
                 spreads = [(r[call]["max_ms"] - r[call]["min_ms"]) / r[call]["median_ms"] for r in runs]
                 summary[call] = {"mean_of_medians_ms": mean, "this_over_parent": mean["this"] / mean["parent"],
                                  "largest_spread_of_a_run": max(spreads), "smallest_spread_of_a_run": min(spreads)}
-            out["old_entry_ab"] = {"what": "the four older device entry points through the parent commit's library and through this tree's, over "
+            out["old_entry_ab"] = {"what": "the five device entry points through the parent commit's library and through this tree's, over "
                                            "the same device buffers in one process, HIP events, median of %d calls after %d, in the order "
-                                           "given" % (args.steps, args.warmup), "config": out["config"], "runs": runs, "summary": summary}
+                                           "given; the two host forms over host copies of the same arrays, wall clock, median of 3 calls"
+                                           % (args.steps, args.warmup), "config": out["config"], "runs": runs, "summary": summary}
     finally:
         for q in held:
             hip.hipFree(q)
