@@ -1035,6 +1035,68 @@ int  sigax_join_host(sigax_index*, uint64_t n_unitigs, const uint64_t* seq_offs,
                      const uint64_t* sc_lay_offs, const sigax_placement* sc_layout, const char* sseqs, const sigax_join_opts* opts,
                      uint64_t** sc_offs_out, sigax_placement** sc_layout_out, char** sseqs_out, sigax_join** joins, uint64_t* n_joins,
                      uint64_t status16[16]);
+/* ---- `siga unitig --scaffold --join-overlaps --join-mismatches`: ends that nearly agree (csrc/sigax_join.hip) -------------------------
+ * On reads with errors a unitig's last read often carries a substitution in the stretch no other read of its chain covers, so the
+ * two copies of an overlap differ in a base or two and the byte-exact match of the block above finds nothing.  This pass accepts,
+ * where no length matches exactly, the one length whose two ends differ in a few bases, takes at each differing base the one the
+ * reads support, tests the whole junction for read support and writes the consensus.  The rules are this library's own.
+ * DESIGN.md 9m; the serial restatement is tests/join_approx_cases.py::expected_join_approx.
+ *
+ * Input and preconditions are sigax_join_*'s, with sigax_join_approx_opts {flags = 0, min_overlap, max_overlap, slack, k,
+ * min_count, max_mismatches, mismatch_permille, reserved = 0}, 0 <= max_mismatches <= 16, 1 <= mismatch_permille <= 250; anything
+ * else is SIGAX_E_ARG.  Placements, gaps, G, L, R, lo, hi and the classes MALFORMED, CLOSED, FAR and SHORT are the block above's.
+ *
+ * 1. Exact first.  M0 is the block above's M.  If M0 is not empty, the gap's class, record, support test and output are exactly
+ *    the block above's and mm[g] = 0: no gap that the exact pass classes as anything but NONE changes.  With max_mismatches = 0
+ *    the call equals sigax_join_* in every table, base, record and status[0..15]; mm is zeros and status[16..23] are zero.
+ * 2. Second match, only for |M0| = 0 and max_mismatches >= 1.  hi' = min(hi, |L| / 2, |R| / 2) (integer division: the patches of
+ *    rule 5 then land on disjoint bytes when a unitig is joined on both sides).  d(v) = the number of j in [0, v) with
+ *    L[|L| - v + j] != R[j]; all 2 v bytes must be upper-case ACGT, else v is out.  B(v) = min(max_mismatches, v *
+ *    mismatch_permille / 1000), in u64, the division rounded down.  M1 = {v in [lo, hi'] : d(v) <= B(v)}.  |M1| = 0 gives NONE
+ *    with matches = 0; |M1| >= 2 gives AMBIGUOUS with matches = min(|M1|, 255); one v goes on with matches = 1, overlap = v and
+ *    its columns j_0 < ... < j_(m-1), m = d(v), 1 <= m <= 16.
+ * 3. Choice.  J^L = L ++ R[v:] and J^R = L[:|L| - v] ++ R have the same length |J| and differ in the m columns only.  |J| < k
+ *    gives UNSUPPORTED with windows = 0 and taken_right = 0.  Column i lies at x_i = |L| - v + j_i; its window starts at w_i =
+ *    min(max(x_i, k / 2) - k / 2, |J| - k).  c_L = count(J^L[w_i .. w_i + k)), c_R likewise over J^R; count is the gapfill
+ *    block's (both strands, 0 for a window with a byte outside ACGT).  The column takes R's base iff c_R > c_L, else L's.
+ *    taken_right is the number that took R's.  J* is J^L with those columns replaced.
+ * 4. Support.  Every k-window of J* that starts in [max(0, |L| - v - k + 1), min(|L| - 1, |J| - k)] -- every window that touches
+ *    the overlap or crosses the junction, at most v + k - 1 <= 4223 -- must have count >= min_count.  windows is that number
+ *    whether or not an early one failed.  A window below min_count gives UNSUPPORTED, otherwise the gap is JOINED.  This is
+ *    stricter than the exact join's test on purpose: bytes are being changed.
+ * 5. Output.  Tables and compaction are the block above's with this v.  Then for each approximately JOINED gap (p, p+1) of
+ *    scaffold s and each column that took R's base: out[sc_offs'[s] + offset'[p+1] + j_i] = R[j_i], R read from the input.  The
+ *    patches are written only where the bases are (status[14] = 0).  By the half rule no two patches, and no patch and deletion
+ *    of a neighbouring approximate join, meet.  The block above's sentence "deleted bytes equal kept ones" holds for exact joins
+ *    only: an approximate join deletes R's copy of the overlap and keeps L's, patched.
+ *
+ * One sigax_join per gap as above, plus mm[g] = mismatches | taken_right << 8 | (approximate ? 1 << 16 : 0) for a gap that went on
+ * from the second match with one v (JOINED or UNSUPPORTED), else 0.  status24: 0..15 as status16; 16 gaps JOINED through an
+ * approximate match; 17 their mismatch columns; 18 columns written from the right neighbour; 19 approximate candidates tested,
+ * max(0, hi' - lo + 1) over the gaps that came to the second match; 20 choice windows looked up, 2 m over the gaps that came to
+ * the choice; 21..23 zero.  No result depends on lane order, scheduling, the index's optional tables or narrow/wide positions.
+ *
+ * sigax_join_approx_device / _host: the buffer rules, alignment, limits and the "never waits, allocates nothing" contract are
+ * sigax_join_device's / _host's.  Added: d_mm u32[max_unitigs], 4-byte aligned, entries beyond the gaps not written; d_status24
+ * 24 u64; d_work = sigax_join_approx_workspace(max_unitigs) bytes (156 per unitig).  *mm u32[*n_joins], malloc'd.  Added loop
+ * bounds: the second match max_overlap candidates of max_overlap bases, the choice 32 windows, the support test v + k - 1
+ * windows of k symbols, each base at most 16 column look-ups. */
+typedef struct sigax_join_approx_opts {
+  uint32_t flags, min_overlap, max_overlap, slack, k, min_count; /* as sigax_join_opts; flags = 0 */
+  uint32_t max_mismatches;                                      /* 0 .. 16 */
+  uint32_t mismatch_permille;                                   /* 1 .. 250 */
+  uint32_t reserved;                                            /* 0 */
+} sigax_join_approx_opts; /* 36 bytes */
+int  sigax_join_approx_workspace(uint64_t max_unitigs, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_join_approx_device(sigax_index*, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_n_scaffolds,
+                              const void* d_sc_offs, const void* d_sc_lay_offs, const sigax_placement* d_sc_layout, const void* d_sseqs,
+                              uint64_t sseqs_bytes, const sigax_join_approx_opts* opts, void* d_sc_offs_out, sigax_placement* d_sc_layout_out,
+                              void* d_sseqs_out, uint64_t sseqs_capacity, sigax_join* d_joins, uint32_t* d_mm, void* d_status24, void* d_work,
+                              uint64_t work_bytes, void* stream);
+int  sigax_join_approx_host(sigax_index*, uint64_t n_unitigs, const uint64_t* seq_offs, uint64_t n_scaffolds, const uint64_t* sc_offs,
+                            const uint64_t* sc_lay_offs, const sigax_placement* sc_layout, const char* sseqs, const sigax_join_approx_opts* opts,
+                            uint64_t** sc_offs_out, sigax_placement** sc_layout_out, char** sseqs_out, sigax_join** joins, uint64_t* n_joins,
+                            uint32_t** mm, uint64_t status24[24]);
 /* OverlapBuilder::overlap for a batch (host buffers in, host buffers out).  seqs = concatenated read bytes,
  * offs[n_reads+1]; read r of the batch is read `read_base + r` of the indexed set (only used for edges).
  * The result is filled with malloc'd arrays; release with sigax_result_free. */

@@ -65,6 +65,10 @@ assert JOIN_DTYPE.itemsize == 32
 JOIN_STATUS = ("gaps",) + tuple(c.lower() for c in JOIN_CLASSES) + (
     "overlap_bases_removed", "n_bases_removed", "bases", "candidates", "windows", "bases_not_written", "scaffolds")
 assert len(JOIN_STATUS) == 16
+# sigax_join_approx_*: status24, and the fields of an mm entry
+JOIN_APPROX_STATUS = JOIN_STATUS + ("approx_joined", "mismatch_columns", "columns_from_right", "approx_candidates", "choice_windows", "_21", "_22", "_23")
+assert len(JOIN_APPROX_STATUS) == 24
+JOIN_MM_APPROX = 1 << 16  # mm = mismatches | taken_right << 8 | JOIN_MM_APPROX
 
 
 class TrimOpts(C.Structure):  # sigax_trim_opts
@@ -102,6 +106,11 @@ class GapfillOpts(C.Structure):  # sigax_gapfill_opts
 
 class JoinOpts(C.Structure):  # sigax_join_opts
     _fields_ = [(n, C.c_uint32) for n in ("flags", "min_overlap", "max_overlap", "slack", "k", "min_count", "reserved")]
+
+
+class JoinApproxOpts(C.Structure):  # sigax_join_approx_opts
+    _fields_ = [(n, C.c_uint32) for n in ("flags", "min_overlap", "max_overlap", "slack", "k", "min_count", "max_mismatches", "mismatch_permille",
+                                          "reserved")]
 
 
 class Stats(C.Structure):
@@ -155,6 +164,7 @@ SYMBOLS = [
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
     "sigax_join_workspace", "sigax_join_device", "sigax_join_host",
+    "sigax_join_approx_workspace", "sigax_join_approx_device", "sigax_join_approx_host",
     "sigax_edges_order_workspace", "sigax_edges_restore_order", "sigax_edges_restore_order_host", "sigax_flags_by_read_id",
 ]
 
@@ -278,6 +288,9 @@ def lib():
     L.sigax_join_workspace.argtypes = [u64, C.POINTER(u64)]
     L.sigax_join_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(JoinOpts), vp, vp, vp, u64, vp, vp, vp, u64, vp]
     L.sigax_join_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(JoinOpts), pvp, pvp, pvp, pvp, C.POINTER(u64), vp]
+    L.sigax_join_approx_workspace.argtypes = [u64, C.POINTER(u64)]
+    L.sigax_join_approx_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(JoinApproxOpts), vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.sigax_join_approx_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, C.POINTER(JoinApproxOpts), pvp, pvp, pvp, pvp, C.POINTER(u64), pvp, vp]
     # (not in include/sigax.h: the measurement aid of tools/scaffold_bench.py, sigax_internal.h)
     L.sigax_scaffold_bases_device.argtypes = L.sigax_scaffold_device.argtypes
     # (not in include/sigax.h: the measurement aid of tools/unitig_bench.py, sigax_internal.h)

@@ -10,16 +10,23 @@
 //                    codes in LDS, 32 bases a word (2 KB at the limit), and the run of ACGT at L's end and R's start bounds the
 //                    candidates, so no validity bit is kept.  Lane i tests v = lo + i, lo + i + 64, ...: R's head word by word
 //                    against L's tail funnel-shifted into place, leaving at the first word that differs.  The lanes' counts
-//                    summed give |M|, the largest matching v the one v: neither depends on lane order
+//                    summed give |M|, the largest matching v the one v: neither depends on lane order.  <true> (`--join-mismatches`)
+//                    goes on where |M| = 0: over the words still in LDS, v up to hi' = min(hi, |L| / 2, |R| / 2), the differing
+//                    bases counted word by word (popcount of the XOR folded to one bit a base) until they pass B(v); the lane
+//                    that owns the one v writes its columns
+//   k_join_choose    a wave per gap with one approximate v: lanes 0-31 are column i x {J^L, J^R} as the window stands, lanes
+//                    32-63 the reverse complements; the column takes R's base iff count over J^R > count over J^L
 //   k_join_support   a wave per gap with one v and windows across its junction: 32 windows a turn, lanes 0-31 the windows as they
 //                    stand, lanes 32-63 their reverse complements, one backward search of k symbols a lane (search_step,
-//                    sigax_rank.h), forward strand only
+//                    sigax_rank.h), forward strand only.  <.., true>: an approximate v has every window that touches the overlap,
+//                    over J* (L's bases but for the columns that took R's)
 //   launch_scan      G + v of the joined gaps, summed over the placements before each one
 //   k_join_lengths   one lane per scaffold: its new bases; launch_scan gives sc_offs'
 //   k_join_place     one lane per placement: its new offset, the stretch of the output it governs, the gap's record, the counters
 //   k_join_status    status16
 //   k_join_bases     one lane per 16-byte piece of the output: the piece's stretch by bisection, then 16 bytes of the input from a
 //                    source that is in general not aligned, or bytes where the piece meets a junction or the end
+//   k_join_patch     one lane per (gap, column): R's base where an approximately joined gap's column took it
 // Every loop has a bound the host knows and every access is bounds-checked.  Plain vector stores and atomics only.
 #include <hip/hip_runtime.h>
 
@@ -147,6 +154,7 @@ __global__ __launch_bounds__(256) void k_join_classify(JoinArgs A) {
   A.isgap[p] = gap;
   A.open[p] = open;
   A.rem[p] = 0u;
+  if (A.ainfo) A.ainfo[p] = 0u;
   A.gres[p] = make_uint4(cls, 0u, G > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)G, hi);
   A.plen[p] = len;
   A.psrc[p] = src;
@@ -162,14 +170,27 @@ __global__ __launch_bounds__(256) void k_join_list(JoinArgs A) {
 // ---- the match --------------------------------------------------------------------------------------------------------------------
 enum { JOIN_MAX_WORDS = 128 };  // 4096 bases, 32 a word
 
+// L's tail from base `from` on against R's head, word w of v bases: the XOR of the 2-bit codes, bits beyond base v cleared
+__device__ __forceinline__ u64 match_word(const u64* T, const u64* H, u32 from, u32 v, u32 w) {
+  const u32 fw = from >> 5, sh = 2u * (from & 31u);
+  const u64 a = T[fw + w], b = T[fw + w + 1u];
+  u64 x = ((a >> sh) | (sh ? b << (64u - sh) : 0ull)) ^ H[w];
+  const u32 left = v - 32u * w;
+  if (left < 32u) x &= (1ull << (2u * left)) - 1ull;
+  return x;
+}
+// one bit a base (the low bit of its code's place) where the two codes differ
+__device__ __forceinline__ u64 differing(u64 x) { return (x | (x >> 1)) & 0x5555555555555555ull; }
+
 // One wave a workgroup, so that the workgroup's barrier is the wave's: T and H are written by some lanes and read by others.
+template <bool APPROX>
 __global__ __launch_bounds__(64) void k_join_match(JoinArgs A) {
   __shared__ u64 T[JOIN_MAX_WORDS + 2], H[JOIN_MAX_WORDS + 2];  // L's last hi bases and R's first hi, base j at bits 2 (j & 31) of word j >> 5
   const u32 lane = threadIdx.x;
   const u64 n = A.max_unitigs;
   u64 n_open = A.onum[n];
   n_open = n_open < n ? n_open : n;
-  u64 t_cand = 0;
+  u64 t_cand = 0, a_cand = 0;
   for (u64 g = blockIdx.x; g < n_open; g += gridDim.x) {
     const u64 p = A.list[g];
     if (p + 1 >= n) continue;  // (a listed placement has one behind it)
@@ -217,11 +238,63 @@ __global__ __launch_bounds__(64) void k_join_match(JoinArgs A) {
     }
     const u32 m = (u32)wave_sum((u64)mine);
     best = wave_max32(best);
+    // the second match: no exact v (m is the wave's, so the whole wave comes here or none of it)
+    u32 m1 = 0, v1 = 0, d1 = 0;
+    if (APPROX && m == 0u) {
+      u64 half = A.plen[p] >> 1;
+      half = (A.plen[p + 1] >> 1) < half ? A.plen[p + 1] >> 1 : half;
+      const u32 hi2 = (u64)hi < half ? hi : (u32)half;  // hi'
+      u32 mine2 = 0, best2 = 0, dist2 = 0;
+      for (u32 v = lo + lane; v <= hi2 && v <= run; v += 64u) {
+        u64 bud = (u64)v * A.mismatch_permille / 1000ull;
+        bud = bud < (u64)A.max_mismatches ? bud : (u64)A.max_mismatches;
+        const u32 budget = (u32)bud, vw = (v + 31u) >> 5;
+        u32 d = 0;
+        for (u32 w = 0; w < vw && d <= budget; ++w) d += (u32)__popcll(differing(match_word(T, H, hi - v, v, w)));
+        if (d <= budget) {
+          ++mine2;
+          best2 = v;
+          dist2 = d;
+        }
+      }
+      m1 = (u32)wave_sum((u64)mine2);
+      v1 = wave_max32(best2);
+      d1 = wave_max32(mine2 ? dist2 : 0u);  // (read only when m1 == 1: the one lane's)
+      if (m1 == 1u && mine2 == 1u) {  // the one lane that owns the one v: its columns, ascending (d1 <= 16 of them)
+        const u32 vw = (v1 + 31u) >> 5;
+        u32 c = 0;
+        for (u32 w = 0; w < vw; ++w) {
+          u64 x = differing(match_word(T, H, hi - v1, v1, w));
+          for (u32 b = 0; b < 32u && x; ++b) {
+            const u32 j = 32u * w + (((u32)__ffsll((unsigned long long)x) - 1u) >> 1);
+            if (c < (u32)JOIN_MAX_COLUMNS) A.cols[p * JOIN_MAX_COLUMNS + c] = (uint16_t)j;
+            ++c;
+            x &= x - 1ull;
+          }
+        }
+      }
+      a_cand += hi2 >= lo ? (u64)(hi2 - lo) + 1ull : 0ull;
+    }
     __syncthreads();  // T and H are packed again for the wave's next gap
     t_cand += (u64)(hi - lo) + 1ull;
     if (lane == 0u) {
       const u32 matches = m > 255u ? 255u : m;
-      if (m == 0u) {
+      if (APPROX && m == 0u && m1 >= 1u) {
+        if (m1 >= 2u) {
+          A.gres[p] = make_uint4(SIGAX_JOIN_AMBIGUOUS | ((m1 > 255u ? 255u : m1) << 8), 0u, r.z, r.w);
+        } else {
+          // every window of J that touches the overlap or crosses the junction: starts |L| - v - k + 1 .. |L| - 1, clipped to 0 .. |J| - k
+          const u64 lenL = A.plen[p], lenJ = lenL + A.plen[p + 1] - v1, k = A.k;
+          A.ainfo[p] = d1 | (1u << 16);
+          if (lenJ < k) {
+            A.gres[p] = make_uint4(SIGAX_JOIN_UNSUPPORTED | (1u << 8), v1, r.z, r.w);
+          } else {
+            const u64 first = lenL + 1ull > (u64)v1 + k ? lenL + 1ull - v1 - k : 0ull;
+            const u64 last = lenL - 1ull < lenJ - k ? lenL - 1ull : lenJ - k;  // (>= first: |R| >= 1)
+            A.gres[p] = make_uint4(JOIN_APPROX | (1u << 8) | ((u32)(last - first + 1ull) << 16), v1, r.z, r.w);
+          }
+        }
+      } else if (m == 0u) {
         A.gres[p] = make_uint4(SIGAX_JOIN_NONE, 0u, r.z, r.w);
       } else if (m >= 2u) {
         A.gres[p] = make_uint4(SIGAX_JOIN_AMBIGUOUS | (matches << 8), 0u, r.z, r.w);
@@ -245,19 +318,103 @@ __global__ __launch_bounds__(64) void k_join_match(JoinArgs A) {
     }
   }
   if (lane == 0u && t_cand) atomicAdd(&A.cnt[JOIN_C_CAND], t_cand);
+  if (APPROX && lane == 0u && a_cand) atomicAdd(&A.acnt[JOIN_A_CAND], a_cand);
 }
 
-// ---- the support test -------------------------------------------------------------------------------------------------------------
-template <bool WIDE>
-__global__ __launch_bounds__(64) void k_join_support(JoinArgs A) {
+// ---- the choice and the support test --------------------------------------------------------------------------------------------------
+// count(window) of the k bytes that rank(at), rank(at + 1) .. give, for the lane pair (slot, slot + 32): lanes below 32 search the
+// window as it stands, the others its reverse complement.  k and have2 are the wave's: every lane takes the same steps
+template <bool WIDE, class Rank>
+__device__ __forceinline__ u64 window_count(const FmStrand& S, const SearchSh<WIDE>& sh, bool have2, u32 k, bool active, bool rcv, u64 at, Rank rank,
+                                            u32& n_sec) {
   typedef typename PosOf<WIDE>::type P;
+  // symbol j of the chain: the window from its end (as it stands), its complement from its start (reverse complement)
+  auto sym = [&](u32 j) {
+    const u32 rk = rank(at + (rcv ? j : k - 1u - j));
+    return rcv ? comp_rank(rk) : rk;
+  };
+  bool acgt = active;
+  for (u32 j = 0; j < k && acgt; ++j) acgt = rank(at + j) != 0u;
+  P lo = 0, hi = 0;
+  if (acgt) search_init(sh, sym(0), lo, hi);
+  for (u32 j = 1; j < k;) {
+    const bool two = have2 && k - j >= 2u;
+    if (acgt && interval_valid(lo, hi)) search_step<WIDE>(S, sh, sym(j), two ? sym(j + 1u) : 0u, lo, hi, n_sec);
+    j += two ? 2u : 1u;
+  }
+  const u64 occ = acgt && interval_valid(lo, hi) ? (u64)(hi - lo) + 1ull : 0ull;
+  return occ + __shfl_xor(occ, 32, 64);
+}
+
+// `win` windows from `first` on, 32 a turn: whether one of them has count < min_count
+template <bool WIDE, class Rank>
+__device__ __forceinline__ bool windows_fail(const JoinArgs& A, const SearchSh<WIDE>& sh, bool have2, u64 first, u32 win, Rank rank, u32& n_sec) {
+  const u32 lane = threadIdx.x, slot = lane & 31u;
+  bool failed = false;
+  for (u32 w0 = 0; w0 < win; w0 += 32u) {  // at most four turns for an exact v, (v + k - 1 + 31) / 32 <= 132 for an approximate one
+    const bool active = w0 + slot < win;
+    const u64 both = window_count<WIDE>(A.fwd, sh, have2, A.k, active, lane >= 32u, first + w0 + slot, rank, n_sec);
+    failed = failed || __ballot(active && both < (u64)A.min_count) != 0ull;
+  }
+  return failed;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(64) void k_join_choose(JoinArgs A) {
   __shared__ SearchSh<WIDE> sh;
   const FmStrand& S = A.fwd;
   const bool have2 = have_two_step<WIDE>(S);
   search_sh_fill(sh, S);
   __syncthreads();
-  const u32 lane = threadIdx.x, slot = lane & 31u;
-  const bool rcv = lane >= 32u;  // the window's reverse complement
+  const u32 lane = threadIdx.x, col = (lane & 31u) >> 1;
+  const bool right = (lane & 1u) != 0u;  // the window over J^R
+  const u32 k = A.k;
+  const u64 n = A.max_unitigs;
+  u64 n_open = A.onum[n];
+  n_open = n_open < n ? n_open : n;
+  u32 n_sec = 0;
+  u64 looked = 0;
+  for (u64 g = blockIdx.x; g < n_open; g += gridDim.x) {
+    const u64 p = A.list[g];
+    if (p + 1 >= n) continue;
+    const uint4 r = A.gres[p];
+    if ((r.x & 0xFFu) != JOIN_APPROX) continue;
+    const u32 v = r.y, info = A.ainfo[p];
+    u32 m = info & 0xFFu;
+    m = m < (u32)JOIN_MAX_COLUMNS ? m : (u32)JOIN_MAX_COLUMNS;
+    const u64 lenL = A.plen[p], srcL = A.psrc[p], srcR = A.psrc[p + 1];
+    const u64 lenJ = lenL + A.plen[p + 1] - v, cut = lenL - v;  // (the match: |J| >= k, v < |L|)
+    const bool active = col < m;
+    const u64 x = cut + (active ? (u64)A.cols[p * JOIN_MAX_COLUMNS + col] : 0ull);
+    u64 at = (x > (u64)(k / 2u) ? x : (u64)(k / 2u)) - (u64)(k / 2u);
+    at = at < lenJ - k ? at : lenJ - k;
+    // byte y of J^L = L ++ R[v:] or of J^R = L[:|L| - v] ++ R as a rank (0: not ACGT)
+    auto rank_j = [&](u64 y) {
+      const u64 from = right ? (y < cut ? srcL + y : srcR + (y - cut)) : (y < lenL ? srcL + y : srcR + v + (y - lenL));
+      return from < A.sseqs_bytes ? base_rank(A.sseqs_in[from]) : 0u;
+    };
+    const u64 mine = window_count<WIDE>(S, sh, have2, k, active, lane >= 32u, at, rank_j, n_sec);
+    const u64 other = __shfl_xor(mine, 1, 64);  // J^R's count in the lanes of J^L
+    const u64 took = __ballot(active && !right && lane < 32u && other > mine);  // bit 2 i: column i takes R's base
+    u32 mask = 0;
+    for (u32 i = 0; i < (u32)JOIN_MAX_COLUMNS; ++i) mask |= (u32)((took >> (2u * i)) & 1ull) << i;
+    if (lane == 0u) {
+      A.amask[p] = mask;
+      A.ainfo[p] = info | ((u32)__popc(mask) << 8);
+    }
+    looked += 2ull * m;
+  }
+  if (lane == 0u && looked) atomicAdd(&A.acnt[JOIN_A_CHOICE], looked);
+}
+
+template <bool WIDE, bool APPROX>
+__global__ __launch_bounds__(64) void k_join_support(JoinArgs A) {
+  __shared__ SearchSh<WIDE> sh;
+  const FmStrand& S = A.fwd;
+  const bool have2 = have_two_step<WIDE>(S);
+  search_sh_fill(sh, S);
+  __syncthreads();
+  const u32 lane = threadIdx.x;
   const u32 k = A.k;
   const u64 n = A.max_unitigs;
   u64 n_open = A.onum[n];
@@ -267,36 +424,39 @@ __global__ __launch_bounds__(64) void k_join_support(JoinArgs A) {
     const u64 p = A.list[g];
     if (p + 1 >= n) continue;
     const uint4 r = A.gres[p];
-    if ((r.x & 0xFFu) != JOIN_UNIQUE) continue;
-    const u32 v = r.y, win = r.x >> 16;  // win <= k - 2
+    const u32 cls = r.x & 0xFFu;
+    const bool approx = APPROX && cls == JOIN_APPROX;
+    if (cls != JOIN_UNIQUE && !approx) continue;
+    const u32 v = r.y, win = r.x >> 16;  // win <= k - 2, or <= v + k - 1 for an approximate v
     const u64 lenL = A.plen[p], srcL = A.psrc[p], srcR = A.psrc[p + 1];
-    const u64 first = lenL + 1ull > (u64)k ? lenL + 1ull - k : 0ull;
     // byte x of J as a rank (0: not ACGT): L, then R from its base v on
     auto rank_j = [&](u64 x) {
       const u64 at = x < lenL ? srcL + x : srcR + v + (x - lenL);
       return at < A.sseqs_bytes ? base_rank(A.sseqs_in[at]) : 0u;
     };
-    bool failed = false;
-    for (u32 w0 = 0; w0 < win; w0 += 32u) {  // at most four turns
-      const bool active = w0 + slot < win;
-      const u64 at = first + w0 + slot;
-      // symbol j of the chain: the window from its end (as it stands), its complement from its start (reverse complement)
-      auto sym = [&](u32 j) {
-        const u32 rk = rank_j(at + (rcv ? j : k - 1u - j));
-        return rcv ? comp_rank(rk) : rk;
+    bool failed;
+    if (approx) {
+      const u32 mask = A.amask[p];
+      u32 m = A.ainfo[p] & 0xFFu;
+      m = m < (u32)JOIN_MAX_COLUMNS ? m : (u32)JOIN_MAX_COLUMNS;
+      const u64 cut = lenL - v;
+      // byte x of J*: J, but R's base at the columns that took it.  Only at a column do the two copies of the overlap differ
+      auto rank_star = [&](u64 x) {
+        u32 rk = rank_j(x);
+        if (mask && x >= cut && x < lenL) {
+          const u64 j = x - cut, at = srcR + j;
+          const u32 rr = at < A.sseqs_bytes ? base_rank(A.sseqs_in[at]) : 0u;
+          if (rr != rk)
+            for (u32 i = 0; i < m; ++i)
+              if ((mask >> i & 1u) && (u64)A.cols[p * JOIN_MAX_COLUMNS + i] == j) rk = rr;
+        }
+        return rk;
       };
-      bool acgt = active;
-      for (u32 j = 0; j < k && acgt; ++j) acgt = rank_j(at + j) != 0u;
-      P lo = 0, hi = 0;
-      if (acgt) search_init(sh, sym(0), lo, hi);
-      for (u32 j = 1; j < k;) {  // k and have2 are the wave's: every lane takes the same steps
-        const bool two = have2 && k - j >= 2u;
-        if (acgt && interval_valid(lo, hi)) search_step<WIDE>(S, sh, sym(j), two ? sym(j + 1u) : 0u, lo, hi, n_sec);
-        j += two ? 2u : 1u;
-      }
-      const u64 occ = acgt && interval_valid(lo, hi) ? (u64)(hi - lo) + 1ull : 0ull;
-      const u64 both = occ + __shfl_xor(occ, 32, 64);  // count(window), in lanes `slot` and `slot + 32`
-      failed = failed || __ballot(active && both < (u64)A.min_count) != 0ull;
+      const u64 first = lenL + 1ull > (u64)v + k ? lenL + 1ull - v - k : 0ull;
+      failed = windows_fail<WIDE>(A, sh, have2, first, win, rank_star, n_sec);
+    } else {
+      const u64 first = lenL + 1ull > (u64)k ? lenL + 1ull - k : 0ull;
+      failed = windows_fail<WIDE>(A, sh, have2, first, win, rank_j, n_sec);
     }
     if (lane == 0u) {
       A.gres[p] = make_uint4((failed ? SIGAX_JOIN_UNSUPPORTED : SIGAX_JOIN_JOINED) | (r.x & 0xFFFFFF00u), v, r.z, r.w);
@@ -325,7 +485,7 @@ __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
   const u64 n = A.max_unitigs;
   const JoinCounts c = join_counts(A);
   u32 cls = JOIN_NO_GAP;
-  u64 ov = 0, gone = 0, win = 0;
+  u64 ov = 0, gone = 0, win = 0, acols = 0, aright = 0, ajoined = 0;
   if (p <= c.S && p <= n) A.sc_offs[p] = A.slo[p] + (A.shi[p] << 32);
   if (p == 0) A.pkey[c.P] = A.slo[c.S] + (A.shi[c.S] << 32);
   if (p < c.P) {
@@ -361,6 +521,13 @@ __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
         uint4* rec = reinterpret_cast<uint4*>(A.joins + g);
         rec[0] = make_uint4((u32)s, v.x, right, r.z);
         rec[1] = make_uint4(tested ? r.y : 0u, cls | (r.x & 0xFF00u) | ((u32)win << 16), (u32)at, (u32)(at >> 32));
+        const u32 info = tested && A.ainfo ? A.ainfo[p] : 0u;
+        if (A.mm) A.mm[g] = info;
+        if (cls == SIGAX_JOIN_JOINED && info) {
+          ajoined = 1;
+          acols = info & 0xFFu;
+          aright = (info >> 8) & 0xFFu;
+        }
       }
     }
   }
@@ -371,12 +538,17 @@ __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
   count_sum(A, JOIN_C_OVERLAP, ov);
   count_sum(A, JOIN_C_N, gone);
   count_sum(A, JOIN_C_WINDOWS, win);
+  if (A.acnt) {
+    const u64 sums[3] = {wave_sum(ajoined), wave_sum(acols), wave_sum(aright)};
+    for (u32 k = 0; k < 3u; ++k)
+      if (sums[k] && (threadIdx.x & 63u) == 0u) atomicAdd(&A.acnt[JOIN_A_JOINED + k], sums[k]);
+  }
 }
 
-// one wave: lane c < 16 writes status entry c
+// one wave: lane c < 16 (24 with `--join-mismatches`) writes status entry c
 __global__ __launch_bounds__(64) void k_join_status(JoinArgs A) {
   const u32 c = threadIdx.x;
-  if (blockIdx.x != 0u || c >= 16u) return;
+  if (blockIdx.x != 0u || c >= A.n_status || c >= 24u) return;
   const JoinCounts g = join_counts(A);
   const u64 bases = A.slo[g.S] + (A.shi[g.S] << 32);
   u64 out = 0;
@@ -388,7 +560,8 @@ __global__ __launch_bounds__(64) void k_join_status(JoinArgs A) {
   else if (c == 12u) out = A.cnt[JOIN_C_CAND];
   else if (c == 13u) out = A.cnt[JOIN_C_WINDOWS];
   else if (c == 14u) out = bases > A.sseqs_capacity ? 1ull : 0ull;
-  else out = g.S;
+  else if (c == 15u) out = g.S;
+  else out = c < 16u + 5u && A.acnt ? A.acnt[c - 16u] : 0ull;
   A.status[c] = out;
 }
 
@@ -437,6 +610,24 @@ __global__ __launch_bounds__(256) void k_join_bases(JoinArgs A) {
   }
 }
 
+// ---- the patches ------------------------------------------------------------------------------------------------------------------
+// lane (p, i): column i of the gap behind placement p, where that gap is joined approximately and the column took R's base
+__global__ __launch_bounds__(256) void k_join_patch(JoinArgs A) {
+  const u64 t = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 p = t / JOIN_MAX_COLUMNS;
+  const u32 i = (u32)(t % JOIN_MAX_COLUMNS);
+  const JoinCounts c = join_counts(A);
+  const u64 total = A.slo[c.S] + (A.shi[c.S] << 32);
+  if (total > A.sseqs_capacity || p + 1 >= c.P || p + 1 >= A.max_unitigs || !A.isgap[p]) return;
+  const uint4 r = A.gres[p];
+  const u32 info = A.ainfo[p];
+  if ((r.x & 0xFFu) != SIGAX_JOIN_JOINED || !(info >> 16) || i >= (info & 0xFFu) || !(A.amask[p] >> i & 1u)) return;
+  const u64 s = A.sof[p];
+  const u64 j = A.cols[p * JOIN_MAX_COLUMNS + i];
+  const u64 to = A.slo[s] + (A.shi[s] << 32) + placement_offset(A.sc_layout_out, p + 1) + j, from = A.psrc[p + 1] + j;
+  if (to < total && from < A.sseqs_bytes) A.sseqs[to] = A.sseqs_in[from];
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 // one-wave workgroups for the gaps that come to the match: no more than the device holds at a time, the rest in strides
 unsigned gap_waves(u64 n, int n_cu) {
@@ -448,6 +639,7 @@ unsigned gap_waves(u64 n, int n_cu) {
 void launch_join_bases(const JoinArgs& a, hipStream_t st) {
   if (a.max_unitigs == 0 || !a.sseqs || a.sseqs_capacity == 0) return;
   hipLaunchKernelGGL(k_join_bases, dim3(blocks_of((a.sseqs_capacity + 15) / 16)), dim3(256), 0, st, a);
+  if (a.max_mismatches) hipLaunchKernelGGL(k_join_patch, dim3(blocks_of(a.max_unitigs * JOIN_MAX_COLUMNS)), dim3(256), 0, st, a);
 }
 
 hipError_t launch_join(const JoinArgs& a, bool wide, int n_cu, hipStream_t st) {
@@ -459,9 +651,23 @@ hipError_t launch_join(const JoinArgs& a, bool wide, int n_cu, hipStream_t st) {
   launch_scan(a.isgap, n, a.partial, a.gnum, a.scan_total, st);
   launch_scan(a.open, n, a.partial, a.onum, a.scan_total, st);
   hipLaunchKernelGGL(k_join_list, dim3(blocks_of(n)), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_join_match, dim3(gap_waves(n, n_cu)), dim3(64), 0, st, a);
-  if (wide) hipLaunchKernelGGL(k_join_support<true>, dim3(gap_waves(n, n_cu)), dim3(64), 0, st, a);
-  else hipLaunchKernelGGL(k_join_support<false>, dim3(gap_waves(n, n_cu)), dim3(64), 0, st, a);
+  const dim3 waves(gap_waves(n, n_cu));
+  if (a.max_mismatches) {  // `--join-mismatches`: the second match, the choice, the wider support test
+    e = hipMemsetAsync(a.acnt, 0, JOIN_AWORDS * 8, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_join_match<true>, waves, dim3(64), 0, st, a);
+    if (wide) {
+      hipLaunchKernelGGL(k_join_choose<true>, waves, dim3(64), 0, st, a);
+      hipLaunchKernelGGL((k_join_support<true, true>), waves, dim3(64), 0, st, a);
+    } else {
+      hipLaunchKernelGGL(k_join_choose<false>, waves, dim3(64), 0, st, a);
+      hipLaunchKernelGGL((k_join_support<false, true>), waves, dim3(64), 0, st, a);
+    }
+  } else {
+    hipLaunchKernelGGL(k_join_match<false>, waves, dim3(64), 0, st, a);
+    if (wide) hipLaunchKernelGGL((k_join_support<true, false>), waves, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_join_support<false, false>), waves, dim3(64), 0, st, a);
+  }
   launch_scan(a.rem, n, a.partial, a.esum, a.scan_total, st);
   hipLaunchKernelGGL(k_join_lengths, dim3(blocks_of(n)), dim3(256), 0, st, a);
   launch_scan(a.lenlo, n, a.partial, a.slo, a.scan_total, st);

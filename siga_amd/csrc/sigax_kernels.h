@@ -568,12 +568,23 @@ struct JoinArgs {
   unsigned long long* psrc;              // [n]: where in sseqs_in X(p) begins
   unsigned long long* pkey;              // [n + 1]: the output byte from which placement p's shift holds; [P] = all bases
   unsigned long long* pshift;            // [n]: output byte x of that stretch is input byte x + pshift[p] (modulo 2^64)
+  // `--join-mismatches` (sigax_join_approx_*): all zero and NULL in a sigax_join_* call, which writes 16 status entries
+  uint32_t max_mismatches, mismatch_permille;
+  uint32_t n_status;                     // 16 or 24
+  uint32_t* mm;                          // [n], written per gap: mismatches | taken_right << 8 | approximate << 16; or NULL
+  unsigned long long* acnt;              // JOIN_AWORDS u64, zeroed: the JOIN_A_* counters
+  uint16_t* cols;                        // [16 n]: the mismatch columns j_0 < j_1 < ... of a gap with one approximate v
+  uint32_t* ainfo;                       // [n]: mm of the gap at placement p, 0 where the exact match decided
+  uint32_t* amask;                       // [n]: bit i set where column i takes R's base
 };
 // counters 0 .. 7 are the classes
 enum { JOIN_C_GAPS = 8, JOIN_C_OVERLAP = 9, JOIN_C_N = 10, JOIN_C_CAND = 11, JOIN_C_WINDOWS = 12, JOIN_WORDS = 16 };
-static const uint32_t JOIN_OPEN = 0xFFu, JOIN_NO_GAP = 0xFEu, JOIN_UNIQUE = 0xFDu;
+enum { JOIN_A_JOINED = 0, JOIN_A_COLUMNS = 1, JOIN_A_RIGHT = 2, JOIN_A_CAND = 3, JOIN_A_CHOICE = 4, JOIN_AWORDS = 8 };  // status 16 + c
+enum { JOIN_MAX_COLUMNS = 16 };
+// JOIN_APPROX: one approximate v, between the match and the support test (the choice in between leaves the class as it is)
+static const uint32_t JOIN_OPEN = 0xFFu, JOIN_NO_GAP = 0xFEu, JOIN_UNIQUE = 0xFDu, JOIN_APPROX = 0xFCu;
 hipError_t launch_join(const JoinArgs& a, bool wide, int n_cu, hipStream_t st);
-void launch_join_bases(const JoinArgs& a, hipStream_t st);  // the last phase alone, over what launch_join left
+void launch_join_bases(const JoinArgs& a, hipStream_t st);  // the last phase alone, over what launch_join left (the patches with it)
 
 void launch_occ_batch(const FmStrand& s, bool wide, const unsigned long long* pos, unsigned long long n,
                       unsigned long long* out, hipStream_t st);

@@ -81,9 +81,11 @@ const char* const kJoinClasses[8] = {"JOINED", "CLOSED", "FAR", "SHORT", "NONE",
 // bases and the offsets are the new ones, the gap before is signed, -<overlap> for a joined pair, every header ends in
 // " joined=<gaps joined>", and rq.joins gets one line per gap:
 // "JN\tscaffold-<n>\tunitig-<left>\tunitig-<right>\t<laid>\t<class>\t<overlap>\t<matches>\t<windows>\t<offset>"
+// With rq.joinMismatches > 0 the join is sigax_join_approx_host: the headers go on with " corrected=<columns taken from the right
+// neighbour>" and every JN line with "\t<mismatches>\t<taken from the right>"
 std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint32_t* uflags, const char* useqs,
                          const sigax_pair_link* links, uint64_t n_links, const uint64_t status24[24], const ScaffoldRequest& rq,
-                         uint64_t status16[16], uint64_t gap24[24], uint64_t join16[16]) {
+                         uint64_t status16[16], uint64_t gap24[24], uint64_t join24[24]) {
   if (!rq.haveInsertSize && status24[14] == 0)
     return "no pair of the library's orientation lies inside a unitig: there is no insert size to estimate the gaps from; give --insert-size";
   sigax_scaffold_opts opts;
@@ -102,7 +104,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
                           status16) != SIGAX_OK)
     return std::string("scaffold failed: ") + sigax_last_error();
   std::string fa, lt, gt, jt;
-  std::vector<uint64_t> filled, joined;
+  std::vector<uint64_t> filled, joined, corrected;
   if (rq.index) {
     sigax_gapfill_opts go = {0u, rq.gapKmer, rq.gapMinCount, rq.gapSlack, rq.gapMaxFill, 0u};
     uint64_t *offs2 = nullptr, ng = 0, st[24];
@@ -154,11 +156,17 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
   }
   if (rq.joinIndex) {
     sigax_join_opts jo = {0u, rq.joinMinOverlap, rq.joinMaxOverlap, rq.joinSlack, rq.joinKmer, rq.joinMinCount, 0u};
-    uint64_t *offs2 = nullptr, nj = 0, st[16];
+    sigax_join_approx_opts ao = {0u, rq.joinMinOverlap, rq.joinMaxOverlap, rq.joinSlack, rq.joinKmer, rq.joinMinCount, rq.joinMismatches,
+                                 rq.joinMismatchPermille, 0u};
+    uint64_t *offs2 = nullptr, nj = 0, st[24] = {0};
     sigax_placement* lay2 = nullptr;
     char* seqs2 = nullptr;
     sigax_join* recs = nullptr;
-    if (sigax_join_host(rq.joinIndex, n_unitigs, seq_offs, ns, sc_offs, sc_lay, lay, seqs, &jo, &offs2, &lay2, &seqs2, &recs, &nj, st) != SIGAX_OK) {
+    uint32_t* mm = nullptr;  // with --join-mismatches: per gap mismatches | taken from the right << 8 | approximate << 16
+    const int rc = rq.joinMismatches
+                       ? sigax_join_approx_host(rq.joinIndex, n_unitigs, seq_offs, ns, sc_offs, sc_lay, lay, seqs, &ao, &offs2, &lay2, &seqs2, &recs, &nj, &mm, st)
+                       : sigax_join_host(rq.joinIndex, n_unitigs, seq_offs, ns, sc_offs, sc_lay, lay, seqs, &jo, &offs2, &lay2, &seqs2, &recs, &nj, st);
+    if (rc != SIGAX_OK) {
       sigax_free(sc_offs);
       sigax_free(sc_lay);
       sigax_free(sc_flags);
@@ -173,9 +181,11 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
     lay = lay2;
     seqs = seqs2;
     joined.assign(ns, 0);
+    corrected.assign(ns, 0);
     for (uint64_t g = 0; g < nj; ++g) {
       const sigax_join& x = recs[g];
       if (x.cls == SIGAX_JOIN_JOINED && x.scaffold < ns) ++joined[x.scaffold];
+      if (mm && x.cls == SIGAX_JOIN_JOINED && x.scaffold < ns) corrected[x.scaffold] += (mm[g] >> 8) & 0xFFu;
       jt += "JN\tscaffold-";
       append_u64(jt, x.scaffold);
       jt += "\tunitig-";
@@ -194,11 +204,18 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
       append_u64(jt, x.windows);
       jt += '\t';
       append_u64(jt, x.offset);
+      if (mm) {
+        jt += '\t';
+        append_u64(jt, mm[g] & 0xFFu);
+        jt += '\t';
+        append_u64(jt, (mm[g] >> 8) & 0xFFu);
+      }
       jt += '\n';
     }
     sigax_free(recs);
-    if (join16)
-      for (int k = 0; k < 16; ++k) join16[k] = st[k];
+    sigax_free(mm);
+    if (join24)
+      for (int k = 0; k < 24; ++k) join24[k] = st[k];
   }
   for (uint64_t s = 0; s < ns; ++s) {
     const uint64_t k = sc_lay[s + 1] - sc_lay[s];
@@ -219,6 +236,10 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
     if (rq.joinIndex) {
       fa += " joined=";
       append_u64(fa, joined[s]);
+      if (rq.joinMismatches) {
+        fa += " corrected=";
+        append_u64(fa, corrected[s]);
+      }
     }
     fa += '\n';
     fa.append(seqs + sc_offs[s], sc_offs[s + 1] - sc_offs[s]);
@@ -261,7 +282,7 @@ std::string run_scaffold(int device, uint64_t n_unitigs, const uint64_t* seq_off
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
                       const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta, const ScaffoldRequest* sc,
-                      const char* useqs, uint64_t status16[16], uint64_t gap24[24], uint64_t join16[16]) {
+                      const char* useqs, uint64_t status16[16], uint64_t gap24[24], uint64_t join24[24]) {
   sigax_pairs_opts opts;
   opts.flags = rq.outward ? SIGAX_PAIRS_OUTWARD : 0u;
   opts.hist_bins = rq.bins;
@@ -333,7 +354,7 @@ std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::
     if (!ok) bad = rq.links;
   }
   std::string e = ok ? std::string() : "Failed to write " + bad;
-  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16, gap24, join16);
+  if (ok && sc && !sc->fasta.empty()) e = run_scaffold(device, n_unitigs, seq_offs, uflags, useqs, links, status24[22], status24, *sc, status16, gap24, join24);
   sigax_free(hist);
   sigax_free(links);
   return e;

@@ -34,17 +34,19 @@ struct ScaffoldRequest {
   // overlapping neighbours joined behind the scaffold or gapfill call (sigax_join_host): joinIndex NULL = none; joins may be empty
   sigax_index* joinIndex = nullptr;
   uint32_t joinMinOverlap = 16, joinMaxOverlap = 1000, joinSlack = 100, joinKmer = 31, joinMinCount = 3;
+  uint32_t joinMismatches = 0, joinMismatchPermille = 50;  // joinMismatches > 0: sigax_join_approx_host
   std::string joins;
 };
 // sigax_unitigs_pairs_host over a unitig call's result, then the two files; with sc->fasta also sigax_scaffold_host over the
 // unitigs (useqs: their bases) and the links, then its two files and status16; with sc->index also sigax_gapfill_host over the
-// scaffolds before they are written, sc->gaps and gap24; with sc->joinIndex then sigax_join_host, sc->joins and join16.
+// scaffolds before they are written, sc->gaps and gap24; with sc->joinIndex then sigax_join_host (sigax_join_approx_host with sc->joinMismatches), sc->joins and
+// join24 (entries 16 .. 23 zero without mismatches).
 // -> "" or what went wrong
 std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::vector<uint32_t>& lengths, uint64_t n_unitigs,
                       const uint64_t* seq_offs, const uint64_t* lay_offs, const uint32_t* uflags, const sigax_placement* layout,
                       const PairsRequest& rq, uint64_t status24[24], uint64_t* insert_size, uint64_t* delta,
                       const ScaffoldRequest* sc = nullptr, const char* useqs = nullptr, uint64_t status16[16] = nullptr,
-                      uint64_t gap24[24] = nullptr, uint64_t join16[16] = nullptr);
+                      uint64_t gap24[24] = nullptr, uint64_t join24[24] = nullptr);
 
 }  // namespace sigah
 

@@ -325,6 +325,15 @@ class Unitigger {
   uint64_t joinsMade() const { return _joinsMade; }
   uint64_t joinOverlapBases() const { return _joinOverlapBases; }
   uint64_t joinNRemoved() const { return _joinNRemoved; }
+  // Ends that nearly agree (sigax_join_approx_host; needs setJoinOverlaps): where no overlap length matches exactly, the one length
+  // whose ends differ in at most min(mismatches, v * permille / 1000) bases is taken, each differing base settled by the reads.
+  // The headers then go on with " corrected=<n>" and the JN lines with "\t<mismatches>\t<taken from the right>".  0 = off.
+  void setJoinMismatches(size_t mismatches, size_t permille = 50) {
+    _joinMismatches = mismatches;
+    _joinMismatchPermille = permille;
+  }
+  uint64_t joinsApproximate() const { return _joinsApprox; }
+  uint64_t joinCorrected() const { return _joinCorrected; }
   uint64_t gaps() const { return _gaps; }
   uint64_t gapsFilled() const { return _gapsFilled; }
   uint64_t gapFillBases() const { return _gapFillBases; }
@@ -393,6 +402,8 @@ class Unitigger {
   size_t _joinMinOverlap = 16, _joinMaxOverlap = 1000, _joinSlack = 100, _joinKmer = 31, _joinMinCount = 3;
   std::string _joinsOut;
   uint64_t _joinGaps = 0, _joinsMade = 0, _joinOverlapBases = 0, _joinNRemoved = 0;
+  size_t _joinMismatches = 0, _joinMismatchPermille = 50;
+  uint64_t _joinsApprox = 0, _joinCorrected = 0;
   std::string _error;
 };
 

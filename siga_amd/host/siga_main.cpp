@@ -611,7 +611,14 @@ static int unitig_help() {
          "          --join-min-count=N           every k-mer across a junction must occur N times in the reads, either strand (default: 3)\n"
          "          --joins=FILE                 also write one line per gap to FILE: JN, scaffold, the two unitigs, the bases laid, the\n"
          "                                       gap's class, the overlap, the overlaps that matched, the junction k-mers looked up, the\n"
-         "                                       offset at which the right unitig or the gap now starts\n"
+         "                                       offset at which the right unitig or the gap now starts; with --join-mismatches also the\n"
+         "                                       differing bases and how many of them were taken from the right unitig\n"
+         "          --join-mismatches=N          (needs --join-overlaps) where no overlap matches exactly, take the one v whose two copies\n"
+         "                                       differ in at most N bases, 0 to 16, and in at most --join-mismatch-permille of v; at each\n"
+         "                                       such base the copy whose k-mer the reads hold more often is written, and every k-mer that\n"
+         "                                       touches the overlap must then occur --join-min-count times; every header gains\n"
+         "                                       corrected=<bases taken from the right unitig> (default: 0, exact overlaps only)\n"
+         "          --join-mismatch-permille=M   (needs --join-overlaps) at most v * M / 1000 differing bases, 1 to 250 (default: 50)\n"
          "\n"
          "The first step of `siga assemble` (the graph's simplify()) without the ASQG file in between: the overlap stages leave\n"
          "their edge records, and reads joined by an overlap that is the only one at both read ends it touches are merged.\n"
@@ -639,7 +646,8 @@ static int run_unitig(int argc, char** argv) {
          OPT_MAX_SPAN, OPT_OUTWARD, OPT_PAIRS_BINS, OPT_PAIRS_SHIFT, OPT_SCAFFOLD, OPT_SCAFFOLD_LAYOUT, OPT_MIN_PAIRS, OPT_LINK_RATIO,
          OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
          OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
-         OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS };
+         OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS,
+         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -674,6 +682,8 @@ static int run_unitig(int argc, char** argv) {
                                     {"join-max-overlap", required_argument, nullptr, OPT_JOIN_MAX_OVERLAP},
                                     {"join-slack", required_argument, nullptr, OPT_JOIN_SLACK}, {"join-kmer", required_argument, nullptr, OPT_JOIN_KMER},
                                     {"join-min-count", required_argument, nullptr, OPT_JOIN_MIN_COUNT}, {"joins", required_argument, nullptr, OPT_JOINS},
+                                    {"join-mismatches", required_argument, nullptr, OPT_JOIN_MISMATCHES},
+                                    {"join-mismatch-permille", required_argument, nullptr, OPT_JOIN_MISMATCH_PERMILLE},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
@@ -686,7 +696,7 @@ static int run_unitig(int argc, char** argv) {
   size_t gapKmer = 31, gapMinCount = 3, gapSlack = 100, gapMaxFill = 10000;
   std::string gapsOut;
   bool joinOverlaps = false, joinTuned = false;
-  size_t joinMinOverlap = 16, joinMaxOverlap = 1000, joinSlack = 100, joinKmer = 31, joinMinCount = 3;
+  size_t joinMinOverlap = 16, joinMaxOverlap = 1000, joinSlack = 100, joinKmer = 31, joinMinCount = 3, joinMismatches = 0, joinMismatchPermille = 50;
   std::string joinsOut;
   size_t threads = 1, minOverlap = 45, cutTerminal = 0, minBranchLength = 150, delta = 0, numReads = 0, genomeSize = 0;
   size_t chimLength = 0, chimDelta = 0;
@@ -769,6 +779,11 @@ static int run_unitig(int argc, char** argv) {
       case OPT_JOIN_KMER: if (!unitig_number(optarg, "--join-kmer", 128, &joinKmer) || joinKmer < 8) return 1; joinTuned = true; break;
       case OPT_JOIN_MIN_COUNT: if (!unitig_number(optarg, "--join-min-count", 0xFFFFFFFFull, &joinMinCount) || joinMinCount == 0) return 1; joinTuned = true; break;
       case OPT_JOINS: joinsOut = optarg; joinTuned = true; break;
+      case OPT_JOIN_MISMATCHES: if (!unitig_number(optarg, "--join-mismatches", 16, &joinMismatches)) return 1; joinTuned = true; break;
+      case OPT_JOIN_MISMATCH_PERMILLE:
+        if (!unitig_number(optarg, "--join-mismatch-permille", 250, &joinMismatchPermille) || joinMismatchPermille < 1) return 1;
+        joinTuned = true;
+        break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
@@ -835,7 +850,8 @@ static int run_unitig(int argc, char** argv) {
     return 1;
   }
   if (!joinOverlaps && joinTuned) {
-    fprintf(stderr, "siga unitig: --join-min-overlap, --join-max-overlap, --join-slack, --join-kmer, --join-min-count and --joins need --join-overlaps\n");
+    fprintf(stderr, "siga unitig: --join-min-overlap, --join-max-overlap, --join-slack, --join-kmer, --join-min-count, --joins, --join-mismatches and "
+                    "--join-mismatch-permille need --join-overlaps\n");
     return 1;
   }
   if (joinOverlaps && scaffoldOut.empty()) {
@@ -872,6 +888,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setScaffold(scaffoldOut, scaffoldLayout, minPairs, linkRatio, minScaffoldUnitig, haveInsertSize ? (long long)insertSize : -1, minGap, maxGap);
   unitigger.setGapfill(gapfill, gapKmer, gapMinCount, gapSlack, gapMaxFill, gapsOut);
   unitigger.setJoinOverlaps(joinOverlaps, joinMinOverlap, joinMaxOverlap, joinSlack, joinKmer, joinMinCount, joinsOut);
+  unitigger.setJoinMismatches(joinMismatches, joinMismatchPermille);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
@@ -903,6 +920,9 @@ static int run_unitig(int argc, char** argv) {
   if (joinOverlaps)
     fprintf(stderr, "%llu gaps looked at, %llu joined over %llu overlap bases, %llu N removed\n", (unsigned long long)unitigger.joinGaps(),
             (unsigned long long)unitigger.joinsMade(), (unsigned long long)unitigger.joinOverlapBases(), (unsigned long long)unitigger.joinNRemoved());
+  if (joinOverlaps && joinMismatches)
+    fprintf(stderr, "%llu of the joins through ends that nearly agree, %llu bases taken from the right unitig\n",
+            (unsigned long long)unitigger.joinsApproximate(), (unsigned long long)unitigger.joinCorrected());
   return 0;
 }
 

@@ -88,7 +88,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _unitigs = _bases = _merged = _cycles = _trimRounds = _islands = _deadEnds = _readsRemoved = _recordsCut = _cutRounds = _chimUnitigs = _chimReads = _pairs = _pairsSame = _pairsAcross = _pairLinks = _insertSize = _insertDelta = 0;
   _scaffolds = _scJoins = _scAmbiguous = _scGapBases = 0;
   _gaps = _gapsFilled = _gapFillBases = _gapBasesLeft = 0;
-  _joinGaps = _joinsMade = _joinOverlapBases = _joinNRemoved = 0;
+  _joinGaps = _joinsMade = _joinOverlapBases = _joinNRemoved = _joinsApprox = _joinCorrected = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   const HostSettings hs;
@@ -136,7 +136,8 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     return fail("gap filling options out of range");
   if (_join && _scaffoldOut.empty()) return fail("overlaps are only joined in scaffolds");
   if (_join && (_joinMinOverlap < 8 || _joinMaxOverlap < _joinMinOverlap || _joinMaxOverlap > 4096 || _joinSlack >= (1ull << 31) || _joinKmer < 8 ||
-                _joinKmer > 128 || _joinMinCount < 1 || _joinMinCount > 0xFFFFFFFFull))
+                _joinKmer > 128 || _joinMinCount < 1 || _joinMinCount > 0xFFFFFFFFull || _joinMismatches > 16 || _joinMismatchPermille < 1 ||
+                _joinMismatchPermille > 250))
     return fail("overlap joining options out of range");
   if (trim || _delta > 0) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
@@ -243,18 +244,22 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
       sq.joinSlack = (uint32_t)_joinSlack;
       sq.joinKmer = (uint32_t)_joinKmer;
       sq.joinMinCount = (uint32_t)_joinMinCount;
+      sq.joinMismatches = (uint32_t)_joinMismatches;
+      sq.joinMismatchPermille = (uint32_t)_joinMismatchPermille;
       sq.joins = _joinsOut;
     }
     uint64_t st24[24], st16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t gp24[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t jn16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t jn24[24] = {0};
     const std::string e = run_pairs(inf.device, mates_by_name(reads, ranks), lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
-                                    &_insertSize, &_insertDelta, &sq, u.useqs, st16, gp24, jn16);
+                                    &_insertSize, &_insertDelta, &sq, u.useqs, st16, gp24, jn24);
     if (!e.empty()) return fail(e);
-    _joinGaps = jn16[0];
-    _joinsMade = jn16[1];
-    _joinOverlapBases = jn16[9];
-    _joinNRemoved = jn16[10];
+    _joinGaps = jn24[0];
+    _joinsMade = jn24[1];
+    _joinOverlapBases = jn24[9];
+    _joinNRemoved = jn24[10];
+    _joinsApprox = jn24[16];
+    _joinCorrected = jn24[18];
     _gaps = gp24[0];
     _gapsFilled = gp24[1];
     _gapFillBases = gp24[14];

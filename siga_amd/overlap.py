@@ -415,7 +415,7 @@ def scaffolds_gapfill(pair, res, scaf, k=31, min_count=3, slack=100, max_fill=10
     return out
 
 
-def scaffolds_join(pair, res, scaf, min_overlap=16, max_overlap=1000, slack=100, k=31, min_count=3, bases=True):
+def scaffolds_join(pair, res, scaf, min_overlap=16, max_overlap=1000, slack=100, k=31, min_count=3, bases=True, max_mismatches=0, mismatch_permille=50):
     """Neighbours of a scaffold that overlap written as one sequence (sigax_join_host, the rules in include/sigax.h): `pair` is
     the FMIndexPair of the reads (the forward strand is enough), `res` the dict of the unitig call (seq_offs, for the unitigs'
     lengths), `scaf` the dict `unitigs_scaffold` or `scaffolds_gapfill` returned over it, with its bases.  A gap of at most slack
@@ -423,7 +423,11 @@ def scaffolds_join(pair, res, scaf, min_overlap=16, max_overlap=1000, slack=100,
     neighbour's first v and every k-mer across the junction occurs min_count times in the reads (either strand); the N and one
     copy of the overlap then go.  -> the dict shape of `unitigs_scaffold` (sc_lay_offs and sc_flags as they came in, status
     u64[16] named by _lib.JOIN_STATUS) plus joins, one _lib.JOIN_DTYPE record per gap in scaffold order: its class
-    (_lib.JOIN_CLASSES), the overlap, how many lengths matched, the junction windows looked up and where the gap lies now."""
+    (_lib.JOIN_CLASSES), the overlap, how many lengths matched, the junction windows looked up and where the gap lies now.
+    max_mismatches > 0 (sigax_join_approx_host): where no length matches exactly, the one length whose ends differ in at most
+    min(max_mismatches, v * mismatch_permille / 1000) bases is taken, each differing base settled by the reads; the dict gains
+    "mm" (u32 per gap: mismatches | columns taken from the right << 8 | _lib.JOIN_MM_APPROX) and status is u64[24]
+    (_lib.JOIN_APPROX_STATUS)."""
     so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
     u = len(so) - 1
     sco = np.ascontiguousarray(scaf["sc_offs"], dtype=np.uint64)
@@ -439,20 +443,29 @@ def scaffolds_join(pair, res, scaf, min_overlap=16, max_overlap=1000, slack=100,
     if len(sq) < int(sco[s]):
         raise ValueError("seqs shorter than sc_offs says")
     L = _lib.lib()
-    opts = _lib.JoinOpts(0, int(min_overlap), int(max_overlap), int(slack), int(k), int(min_count), 0)
-    po, play, ps, pj = (C.c_void_p() for _ in range(4))
+    approx = int(max_mismatches) > 0
+    po, play, ps, pj, pm = (C.c_void_p() for _ in range(5))
     nj = C.c_uint64()
-    st = np.zeros(16, dtype=np.uint64)
-    _check(L.sigax_join_host(pair.handle, u, so.ctypes.data, s, sco.ctypes.data, slo.ctypes.data, lay.ctypes.data if len(lay) else None,
-                             sq.ctypes.data if len(sq) else None, C.byref(opts), C.byref(po), C.byref(play), C.byref(ps) if bases else None,
-                             C.byref(pj), C.byref(nj), st.ctypes.data), "sigax_join_host")
+    st = np.zeros(24 if approx else 16, dtype=np.uint64)
+    tables = (pair.handle, u, so.ctypes.data, s, sco.ctypes.data, slo.ctypes.data, lay.ctypes.data if len(lay) else None,
+              sq.ctypes.data if len(sq) else None)
+    outs = (C.byref(po), C.byref(play), C.byref(ps) if bases else None, C.byref(pj), C.byref(nj))
+    if approx:
+        opts = _lib.JoinApproxOpts(0, int(min_overlap), int(max_overlap), int(slack), int(k), int(min_count), int(max_mismatches),
+                                   int(mismatch_permille), 0)
+        _check(L.sigax_join_approx_host(*tables, C.byref(opts), *outs, C.byref(pm), st.ctypes.data), "sigax_join_approx_host")
+    else:
+        opts = _lib.JoinOpts(0, int(min_overlap), int(max_overlap), int(slack), int(k), int(min_count), 0)
+        _check(L.sigax_join_host(*tables, C.byref(opts), *outs, st.ctypes.data), "sigax_join_host")
     try:
         out = {"sc_offs": _copy_records(po, s + 1, np.dtype(np.uint64)), "sc_lay_offs": slo.copy(),
                "sc_flags": np.array(scaf["sc_flags"], dtype=np.uint32), "layout": _copy_records(play, int(slo[s]) if u else 0, PLACEMENT_DTYPE),
                "status": st, "joins": _copy_records(pj, int(nj.value), _lib.JOIN_DTYPE)}
         out["seqs"] = _copy_records(ps, int(st[11]), np.dtype(np.uint8)) if bases else None
+        if approx:
+            out["mm"] = _copy_records(pm, int(nj.value), np.dtype(np.uint32))
     finally:
-        for p in (po, play, ps, pj):
+        for p in (po, play, ps, pj, pm):
             L.sigax_free(p)
     return out
 

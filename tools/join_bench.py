@@ -10,10 +10,16 @@ child process under a `timeout` of its own; a step is not started when the one b
             defaults, each with a bases buffer of exactly its size.  From the join call's status and records: gaps by class, how
             many of the gaps the gapfill call left open are now joined (by the gapfill call's class), the N left, candidate
             overlaps tested and junction windows looked up.  Every joined junction is then looked up in the simulated genome:
-            the k bases on either side of it must occur there on one strand or the other.
+            the k bases on either side of it must occur there on one strand or the other.  With --mismatches N > 0 then
+            sigax_join_approx_device over the same tables (--permille M), timed likewise next to the exact call: gaps by class,
+            approximate joins, their columns taken from the left and from the right neighbour, and every approximately joined
+            junction -- its whole overlap and the k bases on either side -- looked up in the genome.  The ends of the gaps that
+            stay NONE are then compared on the host, without the half rule: per gap the overlap length in lo .. hi whose two
+            copies differ in the smallest share of their bases, so that the profile says what keeps those ends apart.
 One JSON document on stdout (and in --out).  Needs a GPU; nothing but this repository.
 
     python tools/join_bench.py --out profiles/join_configs1.json
+    python tools/join_bench.py --mismatches 2 --out profiles/join_approx_configs1.json
 """
 import argparse
 import ctypes as C
@@ -30,6 +36,43 @@ sys.path.insert(0, ROOT)
 
 from tools.gapfill_bench import genome_of  # noqa: E402
 from tools.pairs_bench import STATUS6, reads_of, step_index  # noqa: E402
+
+
+def nearest_overlaps(seqs, sco, scl, lay, so, recs, sel, lo, max_overlap):
+    """for the gaps sel (numbered in placement order, as the records are): the v in lo .. min(max_overlap, |L| - 1, |R| - 1) whose
+    two copies differ in the smallest share of their bases (all of them ACGT) -> a summary over those gaps"""
+    ok = np.zeros(256, dtype=bool)
+    ok[list(b"ACGT")] = True
+    buf = np.frombuffer(seqs, dtype=np.uint8)
+    rows, g = [], 0
+    for s in range(len(scl) - 1):
+        for p in range(int(scl[s]), int(scl[s + 1]) - 1):
+            if sel[g]:
+                ends = []
+                for q in (p, p + 1):
+                    u = int(lay[q]["read"])
+                    at = int(sco[s]) + int(lay[q]["offset"])
+                    ends.append(buf[at:at + int(so[u + 1] - so[u])])
+                L, R = ends
+                hi = min(max_overlap, len(L) - 1, len(R) - 1)
+                best = None
+                for v in range(lo, hi + 1):
+                    a, b = L[len(L) - v:], R[:v]
+                    if not (ok[a].all() and ok[b].all()):
+                        continue
+                    d = int((a != b).sum())
+                    if best is None or d * best[0] < best[1] * v:
+                        best = (v, d)
+                rows.append((len(L), len(R), hi) + (best or (0, -1)))
+            g += 1
+    assert g == len(recs)
+    near = [r for r in rows if r[4] >= 0 and 20 * r[4] <= r[3]]  # at most 5 % of the bases differ
+    return {"gaps": len(rows), "with_an_overlap_within_50_permille": len(near),
+            "of_them_beyond_half_of_the_shorter_unitig": sum(1 for r in near if r[3] > min(r[0], r[1]) // 2),
+            "their_differing_bases": {str(d): sum(1 for r in near if r[4] == d) for d in sorted(set(r[4] for r in near))},
+            "their_overlap_lengths": {"min": min((r[3] for r in near), default=0), "max": max((r[3] for r in near), default=0)},
+            "unitig_bases_at_those_gaps": {"min": min((min(r[0], r[1]) for r in rows), default=0), "max": max((max(r[0], r[1]) for r in rows), default=0)},
+            "smallest_share_elsewhere_permille": sorted(1000 * r[4] // r[3] for r in rows if r[4] >= 0 and 20 * r[4] > r[3])[:5]}
 
 
 def step_measure(args):
@@ -191,6 +234,53 @@ def step_measure(args):
             differ += piece not in genome and piece not in other
         out["junctions_checked"] = checked
         out["junctions_that_differ_from_the_genome"] = differ
+        if args.mismatches > 0:
+            wa = C.c_uint64()
+            assert L.sigax_join_approx_workspace(n, C.byref(wa)) == 0
+            d_mm, d_ast, d_awork = dbuf(4 * n), dbuf(192), dbuf(wa.value)
+            aopts = _lib.JoinApproxOpts(0, args.join_min_overlap, args.join_max_overlap, args.join_slack, args.join_kmer, args.join_min_count,
+                                        args.mismatches, args.permille, 0)
+
+            def approx_call(d_aout, cap):
+                return L.sigax_join_approx_device(pair.handle, d_stat, n, d_so, d_st16, d_gco, d_scl, d_glay, d_gout, gtotal, C.byref(aopts), d_jco, d_jlay,
+                                                  d_aout, cap, d_joins, d_mm, d_ast, d_awork, wa.value, stream)
+
+            assert approx_call(None, 0) == 0, _lib.last_error()
+            assert hip.hipStreamSynchronize(stream) == 0
+            atotal = int(fetch(d_ast, 24)[11])
+            d_aout = dbuf(atotal)
+            exact_ms = t["median_ms"]
+            t = timed(lambda: approx_call(d_aout, atotal))
+            astat = dict(zip(_lib.JOIN_APPROX_STATUS, [int(x) for x in fetch(d_ast, 24)]))
+            assert astat["bases_not_written"] == 0 and astat["gaps"] == jstat["gaps"]
+            arecs = fetch(d_joins, astat["gaps"], _lib.JOIN_DTYPE)
+            mm = fetch(d_mm, astat["gaps"], np.uint32)
+            approx = (arecs["cls"] == 0) & (mm >> 16 != 0)
+            was = jrecs["cls"]  # the exact call's class of the same gap
+            assert bool(((arecs["cls"] == was) | (was == 4)).all()), "a gap the exact call did not class NONE changed"
+            aseqs = fetch(d_aout, atotal, np.uint8).tobytes()
+            asco = fetch(d_jco, sstat["scaffolds"] + 1)
+            checked = differ = 0
+            for r in arecs[approx][:args.check]:
+                lo_, hi_ = int(asco[r["scaffold"]]), int(asco[r["scaffold"] + 1])
+                at = lo_ + int(r["offset"])  # where the overlap begins
+                piece = aseqs[max(at - k, lo_):min(at + int(r["overlap"]) + k, hi_)]
+                checked += 1
+                differ += piece not in genome and piece not in other
+            t.update({"call": "join_approx_device", "max_mismatches": args.mismatches, "mismatch_permille": args.permille, "status": astat,
+                      "over_join_device": t["median_ms"] / exact_ms, "workspace_bytes": int(wa.value),
+                      "approximate_joins": int(approx.sum()), "columns_taken_left": astat["mismatch_columns"] - astat["columns_from_right"],
+                      "columns_taken_right": astat["columns_from_right"],
+                      "exact_NONE_gaps_now": {_lib.JOIN_CLASSES[c]: int((arecs["cls"][was == 4] == c).sum())
+                                              for c in sorted(set(int(x) for x in arecs["cls"][was == 4]))},
+                      "mismatches_of_approximate_joins": {str(d): int(((mm & 0xFF)[approx] == d).sum()) for d in sorted(set(int(x) for x in (mm & 0xFF)[approx]))},
+                      "overlap_lengths_joined_approximately": {"min": int(arecs["overlap"][approx].min()) if approx.any() else 0,
+                                                               "max": int(arecs["overlap"][approx].max()) if approx.any() else 0},
+                      "approximate_junctions_checked": checked, "approximate_junctions_that_differ_from_the_genome": differ})
+            t["ends_of_the_gaps_still_NONE"] = nearest_overlaps(fetch(d_gout, gtotal, np.uint8).tobytes(), fetch(d_gco, sstat["scaffolds"] + 1),
+                                                                fetch(d_scl, sstat["scaffolds"] + 1), fetch(d_glay, n, _lib.PLACEMENT_DTYPE),
+                                                                fetch(d_so, n + 1), arecs, arecs["cls"] == 4, args.join_min_overlap, args.join_max_overlap)
+            out["calls"].append(t)
     finally:
         for q in held:
             hip.hipFree(q)
@@ -232,6 +322,8 @@ def main():
     ap.add_argument("--join-slack", type=int, default=100)
     ap.add_argument("--join-kmer", type=int, default=31)
     ap.add_argument("--join-min-count", type=int, default=3)
+    ap.add_argument("--mismatches", type=int, default=0, help="also measure sigax_join_approx_device with this max_mismatches (0: the exact call alone)")
+    ap.add_argument("--permille", type=int, default=50, help="its mismatch_permille")
     ap.add_argument("--check", type=int, default=20000, help="joined junctions to look up in the genome, at most")
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dir", default=None, help=argparse.SUPPRESS)
@@ -250,7 +342,7 @@ def main():
                        "--error-rate", str(rate)]
                 for key in ("reads", "genome", "length", "insert", "seed", "min_overlap", "bins", "max_span", "min_pairs", "link_ratio",
                             "min_unitig_bases", "max_gap", "steps", "warmup", "check", "gap_kmer", "gap_min_count", "gap_slack", "gap_max_fill", "walk_bases",
-                            "join_min_overlap", "join_max_overlap", "join_slack", "join_kmer", "join_min_count"):
+                            "join_min_overlap", "join_max_overlap", "join_slack", "join_kmer", "join_min_count", "mismatches", "permille"):
                     cmd += ["--" + key.replace("_", "-"), str(getattr(args, key))]
                 rc = subprocess.call(cmd, cwd=ROOT)
                 if rc != 0:
