@@ -611,7 +611,7 @@ int  sigax_unitigs_chimeric_host(int device, const sigax_edge* edges, uint64_t n
  *             and is counted.
  *   4. MARK   All reads of a popped arm get removed[read] = r | SIGAX_REMOVED_BUBBLE.  Only these entry points ever set that bit.
  *             A winner is never removed by this step.  An arm is in exactly one group.
- * Out of scope: arms of different span (indel bubbles); bubbles whose arms are themselves branched (paths, not unitigs); a
+ * Out of scope: arms of different span (indel bubbles: the `--bubble-edits` block below); bubbles whose arms are themselves branched (paths, not unitigs); a
  * second candidate winner when the first fails the bases test.  Not held: inputs beyond 2^32 bases (nor are the prune and
  * chimeric rounds).
  *
@@ -649,6 +649,72 @@ int  sigax_unitigs_bubble_host(int device, const sigax_edge* edges, uint64_t n_e
                                uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                                sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                uint64_t status24[24]);
+/* ---- `siga unitig -x -b --bubble-edits`: indel bubble popping in the rounds (csrc/sigax_unitig.hip) ---------------------------------
+ * The bubble step above pops an arm only where it holds as many bases between its two neighbours as the winner: substitutions.  An
+ * inserted or deleted base gives two arms of different span, which no other step takes: both carry full-length overlaps at both
+ * ends.  The INDEL STEP compares such arms by a bounded edit distance.  Nothing of it is in the reference (SmoothingVisitor::visit
+ * returns false); the rules are this library's own, and no decision depends on the order of records, reads, lanes or table slots.
+ * Everything not said here is as in the `-b` block above: live records, PARTICIPANTS, ARM, key(U) = (lo, hi), o_lo, o_hi, span,
+ * A(U), K, bases(U).  DESIGN.md 9n; the serial restatement the tests hold this against is tests/indel_cases.py::expected_indel.
+ *
+ * sigax_indel_opts: bubble = the sigax_bubble_opts of the block above (its reserved3 still 0); max_edits E (--bubble-edits; 0 = no
+ * indel step; at most 31), max_edit_permille De (--bubble-edit-permille), reserved4 = 0.  With E > 0 the call needs 0 <
+ * max_bubble_span <= 4096: Lb bounds the windows, and 4096 bytes per window is what one wave stages.
+ *
+ * One round r = 1, 2, ...: CUT STEP, TRIM STEP, BUBBLE STEP (when Lb > 0), INDEL STEP (when E > 0), CHIMERIC STEP.  Each step runs over
+ * the state the step before left and takes every decision from the state at its own start.  A round in which no step changed
+ * anything ends the loop and is not counted.  The indel step comes before the chimeric step for the reason the bubble step does.
+ *
+ * The indel verdict, for the unitigs of the state at the start of the step:
+ *   1. ARM    As in the bubble block, and an arm takes part iff 1 <= span(U) <= Lb.
+ *   2. GROUP  The arms that take part and share (lo, hi) form a group, whatever their spans.  A group of one does nothing.  The
+ *             WINNER W is the arm with the largest K, then the smallest id of its first read; every other arm is a LOSER.
+ *   3. PAIR   For a loser L with a = span(L), b = span(W): a == b: SAME_SPAN, the bubble step's business; it is not compared here
+ *             and stays.  |a - b| > E: FAR; it stays.  Otherwise the pair is compared.
+ *   4. EDITS  X(U) = A(U)[o_lo(U) .. o_lo(U) + span(U)).  ed = the unit-cost Levenshtein distance between X(L) and X(W), bytes
+ *             compared as bytes (N equals N, lower case differs from upper case), computed exactly up to E and "more than E"
+ *             beyond.  L is POPPED iff ed <= E and ed * 1000 <= De * min(bases(L), bases(W)) in u64: the divergence is measured
+ *             against the shorter arm, not against the window.  A compared loser that fails stays and is counted.
+ *   5. MARK   All reads of a popped arm get removed[read] = r | SIGAX_REMOVED_INDEL.  Only these entry points ever set that bit.  A
+ *             winner is never removed by this step.
+ * Out of scope: arms with span < 1 (the neighbours reach into each other: tandem indels, an indel inside a repeat longer than the
+ * window); bubbles whose arms are themselves branched; a second candidate winner when the first fails; inputs beyond 2^32 bases
+ * (the bubble rounds do not hold them either).
+ *
+ * status32 = 32 u64, written: 0-23 as status24, with 6 = rounds in which any step changed something and 9 = all removed reads, both
+ * including this step; 24 arms the indel steps popped, 25 their reads, 26 rounds in which an indel step removed something, 27
+ * compared losers kept, 28 losers not compared (SAME_SPAN + FAR), 27 and 28 summed over the rounds that ran; 29-31 zero.
+ *
+ * sigax_unitigs_indel_device: sigax_unitigs_bubble_device with these options and d_status32.  Asynchronous on `stream`, allocates
+ * nothing, never waits for the device; it enqueues max_rounds rounds, whose kernels return at once after a round that changed
+ * nothing (the prefix sum of an indel step has no such form; nothing reads its result then).  Every index is checked against its
+ * buffer; the recurrence runs at most E + 1 turns, a slide at most Lb steps, the bisection over a unitig's placements 32 steps, the
+ * group table's probes its capacity.  d_work = sigax_unitigs_indel_workspace(n_reads, n_edges, d_uedges != NULL, careful) bytes: the
+ * bubble call's scratch, then 33 408 bytes of counters and 4 bytes per read, each piece rounded up to 16 bytes.  max_edits = 0 gives
+ * exactly the bubble call's result, status 24-31 zero and no new flag bit.  Refusals as for the bubble call, and reserved4 != 0,
+ * max_edits > 31, max_edits > 0 with max_bubble_span == 0 or > 4096: SIGAX_E_ARG.  Whatever the records hold, nothing outside the
+ * buffers is touched. */
+#define SIGAX_REMOVED_INDEL 0x20000000u
+#define SIGAX_INDEL_MAX_EDITS 31u
+#define SIGAX_INDEL_MAX_SPAN 4096u
+typedef struct sigax_indel_opts {
+  sigax_bubble_opts bubble;
+  uint32_t max_edits;          /* E; 0 = no indel step; at most SIGAX_INDEL_MAX_EDITS */
+  uint32_t max_edit_permille;  /* De */
+  uint32_t reserved4[2];       /* = 0 */
+} sigax_indel_opts;
+int  sigax_unitigs_indel_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_indel_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts,
+                                void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status32, void* d_work,
+                                uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_bubble_host, with status32.  It stops after the first round that changed nothing. */
+int  sigax_unitigs_indel_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                              const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts,
+                              uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                              sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                              uint64_t status32[32]);
 /* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
  * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
  * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain

@@ -32,6 +32,11 @@ SIGAX_TRIM_NO_COVERAGE = 0xFFFFFFFF
 SIGAX_REMOVED_CHIMERIC = 0x80000000
 SIGAX_REMOVED_BUBBLE = 0x40000000
 SIGAX_BUBBLE_NO_BASES = 0xFFFFFFFF
+SIGAX_REMOVED_INDEL = 0x20000000
+SIGAX_INDEL_MAX_EDITS = 31
+SIGAX_INDEL_MAX_SPAN = 4096
+# the entries 24-31 of sigax_unitigs_indel_*'s status32, by name
+INDEL_STATUS = ("indel_popped", "indel_reads", "indel_rounds", "indel_kept", "indel_not_compared", "_29", "_30", "_31")
 TRIM_MAX_ROUNDS = 64
 SIGAX_NO_MATE = 0xFFFFFFFF
 SIGAX_PAIRS_OUTWARD = 1
@@ -89,6 +94,10 @@ class ChimericOpts(C.Structure):  # sigax_chimeric_opts
 class BubbleOpts(C.Structure):  # sigax_bubble_opts
     _fields_ = [("chimeric", ChimericOpts), ("max_bubble_span", C.c_uint32), ("max_divergence_permille", C.c_uint32),
                 ("reserved3", C.c_uint32 * 2)]
+
+
+class IndelOpts(C.Structure):  # sigax_indel_opts
+    _fields_ = [("bubble", BubbleOpts), ("max_edits", C.c_uint32), ("max_edit_permille", C.c_uint32), ("reserved4", C.c_uint32 * 2)]
 
 
 class PairsOpts(C.Structure):  # sigax_pairs_opts
@@ -160,6 +169,7 @@ SYMBOLS = [
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
     "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
     "sigax_unitigs_bubble_workspace", "sigax_unitigs_bubble_device", "sigax_unitigs_bubble_host",
+    "sigax_unitigs_indel_workspace", "sigax_unitigs_indel_device", "sigax_unitigs_indel_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
@@ -275,6 +285,11 @@ def lib():
                                               vp, u64, vp]
     L.sigax_unitigs_bubble_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(BubbleOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
                                             pvp, pvp, pvp, pvp, vp]
+    L.sigax_unitigs_indel_workspace.argtypes = [u64, u64, ci, ci, C.POINTER(u64)]
+    L.sigax_unitigs_indel_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(IndelOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, u64, vp]
+    L.sigax_unitigs_indel_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(IndelOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
+                                           pvp, pvp, pvp, pvp, vp]
     L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]

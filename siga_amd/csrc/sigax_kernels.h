@@ -398,6 +398,26 @@ static const uint32_t BUBBLE_NO_BASES = 0xFFFFFFFFu;
 // step clears its own scratch.  launch_bubble_status: status[20 .. 23], after launch_chimeric_status.
 void launch_bubble_round(const UnitigBubbleArgs& a, hipStream_t st);
 void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st);
+// indel bubble popping (sigax_unitigs_indel_*): the bubble block and what a round's indel step needs.  The step runs after the bubble
+// step over the same scratch (neighbours, arms, placements, group table, verdicts); only its own kernels see the fields below.
+struct UnitigIndelArgs : UnitigBubbleArgs {
+  uint32_t* pairs;                       // [n_reads]: the heads of the losers that wait for the edit distance, as appended
+  unsigned long long* ind;               // IND_WORDS u64, zeroed before round 1: the IND_C_* counters, slotted as the trim counters are;
+                                         // the appended pairs at IND_APPENDED; at IND_ROUND0 + r whether round r's step removed something
+  uint32_t max_edits, max_edit_permille;
+};
+enum { IND_C_POPPED = 0, IND_C_READS = 1, IND_C_KEPT = 2, IND_C_SKIPPED = 3, IND_COUNTERS = 4,
+       IND_APPENDED = IND_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, IND_ROUND0 = IND_APPENDED + 8, IND_WORDS = IND_ROUND0 + TRIM_MAX_ROUNDS + 8,
+       IND_MAX_SPAN = 4096, IND_MAX_EDITS = 31 };
+static const uint32_t REMOVED_INDEL = 0x20000000u;
+// one round's indel step (a.round >= 1, a.maxlen = NULL, 0 < a.max_bubble_span <= IND_MAX_SPAN, 0 < a.max_edits <= IND_MAX_EDITS), after
+// launch_bubble_round and before launch_chimeric_round: the graph of the live records, the arms as the bubble step finds them, their
+// groups by (lo, hi) alone, a group's winner, the bounded edit distance of every other arm whose span is within max_edits of the
+// winner's and not equal to it, removed[] marked with REMOVED_INDEL.  Its kernels leave at once when the round before changed nothing.
+// The caller resets as for launch_trim_round; the step clears its own scratch.  launch_indel_status: status[24 .. 31], after
+// launch_bubble_status.
+void launch_indel_round(const UnitigIndelArgs& a, hipStream_t st);
+void launch_indel_status(const UnitigIndelArgs& a, hipStream_t st);
 
 // `siga unitig --pairs` (sigax_pairs.hip): mate-pair statistics and links over the layout a unitig call left.  Everything below
 // `status` is the caller's scratch (sigax_pairs.cpp lays it out).

@@ -8,12 +8,12 @@ static_assert(sizeof(sigax_placement) == 16, "sigax_placement must be 16 bytes")
 namespace {
 
 // What a call does beyond the plain unitigs: every level is the one below it with one more step in its rounds, a longer
-// status block (6, 12, 16, 20, 24 counts) and more scratch behind the same pieces.
-enum Level { UNITIG = 0, TRIM = 1, PRUNE = 2, CHIMERIC = 3, BUBBLE = 4 };
-const char* const LEVEL_NAME[] = {"unitig", "trim", "prune", "chimeric", "bubble"};
+// status block (6, 12, 16, 20, 24, 32 counts) and more scratch behind the same pieces.
+enum Level { UNITIG = 0, TRIM = 1, PRUNE = 2, CHIMERIC = 3, BUBBLE = 4, INDEL = 5 };
+const char* const LEVEL_NAME[] = {"unitig", "trim", "prune", "chimeric", "bubble", "indel"};
 const char* const WORKSPACE_FN[] = {"sigax_unitigs_workspace", "sigax_unitigs_trim_workspace", "sigax_unitigs_prune_workspace",
-                                    "sigax_unitigs_chimeric_workspace", "sigax_unitigs_bubble_workspace"};
-u64 status_words(int level) { return level == UNITIG ? 6 : 8 + 4 * (u64)level; }
+                                    "sigax_unitigs_chimeric_workspace", "sigax_unitigs_bubble_workspace", "sigax_unitigs_indel_workspace"};
+u64 status_words(int level) { return level == UNITIG ? 6 : level == INDEL ? 32 : 8 + 4 * (u64)level; }
 
 // where the pieces of the caller's scratch lie (every piece 16-byte aligned).  A level's pieces follow those of the level below
 // at the same offsets: a call whose upper steps are off runs as the lower one over the same scratch.
@@ -24,6 +24,7 @@ struct RoundsWork {
   u64 prune, maxlen, uniq, maxself, keys, key_cap;                                    // PRUNE: a round's cut step
   u64 chim, prune_aside, nbr, minb[2], mink[2];                                       // CHIMERIC: a round's chimeric step
   u64 bub, bnbr, blen, arm, where, aside, gslot, losers, table, best, group_cap;      // BUBBLE: a round's bubble step
+  u64 ind, pairs;                                                                     // INDEL: a round's indel step
   u64 bytes;
 };
 RoundsWork rounds_work(Level level, u64 n, u64 n_edges, bool graph, bool careful) {
@@ -92,7 +93,10 @@ RoundsWork rounds_work(Level level, u64 n, u64 n_edges, bool graph, bool careful
   while (w.group_cap < 2 * n) w.group_cap <<= 1;
   w.table = take(w.group_cap * 4);
   w.best = take(w.group_cap * 8);
-  ends_at(BUBBLE);
+  if (ends_at(BUBBLE)) return w;
+  w.ind = take(IND_WORDS * 8);
+  w.pairs = take(n * 4);
+  ends_at(INDEL);
   return w;
 }
 
@@ -110,35 +114,42 @@ int workspace_of(Level level, u64 n_reads, u64 n_edges, int want_graph, int care
   return SIGAX_OK;
 }
 
-// The options of every rounds call as the bubble call's: a lower level leaves the fields of the upper ones zero, and a step
+// The options of every rounds call as the indel call's: a lower level leaves the fields of the upper ones zero, and a step
 // whose own threshold is zero is off.  NULL stays NULL (opts_ok refuses it).
-const sigax_bubble_opts* opts_view(const sigax_trim_opts* o, sigax_bubble_opts* v) {
+const sigax_indel_opts* opts_view(const sigax_trim_opts* o, sigax_indel_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  sigax_prune_opts& p = v->chimeric.prune;
+  sigax_prune_opts& p = v->bubble.chimeric.prune;
   p.max_rounds = o->max_rounds;
   p.min_branch_length = o->min_branch_length;
   p.min_branch_coverage = o->min_branch_coverage;
   p.reserved = o->reserved;
   return v;
 }
-const sigax_bubble_opts* opts_view(const sigax_prune_opts* o, sigax_bubble_opts* v) {
+const sigax_indel_opts* opts_view(const sigax_prune_opts* o, sigax_indel_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  v->chimeric.prune = *o;
+  v->bubble.chimeric.prune = *o;
   return v;
 }
-const sigax_bubble_opts* opts_view(const sigax_chimeric_opts* o, sigax_bubble_opts* v) {
+const sigax_indel_opts* opts_view(const sigax_chimeric_opts* o, sigax_indel_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  v->chimeric = *o;
+  v->bubble.chimeric = *o;
   return v;
 }
-const sigax_bubble_opts* opts_view(const sigax_bubble_opts* o, sigax_bubble_opts*) { return o; }
+const sigax_indel_opts* opts_view(const sigax_bubble_opts* o, sigax_indel_opts* v) {
+  if (!o) return nullptr;
+  *v = {};
+  v->bubble = *o;
+  return v;
+}
+const sigax_indel_opts* opts_view(const sigax_indel_opts* o, sigax_indel_opts*) { return o; }
 
-// prune's refusals, then chimeric's, then bubble's.  The bubble step alone needs neither G nor N.
-int opts_ok(Level level, const sigax_bubble_opts* o, u64 n_reads) {
-  if (!o) return sigax_fail(SIGAX_E_ARG, "NULL where the %s options are required", LEVEL_NAME[level]);
+// prune's refusals, then chimeric's, then bubble's, then indel's.  The bubble and the indel step need neither G nor N.
+int opts_ok(Level level, const sigax_indel_opts* io, u64 n_reads) {
+  if (!io) return sigax_fail(SIGAX_E_ARG, "NULL where the %s options are required", LEVEL_NAME[level]);
+  const sigax_bubble_opts* o = &io->bubble;
   const sigax_prune_opts& p = o->chimeric.prune;
   if (p.reserved != 0) return sigax_fail(SIGAX_E_ARG, "sigax_%s_opts.reserved must be 0", level == TRIM ? "trim" : "prune");
   if (p.careful > 1) return sigax_fail(SIGAX_E_ARG, "careful %u: 0 or 1", p.careful);
@@ -153,6 +164,12 @@ int opts_ok(Level level, const sigax_bubble_opts* o, u64 n_reads) {
       return sigax_fail(SIGAX_E_ARG, "genome_size must be given with min_chimeric_length > 0");
   }
   if (level >= BUBBLE && (o->reserved3[0] != 0 || o->reserved3[1] != 0)) return sigax_fail(SIGAX_E_ARG, "sigax_bubble_opts.reserved3 must be 0");
+  if (level >= INDEL) {
+    if (io->reserved4[0] != 0 || io->reserved4[1] != 0) return sigax_fail(SIGAX_E_ARG, "sigax_indel_opts.reserved4 must be 0");
+    if (io->max_edits > SIGAX_INDEL_MAX_EDITS) return sigax_fail(SIGAX_E_ARG, "max_edits %u: at most %u", io->max_edits, SIGAX_INDEL_MAX_EDITS);
+    if (io->max_edits > 0 && (o->max_bubble_span == 0 || o->max_bubble_span > SIGAX_INDEL_MAX_SPAN))
+      return sigax_fail(SIGAX_E_ARG, "max_bubble_span %u with max_edits > 0: 1 to %u", o->max_bubble_span, SIGAX_INDEL_MAX_SPAN);
+  }
   return SIGAX_OK;
 }
 
@@ -294,19 +311,28 @@ void bubble_args(UnitigBubbleArgs& a, const UnitigBufs& b, const RoundsWork& w, 
   a.max_divergence_permille = o.max_divergence_permille;
 }
 
-// The rounds of every form, device and host.  A round is up to four steps, each over the graph the step before left: cut
-// (PRUNE up, delta > 0), trim, bubble (BUBBLE), chimeric (CHIMERIC up, Lc > 0); then the unitigs of what is left, the lifted
+void indel_args(UnitigIndelArgs& a, const UnitigBufs& b, const RoundsWork& w, const sigax_indel_opts& o) {
+  char* base = (char*)b.work;
+  a.pairs = (uint32_t*)(base + w.pairs);
+  a.ind = (u64*)(base + w.ind);
+  a.max_edits = o.max_edits;
+  a.max_edit_permille = o.max_edit_permille;
+}
+
+// The rounds of every form, device and host.  A round is up to five steps, each over the graph the step before left: cut
+// (PRUNE up, delta > 0), trim, bubble (BUBBLE up, Lb > 0), indel (INDEL, E > 0), chimeric (CHIMERIC up, Lc > 0); then the unitigs of what is left, the lifted
 // records and the counts.  A call whose top step is off runs as the level below -- down to the trim kernels over the trim
 // block when nothing cuts -- and the counts of the steps that are off are zeroed behind it; the scratch is still asked for as
 // the requested level lays it out.
 // paced: the host form's loop -- it reads each round's flag and stops after the first round that changed nothing, where the
 // device form enqueues every round and lets the idle ones leave at once.
-int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts, const UnitigBufs& b,
+int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t min_overlap, const sigax_indel_opts* iopts, const UnitigBufs& b,
                    void* stream, bool paced) {
   const int rl = unitig_limits(n_reads, n_edges);
   if (rl != SIGAX_OK) return rl;
-  const int ro = opts_ok(level, opts, n_reads);
+  const int ro = opts_ok(level, iopts, n_reads);
   if (ro != SIGAX_OK) return ro;
+  const sigax_bubble_opts* const opts = &iopts->bubble;
   const sigax_chimeric_opts& co = opts->chimeric;
   const sigax_prune_opts& po = co.prune;
   const RoundsWork w = rounds_work(level, n_reads, n_edges, b.uedges != nullptr, po.careful != 0);
@@ -321,16 +347,18 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
     return SIGAX_OK;
   }
   int eff = level;  // the level the call runs as
+  if (eff == INDEL && iopts->max_edits == 0) eff = BUBBLE;
   if (eff == BUBBLE && opts->max_bubble_span == 0) eff = CHIMERIC;
   if (eff == CHIMERIC && co.min_chimeric_length == 0) eff = PRUNE;
   if (eff == PRUNE && po.delta == 0) eff = TRIM;
 
-  UnitigBubbleArgs a = {};
+  UnitigIndelArgs a = {};
   static_cast<UnitigArgs&>(a) = unitig_args(b, w, n_edges, n_reads, min_overlap);
   trim_args(a, b, w, po);
   if (eff >= PRUNE) prune_args(a, b, w, po);
   if (eff >= CHIMERIC) chimeric_args(a, b, w, co);
   if (eff >= BUBBLE) bubble_args(a, b, w, *opts);
+  if (eff >= INDEL) indel_args(a, b, w, *iopts);
   char* base = (char*)b.work;
   uint32_t* const maxlen = (uint32_t*)(base + w.maxlen);
 
@@ -343,6 +371,7 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
     HIP_TRY(hipMemsetAsync(a.prune_aside, 0, PRUNE_WORDS * 8, st));
   }
   if (eff >= BUBBLE) HIP_TRY(hipMemsetAsync(a.bub, 0, BUB_WORDS * 8, st));
+  if (eff >= INDEL) HIP_TRY(hipMemsetAsync(a.ind, 0, IND_WORDS * 8, st));
   auto reset = [&]() -> hipError_t {  // every pass over degrees, links and counts of its own
     const hipError_t e = hipMemsetAsync(base + w.zero_from, 0, (size_t)w.zero_bytes, st);
     return e != hipSuccess ? e : hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st);
@@ -363,6 +392,10 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
     if (eff >= BUBBLE) {
       HIP_TRY(reset());  // the bubble step, over what the trim step left
       launch_bubble_round(a, st);
+    }
+    if (eff >= INDEL) {
+      HIP_TRY(reset());  // the indel step, over what the bubble step left
+      launch_indel_round(a, st);
     }
     if (eff >= CHIMERIC && co.min_chimeric_length > 0) {
       HIP_TRY(reset());  // the chimeric step, over what the step before left
@@ -386,9 +419,10 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
   }
   if (eff >= CHIMERIC) launch_chimeric_status(a, st);
   if (eff >= BUBBLE) launch_bubble_status(a, st);
+  if (eff >= INDEL) launch_indel_status(a, st);
   HIP_TRY(hipGetLastError());
-  for (int l = eff + 1; l <= level; ++l) {  // the steps that are off: their four counts zero, and no record cut
-    HIP_TRY(hipMemsetAsync((u64*)b.status + status_words(l - 1), 0, 32, st));
+  for (int l = eff + 1; l <= level; ++l) {  // the steps that are off: their counts zero, and no record cut
+    HIP_TRY(hipMemsetAsync((u64*)b.status + status_words(l - 1), 0, (size_t)(status_words(l) - status_words(l - 1)) * 8, st));
     if (l == PRUNE && n_edges) HIP_TRY(hipMemsetAsync(b.cut, 0, (size_t)n_edges * 4, st));
   }
   return SIGAX_OK;
@@ -433,7 +467,7 @@ int stage_reads(DevGuard& g, int device, const sigax_edge* edges, u64 n_edges, c
 // The host form of every level.  UNITIG: no options, no removed, cut or uedges, six counts, and *layout holds all n_reads
 // placements.  TRIM: no cut.  `status_out` holds status_words(level) counts.
 int unitigs_host(Level level, int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs, const uint64_t* offs,
-                 uint64_t n_reads, uint32_t min_overlap, const sigax_bubble_opts* opts, uint64_t* n_unitigs, uint64_t** seq_offs,
+                 uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts, uint64_t* n_unitigs, uint64_t** seq_offs,
                  uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut,
                  sigax_edge** uedges, uint64_t* status_out) {
   const u64 n_status = status_words(level);
@@ -457,14 +491,14 @@ int unitigs_host(Level level, int device, const sigax_edge* edges, uint64_t n_ed
     if (ro != SIGAX_OK) return ro;
   }
   const u64 n = n_reads;
-  u64 status[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  u64 status[32] = {0};
   DevGuard g;
   UnitigBufs b = {};
   u64 nb = 0;
   const int rs = stage_reads(g, device, edges, n_edges, lengths, seqs, offs, n, &b, &nb);
   if (rs != SIGAX_OK) return rs;
   if (n) {
-    b.work_bytes = rounds_work(level, n, n_edges, uedges != nullptr, level >= PRUNE && opts->chimeric.prune.careful != 0).bytes;
+    b.work_bytes = rounds_work(level, n, n_edges, uedges != nullptr, level >= PRUNE && opts->bubble.chimeric.prune.careful != 0).bytes;
     HIP_TRY(g.alloc(&b.seq_offs, ((size_t)n + 1) * 8));
     HIP_TRY(g.alloc(&b.lay_offs, ((size_t)n + 1) * 8));
     HIP_TRY(g.alloc(&b.uflags, (size_t)n * 4));
@@ -595,14 +629,14 @@ extern "C" int sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t 
 }
 
 // ---- the rounds calls: tip trimming and the lifted records, non-maximal overlap cutting, chimeric unitig removal, bubble
-// popping.  Each is the driver at its level over its options seen as the bubble call's. ----
+// popping, indel bubble popping.  Each is the driver at its level over its options seen as the indel call's. ----
 #define SIGAX_ROUNDS_DEVICE(LEVEL, OPTS, CUT)                                                                                          \
-  sigax_bubble_opts v;                                                                                                                 \
+  sigax_indel_opts v;                                                                                                                  \
   const UnitigBufs b = {d_edges, d_lengths, d_seqs, d_offs, d_seq_offs, d_lay_offs, d_uflags, d_layout, d_useqs, d_removed, CUT, d_uedges, \
                         d_status, d_work, work_bytes};                                                                                 \
   return unitigs_rounds(LEVEL, device, n_edges, n_reads, min_overlap, opts_view(OPTS, &v), b, stream, false)
 #define SIGAX_ROUNDS_HOST(LEVEL, OPTS, CUT)                                                                                              \
-  sigax_bubble_opts v;                                                                                                                 \
+  sigax_indel_opts v;                                                                                                                  \
   return unitigs_host(LEVEL, device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, opts_view(OPTS, &v), n_unitigs, seq_offs, \
                       lay_offs, uflags, layout, useqs, removed, CUT, uedges, status)
 
@@ -675,4 +709,22 @@ extern "C" int sigax_unitigs_bubble_host(int device, const sigax_edge* edges, ui
                                          sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                          uint64_t status[24]) {
   SIGAX_ROUNDS_HOST(BUBBLE, opts, cut);
+}
+
+extern "C" int sigax_unitigs_indel_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes) {
+  return workspace_of(INDEL, n_reads, n_edges, want_graph, careful, bytes);
+}
+extern "C" int sigax_unitigs_indel_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                          const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts,
+                                          void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                          void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status, void* d_work,
+                                          uint64_t work_bytes, void* stream) {
+  SIGAX_ROUNDS_DEVICE(INDEL, opts, d_cut);
+}
+extern "C" int sigax_unitigs_indel_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                        const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts,
+                                        uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                        sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                                        uint64_t status[32]) {
+  SIGAX_ROUNDS_HOST(INDEL, opts, cut);
 }

@@ -58,10 +58,18 @@
 //   k_bub_losers   one lane per read: an arm that is not its group's maximum is popped (no bases test) or appended to a list
 //   k_bub_compare  one wave per appended loser: lanes stride over the window, each base found by bisecting the placements
 //   k_bub_mark     one lane per read: removed[r] = round | 0x40000000 under a popped head
+// Indel bubble popping (sigax_unitigs_indel_*; tests/indel_cases.py::expected_indel): a step between the bubble and the
+// chimeric step of a round, over the <TRIM = 2> kernels, k_bub_ends, k_bub_place and k_bub_arms as they are, and
+//   k_ind_clear    k_bub_clear's work, and no pair appended
+//   k_ind_group    one lane per read: k_bub_group under the key (lo, hi) alone
+//   k_ind_losers   one lane per read: a loser of the winner's span, or more than E bases from it, stays; another is appended to a list
+//   k_ind_compare  one wave per appended pair: both windows staged as bytes in LDS (at most 4096 + 4096), then the furthest-reaching
+//                  recurrence over the 2 E + 1 diagonals, one per lane, neighbours by shuffles, at most E + 1 turns
+//   k_ind_mark     one lane per read: removed[r] = round | 0x20000000 under a popped head
 // The tables' probe loops are bounded by their capacity, which holds at least twice the keys that can go in.
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
 // consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
-// beyond the 64 descriptors, no MFMA.
+// beyond the 64 descriptors and the indel step's two windows, no MFMA.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -1085,6 +1093,196 @@ __global__ void k_bub_status(UnitigBubbleArgs A) {
   A.status[23] = bub_count(A, BUB_C_KEPT);
 }
 
+// ---- indel bubble popping: one round's indel step, after the bubble step (the rules are sigax.h's own, as the bubble step's) ----
+__device__ __forceinline__ u64* ind_slot(const UnitigIndelArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  return A.ind + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 ind_count(const UnitigIndelArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.ind[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+
+// Before an indel step: what k_bub_clear empties, and no pair appended.
+__global__ __launch_bounds__(256) void k_ind_clear(UnitigIndelArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < 2 * A.n_reads) {
+    A.bnbr[i] = NIL;
+    A.blen[i] = 0u;
+  }
+  if (i < A.group_cap) {
+    A.table[i] = NIL;
+    A.best[i] = 0ull;
+  }
+  if (i == 0) A.ind[IND_APPENDED] = 0ull;
+}
+
+// One lane per read, as k_bub_group with the key (lo, hi) alone: arms of every span that takes part meet in one group.
+__global__ __launch_bounds__(256) void k_ind_group(UnitigIndelArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (r >= A.n_reads) return;
+  const uint4 arm = A.arm[r];
+  if (arm.z == 0u) return;
+  const u64 mask = A.group_cap - 1ull;
+  u64 at = key_hash(((u64)arm.x << 32) | arm.y) & mask;
+  for (u64 p = 0; p < A.group_cap; ++p, at = (at + 1ull) & mask) {  // (never more than group_cap probes; at most half the table fills)
+    const u32 was = atomicCAS(&A.table[at], NIL, (u32)r);
+    bool mine = was == NIL || was == (u32)r;
+    if (!mine && (u64)was < A.n_reads) {
+      const uint4 o = A.arm[was];
+      mine = o.x == arm.x && o.y == arm.y;
+    }
+    if (mine) {
+      A.gslot[r] = (u32)at;
+      atomicMax(&A.best[at], (unit_reads(A, (u32)r) << 32) | (u64)(~(u32)r));
+      return;
+    }
+  }
+}
+
+// One lane per read.  An arm that is not its group's maximum is a loser: of the winner's span (the bubble step's business) or more
+// than max_edits bases from it, it stays and is counted; otherwise it is appended to the list k_ind_compare walks.
+__global__ __launch_bounds__(256) void k_ind_losers(UnitigIndelArgs A) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  const u32 lane = threadIdx.x & 63u;
+  bool loser = false, compared = false;
+  if (r < n) {
+    A.verdict[r] = 0u;
+    const u32 g = A.gslot[r];
+    if ((u64)g < A.group_cap) {
+      const u32 w = (u32)(~A.best[g]);
+      if (w != (u32)r && (u64)w < n) {
+        loser = true;
+        const u32 a = A.arm[r].z, b = A.arm[w].z;
+        compared = a != b && (a > b ? a - b : b - a) <= A.max_edits;
+      }
+    }
+  }
+  const u64 skipped = __ballot(loser && !compared), listed = __ballot(compared);
+  if (lane == 0u && skipped) atomicAdd(ind_slot(A, IND_C_SKIPPED), (u64)__popcll(skipped));
+  if (!listed) return;
+  u64 base = 0;
+  if (lane == 0u) base = atomicAdd(A.ind + IND_APPENDED, (u64)__popcll(listed));
+  base = __shfl(base, 0, 64);
+  const u64 at = base + (u64)__popcll(listed & ((1ull << lane) - 1ull));
+  if (compared && at < n) A.pairs[at] = (u32)r;
+}
+
+// the two windows of a pair, as bytes: X the loser's, Y the winner's
+struct IndelSh {
+  unsigned char x[IND_MAX_SPAN], y[IND_MAX_SPAN];
+};
+
+// One wave (one workgroup of 64) per appended pair, the grid striding over the list (at most n_reads / W + 1 turns).  Both windows are
+// staged in LDS through arm_base, one bisection per base.  Then the furthest-reaching recurrence over diagonals (Landau-Vishkin):
+// lane l owns diagonal d = l - E of the (loser, winner) matrix, column - row = d, and after turn e holds the furthest row that at most e
+// edits reach on it, or a negative value where none does.  A turn takes the two neighbours' reach by shuffles, keeps what stays
+// inside the matrix, and slides while the bytes agree (at most Lb steps).  At most E + 1 turns; the distance is the first e at which
+// diagonal b - a reaches row a.  Popped iff ed <= E and ed * 1000 <= De * min(bases(L), bases(W)).
+__global__ __launch_bounds__(64) void k_ind_compare(UnitigIndelArgs A) {
+  __shared__ IndelSh sh;
+  if (idle_round<2>(A)) return;
+  const u64 n = A.n_reads;
+  const u32 lane = threadIdx.x & 63u;
+  const int E = (int)(A.max_edits < (u32)IND_MAX_EDITS ? A.max_edits : (u32)IND_MAX_EDITS);
+  const int NONE = -0x40000000;
+  u64 appended = A.ind[IND_APPENDED];
+  if (appended > n) appended = n;
+  const u64 src_end = A.offs[n];
+  u64 popped = 0, kept = 0;
+  for (u64 i = blockIdx.x; i < appended; i += gridDim.x) {  // (every value that decides a branch here is the same in all lanes)
+    const u32 h = A.pairs[i];
+    if ((u64)h >= n) continue;
+    const u32 g = A.gslot[h];
+    if ((u64)g >= A.group_cap) continue;
+    const u32 w = (u32)(~A.best[g]);
+    if ((u64)w >= n) continue;
+    const uint4 al = A.arm[h], aw = A.arm[w];
+    const u32 sl = A.aside[h], sw = A.aside[w];
+    if (al.z == 0u || aw.z == 0u || al.z > (u32)IND_MAX_SPAN || aw.z > (u32)IND_MAX_SPAN) continue;
+    const int a = (int)al.z, b = (int)aw.z;
+    if (a - b > E || b - a > E) continue;
+    for (u32 t = lane; t < al.z; t += 64) sh.x[t] = (unsigned char)arm_base(A, h, al, sl, t, src_end);
+    for (u32 t = lane; t < aw.z; t += 64) sh.y[t] = (unsigned char)arm_base(A, w, aw, sw, t, src_end);
+    __syncthreads();
+    const int d = (int)lane - E, lim = a < b - d ? a : b - d;  // rows of diagonal d end at lim
+    int fr = NONE;
+    u32 ed = (u32)E + 1u;
+    for (int e = 0; e <= E; ++e) {
+      int t;
+      if (e == 0) {
+        t = d == 0 ? 0 : NONE;
+      } else {
+        int up = __shfl_up(fr, 1, 64), dn = __shfl_down(fr, 1, 64);  // diagonals d - 1 and d + 1
+        if (lane == 0u) up = NONE;
+        if (lane == 63u) dn = NONE;
+        t = fr >= 0 && fr < lim ? fr + 1 : fr;             // a substitution
+        if (up >= 0 && up + d <= b && up > t) t = up;      // a base the winner has and the loser lacks
+        if (dn >= 0 && dn < a && dn + 1 > t) t = dn + 1;   // a base the loser has and the winner lacks
+      }
+      if (lane > 2u * (u32)E) t = NONE;
+      if (t >= 0)
+        while (t < lim && (u32)(t + d) < (u32)b && sh.x[t] == sh.y[t + d]) ++t;
+      fr = t;
+      if (__shfl(fr, b - a + E, 64) >= a) {
+        ed = (u32)e;
+        break;
+      }
+    }
+    __syncthreads();  // (the next pair's bytes go where these lie)
+    const u64 bl = unit_bases(A, h), bw = unit_bases(A, w);
+    if (ed <= (u32)E && (u64)ed * 1000ull <= (u64)A.max_edit_permille * (bl < bw ? bl : bw)) {
+      if (lane == 0u) A.verdict[h] = 1u;
+      ++popped;
+    } else {
+      ++kept;
+    }
+  }
+  if (lane == 0u) {
+    if (popped) atomicAdd(ind_slot(A, IND_C_POPPED), popped);
+    if (kept) atomicAdd(ind_slot(A, IND_C_KEPT), kept);
+  }
+}
+
+// One lane per read, as k_bub_mark: the verdict lies under its head.
+__global__ __launch_bounds__(256) void k_ind_mark(UnitigIndelArgs A, const uint4* __restrict__ rk) {
+  if (idle_round<2>(A)) return;
+  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+  const u64 n = A.n_reads;
+  u32 gone = 0;
+  if (r < n && A.removed[r] == 0u) {
+    const u32 h = head_of(A, rk, 2u * (u32)r);
+    if (h != NIL && A.verdict[h] != 0u) {
+      A.removed[r] = A.round | REMOVED_INDEL;
+      gone = 1;
+    }
+  }
+  const u64 tg = wave_total(gone);
+  if ((threadIdx.x & 63u) == 0u && tg) {
+    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
+    atomicAdd(ind_slot(A, IND_C_READS), tg);
+    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+    A.ind[IND_ROUND0 + A.round] = 1ull;
+  }
+}
+
+__global__ void k_ind_status(UnitigIndelArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.ind[IND_ROUND0 + r] != 0ull;
+  A.status[24] = ind_count(A, IND_C_POPPED);
+  A.status[25] = ind_count(A, IND_C_READS);
+  A.status[26] = rounds;
+  A.status[27] = ind_count(A, IND_C_KEPT);
+  A.status[28] = ind_count(A, IND_C_SKIPPED);
+  A.status[29] = A.status[30] = A.status[31] = 0ull;
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
@@ -1243,4 +1441,30 @@ void launch_bubble_round(const UnitigBubbleArgs& a, hipStream_t st) {
 void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st) {
   if (a.n_reads == 0 || !a.removed) return;
   hipLaunchKernelGGL(k_bub_status, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_indel_round(const UnitigIndelArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads;
+  if (n == 0 || !a.removed || a.maxlen || !a.bnbr || !a.where || !a.pairs || !a.ind || a.max_bubble_span == 0u ||
+      a.max_bubble_span > (u32)IND_MAX_SPAN || a.max_edits == 0u || a.max_edits > (u32)IND_MAX_EDITS || a.round == 0u || a.round > TRIM_MAX_ROUNDS)
+    return;
+  hipLaunchKernelGGL(k_ind_clear, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
+  const UnitigPruneArgs& pa = a;
+  const UnitigBubbleArgs& ba = a;  // the bubble step's own kernels, over the block they know
+  const unsigned f = launch_graph<2>(pa, st);
+  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
+  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
+  if (a.n_edges) hipLaunchKernelGGL(k_bub_ends, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, ba);
+  launch_scan(a.cnt + (n + 1), n, a.partial, a.scan + (n + 1), a.scan_total, st);  // (no idle form, as in the bubble step)
+  hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, ba, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_bub_arms, dim3(blocks_of(n)), dim3(256), 0, st, ba, fin);
+  hipLaunchKernelGGL(k_ind_group, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_ind_losers, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_ind_compare, dim3((unsigned)(n < BUB_COMPARE_WAVES ? n : BUB_COMPARE_WAVES)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_ind_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+}
+
+void launch_indel_status(const UnitigIndelArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed || !a.ind) return;
+  hipLaunchKernelGGL(k_ind_status, dim3(1), dim3(64), 0, st, a);
 }

@@ -56,6 +56,11 @@ def lib():
                                                C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
                                                C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
                                                C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_uint64]
+        L.sigah_unitig_indel_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                              C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
+                                              C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
+                                              C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_char_p,
+                                              C.c_uint64]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -152,7 +157,8 @@ def locate_files(paths, prefix, rc=True, max_hits=1000, max_len=None, device=0, 
 def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreducible=True, rc=True, device=0, piece_reads=0, cut_terminal=0,
                 min_branch_length=150, min_branch_coverage=None, graph=None, removed=None, max_overlap_delta=0, max_overlap_carefully=False,
                 num_reads=None, genome_size=None, uniq_threshold=13.0, cut_edges=None, min_chimeric_length=0, min_chimeric_coverage=None,
-                max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None, max_bubble_span=0, bubble_divergence=50, bubbles=None):
+                max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None, max_bubble_span=0, bubble_divergence=50, bubbles=None,
+                bubble_edits=0, bubble_edit_permille=50):
     """`siga unitig`: FMIndex::load + Unitigger::run; the FASTA goes to the file `out`, or to stdout, the placements to the file
     `layout` when one is named.  piece_reads: reads per overlap call (0: 2^20); the result does not depend on it.
     cut_terminal (-x), min_branch_length (-n), min_branch_coverage (-C, None: no coverage test): tip trimming, 0 rounds = none;
@@ -166,8 +172,27 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
     of "name<TAB>round" lines of the reads it removed.  With a length the dict also holds chimeric_unitigs and chimeric_reads.
     max_bubble_span (-b; 0: none), bubble_divergence (--bubble-divergence, per mille; None: --no-bubble-bases): bubble popping between
     the trim and the chimeric step of a round; bubbles: the file of "name<TAB>round" lines of the reads it removed.  With a span the
-    dict also holds bubbles_popped, bubble_reads and bubbles_kept."""
+    dict also holds bubbles_popped, bubble_reads and bubbles_kept.
+    bubble_edits (--bubble-edits; 0: none; at most 31, with a span of at most 4096), bubble_edit_permille (--bubble-edit-permille):
+    indel bubble popping between the bubble and the chimeric step of a round; `bubbles` then also lists the reads it removed, as
+    "name<TAB>round<TAB>indel" lines behind the others.  With edits the dict also holds indels_popped, indel_reads, indels_kept and
+    indels_not_compared."""
     err = C.create_string_buffer(512)
+    if bubble_edits:
+        status = np.zeros(19, dtype=np.uint64)
+        if lib().sigah_unitig_indel_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,
+                                         (out or "").encode(), (layout or "").encode(), piece_reads, int(cut_terminal), int(min_branch_length),
+                                         -1 if min_branch_coverage is None else int(min_branch_coverage), (graph or "").encode(),
+                                         (removed or "").encode(), int(max_overlap_delta), int(max_overlap_carefully), int(num_reads or 0),
+                                         int(genome_size or 0), float(uniq_threshold), (cut_edges or "").encode(), int(min_chimeric_length),
+                                         -1 if min_chimeric_coverage is None else int(min_chimeric_coverage), int(max_chimeric_delta),
+                                         float(chimeric_threshold), (chimeric or "").encode(), int(max_bubble_span),
+                                         -1 if bubble_divergence is None else int(bubble_divergence), (bubbles or "").encode(),
+                                         int(bubble_edits), int(bubble_edit_permille), status.ctypes.data, err, 512) != 0:
+            raise RuntimeError("siga unitig failed: " + err.value.decode())
+        return dict(zip(("unitigs", "bases", "merged", "circular", "rounds", "islands", "dead_ends", "reads_removed", "records_cut", "cut_rounds",
+                         "chimeric_unitigs", "chimeric_reads", "bubbles_popped", "bubble_reads", "bubbles_kept", "indels_popped", "indel_reads",
+                         "indels_kept", "indels_not_compared"), (int(x) for x in status)))
     if max_bubble_span:
         status = np.zeros(15, dtype=np.uint64)
         if lib().sigah_unitig_bubble_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,

@@ -354,6 +354,39 @@ int sigah_unitig_bubble_file(const char* reads_path, const char* prefix, uint64_
   }
   return r;
 }
+// ... and with indel bubble popping between the bubble and the chimeric step of a round (bubble_edits 0 = none; at most 31, and then
+// max_bubble_span 1 to 4096); bubbles_path also lists the reads it removed ("name<TAB>round<TAB>indel"); status19 (unless NULL) =
+// status15, then {arms the indel steps popped, their reads, compared losers kept, losers not compared}
+int sigah_unitig_indel_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                            const char* fasta_path, const char* layout_path, uint64_t piece_reads, uint64_t cut_terminal,
+                            uint64_t min_branch_length, int64_t min_branch_coverage, const char* graph_path, const char* removed_path,
+                            uint64_t delta, int careful, uint64_t num_reads, uint64_t genome_size, double uniq_threshold,
+                            const char* cut_path, uint64_t min_chimeric_length, int64_t min_chimeric_coverage, uint64_t chimeric_delta,
+                            double chimeric_threshold, const char* chimeric_path, uint64_t max_bubble_span, int64_t bubble_divergence,
+                            const char* bubbles_path, uint64_t bubble_edits, uint64_t bubble_edit_permille, uint64_t* status19, char* err,
+                            uint64_t errcap) {
+  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  unitigger.setTrim((size_t)cut_terminal, (size_t)min_branch_length, (long)min_branch_coverage);
+  unitigger.setGraph(graph_path ? graph_path : "");
+  unitigger.setRemoved(removed_path ? removed_path : "");
+  unitigger.setMaxOverlap((size_t)delta, careful != 0, (size_t)num_reads, (size_t)genome_size, uniq_threshold);
+  unitigger.setCutEdges(cut_path ? cut_path : "");
+  unitigger.setChimeric((size_t)min_chimeric_length, (long)min_chimeric_coverage, (size_t)chimeric_delta, chimeric_threshold);
+  unitigger.setChimericOut(chimeric_path ? chimeric_path : "");
+  unitigger.setBubble((size_t)max_bubble_span, (long)bubble_divergence);
+  unitigger.setBubbleOut(bubbles_path ? bubbles_path : "");
+  unitigger.setBubbleEdits((size_t)bubble_edits, (size_t)bubble_edit_permille);
+  const int r = unitig_file(unitigger, reads_path, prefix, min_overlap, device, fasta_path, layout_path, piece_reads, err, errcap);
+  if (r == 0 && status19) {
+    const uint64_t s[19] = {unitigger.unitigs(),  unitigger.bases(),        unitigger.merged(),     unitigger.cycles(),    unitigger.trimRounds(),
+                            unitigger.islands(),  unitigger.deadEnds(),     unitigger.readsRemoved(), unitigger.recordsCut(), unitigger.cutRounds(),
+                            unitigger.chimericUnitigs(), unitigger.chimericReads(), unitigger.bubblesPopped(), unitigger.bubbleReads(),
+                            unitigger.bubblesKept(), unitigger.indelsPopped(), unitigger.indelReads(), unitigger.indelsKept(),
+                            unitigger.indelsNotCompared()};
+    for (int k = 0; k < 19; ++k) status19[k] = s[k];
+  }
+  return r;
+}
 
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty
 int sigah_preqc(const char* prefix, uint64_t k, uint64_t samples, uint64_t seed, int all, uint64_t max_count, int device,

@@ -258,7 +258,17 @@ class Unitigger {
     _bubbleSpan = maxSpan;
     _bubbleDivergence = divergence;
   }
-  // one "name\tround" line per read a bubble step removed, in read order
+  // Indel bubble popping between the bubble and the chimeric step of every round (the rules are include/sigax.h's): the arms that
+  // join the same two read ends form one group whatever their spans; an arm whose span differs from the winner's by 1 to maxEdits
+  // (--bubble-edits; 0, the default: none; at most 31) goes where the edit distance of the two windows is at most maxEdits and at
+  // most `permille` per mille (--bubble-edit-permille) of the bases of the shorter of the two unitigs.  Needs setBubble with a span of
+  // at most 4096.  (sigax_unitigs_indel_host.)
+  void setBubbleEdits(size_t maxEdits, size_t permille = 50) {
+    _bubbleEdits = maxEdits;
+    _bubbleEditPermille = permille;
+  }
+  // one "name\tround" line per read a bubble step removed, in read order; then, with setBubbleEdits, one "name\tround\tindel" line
+  // per read an indel step removed, in read order
   void setBubbleOut(const std::string& path) { _bubbleOut = path; }
   // The paired-end side (sigax_unitigs_pairs_host; the rules in include/sigax.h): mates are found by name as PairEnd::id does
   // (src/reads.cpp:19-41; the last character swaps 1<->2, A<->B, f<->r), every pair is looked up in the unitigs this run built,
@@ -353,6 +363,10 @@ class Unitigger {
   uint64_t bubblesPopped() const { return _bubPopped; }  // arms popped
   uint64_t bubbleReads() const { return _bubReads; }
   uint64_t bubblesKept() const { return _bubKept; }      // losers kept because they failed the bases test, over the rounds
+  uint64_t indelsPopped() const { return _indPopped; }   // arms the indel steps popped
+  uint64_t indelReads() const { return _indReads; }
+  uint64_t indelsKept() const { return _indKept; }       // compared losers kept, over the rounds
+  uint64_t indelsNotCompared() const { return _indSkipped; }  // losers of the winner's span or more than maxEdits from it, over the rounds
   uint64_t recordsCut() const { return _recordsCut; }
   uint64_t cutRounds() const { return _cutRounds; }    // rounds in which something was cut
   uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something (with setMaxOverlap: or cut something)
@@ -385,6 +399,8 @@ class Unitigger {
   long _bubbleDivergence = 50;
   std::string _bubbleOut;
   uint64_t _bubPopped = 0, _bubReads = 0, _bubKept = 0;
+  size_t _bubbleEdits = 0, _bubbleEditPermille = 50;
+  uint64_t _indPopped = 0, _indReads = 0, _indKept = 0, _indSkipped = 0;
   std::string _pairsOut, _linksOut;
   uint64_t _maxSpan = 0;
   bool _outward = false;

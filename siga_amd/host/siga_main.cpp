@@ -561,6 +561,12 @@ static int unitig_help() {
          "                                       PERMILLE per mille of those bases (default: 50)\n"
          "          --no-bubble-bases            ... whatever its bases\n"
          "          --bubbles=FILE               write one line per read removed as a bubble arm to FILE: read name, the round it went in\n"
+         "                                       (with --bubble-edits: then the reads an indel step removed, with a third column `indel`)\n"
+         "          --bubble-edits=E             (needs -b, at most 4096) also compare the unitigs between the same two unitig ends whose\n"
+         "                                       bases between them differ in number by 1 to E, 0 to 31: remove another than the kept one\n"
+         "                                       if at most E edits (substituted, inserted or deleted bases) turn its bases between the\n"
+         "                                       ends into the kept one's (default: 0, none)\n"
+         "          --bubble-edit-permille=M     ... and at most M per mille of the bases of the shorter of the two unitigs (default: 50)\n"
          "\n"
          "Paired-end parameters (mates by name: the last character swaps 1 and 2, A and B, f and r):\n"
          "          --pairs=FILE                 look every pair up in the unitigs and write the statistics to FILE as JSON: the counts\n"
@@ -647,7 +653,7 @@ static int run_unitig(int argc, char** argv) {
          OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
          OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
          OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS,
-         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE };
+         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -664,6 +670,8 @@ static int run_unitig(int argc, char** argv) {
                                     {"max-bubble-span", required_argument, nullptr, 'b'},
                                     {"bubble-divergence", required_argument, nullptr, OPT_BUBBLE_DIVERGENCE},
                                     {"no-bubble-bases", no_argument, nullptr, OPT_NO_BUBBLE_BASES}, {"bubbles", required_argument, nullptr, OPT_BUBBLES},
+                                    {"bubble-edits", required_argument, nullptr, OPT_BUBBLE_EDITS},
+                                    {"bubble-edit-permille", required_argument, nullptr, OPT_BUBBLE_EDIT_PERMILLE},
                                     {"pairs", required_argument, nullptr, OPT_PAIRS}, {"links", required_argument, nullptr, OPT_LINKS},
                                     {"max-span", required_argument, nullptr, OPT_MAX_SPAN}, {"outward", no_argument, nullptr, OPT_OUTWARD},
                                     {"pairs-bins", required_argument, nullptr, OPT_PAIRS_BINS},
@@ -702,6 +710,8 @@ static int run_unitig(int argc, char** argv) {
   size_t chimLength = 0, chimDelta = 0;
   size_t bubbleSpan = 0, bubbleDivergence = 50;
   bool noBubbleBases = false, bubbleTuned = false;
+  size_t bubbleEdits = 0, bubbleEditPermille = 50;
+  bool editsTuned = false;
   std::string bubblesOut;
   long minBranchCoverage = -1, chimCoverage = -1;
   double uniqThreshold = 13.0, chimThreshold = 0.0;  // (-T sets both: src/assembler.cpp:55-67)
@@ -752,6 +762,8 @@ static int run_unitig(int argc, char** argv) {
       case OPT_BUBBLE_DIVERGENCE: if (!unitig_number(optarg, "--bubble-divergence", 0xFFFFFFFEull, &bubbleDivergence)) return 1; bubbleTuned = true; break;
       case OPT_NO_BUBBLE_BASES: noBubbleBases = bubbleTuned = true; break;
       case OPT_BUBBLES: bubblesOut = optarg; break;
+      case OPT_BUBBLE_EDITS: if (!unitig_number(optarg, "--bubble-edits", 31, &bubbleEdits)) return 1; break;
+      case OPT_BUBBLE_EDIT_PERMILLE: if (!unitig_number(optarg, "--bubble-edit-permille", 0xFFFFFFFFull, &bubbleEditPermille)) return 1; editsTuned = true; break;
       case OPT_PAIRS: pairsOut = optarg; break;
       case OPT_LINKS: linksOut = optarg; break;
       case OPT_MAX_SPAN: if (!unitig_number(optarg, "--max-span", ~0ull, &maxSpan)) return 1; pairsTuned = true; break;
@@ -829,6 +841,14 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "siga unitig: --bubble-divergence, --no-bubble-bases and --bubbles need -b, --max-bubble-span\n");
     return 1;
   }
+  if (bubbleEdits > 0 && (bubbleSpan == 0 || bubbleSpan > 4096)) {
+    fprintf(stderr, "siga unitig: --bubble-edits needs -b, --max-bubble-span from 1 to 4096\n");
+    return 1;
+  }
+  if (bubbleEdits == 0 && editsTuned) {
+    fprintf(stderr, "siga unitig: --bubble-edit-permille needs --bubble-edits\n");
+    return 1;
+  }
   if (pairsOut.empty() && (!linksOut.empty() || pairsTuned)) {
     fprintf(stderr, "siga unitig: --links, --max-span, --outward, --pairs-bins and --pairs-shift need --pairs\n");
     return 1;
@@ -879,6 +899,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setChimericOut(chimericOut);
   unitigger.setBubble(bubbleSpan, noBubbleBases ? -1 : (long)bubbleDivergence);
   unitigger.setBubbleOut(bubblesOut);
+  unitigger.setBubbleEdits(bubbleEdits, bubbleEditPermille);
   unitigger.setTrim(cutTerminal, minBranchLength, minBranchCoverage);
   unitigger.setGraph(graph);
   unitigger.setRemoved(removed);
@@ -906,6 +927,10 @@ static int run_unitig(int argc, char** argv) {
   if (bubbleSpan)
     fprintf(stderr, "%llu bubble arms popped, %llu reads, %llu kept on divergence\n", (unsigned long long)unitigger.bubblesPopped(),
             (unsigned long long)unitigger.bubbleReads(), (unsigned long long)unitigger.bubblesKept());
+  if (bubbleEdits)
+    fprintf(stderr, "%llu indel arms popped, %llu reads, %llu kept on edits, %llu not compared\n", (unsigned long long)unitigger.indelsPopped(),
+            (unsigned long long)unitigger.indelReads(), (unsigned long long)unitigger.indelsKept(),
+            (unsigned long long)unitigger.indelsNotCompared());
   if (!pairsOut.empty())
     fprintf(stderr, "%llu pairs, %llu in one unitig (insert size %llu, delta %llu), %llu across unitigs in %llu links\n",
             (unsigned long long)unitigger.pairs(), (unsigned long long)unitigger.pairsSame(), (unsigned long long)unitigger.insertSize(),

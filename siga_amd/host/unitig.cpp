@@ -118,10 +118,12 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  uint64_t status[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t status[32] = {0};
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
   if (!_chimericOut.empty() && _chimLength == 0) return fail("chimeric reads are only written with a min-chimeric length");
   if (!_bubbleOut.empty() && _bubbleSpan == 0) return fail("bubble reads are only written with a max-bubble span");
+  if (_bubbleEdits > 0 && (_bubbleSpan == 0 || _bubbleSpan > SIGAX_INDEL_MAX_SPAN)) return fail("bubble edits need a max-bubble span of 1 to 4096");
+  if (_bubbleEdits > SIGAX_INDEL_MAX_EDITS || _bubbleEditPermille > 0xFFFFFFFFull) return fail("bubble edits or their per mille out of range");
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
   if (_pairsOut.empty() && !_linksOut.empty()) return fail("links are only written with the pairs statistics");
   if (!_pairsOut.empty() && (_pairsBins == 0 || _pairsBins > SIGAX_PAIRS_MAX_BINS || _pairsShift > 31)) return fail("pairs bins or shift out of range");
@@ -144,12 +146,13 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
   }
   // the steps asked for: each call is the one before it with one more step in its rounds, and more scratch
-  const int level = _bubbleSpan > 0 ? 4 : _chimLength > 0 ? 3 : _delta > 0 ? 2 : trim ? 1 : 0;
+  const int level = _bubbleEdits > 0 ? 5 : _bubbleSpan > 0 ? 4 : _chimLength > 0 ? 3 : _delta > 0 ? 2 : trim ? 1 : 0;
   if (level >= 2 && _delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
   if (level >= 3 && (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll))
     return fail("chimeric length, delta or coverage out of range");
   if (level >= 4 && (_bubbleSpan > 0xFFFFFFFFull || _bubbleDivergence >= (long)0xFFFFFFFFll)) return fail("bubble span or divergence out of range");
-  sigax_bubble_opts opts;
+  sigax_indel_opts iopts;
+  sigax_bubble_opts& opts = iopts.bubble;
   sigax_chimeric_opts& co = opts.chimeric;
   sigax_prune_opts& po = co.prune;
   po.max_rounds = (uint32_t)_rounds;
@@ -169,8 +172,16 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   opts.max_bubble_span = (uint32_t)_bubbleSpan;
   opts.max_divergence_permille = _bubbleDivergence < 0 ? SIGAX_BUBBLE_NO_BASES : (uint32_t)_bubbleDivergence;
   opts.reserved3[0] = opts.reserved3[1] = 0;
+  iopts.max_edits = (uint32_t)_bubbleEdits;
+  iopts.max_edit_permille = (uint32_t)_bubbleEditPermille;
+  iopts.reserved4[0] = iopts.reserved4[1] = 0;
   sigax_edge** const uedges = _graph.empty() ? nullptr : &u.uedges;
-  if (level == 4) {
+  if (level == 5) {
+    if (sigax_unitigs_indel_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
+                                 (uint32_t)minOverlap, &iopts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                 uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else if (level == 4) {
     if (sigax_unitigs_bubble_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
                                   (uint32_t)minOverlap, &opts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
                                   uedges, status) != SIGAX_OK)
@@ -211,6 +222,10 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _bubPopped = status[20];
   _bubReads = status[21];
   _bubKept = status[23];
+  _indPopped = status[24];
+  _indReads = status[25];
+  _indKept = status[27];
+  _indSkipped = status[28];
   if (!_pairsOut.empty()) {  // over the unitigs as they stand, whichever call built them; the other outputs do not depend on it
     PairsRequest rq;
     rq.json = _pairsOut;
@@ -312,7 +327,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
         const std::string_view name = reads.name(r);
         t.append(name.data(), name.size());
         t += '\t';
-        append_u64(t, u.removed[r] & ~(SIGAX_REMOVED_CHIMERIC | SIGAX_REMOVED_BUBBLE));
+        append_u64(t, u.removed[r] & ~(SIGAX_REMOVED_CHIMERIC | SIGAX_REMOVED_BUBBLE | SIGAX_REMOVED_INDEL));
         t += '\n';
       }
     ok = write_all(rf, t);
@@ -348,6 +363,14 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
         t += '\t';
         append_u64(t, u.removed[r] & ~SIGAX_REMOVED_BUBBLE);
         t += '\n';
+      }
+    for (size_t r = 0; r < n; ++r)  // the reads of the indel steps behind them, marked: lines of the old kind are as they were
+      if (u.removed[r] & SIGAX_REMOVED_INDEL) {
+        const std::string_view name = reads.name(r);
+        t.append(name.data(), name.size());
+        t += '\t';
+        append_u64(t, u.removed[r] & ~SIGAX_REMOVED_INDEL);
+        t += "\tindel\n";
       }
     ok = write_all(rf, t);
     if (fclose(rf) != 0) ok = false;

@@ -149,8 +149,8 @@ def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
 
 def _rounds_opts(level, n, max_rounds, min_branch_length, min_branch_coverage, delta=0, careful=False, num_reads=None, genome_size=None,
                  uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None, chimeric_delta=0, chimeric_threshold=0.0,
-                 max_bubble_span=0, bubble_divergence=50):
-    """The options object of the rounds call `level` ("trim", "prune", "chimeric" or "bubble") over n reads."""
+                 max_bubble_span=0, bubble_divergence=50, max_edits=0, edit_permille=50):
+    """The options object of the rounds call `level` ("trim", "prune", "chimeric", "bubble" or "indel") over n reads."""
     none = _lib.SIGAX_TRIM_NO_COVERAGE
     branch = (int(max_rounds), int(min_branch_length), none if min_branch_coverage is None else int(min_branch_coverage))
     if level == "trim":
@@ -163,8 +163,11 @@ def _rounds_opts(level, n, max_rounds, min_branch_length, min_branch_coverage, d
                              int(chimeric_delta), 0, float(chimeric_threshold))
     if level == "chimeric":
         return opts
-    return _lib.BubbleOpts(opts, int(max_bubble_span), _lib.SIGAX_BUBBLE_NO_BASES if bubble_divergence is None else int(bubble_divergence),
+    opts = _lib.BubbleOpts(opts, int(max_bubble_span), _lib.SIGAX_BUBBLE_NO_BASES if bubble_divergence is None else int(bubble_divergence),
                            (C.c_uint32 * 2)(0, 0))
+    if level == "bubble":
+        return opts
+    return _lib.IndelOpts(opts, int(max_edits), int(edit_permille), (C.c_uint32 * 2)(0, 0))
 
 
 def _unitigs_rounds(level, n_status, with_cut, edges, lengths, seqs, offs, min_overlap, graph, bases, device, **opt):
@@ -251,6 +254,26 @@ def unitigs_bubble(edges, lengths, seqs, offs, min_overlap, max_rounds, min_bran
                            num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
                            min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold,
                            max_bubble_span=max_bubble_span, bubble_divergence=bubble_divergence)
+
+
+def unitigs_indel(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
+                  num_reads=None, genome_size=None, uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None,
+                  chimeric_delta=0, chimeric_threshold=0.0, max_bubble_span=0, bubble_divergence=50, max_edits=0, edit_permille=50,
+                  graph=True, bases=True, device=0):
+    """`unitigs_bubble` with indel bubble popping between the bubble and the chimeric step of every round (sigax_unitigs_indel_host, the
+    rules in include/sigax.h): the unitigs that join the same two read ends through one participant record at each end and hold 1 to
+    max_bubble_span bases between them form one group whatever those spans; the one with the most reads (then the smallest first read)
+    stays.  Another whose span differs from the winner's by 1 to max_edits goes where the edit distance ed between the two windows
+    (unit cost, bytes as bytes, exact up to max_edits) is at most max_edits and ed * 1000 <= edit_permille * the bases of the shorter
+    of the two unitigs.  One of the winner's span is the bubble step's business and stays.  max_edits = 0 is `unitigs_bubble`; with
+    max_edits > 0 (at most 31) max_bubble_span must be 1 to 4096.  -> its dict; removed carries _lib.SIGAX_REMOVED_INDEL on the reads
+    an indel step removed; status u64[32]: as there, then {arms popped, their reads, rounds with one, compared losers kept, losers
+    not compared, 0, 0, 0} (_lib.INDEL_STATUS)."""
+    return _unitigs_rounds("indel", 32, True, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage, delta=delta, careful=careful,
+                           num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
+                           min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold,
+                           max_bubble_span=max_bubble_span, bubble_divergence=bubble_divergence, max_edits=max_edits, edit_permille=edit_permille)
 
 
 def mates_by_name(names):
