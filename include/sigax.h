@@ -715,6 +715,75 @@ int  sigax_unitigs_indel_host(int device, const sigax_edge* edges, uint64_t n_ed
                               uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                               sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                               uint64_t status32[32]);
+/* ---- `siga unitig --reduce`: transitive reduction in the rounds (csrc/sigax_unitig.hip) --------------------------------------------
+ * An irreducible overlap run decides once, at overlap time, which overlaps a third read explains, and an exhaustive run keeps them
+ * all: about 21 records per read instead of 1.1, nearly every read end branched.  A REDUCTION PASS decides it on the graph, over
+ * what is alive now: it turns an exhaustive record set back into a string graph, and it lets a record return whose witness a later
+ * round removed.  The reference declares this step and leaves it empty (TransitiveReductionVisitor, src/bigraph_visitors.cpp:1084-1093);
+ * the rules are this library's own, and on error-free reads without duplicate or contained reads they leave exactly the records
+ * the reference's irreducible overlap run writes (tests/test_reduce_cases.py holds that).  No decision depends on the order of
+ * records, reads, lanes or table slots.  Everything not said here is as in the blocks above: record classes, B/E ends, states
+ * 2 * read + end, degrees, live records, simple records, rings, lifted records.  DESIGN.md 9o; the serial restatement the tests hold
+ * this against is tests/reduce_cases.py::expected_reduce.
+ *
+ * PARTICIPANTS of a pass: the records that are kept, have both reads alive, were not cut in an earlier round
+ *             (cut[i] & 0x7FFFFFFF == 0), and are neither a containment nor a self edge.  A participant between states a and b of
+ *             reads ra, rb with overlap len has two extensions: ext(a -> b) = L[rb] - len and ext(b -> a) = L[ra] - len.
+ * TRANSITIVE  Seen from a, participant i is transitive iff a participant j != i exists between a and a state w of a third read, and
+ *             a participant k exists between w ^ 1 (the other end of that read) and b, with
+ *             ext(a -> w) + ext((w ^ 1) -> b) == ext(a -> b).  The equality is exact, as the overlaps are; there is no fuzz.  Record i
+ *             is transitive in this pass iff it is so seen from a or seen from b.
+ * WITNESSES   ignore the flag: j and k may themselves be transitive.  So the verdicts of a pass depend neither on record order nor
+ *             on each other; every decision uses the participant set at the start of the pass.
+ * NOT TAKING PART  A containment or a self edge is never flagged and never a witness.  Two records between the same two states with
+ *             different lengths are judged one by one; the sum rule keeps a record at one offset from being explained through a
+ *             witness at another.
+ * THE FLAG    Bit 31 of cut[i], SIGAX_CUT_TRANSITIVE: transitive in the latest pass.  Every pass clears it on all records and sets
+ *             it anew.  The low 31 bits keep the round of a `-d` cut.  Every step of a round takes a record with cut[i] != 0 as not
+ *             there, whichever bits are set; whoever reads cut[] as a round masks bit 31 off.
+ * WHEN        With reduce = 1 a pass is the first step of every round: reduce, cut, trim, bubble, indel, chimeric.  One more pass
+ *             runs before the final unitigs and the lifted records, so a record whose only witnesses went in the last round is live
+ *             again and can be merged.  With max_rounds = 0 that is the only pass: "reduce, then simplify()".
+ * IDLE        A pass after a round that changed nothing leaves at once, like every other step; the flags of the pass before still
+ *             hold.  A pass does not count as a change for the purpose of ending the loop: it removes nothing that anything else
+ *             could have used.  The first pass of a call always runs.
+ * Flagged records are not lifted: d_uedges and the `--graph` ASQG leave them out.  status[10] does not count them.
+ * Out of scope: any fuzz or inexact reduction; reduction over containments.
+ *
+ * sigax_reduce_opts: indel = the sigax_indel_opts of the block above (its reserved4 still 0); reduce 0 or 1; reserved5 = 0.
+ *
+ * status40 = 40 u64, written: 0-31 as status32; 32 records flagged by the first pass of the call, 33 records flagged in the final
+ * graph (by the last pass that ran), 34 passes that ran and were not idle, 35 participants of the last pass that ran; 36-39 zero.
+ *
+ * sigax_unitigs_reduce_device: sigax_unitigs_indel_device with these options and d_status40.  Asynchronous on `stream`, allocates
+ * nothing, never waits for the device.  A pass counts the participants per state, takes the exclusive prefix sum, writes {other
+ * state, extension} into both states' segments and the record's index into an open-addressing table keyed exactly by (state, state,
+ * overlap), and then walks, one lane per record, the segment of each of its ends: trips bounded by the end's degree, probes by the
+ * table's capacity.  No cap changes a verdict: a read end of degree 5000 is slow, not wrong.  d_work =
+ * sigax_unitigs_reduce_workspace(n_reads, n_edges, d_uedges != NULL, careful) bytes: the indel call's scratch, then 16 448 bytes of
+ * counters, (2 n + 1) * 4, 2 n * 4 and (2 n + 1) * 8 bytes of counts and offsets, the prefix sum's partials, 8 bytes, 16 bytes per
+ * record of segments and 4 bytes per table slot, the slots the smallest power of two that is at least 16 and at least 4 n_edges, each
+ * piece rounded up to 16 bytes.  reduce = 0 gives exactly the indel call's result, bit 31 never set and status 32-39 zero.  Refusals
+ * as for the indel call, and reserved5 != 0, reduce > 1, reduce = 1 with 2^32 records: SIGAX_E_ARG.  Whatever the records hold,
+ * nothing outside the buffers is touched. */
+#define SIGAX_CUT_TRANSITIVE 0x80000000u
+typedef struct sigax_reduce_opts {
+  sigax_indel_opts indel;
+  uint32_t reduce;        /* 0 or 1 */
+  uint32_t reserved5[3];  /* = 0 */
+} sigax_reduce_opts;
+int  sigax_unitigs_reduce_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_unitigs_reduce_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                 const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_reduce_opts* opts,
+                                 void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                 void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status40, void* d_work,
+                                 uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous; as sigax_unitigs_indel_host, with status40.  It stops after the first round that changed nothing. */
+int  sigax_unitigs_reduce_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                               const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_reduce_opts* opts,
+                               uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                               sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                               uint64_t status40[40]);
 /* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
  * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
  * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain

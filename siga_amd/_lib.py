@@ -37,6 +37,10 @@ SIGAX_INDEL_MAX_EDITS = 31
 SIGAX_INDEL_MAX_SPAN = 4096
 # the entries 24-31 of sigax_unitigs_indel_*'s status32, by name
 INDEL_STATUS = ("indel_popped", "indel_reads", "indel_rounds", "indel_kept", "indel_not_compared", "_29", "_30", "_31")
+# bit 31 of cut[]: transitive in the latest reduction pass (sigax_unitigs_reduce_*); the low bits stay the round of a -d cut
+SIGAX_CUT_TRANSITIVE = 0x80000000
+# the entries 32-39 of sigax_unitigs_reduce_*'s status40, by name
+REDUCE_STATUS = ("reduce_first", "reduce_final", "reduce_passes", "reduce_participants", "_36", "_37", "_38", "_39")
 TRIM_MAX_ROUNDS = 64
 SIGAX_NO_MATE = 0xFFFFFFFF
 SIGAX_PAIRS_OUTWARD = 1
@@ -98,6 +102,10 @@ class BubbleOpts(C.Structure):  # sigax_bubble_opts
 
 class IndelOpts(C.Structure):  # sigax_indel_opts
     _fields_ = [("bubble", BubbleOpts), ("max_edits", C.c_uint32), ("max_edit_permille", C.c_uint32), ("reserved4", C.c_uint32 * 2)]
+
+
+class ReduceOpts(C.Structure):  # sigax_reduce_opts
+    _fields_ = [("indel", IndelOpts), ("reduce", C.c_uint32), ("reserved5", C.c_uint32 * 3)]
 
 
 class PairsOpts(C.Structure):  # sigax_pairs_opts
@@ -170,6 +178,7 @@ SYMBOLS = [
     "sigax_unitigs_chimeric_workspace", "sigax_unitigs_chimeric_device", "sigax_unitigs_chimeric_host",
     "sigax_unitigs_bubble_workspace", "sigax_unitigs_bubble_device", "sigax_unitigs_bubble_host",
     "sigax_unitigs_indel_workspace", "sigax_unitigs_indel_device", "sigax_unitigs_indel_host",
+    "sigax_unitigs_reduce_workspace", "sigax_unitigs_reduce_device", "sigax_unitigs_reduce_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
@@ -290,6 +299,11 @@ def lib():
                                              vp, u64, vp]
     L.sigax_unitigs_indel_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(IndelOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
                                            pvp, pvp, pvp, pvp, vp]
+    L.sigax_unitigs_reduce_workspace.argtypes = [u64, u64, ci, ci, C.POINTER(u64)]
+    L.sigax_unitigs_reduce_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, C.POINTER(ReduceOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, u64, vp]
+    L.sigax_unitigs_reduce_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(ReduceOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
+                                            pvp, pvp, pvp, pvp, vp]
     L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]

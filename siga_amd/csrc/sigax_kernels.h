@@ -418,6 +418,31 @@ static const uint32_t REMOVED_INDEL = 0x20000000u;
 // launch_bubble_status.
 void launch_indel_round(const UnitigIndelArgs& a, hipStream_t st);
 void launch_indel_status(const UnitigIndelArgs& a, hipStream_t st);
+// transitive reduction (sigax_unitigs_reduce_*): the indel block and what a reduction pass needs.  A pass flags records in cut[]
+// (CUT_TRANSITIVE); every older kernel already takes a record with cut[i] != 0 as not there.  Only the pass's kernels see the fields below.
+struct UnitigReduceArgs : UnitigIndelArgs {
+  unsigned long long* red;               // RED_WORDS u64, zeroed before the first pass: the RED_C_* counters of the pass that ran last,
+                                         // slotted as the trim counters are, and the call's counts at RED_FIRST .. RED_PASSES
+  uint32_t* rcnt;                        // [2 n_reads + 1]: participants per state
+  uint32_t* rfill;                       // [2 n_reads]: how many entries of a state's segment are written
+  unsigned long long* roff;              // [2 n_reads + 1]: where a state's segment of the adjacency begins
+  unsigned long long* rpartial;          // scan_partials_needed(2 n_reads) u64
+  unsigned long long* rtotal;            // 1 u64
+  uint2* radj;                           // [2 n_edges]: {the state at the other side, the extension towards it}, by state
+  uint32_t* rtable;                      // [red_cap]: open addressing over (state, state, overlap); an entry names a participant record
+  unsigned long long red_cap;            // a power of two, at least 4 n_edges
+  uint32_t red_prev;                     // the round before this pass (0: none); the pass is idle when that round changed nothing
+};
+enum { RED_C_FLAGGED = 0, RED_C_PART = 1, RED_COUNTERS = 2, RED_FIRST = RED_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, RED_LAST = RED_FIRST + 1,
+       RED_PASSES = RED_FIRST + 2, RED_LAST_PART = RED_FIRST + 3, RED_WORDS = RED_FIRST + 8 };
+static const uint32_t CUT_TRANSITIVE = 0x80000000u;
+// One reduction pass over the records as removed[] and the low bits of cut[] stand (a.maxlen = NULL, n_edges < 2^32): bit 31 of every
+// cut[i] cleared, the participants counted per state, launch_scan, the adjacency and the table filled, then one lane per participant
+// walks the segments of its two states and probes the table; bit 31 set where a third read explains the record.  a.red_prev names the
+// round whose flag decides whether the pass is idle; an idle pass writes nothing.  launch_reduce_status: status[32 .. 39], after
+// launch_indel_status.
+void launch_reduce_pass(const UnitigReduceArgs& a, hipStream_t st);
+void launch_reduce_status(const UnitigReduceArgs& a, hipStream_t st);
 
 // `siga unitig --pairs` (sigax_pairs.hip): mate-pair statistics and links over the layout a unitig call left.  Everything below
 // `status` is the caller's scratch (sigax_pairs.cpp lays it out).

@@ -8,12 +8,13 @@ static_assert(sizeof(sigax_placement) == 16, "sigax_placement must be 16 bytes")
 namespace {
 
 // What a call does beyond the plain unitigs: every level is the one below it with one more step in its rounds, a longer
-// status block (6, 12, 16, 20, 24, 32 counts) and more scratch behind the same pieces.
-enum Level { UNITIG = 0, TRIM = 1, PRUNE = 2, CHIMERIC = 3, BUBBLE = 4, INDEL = 5 };
-const char* const LEVEL_NAME[] = {"unitig", "trim", "prune", "chimeric", "bubble", "indel"};
+// status block (6, 12, 16, 20, 24, 32, 40 counts) and more scratch behind the same pieces.
+enum Level { UNITIG = 0, TRIM = 1, PRUNE = 2, CHIMERIC = 3, BUBBLE = 4, INDEL = 5, REDUCE = 6 };
+const char* const LEVEL_NAME[] = {"unitig", "trim", "prune", "chimeric", "bubble", "indel", "reduce"};
 const char* const WORKSPACE_FN[] = {"sigax_unitigs_workspace", "sigax_unitigs_trim_workspace", "sigax_unitigs_prune_workspace",
-                                    "sigax_unitigs_chimeric_workspace", "sigax_unitigs_bubble_workspace", "sigax_unitigs_indel_workspace"};
-u64 status_words(int level) { return level == UNITIG ? 6 : level == INDEL ? 32 : 8 + 4 * (u64)level; }
+                                    "sigax_unitigs_chimeric_workspace", "sigax_unitigs_bubble_workspace", "sigax_unitigs_indel_workspace",
+                                    "sigax_unitigs_reduce_workspace"};
+u64 status_words(int level) { return level == UNITIG ? 6 : level == REDUCE ? 40 : level == INDEL ? 32 : 8 + 4 * (u64)level; }
 
 // where the pieces of the caller's scratch lie (every piece 16-byte aligned).  A level's pieces follow those of the level below
 // at the same offsets: a call whose upper steps are off runs as the lower one over the same scratch.
@@ -25,6 +26,7 @@ struct RoundsWork {
   u64 chim, prune_aside, nbr, minb[2], mink[2];                                       // CHIMERIC: a round's chimeric step
   u64 bub, bnbr, blen, arm, where, aside, gslot, losers, table, best, group_cap;      // BUBBLE: a round's bubble step
   u64 ind, pairs;                                                                     // INDEL: a round's indel step
+  u64 red, rcnt, rfill, roff, rpartial, rtotal, radj, rtable, red_cap;                // REDUCE: a reduction pass
   u64 bytes;
 };
 RoundsWork rounds_work(Level level, u64 n, u64 n_edges, bool graph, bool careful) {
@@ -96,7 +98,18 @@ RoundsWork rounds_work(Level level, u64 n, u64 n_edges, bool graph, bool careful
   if (ends_at(BUBBLE)) return w;
   w.ind = take(IND_WORDS * 8);
   w.pairs = take(n * 4);
-  ends_at(INDEL);
+  if (ends_at(INDEL)) return w;
+  w.red = take(RED_WORDS * 8);
+  w.rcnt = take((2 * n + 1) * 4);
+  w.rfill = take(2 * n * 4);
+  w.roff = take((2 * n + 1) * 8);
+  w.rpartial = take(scan_partials_needed(2 * n) * 8);
+  w.rtotal = take(8);
+  w.radj = take(2 * n_edges * 8);
+  w.red_cap = 16;
+  while (w.red_cap < 4 * n_edges) w.red_cap <<= 1;
+  w.rtable = take(w.red_cap * 4);
+  ends_at(REDUCE);
   return w;
 }
 
@@ -114,41 +127,49 @@ int workspace_of(Level level, u64 n_reads, u64 n_edges, int want_graph, int care
   return SIGAX_OK;
 }
 
-// The options of every rounds call as the indel call's: a lower level leaves the fields of the upper ones zero, and a step
+// The options of every rounds call as the reduce call's: a lower level leaves the fields of the upper ones zero, and a step
 // whose own threshold is zero is off.  NULL stays NULL (opts_ok refuses it).
-const sigax_indel_opts* opts_view(const sigax_trim_opts* o, sigax_indel_opts* v) {
+const sigax_reduce_opts* opts_view(const sigax_trim_opts* o, sigax_reduce_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  sigax_prune_opts& p = v->bubble.chimeric.prune;
+  sigax_prune_opts& p = v->indel.bubble.chimeric.prune;
   p.max_rounds = o->max_rounds;
   p.min_branch_length = o->min_branch_length;
   p.min_branch_coverage = o->min_branch_coverage;
   p.reserved = o->reserved;
   return v;
 }
-const sigax_indel_opts* opts_view(const sigax_prune_opts* o, sigax_indel_opts* v) {
+const sigax_reduce_opts* opts_view(const sigax_prune_opts* o, sigax_reduce_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  v->bubble.chimeric.prune = *o;
+  v->indel.bubble.chimeric.prune = *o;
   return v;
 }
-const sigax_indel_opts* opts_view(const sigax_chimeric_opts* o, sigax_indel_opts* v) {
+const sigax_reduce_opts* opts_view(const sigax_chimeric_opts* o, sigax_reduce_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  v->bubble.chimeric = *o;
+  v->indel.bubble.chimeric = *o;
   return v;
 }
-const sigax_indel_opts* opts_view(const sigax_bubble_opts* o, sigax_indel_opts* v) {
+const sigax_reduce_opts* opts_view(const sigax_bubble_opts* o, sigax_reduce_opts* v) {
   if (!o) return nullptr;
   *v = {};
-  v->bubble = *o;
+  v->indel.bubble = *o;
   return v;
 }
-const sigax_indel_opts* opts_view(const sigax_indel_opts* o, sigax_indel_opts*) { return o; }
+const sigax_reduce_opts* opts_view(const sigax_indel_opts* o, sigax_reduce_opts* v) {
+  if (!o) return nullptr;
+  *v = {};
+  v->indel = *o;
+  return v;
+}
+const sigax_reduce_opts* opts_view(const sigax_reduce_opts* o, sigax_reduce_opts*) { return o; }
 
-// prune's refusals, then chimeric's, then bubble's, then indel's.  The bubble and the indel step need neither G nor N.
-int opts_ok(Level level, const sigax_indel_opts* io, u64 n_reads) {
-  if (!io) return sigax_fail(SIGAX_E_ARG, "NULL where the %s options are required", LEVEL_NAME[level]);
+// prune's refusals, then chimeric's, then bubble's, then indel's, then reduce's.  The bubble and the indel step and the reduction
+// need neither G nor N.
+int opts_ok(Level level, const sigax_reduce_opts* ro, u64 n_reads, u64 n_edges) {
+  if (!ro) return sigax_fail(SIGAX_E_ARG, "NULL where the %s options are required", LEVEL_NAME[level]);
+  const sigax_indel_opts* io = &ro->indel;
   const sigax_bubble_opts* o = &io->bubble;
   const sigax_prune_opts& p = o->chimeric.prune;
   if (p.reserved != 0) return sigax_fail(SIGAX_E_ARG, "sigax_%s_opts.reserved must be 0", level == TRIM ? "trim" : "prune");
@@ -169,6 +190,11 @@ int opts_ok(Level level, const sigax_indel_opts* io, u64 n_reads) {
     if (io->max_edits > SIGAX_INDEL_MAX_EDITS) return sigax_fail(SIGAX_E_ARG, "max_edits %u: at most %u", io->max_edits, SIGAX_INDEL_MAX_EDITS);
     if (io->max_edits > 0 && (o->max_bubble_span == 0 || o->max_bubble_span > SIGAX_INDEL_MAX_SPAN))
       return sigax_fail(SIGAX_E_ARG, "max_bubble_span %u with max_edits > 0: 1 to %u", o->max_bubble_span, SIGAX_INDEL_MAX_SPAN);
+  }
+  if (level >= REDUCE) {
+    if (ro->reserved5[0] != 0 || ro->reserved5[1] != 0 || ro->reserved5[2] != 0) return sigax_fail(SIGAX_E_ARG, "sigax_reduce_opts.reserved5 must be 0");
+    if (ro->reduce > 1) return sigax_fail(SIGAX_E_ARG, "reduce %u: 0 or 1", ro->reduce);
+    if (ro->reduce && n_edges >= (1ull << 32)) return sigax_fail(SIGAX_E_ARG, "reduce with 2^32 records: a table slot names a record in 32 bits");
   }
   return SIGAX_OK;
 }
@@ -319,19 +345,36 @@ void indel_args(UnitigIndelArgs& a, const UnitigBufs& b, const RoundsWork& w, co
   a.max_edit_permille = o.max_edit_permille;
 }
 
-// The rounds of every form, device and host.  A round is up to five steps, each over the graph the step before left: cut
-// (PRUNE up, delta > 0), trim, bubble (BUBBLE up, Lb > 0), indel (INDEL, E > 0), chimeric (CHIMERIC up, Lc > 0); then the unitigs of what is left, the lifted
+void reduce_args(UnitigReduceArgs& a, const UnitigBufs& b, const RoundsWork& w) {
+  char* base = (char*)b.work;
+  a.red = (u64*)(base + w.red);
+  a.rcnt = (uint32_t*)(base + w.rcnt);
+  a.rfill = (uint32_t*)(base + w.rfill);
+  a.roff = (u64*)(base + w.roff);
+  a.rpartial = (u64*)(base + w.rpartial);
+  a.rtotal = (u64*)(base + w.rtotal);
+  a.radj = (uint2*)(base + w.radj);
+  a.rtable = (uint32_t*)(base + w.rtable);
+  a.red_cap = w.red_cap;
+  a.red_prev = 0;
+}
+
+// The rounds of every form, device and host.  A round is up to six steps, each over the graph the step before left: reduce (REDUCE,
+// reduce = 1: a pass that flags records and removes nothing, so it never keeps the loop going), cut (PRUNE up, delta > 0), trim,
+// bubble (BUBBLE up, Lb > 0), indel (INDEL, E > 0), chimeric (CHIMERIC up, Lc > 0); then the unitigs of what is left, the lifted
 // records and the counts.  A call whose top step is off runs as the level below -- down to the trim kernels over the trim
 // block when nothing cuts -- and the counts of the steps that are off are zeroed behind it; the scratch is still asked for as
-// the requested level lays it out.
+// the requested level lays it out.  With reduce = 1 the call runs as PRUNE at the least: the kernels that skip cut[i] != 0.  One more
+// reduction pass runs before the final unitigs; it is idle when the last round that ran changed nothing.
 // paced: the host form's loop -- it reads each round's flag and stops after the first round that changed nothing, where the
 // device form enqueues every round and lets the idle ones leave at once.
-int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t min_overlap, const sigax_indel_opts* iopts, const UnitigBufs& b,
+int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t min_overlap, const sigax_reduce_opts* ropts, const UnitigBufs& b,
                    void* stream, bool paced) {
   const int rl = unitig_limits(n_reads, n_edges);
   if (rl != SIGAX_OK) return rl;
-  const int ro = opts_ok(level, iopts, n_reads);
+  const int ro = opts_ok(level, ropts, n_reads, n_edges);
   if (ro != SIGAX_OK) return ro;
+  const sigax_indel_opts* const iopts = &ropts->indel;
   const sigax_bubble_opts* const opts = &iopts->bubble;
   const sigax_chimeric_opts& co = opts->chimeric;
   const sigax_prune_opts& po = co.prune;
@@ -347,18 +390,22 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
     return SIGAX_OK;
   }
   int eff = level;  // the level the call runs as
+  const bool red = level == REDUCE && ropts->reduce != 0;
+  if (eff == REDUCE) eff = INDEL;  // (the reduction is no level of its own below: `red` says whether its passes run)
   if (eff == INDEL && iopts->max_edits == 0) eff = BUBBLE;
   if (eff == BUBBLE && opts->max_bubble_span == 0) eff = CHIMERIC;
   if (eff == CHIMERIC && co.min_chimeric_length == 0) eff = PRUNE;
   if (eff == PRUNE && po.delta == 0) eff = TRIM;
+  if (red && eff < PRUNE) eff = PRUNE;
 
-  UnitigIndelArgs a = {};
+  UnitigReduceArgs a = {};
   static_cast<UnitigArgs&>(a) = unitig_args(b, w, n_edges, n_reads, min_overlap);
   trim_args(a, b, w, po);
   if (eff >= PRUNE) prune_args(a, b, w, po);
   if (eff >= CHIMERIC) chimeric_args(a, b, w, co);
   if (eff >= BUBBLE) bubble_args(a, b, w, *opts);
   if (eff >= INDEL) indel_args(a, b, w, *iopts);
+  if (red) reduce_args(a, b, w);
   char* base = (char*)b.work;
   uint32_t* const maxlen = (uint32_t*)(base + w.maxlen);
 
@@ -372,12 +419,18 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
   }
   if (eff >= BUBBLE) HIP_TRY(hipMemsetAsync(a.bub, 0, BUB_WORDS * 8, st));
   if (eff >= INDEL) HIP_TRY(hipMemsetAsync(a.ind, 0, IND_WORDS * 8, st));
+  if (red) HIP_TRY(hipMemsetAsync(a.red, 0, RED_WORDS * 8, st));
   auto reset = [&]() -> hipError_t {  // every pass over degrees, links and counts of its own
     const hipError_t e = hipMemsetAsync(base + w.zero_from, 0, (size_t)w.zero_bytes, st);
     return e != hipSuccess ? e : hipMemsetAsync(a.link, 0xFF, (size_t)n_reads * 16, st);
   };
+  uint32_t last = 0;  // the last round that ran
   for (uint32_t r = 1; r <= po.max_rounds; ++r) {
-    a.round = r;
+    a.round = last = r;
+    if (red) {  // the reduction pass, over what the round before left
+      a.red_prev = r - 1;
+      launch_reduce_pass(a, st);
+    }
     if (eff >= PRUNE && po.delta > 0) {  // the cut step
       HIP_TRY(reset());
       a.maxlen = maxlen;
@@ -409,6 +462,10 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
     }
   }
   a.round = 0;  // the unitigs of what is left
+  if (red) {  // one more pass: a record whose only witnesses went in the last round is live again
+    a.red_prev = last;
+    launch_reduce_pass(a, st);
+  }
   HIP_TRY(reset());
   if (eff >= PRUNE) {
     launch_unitigs_prune(a, st);
@@ -420,8 +477,10 @@ int unitigs_rounds(Level level, int device, u64 n_edges, u64 n_reads, uint32_t m
   if (eff >= CHIMERIC) launch_chimeric_status(a, st);
   if (eff >= BUBBLE) launch_bubble_status(a, st);
   if (eff >= INDEL) launch_indel_status(a, st);
+  if (red) launch_reduce_status(a, st);
   HIP_TRY(hipGetLastError());
   for (int l = eff + 1; l <= level; ++l) {  // the steps that are off: their counts zero, and no record cut
+    if (l == REDUCE && red) continue;
     HIP_TRY(hipMemsetAsync((u64*)b.status + status_words(l - 1), 0, (size_t)(status_words(l) - status_words(l - 1)) * 8, st));
     if (l == PRUNE && n_edges) HIP_TRY(hipMemsetAsync(b.cut, 0, (size_t)n_edges * 4, st));
   }
@@ -467,7 +526,7 @@ int stage_reads(DevGuard& g, int device, const sigax_edge* edges, u64 n_edges, c
 // The host form of every level.  UNITIG: no options, no removed, cut or uedges, six counts, and *layout holds all n_reads
 // placements.  TRIM: no cut.  `status_out` holds status_words(level) counts.
 int unitigs_host(Level level, int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs, const uint64_t* offs,
-                 uint64_t n_reads, uint32_t min_overlap, const sigax_indel_opts* opts, uint64_t* n_unitigs, uint64_t** seq_offs,
+                 uint64_t n_reads, uint32_t min_overlap, const sigax_reduce_opts* opts, uint64_t* n_unitigs, uint64_t** seq_offs,
                  uint64_t** lay_offs, uint32_t** uflags, sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut,
                  sigax_edge** uedges, uint64_t* status_out) {
   const u64 n_status = status_words(level);
@@ -487,18 +546,18 @@ int unitigs_host(Level level, int device, const sigax_edge* edges, uint64_t n_ed
   const int rl = unitig_limits(n_reads, n_edges);
   if (rl != SIGAX_OK) return rl;
   if (level >= TRIM) {
-    const int ro = opts_ok(level, opts, n_reads);
+    const int ro = opts_ok(level, opts, n_reads, n_edges);
     if (ro != SIGAX_OK) return ro;
   }
   const u64 n = n_reads;
-  u64 status[32] = {0};
+  u64 status[40] = {0};
   DevGuard g;
   UnitigBufs b = {};
   u64 nb = 0;
   const int rs = stage_reads(g, device, edges, n_edges, lengths, seqs, offs, n, &b, &nb);
   if (rs != SIGAX_OK) return rs;
   if (n) {
-    b.work_bytes = rounds_work(level, n, n_edges, uedges != nullptr, level >= PRUNE && opts->bubble.chimeric.prune.careful != 0).bytes;
+    b.work_bytes = rounds_work(level, n, n_edges, uedges != nullptr, level >= PRUNE && opts->indel.bubble.chimeric.prune.careful != 0).bytes;
     HIP_TRY(g.alloc(&b.seq_offs, ((size_t)n + 1) * 8));
     HIP_TRY(g.alloc(&b.lay_offs, ((size_t)n + 1) * 8));
     HIP_TRY(g.alloc(&b.uflags, (size_t)n * 4));
@@ -629,14 +688,14 @@ extern "C" int sigax_unitigs_host(int device, const sigax_edge* edges, uint64_t 
 }
 
 // ---- the rounds calls: tip trimming and the lifted records, non-maximal overlap cutting, chimeric unitig removal, bubble
-// popping, indel bubble popping.  Each is the driver at its level over its options seen as the indel call's. ----
+// popping, indel bubble popping, transitive reduction.  Each is the driver at its level over its options seen as the reduce call's. ----
 #define SIGAX_ROUNDS_DEVICE(LEVEL, OPTS, CUT)                                                                                          \
-  sigax_indel_opts v;                                                                                                                  \
+  sigax_reduce_opts v;                                                                                                                 \
   const UnitigBufs b = {d_edges, d_lengths, d_seqs, d_offs, d_seq_offs, d_lay_offs, d_uflags, d_layout, d_useqs, d_removed, CUT, d_uedges, \
                         d_status, d_work, work_bytes};                                                                                 \
   return unitigs_rounds(LEVEL, device, n_edges, n_reads, min_overlap, opts_view(OPTS, &v), b, stream, false)
 #define SIGAX_ROUNDS_HOST(LEVEL, OPTS, CUT)                                                                                              \
-  sigax_indel_opts v;                                                                                                                  \
+  sigax_reduce_opts v;                                                                                                                 \
   return unitigs_host(LEVEL, device, edges, n_edges, lengths, seqs, offs, n_reads, min_overlap, opts_view(OPTS, &v), n_unitigs, seq_offs, \
                       lay_offs, uflags, layout, useqs, removed, CUT, uedges, status)
 
@@ -727,4 +786,22 @@ extern "C" int sigax_unitigs_indel_host(int device, const sigax_edge* edges, uin
                                         sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                         uint64_t status[32]) {
   SIGAX_ROUNDS_HOST(INDEL, opts, cut);
+}
+
+extern "C" int sigax_unitigs_reduce_workspace(uint64_t n_reads, uint64_t n_edges, int want_graph, int careful, uint64_t* bytes) {
+  return workspace_of(REDUCE, n_reads, n_edges, want_graph, careful, bytes);
+}
+extern "C" int sigax_unitigs_reduce_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
+                                           const void* d_offs, uint64_t n_reads, uint32_t min_overlap, const sigax_reduce_opts* opts,
+                                           void* d_seq_offs, void* d_lay_offs, void* d_uflags, sigax_placement* d_layout, void* d_useqs,
+                                           void* d_removed, void* d_cut, sigax_edge* d_uedges, void* d_status, void* d_work,
+                                           uint64_t work_bytes, void* stream) {
+  SIGAX_ROUNDS_DEVICE(REDUCE, opts, d_cut);
+}
+extern "C" int sigax_unitigs_reduce_host(int device, const sigax_edge* edges, uint64_t n_edges, const uint32_t* lengths, const char* seqs,
+                                         const uint64_t* offs, uint64_t n_reads, uint32_t min_overlap, const sigax_reduce_opts* opts,
+                                         uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
+                                         sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
+                                         uint64_t status[40]) {
+  SIGAX_ROUNDS_HOST(REDUCE, opts, cut);
 }

@@ -66,9 +66,27 @@
 //   k_ind_compare  one wave per appended pair: both windows staged as bytes in LDS (at most 4096 + 4096), then the furthest-reaching
 //                  recurrence over the 2 E + 1 diagonals, one per lane, neighbours by shuffles, at most E + 1 turns
 //   k_ind_mark     one lane per read: removed[r] = round | 0x20000000 under a popped head
+// Transitive reduction (sigax_unitigs_reduce_*; tests/reduce_cases.py::expected_reduce): a pass before the cut step of
+// every round and one more before the final unitigs.  It flags records in bit 31 of cut[], and every kernel above already takes a
+// record with cut[i] != 0 as not there, so none of them changed.  A record a-b of overlap len is explained through a third read's
+// state w iff records a-w and (w ^ 1)-b exist with ext(a -> w) + ext((w ^ 1) -> b) == ext(a -> b): given a-w, the one record that
+// can close the triangle has the overlap len + ext(a -> w).  So the pass keeps the participants twice: by state (an adjacency in CSR
+// form: the walk needs "every w at a") and by exact key (an open-addressing table: the walk then asks one yes/no question per w).
+//   k_red_clear    bit 31 off every cut[i]; the counts, the table and the pass's counters emptied (a kernel: an idle pass writes nothing)
+//   k_red_count    one lane per record: a participant adds to the count of both its states; launch_scan gives the segments
+//   k_red_fill     one lane per record: {other state, extension} into both segments (8 bytes each), and the record's index into the
+//                  table under (smaller state, larger state, overlap); a slot names a record, a probe compares that record's fields,
+//                  so the 96-bit key is exact and the table is 4 bytes a slot, at least four slots a record
+//   k_red_walk     one lane per record: over the segment of a, then of b, entries with a smaller extension on a third read are
+//                  probed; the first hit sets cut[i] = 0x80000000.  One lane per record and not a lane group: at 21 records per read
+//                  end (exhaustive, 30-fold) a segment is a third of a wave, and a hit ends the walk early; an end of degree 5000 is
+//                  5000 turns of one lane, slow and not wrong.  Witnesses are read from the adjacency and the table alone, which this
+//                  kernel does not write: verdicts do not depend on each other.
+//   k_red_note     one lane: the pass's counts into the call's (first pass, latest pass, passes that ran)
 // The tables' probe loops are bounded by their capacity, which holds at least twice the keys that can go in.
 // No loop's trip count depends on the records: ignored records never enter the links, and the links of simple records are
-// consistent by construction.  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
+// consistent by construction -- but for the reduction's walk, whose trips are the degree of a read end (at most 2 n_edges, the
+// adjacency's size, which the host knows).  Every store is bounds-checked all the same.  Plain vector stores only; integer work, no LDS
 // beyond the 64 descriptors and the indel step's two windows, no MFMA.
 #include <hip/hip_runtime.h>
 
@@ -1283,6 +1301,157 @@ __global__ void k_ind_status(UnitigIndelArgs A) {
   A.status[29] = A.status[30] = A.status[31] = 0ull;
 }
 
+// ---- transitive reduction: one pass (the rules in include/sigax.h; nothing of it is in the reference, whose
+// TransitiveReductionVisitor is empty) ----
+// a pass after a round that changed nothing has nothing to do: the flags of the pass before still hold
+__device__ __forceinline__ bool red_idle(const UnitigReduceArgs& A) {
+  return A.red_prev >= 1u && A.red_prev <= (u32)TRIM_MAX_ROUNDS && A.trim[TRIM_ROUND0 + A.red_prev] == 0ull;
+}
+__device__ __forceinline__ u64* red_slot(const UnitigReduceArgs& A, u32 c) {
+  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  return A.red + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
+}
+__device__ __forceinline__ u64 red_count(const UnitigReduceArgs& A, u32 c) {
+  u64 v = 0;
+  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.red[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
+  return v;
+}
+// a participant of a pass: kept, both reads alive, not cut in an earlier round (k_red_clear has taken bit 31 off), neither a
+// containment nor a self edge -> its two read ends and its length
+__device__ __forceinline__ bool red_participant(const UnitigReduceArgs& A, u64 i, u32& a, u32& b, u32& len) {
+  const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[i];
+  const RecClass c = classify(rec, A);
+  a = c.sq;
+  b = c.st;
+  len = rec.z;
+  return c.kind == 2u && !c.contain && !c.self && A.cut[i] == 0u && live_pair<2>(A, c);
+}
+// The table's key is (the smaller state, the larger state, overlap): 96 bits, so a slot names a participant record and a probe
+// compares against that record's own fields.  A record that went in was classified: its states follow from q, t and af alone.
+__device__ __forceinline__ u64 red_hash(u32 lo, u32 hi, u32 len) { return key_hash((((u64)lo << 32) | hi) ^ ((u64)len * 0x9E3779B97F4A7C15ull)); }
+__device__ __forceinline__ bool red_same(const UnitigReduceArgs& A, u32 j, u32 lo, u32 hi, u32 len) {
+  if ((u64)j >= A.n_edges) return false;
+  const uint4 rec = reinterpret_cast<const uint4*>(A.edges)[j];
+  if (rec.z != len) return false;
+  const u32 sq = 2u * rec.x + ((rec.w & 1u) ? 0u : 1u), st = 2u * rec.y + ((rec.w & 2u) ? 1u : 0u);
+  return (sq == lo && st == hi) || (sq == hi && st == lo);
+}
+__device__ __forceinline__ void red_insert(const UnitigReduceArgs& A, u32 i, u32 s, u32 t, u32 len) {
+  const u32 lo = s < t ? s : t, hi = s < t ? t : s;
+  const u64 mask = A.red_cap - 1ull;
+  u64 at = red_hash(lo, hi, len) & mask;
+  for (u64 p = 0; p < A.red_cap; ++p, at = (at + 1ull) & mask) {  // (never more than red_cap probes; at most a quarter of the table fills)
+    const u32 was = atomicCAS(&A.rtable[at], NIL, i);
+    if (was == NIL || was == i || red_same(A, was, lo, hi, len)) return;  // (a second record of the same key: the key is there)
+  }
+}
+__device__ __forceinline__ bool red_there(const UnitigReduceArgs& A, u32 s, u32 t, u32 len) {
+  const u32 lo = s < t ? s : t, hi = s < t ? t : s;
+  const u64 mask = A.red_cap - 1ull;
+  u64 at = red_hash(lo, hi, len) & mask;
+  for (u64 p = 0; p < A.red_cap; ++p, at = (at + 1ull) & mask) {
+    const u32 is = A.rtable[at];
+    if (is == NIL) return false;
+    if (red_same(A, is, lo, hi, len)) return true;
+  }
+  return false;
+}
+
+// Before a pass: bit 31 off every cut[i], no participant counted, no entry written, the table empty, the pass's counters zero.  A
+// kernel and no memset, so that an idle pass writes nothing and the flags of the pass before hold.
+__global__ __launch_bounds__(256) void k_red_clear(UnitigReduceArgs A) {
+  if (red_idle(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < A.n_edges) {
+    const u32 c = A.cut[i];
+    if (c & CUT_TRANSITIVE) A.cut[i] = c & ~CUT_TRANSITIVE;
+  }
+  if (i <= 2 * A.n_reads) A.rcnt[i] = 0u;
+  if (i < 2 * A.n_reads) A.rfill[i] = 0u;
+  if (i < A.red_cap) A.rtable[i] = NIL;
+  if (i < (u64)RED_FIRST) A.red[i] = 0ull;
+}
+
+// One lane per record: a participant counts at both its states.
+__global__ __launch_bounds__(256) void k_red_count(UnitigReduceArgs A) {
+  if (red_idle(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 a, b, len;
+  if (i >= A.n_edges || !red_participant(A, i, a, b, len)) return;
+  atomicAdd(&A.rcnt[a], 1u);
+  atomicAdd(&A.rcnt[b], 1u);
+}
+
+// One lane per record: a participant writes {other state, extension towards it} into the segments of both its states (the order
+// inside a segment is whatever the atomics give; no verdict depends on it) and its key into the table.
+__global__ __launch_bounds__(256) void k_red_fill(UnitigReduceArgs A) {
+  if (red_idle(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 a, b, len;
+  if (i >= A.n_edges || !red_participant(A, i, a, b, len)) return;
+  const u64 cap = 2 * A.n_edges;
+  const u64 ka = A.roff[a] + atomicAdd(&A.rfill[a], 1u), kb = A.roff[b] + atomicAdd(&A.rfill[b], 1u);
+  if (ka < cap) A.radj[ka] = make_uint2(b, A.lengths[b >> 1] - len);
+  if (kb < cap) A.radj[kb] = make_uint2(a, A.lengths[a >> 1] - len);
+  red_insert(A, (u32)i, a, b, len);
+}
+
+// Is the participant of overlap len between a and b, ext = ext(a -> b), explained seen from a?  Over the segment of a: a state w of a
+// third read with ext(a -> w) < ext, and then the one key that closes the triangle: (w ^ 1, b, len + ext(a -> w)), since
+// ext(a -> w) + (L[b] - len_k) == L[b] - len  <=>  len_k == len + ext(a -> w).  The trip count is a's degree; each probe is bounded by
+// the table's capacity.
+__device__ __forceinline__ bool red_explained(const UnitigReduceArgs& A, u32 a, u32 b, u32 ext, u32 len) {
+  const u64 cap = 2 * A.n_edges;
+  u64 k = A.roff[a], end = A.roff[a + 1u];
+  if (end > cap) end = cap;
+  for (; k < end; ++k) {
+    const uint2 e = A.radj[k];
+    if (e.y >= ext || (e.x >> 1) == (b >> 1) || (e.x >> 1) == (a >> 1)) continue;
+    if (red_there(A, e.x ^ 1u, b, len + e.y)) return true;
+  }
+  return false;
+}
+
+// One lane per record: a participant is flagged iff it is explained seen from either of its ends.  Witnesses are looked up in what
+// k_red_fill left, which no lane of this kernel writes: the verdicts do not depend on each other.
+__global__ __launch_bounds__(256) void k_red_walk(UnitigReduceArgs A) {
+  if (red_idle(A)) return;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 part = 0, flagged = 0;
+  u32 a, b, len;
+  if (i < A.n_edges && red_participant(A, i, a, b, len)) {
+    part = 1;
+    if (red_explained(A, a, b, A.lengths[b >> 1] - len, len) || red_explained(A, b, a, A.lengths[a >> 1] - len, len)) {
+      A.cut[i] = CUT_TRANSITIVE;  // (a participant's cut[i] was 0)
+      flagged = 1;
+    }
+  }
+  const u64 tp = wave_total(part), tf = wave_total(flagged);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (tp) atomicAdd(red_slot(A, RED_C_PART), tp);
+    if (tf) atomicAdd(red_slot(A, RED_C_FLAGGED), tf);
+  }
+}
+
+// After a pass that ran: its counts become the call's "latest", and the call's "first" if none ran before.
+__global__ void k_red_note(UnitigReduceArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u || red_idle(A)) return;
+  const u64 f = red_count(A, RED_C_FLAGGED);
+  if (A.red[RED_PASSES] == 0ull) A.red[RED_FIRST] = f;
+  A.red[RED_LAST] = f;
+  A.red[RED_LAST_PART] = red_count(A, RED_C_PART);
+  A.red[RED_PASSES] += 1ull;
+}
+
+__global__ void k_red_status(UnitigReduceArgs A) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  A.status[32] = A.red[RED_FIRST];
+  A.status[33] = A.red[RED_LAST];
+  A.status[34] = A.red[RED_PASSES];
+  A.status[35] = A.red[RED_LAST_PART];
+  A.status[36] = A.status[37] = A.status[38] = A.status[39] = 0ull;
+}
+
 unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
@@ -1467,4 +1636,26 @@ void launch_indel_round(const UnitigIndelArgs& a, hipStream_t st) {
 void launch_indel_status(const UnitigIndelArgs& a, hipStream_t st) {
   if (a.n_reads == 0 || !a.removed || !a.ind) return;
   hipLaunchKernelGGL(k_ind_status, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_reduce_pass(const UnitigReduceArgs& a, hipStream_t st) {
+  const u64 n = a.n_reads, ne = a.n_edges;
+  if (n == 0 || !a.removed || a.maxlen || !a.red || !a.rcnt || !a.rfill || !a.roff || !a.rpartial || !a.rtotal || !a.rtable || a.red_cap < 16 ||
+      (a.red_cap & (a.red_cap - 1)) || a.red_cap < 4 * ne || ne >= (1ull << 32) || (ne && (!a.cut || !a.radj)) || a.red_prev > TRIM_MAX_ROUNDS)
+    return;
+  u64 lanes = a.red_cap > 2 * n + 1 ? a.red_cap : 2 * n + 1;
+  if (lanes < (u64)RED_FIRST) lanes = RED_FIRST;
+  hipLaunchKernelGGL(k_red_clear, dim3(blocks_of(lanes)), dim3(256), 0, st, a);
+  if (ne) {
+    hipLaunchKernelGGL(k_red_count, dim3(blocks_of(ne)), dim3(256), 0, st, a);
+    launch_scan(a.rcnt, 2 * n, a.rpartial, a.roff, a.rtotal, st);  // (no idle form: after an idle pass's launch nothing reads its result)
+    hipLaunchKernelGGL(k_red_fill, dim3(blocks_of(ne)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_red_walk, dim3(blocks_of(ne)), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_red_note, dim3(1), dim3(64), 0, st, a);
+}
+
+void launch_reduce_status(const UnitigReduceArgs& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed || !a.red) return;
+  hipLaunchKernelGGL(k_red_status, dim3(1), dim3(64), 0, st, a);
 }

@@ -267,6 +267,13 @@ class Unitigger {
     _bubbleEdits = maxEdits;
     _bubbleEditPermille = permille;
   }
+  // Transitive reduction (the rules are include/sigax.h's): a pass before every round's steps and once more before the final unitigs
+  // flags the records a third read explains exactly; a flagged record is not there for any step, for the unitigs or for the graph.
+  // Without rounds it is "reduce, then simplify()": the way to turn the records of an exhaustive overlap run into a string graph.
+  // (sigax_unitigs_reduce_host.)
+  void setReduce(bool reduce) { _reduce = reduce; }
+  // one "query name\ttarget name\tlength" line per record flagged in the final graph, in record order (needs setReduce)
+  void setReducedEdges(const std::string& path) { _reducedEdges = path; }
   // one "name\tround" line per read a bubble step removed, in read order; then, with setBubbleEdits, one "name\tround\tindel" line
   // per read an indel step removed, in read order
   void setBubbleOut(const std::string& path) { _bubbleOut = path; }
@@ -367,6 +374,9 @@ class Unitigger {
   uint64_t indelReads() const { return _indReads; }
   uint64_t indelsKept() const { return _indKept; }       // compared losers kept, over the rounds
   uint64_t indelsNotCompared() const { return _indSkipped; }  // losers of the winner's span or more than maxEdits from it, over the rounds
+  uint64_t reducedFirst() const { return _redFirst; }    // records the first reduction pass flagged
+  uint64_t reducedFinal() const { return _redFinal; }    // records flagged in the final graph
+  uint64_t reducePasses() const { return _redPasses; }   // passes that ran
   uint64_t recordsCut() const { return _recordsCut; }
   uint64_t cutRounds() const { return _cutRounds; }    // rounds in which something was cut
   uint64_t trimRounds() const { return _trimRounds; }  // rounds that removed something (with setMaxOverlap: or cut something)
@@ -401,6 +411,9 @@ class Unitigger {
   uint64_t _bubPopped = 0, _bubReads = 0, _bubKept = 0;
   size_t _bubbleEdits = 0, _bubbleEditPermille = 50;
   uint64_t _indPopped = 0, _indReads = 0, _indKept = 0, _indSkipped = 0;
+  bool _reduce = false;
+  std::string _reducedEdges;
+  uint64_t _redFirst = 0, _redFinal = 0, _redPasses = 0;
   std::string _pairsOut, _linksOut;
   uint64_t _maxSpan = 0;
   bool _outward = false;

@@ -523,7 +523,13 @@ static int unitig_help() {
          "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
          "      -o, --out=FILE                   write the unitigs to FILE (default: <prefix>.unitigs.fa)\n"
          "          --layout=FILE                also write one line per read to FILE: unitig, read name, + or -, offset\n"
-         "          --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges)\n"
+         "          --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges;\n"
+         "                                       see --reduce)\n"
+         "          --reduce                     flag the overlaps a third read explains exactly (transitive reduction) before the\n"
+         "                                       unitigs are built and, with -x, anew before every round over the reads that are left:\n"
+         "                                       a flagged overlap is not there for any step, for the unitigs or for --graph\n"
+         "          --reduced-edges=FILE         (needs --reduce) write one line per overlap flagged in the final graph to FILE: query\n"
+         "                                       name, target name, length\n"
          "          --no-opposite-strand         treat all reads as forward strand\n"
          "      -t, --threads=NUM                host threads that parse READSFILE (default: 1)\n"
          "          --device=NUM                 GPU to use (default: 0)\n"
@@ -653,7 +659,7 @@ static int run_unitig(int argc, char** argv) {
          OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
          OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
          OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS,
-         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE };
+         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE, OPT_REDUCE, OPT_REDUCED_EDGES };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -672,6 +678,7 @@ static int run_unitig(int argc, char** argv) {
                                     {"no-bubble-bases", no_argument, nullptr, OPT_NO_BUBBLE_BASES}, {"bubbles", required_argument, nullptr, OPT_BUBBLES},
                                     {"bubble-edits", required_argument, nullptr, OPT_BUBBLE_EDITS},
                                     {"bubble-edit-permille", required_argument, nullptr, OPT_BUBBLE_EDIT_PERMILLE},
+                                    {"reduce", no_argument, nullptr, OPT_REDUCE}, {"reduced-edges", required_argument, nullptr, OPT_REDUCED_EDGES},
                                     {"pairs", required_argument, nullptr, OPT_PAIRS}, {"links", required_argument, nullptr, OPT_LINKS},
                                     {"max-span", required_argument, nullptr, OPT_MAX_SPAN}, {"outward", no_argument, nullptr, OPT_OUTWARD},
                                     {"pairs-bins", required_argument, nullptr, OPT_PAIRS_BINS},
@@ -694,7 +701,8 @@ static int run_unitig(int argc, char** argv) {
                                     {"join-mismatch-permille", required_argument, nullptr, OPT_JOIN_MISMATCH_PERMILLE},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut;
+  std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut, reducedEdges;
+  bool reduce = false;
   size_t maxSpan = 0, pairsBins = 1024, pairsShift = 0;
   bool outward = false, pairsTuned = false;
   std::string scaffoldOut, scaffoldLayout;
@@ -798,6 +806,8 @@ static int run_unitig(int argc, char** argv) {
         break;
       case OPT_CAREFULLY: carefully = true; break;
       case OPT_CUT_EDGES: cutEdges = optarg; break;
+      case OPT_REDUCE: reduce = true; break;
+      case OPT_REDUCED_EDGES: reducedEdges = optarg; break;
       case OPT_EXHAUSTIVE: exhaustive = true; break;
       case OPT_GRAPH: graph = optarg; break;
       case OPT_REMOVED: removed = optarg; break;
@@ -815,6 +825,10 @@ static int run_unitig(int argc, char** argv) {
   }
   if (delta > 0 && genomeSize == 0) {
     fprintf(stderr, "siga unitig: -d, --max-overlap-delta needs -G, --genome-size\n");
+    return 1;
+  }
+  if (!reduce && !reducedEdges.empty()) {
+    fprintf(stderr, "siga unitig: --reduced-edges needs --reduce\n");
     return 1;
   }
   if (delta == 0 && (carefully || !cutEdges.empty())) {
@@ -905,6 +919,8 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setRemoved(removed);
   unitigger.setMaxOverlap(delta, carefully, numReads, genomeSize, uniqThreshold);
   unitigger.setCutEdges(cutEdges);
+  unitigger.setReduce(reduce);
+  unitigger.setReducedEdges(reducedEdges);
   unitigger.setPairs(pairsOut, linksOut, maxSpan, outward, pairsBins, pairsShift);
   unitigger.setScaffold(scaffoldOut, scaffoldLayout, minPairs, linkRatio, minScaffoldUnitig, haveInsertSize ? (long long)insertSize : -1, minGap, maxGap);
   unitigger.setGapfill(gapfill, gapKmer, gapMinCount, gapSlack, gapMaxFill, gapsOut);
@@ -919,6 +935,9 @@ static int run_unitig(int argc, char** argv) {
   if (cutTerminal)
     fprintf(stderr, "%llu trim rounds, %llu islands and %llu dead ends removed, %llu reads\n", (unsigned long long)unitigger.trimRounds(),
             (unsigned long long)unitigger.islands(), (unsigned long long)unitigger.deadEnds(), (unsigned long long)unitigger.readsRemoved());
+  if (reduce)
+    fprintf(stderr, "%llu records transitive in the final graph, %llu in the first of %llu reduction passes\n",
+            (unsigned long long)unitigger.reducedFinal(), (unsigned long long)unitigger.reducedFirst(), (unsigned long long)unitigger.reducePasses());
   if (delta)
     fprintf(stderr, "%llu records cut in %llu rounds\n", (unsigned long long)unitigger.recordsCut(), (unsigned long long)unitigger.cutRounds());
   if (chimLength)

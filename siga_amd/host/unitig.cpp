@@ -118,13 +118,14 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     sigax_result_free(&res);
   }
   Unitigs u;
-  uint64_t status[32] = {0};
+  uint64_t status[40] = {0};
   const bool trim = _rounds > 0 || !_graph.empty() || !_removed.empty();
   if (!_chimericOut.empty() && _chimLength == 0) return fail("chimeric reads are only written with a min-chimeric length");
   if (!_bubbleOut.empty() && _bubbleSpan == 0) return fail("bubble reads are only written with a max-bubble span");
   if (_bubbleEdits > 0 && (_bubbleSpan == 0 || _bubbleSpan > SIGAX_INDEL_MAX_SPAN)) return fail("bubble edits need a max-bubble span of 1 to 4096");
   if (_bubbleEdits > SIGAX_INDEL_MAX_EDITS || _bubbleEditPermille > 0xFFFFFFFFull) return fail("bubble edits or their per mille out of range");
   if (!_cutEdges.empty() && _delta == 0) return fail("cut records are only written with a max-overlap delta");
+  if (!_reducedEdges.empty() && !_reduce) return fail("transitive records are only written with the reduction");
   if (_pairsOut.empty() && !_linksOut.empty()) return fail("links are only written with the pairs statistics");
   if (!_pairsOut.empty() && (_pairsBins == 0 || _pairsBins > SIGAX_PAIRS_MAX_BINS || _pairsShift > 31)) return fail("pairs bins or shift out of range");
   if (_pairsOut.empty() && !_scaffoldOut.empty()) return fail("scaffolds are only built with the pairs statistics");
@@ -141,17 +142,18 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
                 _joinKmer > 128 || _joinMinCount < 1 || _joinMinCount > 0xFFFFFFFFull || _joinMismatches > 16 || _joinMismatchPermille < 1 ||
                 _joinMismatchPermille > 250))
     return fail("overlap joining options out of range");
-  if (trim || _delta > 0) {
+  if (trim || _delta > 0 || _reduce) {
     if (_rounds > 64) return fail("at most 64 trim rounds");
     if (_minBranchLength > 0xFFFFFFFFull || _minBranchCoverage >= (long)0xFFFFFFFFll) return fail("branch length or coverage out of range");
   }
   // the steps asked for: each call is the one before it with one more step in its rounds, and more scratch
-  const int level = _bubbleEdits > 0 ? 5 : _bubbleSpan > 0 ? 4 : _chimLength > 0 ? 3 : _delta > 0 ? 2 : trim ? 1 : 0;
+  const int level = _reduce ? 6 : _bubbleEdits > 0 ? 5 : _bubbleSpan > 0 ? 4 : _chimLength > 0 ? 3 : _delta > 0 ? 2 : trim ? 1 : 0;
   if (level >= 2 && _delta > 0xFFFFFFFFull) return fail("max-overlap delta out of range");
   if (level >= 3 && (_chimLength > 0xFFFFFFFFull || _chimDelta > 0xFFFFFFFFull || _chimCoverage >= (long)0xFFFFFFFFll))
     return fail("chimeric length, delta or coverage out of range");
   if (level >= 4 && (_bubbleSpan > 0xFFFFFFFFull || _bubbleDivergence >= (long)0xFFFFFFFFll)) return fail("bubble span or divergence out of range");
-  sigax_indel_opts iopts;
+  sigax_reduce_opts ropts;
+  sigax_indel_opts& iopts = ropts.indel;
   sigax_bubble_opts& opts = iopts.bubble;
   sigax_chimeric_opts& co = opts.chimeric;
   sigax_prune_opts& po = co.prune;
@@ -175,8 +177,15 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   iopts.max_edits = (uint32_t)_bubbleEdits;
   iopts.max_edit_permille = (uint32_t)_bubbleEditPermille;
   iopts.reserved4[0] = iopts.reserved4[1] = 0;
+  ropts.reduce = _reduce ? 1u : 0u;
+  ropts.reserved5[0] = ropts.reserved5[1] = ropts.reserved5[2] = 0;
   sigax_edge** const uedges = _graph.empty() ? nullptr : &u.uedges;
-  if (level == 5) {
+  if (level == 6) {
+    if (sigax_unitigs_reduce_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
+                                  (uint32_t)minOverlap, &ropts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
+                                  uedges, status) != SIGAX_OK)
+      return fail(std::string("unitig failed: ") + sigax_last_error());
+  } else if (level == 5) {
     if (sigax_unitigs_indel_host(inf.device, edges.data(), edges.size(), lengths.data(), reads.seqs.data(), reads.offs.data(), n,
                                  (uint32_t)minOverlap, &iopts, &u.n, &u.seq_offs, &u.lay_offs, &u.uflags, &u.layout, &u.useqs, &u.removed, &u.cut,
                                  uedges, status) != SIGAX_OK)
@@ -226,6 +235,9 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _indReads = status[25];
   _indKept = status[27];
   _indSkipped = status[28];
+  _redFirst = status[32];
+  _redFinal = status[33];
+  _redPasses = status[34];
   if (!_pairsOut.empty()) {  // over the unitigs as they stand, whichever call built them; the other outputs do not depend on it
     PairsRequest rq;
     rq.json = _pairsOut;
@@ -382,7 +394,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (!cf) return fail("Failed to create " + _cutEdges);
     t.clear();
     for (size_t i = 0; i < edges.size() && ok; ++i)
-      if (u.cut[i] && edges[i].query < n && edges[i].target < n) {
+      if ((u.cut[i] & ~SIGAX_CUT_TRANSITIVE) && edges[i].query < n && edges[i].target < n) {  // (bit 31 is the reduction's flag, no round)
         const std::string_view q = reads.name(edges[i].query), tg = reads.name(edges[i].target);
         t.append(q.data(), q.size());
         t += '\t';
@@ -390,7 +402,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
         t += '\t';
         append_u64(t, edges[i].length);
         t += '\t';
-        append_u64(t, u.cut[i]);
+        append_u64(t, u.cut[i] & ~SIGAX_CUT_TRANSITIVE);
         t += '\n';
         if (t.size() >= ((size_t)1 << 20)) {
           ok = write_all(cf, t);
@@ -400,6 +412,29 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (ok) ok = write_all(cf, t);
     if (fclose(cf) != 0) ok = false;
     if (!ok) return fail("Failed to write " + _cutEdges);
+    t.clear();
+  }
+  if (!_reducedEdges.empty()) {  // "query name\ttarget name\tlength", the records flagged in the final graph, in record order
+    FILE* cf = fopen(_reducedEdges.c_str(), "wb");
+    if (!cf) return fail("Failed to create " + _reducedEdges);
+    t.clear();
+    for (size_t i = 0; i < edges.size() && ok; ++i)
+      if ((u.cut[i] & SIGAX_CUT_TRANSITIVE) && edges[i].query < n && edges[i].target < n) {
+        const std::string_view q = reads.name(edges[i].query), tg = reads.name(edges[i].target);
+        t.append(q.data(), q.size());
+        t += '\t';
+        t.append(tg.data(), tg.size());
+        t += '\t';
+        append_u64(t, edges[i].length);
+        t += '\n';
+        if (t.size() >= ((size_t)1 << 20)) {
+          ok = write_all(cf, t);
+          t.clear();
+        }
+      }
+    if (ok) ok = write_all(cf, t);
+    if (fclose(cf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _reducedEdges);
     t.clear();
   }
   if (layout.empty()) return true;

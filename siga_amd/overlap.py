@@ -149,8 +149,8 @@ def unitigs(edges, lengths, seqs, offs, min_overlap, device=0, bases=True):
 
 def _rounds_opts(level, n, max_rounds, min_branch_length, min_branch_coverage, delta=0, careful=False, num_reads=None, genome_size=None,
                  uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None, chimeric_delta=0, chimeric_threshold=0.0,
-                 max_bubble_span=0, bubble_divergence=50, max_edits=0, edit_permille=50):
-    """The options object of the rounds call `level` ("trim", "prune", "chimeric", "bubble" or "indel") over n reads."""
+                 max_bubble_span=0, bubble_divergence=50, max_edits=0, edit_permille=50, reduce=False):
+    """The options object of the rounds call `level` ("trim", "prune", "chimeric", "bubble", "indel" or "reduce") over n reads."""
     none = _lib.SIGAX_TRIM_NO_COVERAGE
     branch = (int(max_rounds), int(min_branch_length), none if min_branch_coverage is None else int(min_branch_coverage))
     if level == "trim":
@@ -167,7 +167,10 @@ def _rounds_opts(level, n, max_rounds, min_branch_length, min_branch_coverage, d
                            (C.c_uint32 * 2)(0, 0))
     if level == "bubble":
         return opts
-    return _lib.IndelOpts(opts, int(max_edits), int(edit_permille), (C.c_uint32 * 2)(0, 0))
+    opts = _lib.IndelOpts(opts, int(max_edits), int(edit_permille), (C.c_uint32 * 2)(0, 0))
+    if level == "indel":
+        return opts
+    return _lib.ReduceOpts(opts, int(reduce), (C.c_uint32 * 3)(0, 0, 0))
 
 
 def _unitigs_rounds(level, n_status, with_cut, edges, lengths, seqs, offs, min_overlap, graph, bases, device, **opt):
@@ -274,6 +277,27 @@ def unitigs_indel(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branc
                            num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
                            min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold,
                            max_bubble_span=max_bubble_span, bubble_divergence=bubble_divergence, max_edits=max_edits, edit_permille=edit_permille)
+
+
+def unitigs_reduce(edges, lengths, seqs, offs, min_overlap, max_rounds, min_branch_length, min_branch_coverage=None, delta=0, careful=False,
+                   num_reads=None, genome_size=None, uniq_threshold=13.0, min_chimeric_length=0, min_chimeric_coverage=None,
+                   chimeric_delta=0, chimeric_threshold=0.0, max_bubble_span=0, bubble_divergence=50, max_edits=0, edit_permille=50,
+                   reduce=True, graph=True, bases=True, device=0):
+    """`unitigs_indel` with a transitive reduction pass as the first step of every round and once more before the final unitigs
+    (sigax_unitigs_reduce_host, the rules in include/sigax.h): a record between read ends a and b that is neither a containment nor a
+    self edge is flagged where records a-w and (w ^ 1)-b through a third read exist whose extensions add up to its own, exactly.  A
+    flagged record is not there for any step, for the unitigs or for uedges; every pass clears the flags and sets them anew over what
+    is alive, so a record whose witness a round removed comes back.  With max_rounds = 0 it is "reduce, then `unitigs`": the way to
+    turn exhaustive overlap records into a string graph.  reduce=False is `unitigs_indel`.  -> its dict; cut carries
+    _lib.SIGAX_CUT_TRANSITIVE (bit 31) on the records flagged in the final graph, the low bits the round of a `delta` cut as before;
+    status u64[40]: as there, then {records flagged by the first pass, records flagged in the final graph, passes that ran,
+    participants of the last pass, 0, 0, 0, 0} (_lib.REDUCE_STATUS)."""
+    return _unitigs_rounds("reduce", 40, True, edges, lengths, seqs, offs, min_overlap, graph, bases, device, max_rounds=max_rounds,
+                           min_branch_length=min_branch_length, min_branch_coverage=min_branch_coverage, delta=delta, careful=careful,
+                           num_reads=num_reads, genome_size=genome_size, uniq_threshold=uniq_threshold, min_chimeric_length=min_chimeric_length,
+                           min_chimeric_coverage=min_chimeric_coverage, chimeric_delta=chimeric_delta, chimeric_threshold=chimeric_threshold,
+                           max_bubble_span=max_bubble_span, bubble_divergence=bubble_divergence, max_edits=max_edits, edit_permille=edit_permille,
+                           reduce=reduce)
 
 
 def mates_by_name(names):
