@@ -115,10 +115,10 @@ def _step_strings(units, ring, seqs, unit, deg, at, Lb, D):
 
 # ---- the round loop: chimeric_cases.expected_chimeric's, with the bubble step ----
 def _rounds(step, reads, edges, m, max_rounds, L, C=None, delta=0, careful=False, N=None, G=None, T=13.0, Lc=0, Ac=None, delta_c=0, Tc=0.0,
-            Lb=0, D=50):
+            Lb=0, D=50, tables_only=False):
     n = len(reads)
     N = n if N is None else N
-    lens = [len(r) for r in reads]
+    lens = [uc.nbases(r) for r in reads]
     kept, bad, low = tc._kept(edges, lens, m)
     removed, cut = [0] * n, [0] * len(edges)
     islands = dead_ends = rounds = cut_rounds = uniq_first = chim_units = chim_reads = chim_rounds = 0
@@ -130,7 +130,10 @@ def _rounds(step, reads, edges, m, max_rounds, L, C=None, delta=0, careful=False
         new = {r: k for k, r in enumerate(alive)}
         live = [(i, c) for i, c in kept if not cut[i] and not removed[edges[i][0]] and not removed[edges[i][1]]]
         sub = [(new[edges[i][0]], new[edges[i][1]], edges[i][2], edges[i][3]) for i, _ in live]
-        res = uc.expected([reads[r] for r in alive], sub, m)
+        sub_reads = [reads[r] for r in alive]
+        res = uc.expected(sub_reads, sub, m, tables_only)
+        if tables_only:  # the bytes of an arm are built when a step compares it
+            res["lazy_seqs"] = uc.LazySeqs(sub_reads, res)
         deg = {}
         for _, (sq, st, contain, _s) in live:
             for s in ((sq & ~1, sq | 1, st & ~1, st | 1) if contain else (sq, st)):
@@ -205,7 +208,7 @@ def _rounds(step, reads, edges, m, max_rounds, L, C=None, delta=0, careful=False
             alive, new, live, res, deg, units = graph()
             unit = {r: u for u, (rs, _, _, _) in enumerate(units) for r in rs}
             part, at = participants(live)
-            seqs = [res["useqs"][res["seq_offs"][u]:res["seq_offs"][u + 1]] for u in range(len(units))]
+            seqs = res.pop("lazy_seqs") if tables_only else [res["useqs"][res["seq_offs"][u]:res["seq_offs"][u + 1]] for u in range(len(units))]
             ring = [bool(f & uc.CIRCULAR) for f in res["uflags"]]
             pop, kept_now, lg = step(units, ring, seqs, unit, deg, at, Lb, D)
             kept_div += kept_now
@@ -256,6 +259,7 @@ def _rounds(step, reads, edges, m, max_rounds, L, C=None, delta=0, careful=False
             break
         rounds += 1
     alive, new, live, res, deg, units = graph()
+    res.pop("lazy_seqs", None)
     res["layout"] = [(alive[r], fl, off) for r, fl, off in res["layout"]]
     where, merged = {}, set()
     for u in range(len(res["uflags"])):
@@ -288,7 +292,7 @@ def _rounds(step, reads, edges, m, max_rounds, L, C=None, delta=0, careful=False
 
 def expected_bubble(reads, edges, m, max_rounds, L, C=None, **kw):
     """-> chimeric_cases.expected_chimeric's dict with status [24]; removed carries BUBBLE on the reads a bubble step took; bubble_log:
-    one entry per loser judged"""
+    one entry per loser judged.  tables_only = True: as unitig_cases.expected's; a compared arm's reads must be bytes"""
     return _rounds(_step_frames, reads, edges, m, max_rounds, L, C, **kw)
 
 

@@ -24,6 +24,7 @@ from tests import unitig_cases as uc
 
 B, E = uc.B, uc.E
 SCORE_MARGIN = pc.SCORE_MARGIN
+SCORES = None  # as prune_cases.SCORES, for this module's _unique (the bubble, indel and reduce restatements call it too)
 CHIMERIC = 0x80000000  # SIGAX_REMOVED_CHIMERIC
 SAT = (1 << 32) - 1
 
@@ -34,16 +35,19 @@ def _unique(N, K, bases, G, T):
         return False
     second = math.log(float(G - 2 * bases)) if G > 2 * bases else math.log(0.001)
     score = float(N - K) * (math.log(float(G - bases)) - second) - float(K) * math.log(2.0)
+    if SCORES is not None:
+        SCORES.append((score, T))
     assert abs(score - T) >= SCORE_MARGIN, "a score of %r against %r" % (score, T)
     return score >= T
 
 
 def expected_chimeric(reads, edges, m, max_rounds, L, C=None, delta=0, careful=False, N=None, G=None, T=13.0, Lc=0, Ac=None, delta_c=0,
-                      Tc=0.0):
-    """-> prune_cases.expected_prune's dict with status [20]; removed carries CHIMERIC on the reads a chimeric step took"""
+                      Tc=0.0, tables_only=False):
+    """-> prune_cases.expected_prune's dict with status [20]; removed carries CHIMERIC on the reads a chimeric step took;
+    tables_only: as unitig_cases.expected's"""
     n = len(reads)
     N = n if N is None else N
-    lens = [len(r) for r in reads]
+    lens = [uc.nbases(r) for r in reads]
     kept, bad, low = tc._kept(edges, lens, m)
     removed, cut = [0] * n, [0] * len(edges)
     islands = dead_ends = rounds = cut_rounds = uniq_first = chim_units = chim_reads = chim_rounds = 0
@@ -53,7 +57,7 @@ def expected_chimeric(reads, edges, m, max_rounds, L, C=None, delta=0, careful=F
         new = {r: k for k, r in enumerate(alive)}
         live = [(i, c) for i, c in kept if not cut[i] and not removed[edges[i][0]] and not removed[edges[i][1]]]
         sub = [(new[edges[i][0]], new[edges[i][1]], edges[i][2], edges[i][3]) for i, _ in live]
-        res = uc.expected([reads[r] for r in alive], sub, m)
+        res = uc.expected([reads[r] for r in alive], sub, m, tables_only)
         deg = {}
         for _, (sq, st, contain, _s) in live:
             for s in ((sq & ~1, sq | 1, st & ~1, st | 1) if contain else (sq, st)):

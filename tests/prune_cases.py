@@ -21,6 +21,7 @@ from tests import unitig_cases as uc
 
 B, E = uc.B, uc.E
 SCORE_MARGIN = 1e-6
+SCORES = None  # a list here collects (score, threshold) of every evaluation of _unique (tests/giant_cases.py asserts a wider margin)
 
 
 # ---- the rules, serially ----
@@ -29,15 +30,17 @@ def _unique(N, K, bases, G, T):
         return False
     second = math.log(float(G - 2 * bases)) if G > 2 * bases else math.log(0.001)
     score = float(N - K) * (math.log(float(G - bases)) - second) - float(K) * math.log(2.0)
+    if SCORES is not None:
+        SCORES.append((score, T))
     assert abs(score - T) >= SCORE_MARGIN, "a score of %r against T = %r" % (score, T)
     return score >= T
 
 
-def expected_prune(reads, edges, m, max_rounds, L, C=None, delta=0, careful=False, N=None, G=None, T=13.0):
-    """-> trim_cases.expected_trim's dict plus cut [n_edges], with status [16]"""
+def expected_prune(reads, edges, m, max_rounds, L, C=None, delta=0, careful=False, N=None, G=None, T=13.0, tables_only=False):
+    """-> trim_cases.expected_trim's dict plus cut [n_edges], with status [16]; tables_only: as unitig_cases.expected's"""
     n = len(reads)
     N = n if N is None else N
-    lens = [len(r) for r in reads]
+    lens = [uc.nbases(r) for r in reads]
     kept, bad, low = tc._kept(edges, lens, m)
     removed, cut = [0] * n, [0] * len(edges)
     islands = dead_ends = rounds = cut_rounds = uniq_first = 0
@@ -48,7 +51,7 @@ def expected_prune(reads, edges, m, max_rounds, L, C=None, delta=0, careful=Fals
         live = [(i, c) for i, c in kept if not cut[i] and not removed[edges[i][0]] and not removed[edges[i][1]]]
         sub = [(new[edges[i][0]], new[edges[i][1]], edges[i][2], edges[i][3]) for i, _ in live]
         sub_reads = [reads[r] for r in alive]
-        res = uc.expected(sub_reads, sub, m)
+        res = uc.expected(sub_reads, sub, m, tables_only)
         deg = [0] * (2 * len(alive))
         for _, (sq, st, contain, _s) in live:
             sq, st = 2 * new[sq >> 1] + (sq & 1), 2 * new[st >> 1] + (st & 1)

@@ -65,14 +65,15 @@ def reduce_pass(lens, edges, m, removed, cut):
 
 def expected_reduce(reads, edges, m, max_rounds, L, C=None, reduce=True, **kw):
     """-> indel_cases.expected_indel's dict with status [40]; cut carries TRANSITIVE on the records flagged in the final graph;
-    first_flags: the records the first pass flagged; pass_flags: [(round, or 0 for the final pass, flagged records)] of the passes that ran"""
+    first_flags: the records the first pass flagged; pass_flags: [(round, or 0 for the final pass, flagged records)] of the passes that ran.
+    tables_only = True (among kw): as unitig_cases.expected's"""
     if not reduce:
         res = ic.expected_indel(reads, edges, m, max_rounds, L, C, **kw)
         res["status"] = res["status"] + [0] * 8
         res["first_flags"], res["pass_flags"] = set(), []
         return res
     n = len(reads)
-    lens = [len(r) for r in reads]
+    lens = [uc.nbases(r) for r in reads]
     kw = dict(kw)
     if kw.get("N") is None:
         kw["N"] = n

@@ -35,11 +35,11 @@ def _kept(edges, lens, m):
 
 
 # ---- the rules, serially ----
-def expected_trim(reads, edges, m, max_rounds, L, C=None):
+def expected_trim(reads, edges, m, max_rounds, L, C=None, tables_only=False):
     """-> unitig_cases.expected's dict over the final graph (layout with the original read ids, alive reads only) plus
-    removed [n], uedges [(query, target, length, af)] and status [12]"""
+    removed [n], uedges [(query, target, length, af)] and status [12]; tables_only: as unitig_cases.expected's"""
     n = len(reads)
-    lens = [len(r) for r in reads]
+    lens = [uc.nbases(r) for r in reads]
     kept, bad, low = _kept(edges, lens, m)
     removed = [0] * n
     islands = dead_ends = rounds = 0
@@ -50,9 +50,9 @@ def expected_trim(reads, edges, m, max_rounds, L, C=None):
         sub = [(new[edges[i][0]], new[edges[i][1]], edges[i][2], edges[i][3]) for i, _ in kept
                if not removed[edges[i][0]] and not removed[edges[i][1]]]
         sub_reads = [reads[r] for r in alive]
-        res = uc.expected(sub_reads, sub, m)
+        res = uc.expected(sub_reads, sub, m, tables_only)
         deg = [0] * (2 * len(alive))
-        sub_lens = [len(r) for r in sub_reads]
+        sub_lens = [uc.nbases(r) for r in sub_reads]
         for rec in sub:
             sq, st, contain, _ = uc.classify(rec, sub_lens, m)
             for s in ((sq & ~1, sq | 1, st & ~1, st | 1) if contain else (sq, st)):

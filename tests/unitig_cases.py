@@ -39,11 +39,27 @@ def classify(rec, lens, m):
     return (2 * q + (B if af & 1 else E), 2 * t + (E if af & 2 else B), ln == lens[q] or ln == lens[t], q == t)
 
 
+def nbases(read):
+    """a read's length: a read is its bytes or, where no step reads them (tables_only), a bare length"""
+    return read if isinstance(read, int) else len(read)
+
+
+def unit_bytes(reads, lay):
+    """the bytes of the unitig a layout [(read, flags, offset)] lays out; a read given as a bare length is an assertion failure"""
+    seq = bytearray()
+    for read, fl, off in lay:
+        assert not isinstance(reads[read], int), "the bytes of read %d are needed, and it was given as a length" % read
+        placed = revcomp(reads[read]) if fl & PLACED_REV else bytes(reads[read])
+        seq += placed[len(seq) - off:]
+    return bytes(seq)
+
+
 # ---- the rules, serially ----
-def expected(reads, edges, m):
-    """-> dict(seq_offs, lay_offs, uflags, layout [(read, flags, offset)], useqs bytes, status [6])"""
+def expected(reads, edges, m, tables_only=False):
+    """-> dict(seq_offs, lay_offs, uflags, layout [(read, flags, offset)], useqs bytes, status [6]).  tables_only: no bytes are
+    built, a read may be a bare length, useqs is None and everything else is as without it"""
     n = len(reads)
-    lens = [len(r) for r in reads]
+    lens = [nbases(r) for r in reads]
     deg = [0] * (2 * n)
     bad = low = 0
     kept = []
@@ -114,19 +130,37 @@ def expected(reads, edges, m):
     unitigs.sort(key=lambda u: u[0])
     seq_offs, lay_offs, uflags, layout, useqs = [0], [0], [], [], bytearray()
     for start, lay, cyc, closing in unitigs:
-        seq = bytearray()
-        for read, fl, off in lay:
-            placed = revcomp(reads[read]) if fl & PLACED_REV else bytes(reads[read])
-            seq += placed[len(seq) - off:]
-        assert len(seq) == lay[-1][2] + lens[lay[-1][0]]
-        useqs += seq
+        bases = lay[-1][2] + lens[lay[-1][0]]
+        if not tables_only:
+            seq = unit_bytes(reads, lay)
+            assert len(seq) == bases
+            useqs += seq
         layout += lay
-        seq_offs.append(len(useqs))
+        seq_offs.append(seq_offs[-1] + bases)
         lay_offs.append(len(layout))
         uflags.append((CIRCULAR | (closing << 1)) if cyc else 0)
     ncyc = sum(1 for u in unitigs if u[2])
-    return {"seq_offs": seq_offs, "lay_offs": lay_offs, "uflags": uflags, "layout": layout, "useqs": bytes(useqs),
-            "status": [len(unitigs), len(useqs), bad, low, simple - ncyc, ncyc]}
+    return {"seq_offs": seq_offs, "lay_offs": lay_offs, "uflags": uflags, "layout": layout, "useqs": None if tables_only else bytes(useqs),
+            "status": [len(unitigs), seq_offs[-1], bad, low, simple - ncyc, ncyc]}
+
+
+NEEDED = None  # a set here collects id() of every read object whose bytes a tables_only run asked for
+
+
+class LazySeqs:
+    """the unitigs' bytes of a tables_only result, each built when a step asks for it: seqs[u] as bytes"""
+
+    def __init__(self, reads, res):
+        self.reads, self.res = reads, res
+
+    def __len__(self):
+        return len(self.res["uflags"])
+
+    def __getitem__(self, u):
+        lay = self.res["layout"][self.res["lay_offs"][u]:self.res["lay_offs"][u + 1]]
+        if NEEDED is not None:
+            NEEDED.update(id(self.reads[r]) for r, _, _ in lay)
+        return unit_bytes(self.reads, lay)
 
 
 # ---- the reference's loop ----
