@@ -24,50 +24,16 @@
 // Every loop has a bound the host knows and every access is bounds-checked.  Plain vector stores and atomics only.
 #include <hip/hip_runtime.h>
 
+#include "sigax_device.h"
 #include "sigax_kernels.h"
 #include "sigax_rank.h"
 
 namespace {
 
 // ---- tables ---------------------------------------------------------------------------------------------------------------------
-struct GapCounts {
-  u64 nu, S, P;
-};
-__device__ __forceinline__ GapCounts gap_counts(const GapfillArgs& A) {
-  const u64 n = A.max_unitigs;
-  GapCounts c;
-  c.nu = *A.n_unitigs;
-  c.nu = c.nu < n ? c.nu : n;
-  c.S = *A.n_scaffolds;
-  c.S = c.S < n ? c.S : n;
-  c.P = c.S ? A.sc_lay_offs[c.S] : 0ull;
-  c.P = c.P < n ? c.P : n;
-  return c;
-}
-// the scaffold of placement p: the last s with sc_lay_offs[s] <= p (at most 32 steps: S < 2^31)
-__device__ __forceinline__ u64 scaffold_of(const GapfillArgs& A, u64 S, u64 p) {
-  u64 lo = 0, hi = S;
-  for (int step = 0; step < 32 && hi - lo > 1; ++step) {
-    const u64 mid = (lo + hi) >> 1;
-    if (A.sc_lay_offs[mid] <= p)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ u64 placement_offset(const sigax_placement* lay, u64 p) {
-  const uint4 v = reinterpret_cast<const uint4*>(lay)[p];
-  return (u64)v.z | ((u64)v.w << 32);
-}
-__device__ __forceinline__ u32 comp_byte(u32 b) {
-  return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
-}
+// (the tables' bounds, scaffold_of and placement_offset are sigax_device.h's)
 // this wave's sum of v, added once to counter c
-__device__ __forceinline__ void count_sum(const GapfillArgs& A, u32 c, u64 v) {
-  const u64 t = wave_sum(v);
-  if (t && (threadIdx.x & 63u) == 0u) atomicAdd(&A.cnt[c], t);
-}
+__device__ __forceinline__ void count_sum(const GapfillArgs& A, u32 c, u64 v) { wave_add(&A.cnt[c], v); }
 
 // window w of placement p from k rank codes: base i (rank r(i), 1 .. 4) goes to bits 2 i of its four words; unused bits are 0
 template <typename R>
@@ -86,7 +52,7 @@ __device__ __forceinline__ void window_write(u64* win, u32 k, R rank_of) {
 __global__ __launch_bounds__(256) void k_gap_classify(GapfillArgs A) {
   const u64 p = (u64)blockIdx.x * 256u + threadIdx.x;
   if (p >= A.max_unitigs) return;
-  const GapCounts c = gap_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   const u32 k = A.k;
   u32 cls = GAP_NONE, gap = 0, need = 0, s = 0;
   u64 len = 0, src = 0, G = 0;
@@ -322,7 +288,7 @@ __device__ __forceinline__ u64 shift_before(const GapfillArgs& A, u64 p) { retur
 __global__ __launch_bounds__(256) void k_gap_lengths(GapfillArgs A) {
   const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
   if (s >= A.max_unitigs) return;
-  const GapCounts c = gap_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   u64 bases = 0;
   if (s < c.S) {
     u64 h = A.sc_lay_offs[s], e = A.sc_lay_offs[s + 1];
@@ -337,7 +303,7 @@ __global__ __launch_bounds__(256) void k_gap_lengths(GapfillArgs A) {
 __global__ __launch_bounds__(256) void k_gap_place(GapfillArgs A) {
   const u64 p = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.max_unitigs;
-  const GapCounts c = gap_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   u32 cls = GAP_NONE, dir = 0;
   u64 fill = 0, left = 0;
   if (p <= c.S && p <= n) A.sc_offs[p] = A.slo[p] + (A.shi[p] << 32);
@@ -380,7 +346,7 @@ __global__ __launch_bounds__(256) void k_gap_place(GapfillArgs A) {
 __global__ __launch_bounds__(64) void k_gap_status(GapfillArgs A) {
   const u32 c = threadIdx.x;
   if (blockIdx.x != 0u || c >= 24u) return;
-  const GapCounts g = gap_counts(A);
+  const ScafBounds g = scaffold_bounds(A);
   const u64 bases = A.slo[g.S] + (A.shi[g.S] << 32);
   u64 out = 0;
   if (c == 0u) out = A.cnt[GAP_C_GAPS];
@@ -403,24 +369,14 @@ struct GapDesc {
 };
 
 __global__ __launch_bounds__(256) void k_gap_bases(GapfillArgs A) {
-  const GapCounts c = gap_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   const u64 total = A.slo[c.S] + (A.shi[c.S] << 32);
   const u64 P = c.P;
   const u64 b = ((u64)blockIdx.x * 256u + threadIdx.x) * 16ull;
   if (total > A.sseqs_capacity || P == 0 || b >= total) return;
   const u64* __restrict__ D = A.pdst;
-  // the placement of output byte p: the last k with D[k] <= p (at most 32 steps: P < 2^31)
-  auto find = [&](u64 p) -> u64 {
-    u64 lo = 0, hi = P;
-    for (int step = 0; step < 32 && hi - lo > 1; ++step) {
-      const u64 mid = (lo + hi) >> 1;
-      if (D[mid] <= p)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    return lo;
-  };
+  // the placement of output byte p: the last k with D[k] <= p
+  auto find = [&](u64 p) -> u64 { return last_at_most(D, P, p); };
   auto desc = [&](u64 k) -> GapDesc {
     GapDesc d;
     d.d0 = D[k];
@@ -469,7 +425,8 @@ __global__ __launch_bounds__(256) void k_gap_bases(GapfillArgs A) {
       uint4 x;
       __builtin_memcpy(&x, A.useqs + from, 16);  // (no alignment: the compiler picks the access)
       if (rev) {
-        // byte j of the piece = complement of byte 15 - j of the load
+        // byte j of the piece = complement of byte 15 - j of the load (written out in each bases kernel: as a shared
+        // function it compiles to other code, and these kernels stay as they are)
         const u32 m[4] = {x.w, x.z, x.y, x.x};
         u32 y[4];
 #pragma unroll
@@ -492,7 +449,6 @@ __global__ __launch_bounds__(256) void k_gap_bases(GapfillArgs A) {
   }
 }
 
-unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 void launch_gapfill_bases(const GapfillArgs& a, hipStream_t st) {

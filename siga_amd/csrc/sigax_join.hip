@@ -30,62 +30,17 @@
 // Every loop has a bound the host knows and every access is bounds-checked.  Plain vector stores and atomics only.
 #include <hip/hip_runtime.h>
 
+#include "sigax_device.h"
 #include "sigax_kernels.h"
 #include "sigax_rank.h"
 
 namespace {
 
-struct JoinCounts {
-  u64 nu, S, P;
-};
-__device__ __forceinline__ JoinCounts join_counts(const JoinArgs& A) {
-  const u64 n = A.max_unitigs;
-  JoinCounts c;
-  c.nu = *A.n_unitigs;
-  c.nu = c.nu < n ? c.nu : n;
-  c.S = *A.n_scaffolds;
-  c.S = c.S < n ? c.S : n;
-  c.P = c.S ? A.sc_lay_offs[c.S] : 0ull;
-  c.P = c.P < n ? c.P : n;
-  return c;
-}
-// the scaffold of placement p: the last s with sc_lay_offs[s] <= p (at most 32 steps: S < 2^31)
-__device__ __forceinline__ u64 scaffold_of(const JoinArgs& A, u64 S, u64 p) {
-  u64 lo = 0, hi = S;
-  for (int step = 0; step < 32 && hi - lo > 1; ++step) {
-    const u64 mid = (lo + hi) >> 1;
-    if (A.sc_lay_offs[mid] <= p)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ u64 placement_offset(const sigax_placement* lay, u64 p) {
-  const uint4 v = reinterpret_cast<const uint4*>(lay)[p];
-  return (u64)v.z | ((u64)v.w << 32);
-}
+// (the tables' bounds, scaffold_of, placement_offset and the wave reductions are sigax_device.h's)
 // this wave's sum of v, added once to counter c
-__device__ __forceinline__ void count_sum(const JoinArgs& A, u32 c, u64 v) {
-  const u64 t = wave_sum(v);
-  if (t && (threadIdx.x & 63u) == 0u) atomicAdd(&A.cnt[c], t);
-}
-__device__ __forceinline__ u32 wave_min32(u32 v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const u32 o = (u32)__shfl_xor((int)v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ u32 wave_max32(u32 v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const u32 o = (u32)__shfl_xor((int)v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
+__device__ __forceinline__ void count_sum(const JoinArgs& A, u32 c, u64 v) { wave_add(&A.cnt[c], v); }
 // the first placement of scaffold s, and the one behind its last: sc_lay_offs taken as P when above it
-__device__ __forceinline__ u64 head_of(const JoinArgs& A, const JoinCounts& c, u64 s) {
+__device__ __forceinline__ u64 head_of(const JoinArgs& A, const ScafBounds& c, u64 s) {
   const u64 h = A.sc_lay_offs[s];
   return h < c.P ? h : c.P;
 }
@@ -93,7 +48,7 @@ __device__ __forceinline__ u64 head_of(const JoinArgs& A, const JoinCounts& c, u
 __global__ __launch_bounds__(256) void k_join_classify(JoinArgs A) {
   const u64 p = (u64)blockIdx.x * 256u + threadIdx.x;
   if (p >= A.max_unitigs) return;
-  const JoinCounts c = join_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   u32 cls = JOIN_NO_GAP, gap = 0, open = 0, s = 0, hi = 0;
   u64 len = 0, src = 0, G = 0;
   if (p < c.P) {
@@ -469,7 +424,7 @@ __global__ __launch_bounds__(64) void k_join_support(JoinArgs A) {
 __global__ __launch_bounds__(256) void k_join_lengths(JoinArgs A) {
   const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
   if (s >= A.max_unitigs) return;
-  const JoinCounts c = join_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   u64 bases = 0;
   if (s < c.S) {
     const u64 h = head_of(A, c, s), e = head_of(A, c, s + 1);
@@ -483,7 +438,7 @@ __global__ __launch_bounds__(256) void k_join_lengths(JoinArgs A) {
 __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
   const u64 p = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.max_unitigs;
-  const JoinCounts c = join_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   u32 cls = JOIN_NO_GAP;
   u64 ov = 0, gone = 0, win = 0, acols = 0, aright = 0, ajoined = 0;
   if (p <= c.S && p <= n) A.sc_offs[p] = A.slo[p] + (A.shi[p] << 32);
@@ -539,7 +494,7 @@ __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
   count_sum(A, JOIN_C_N, gone);
   count_sum(A, JOIN_C_WINDOWS, win);
   if (A.acnt) {
-    const u64 sums[3] = {wave_sum(ajoined), wave_sum(acols), wave_sum(aright)};
+    const u64 sums[3] = {wave_sum(ajoined), wave_sum(acols), wave_sum(aright)};  // (all three sums before the first add)
     for (u32 k = 0; k < 3u; ++k)
       if (sums[k] && (threadIdx.x & 63u) == 0u) atomicAdd(&A.acnt[JOIN_A_JOINED + k], sums[k]);
   }
@@ -549,7 +504,7 @@ __global__ __launch_bounds__(256) void k_join_place(JoinArgs A) {
 __global__ __launch_bounds__(64) void k_join_status(JoinArgs A) {
   const u32 c = threadIdx.x;
   if (blockIdx.x != 0u || c >= A.n_status || c >= 24u) return;
-  const JoinCounts g = join_counts(A);
+  const ScafBounds g = scaffold_bounds(A);
   const u64 bases = A.slo[g.S] + (A.shi[g.S] << 32);
   u64 out = 0;
   if (c == 0u) out = A.cnt[JOIN_C_GAPS];
@@ -567,24 +522,14 @@ __global__ __launch_bounds__(64) void k_join_status(JoinArgs A) {
 
 // ---- the bases --------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_join_bases(JoinArgs A) {
-  const JoinCounts c = join_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   const u64 total = A.slo[c.S] + (A.shi[c.S] << 32);
   const u64 P = c.P;
   const u64 b = ((u64)blockIdx.x * 256u + threadIdx.x) * 16ull;
   if (total > A.sseqs_capacity || P == 0 || b >= total) return;
   const u64* __restrict__ D = A.pkey;
-  // the stretch of output byte x: the last placement k with D[k] <= x (at most 32 steps: P < 2^31)
-  auto find = [&](u64 x) -> u64 {
-    u64 lo = 0, hi = P;
-    for (int step = 0; step < 32 && hi - lo > 1; ++step) {
-      const u64 mid = (lo + hi) >> 1;
-      if (D[mid] <= x)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    return lo;
-  };
+  // the stretch of output byte x: the last placement k with D[k] <= x
+  auto find = [&](u64 x) -> u64 { return last_at_most(D, P, x); };
   auto fetch = [&](u64 x, u64 shift) -> u32 {
     const u64 at = x + shift;
     return at < A.sseqs_bytes ? A.sseqs_in[at] : (u32)'N';  // (no consistent input comes to the N)
@@ -616,7 +561,7 @@ __global__ __launch_bounds__(256) void k_join_patch(JoinArgs A) {
   const u64 t = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 p = t / JOIN_MAX_COLUMNS;
   const u32 i = (u32)(t % JOIN_MAX_COLUMNS);
-  const JoinCounts c = join_counts(A);
+  const ScafBounds c = scaffold_bounds(A);
   const u64 total = A.slo[c.S] + (A.shi[c.S] << 32);
   if (total > A.sseqs_capacity || p + 1 >= c.P || p + 1 >= A.max_unitigs || !A.isgap[p]) return;
   const uint4 r = A.gres[p];
@@ -628,7 +573,6 @@ __global__ __launch_bounds__(256) void k_join_patch(JoinArgs A) {
   if (to < total && from < A.sseqs_bytes) A.sseqs[to] = A.sseqs_in[from];
 }
 
-unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 // one-wave workgroups for the gaps that come to the match: no more than the device holds at a time, the rest in strides
 unsigned gap_waves(u64 n, int n_cu) {
   const u64 cap = (u64)(n_cu > 0 ? n_cu : 256) * 16ull;

@@ -293,7 +293,7 @@ struct UnitigTrimArgs : UnitigArgs {
   uint32_t* removed;                     // [n_reads], zeroed before round 1: the round in which a read went, 0 = alive
   uint32_t* verdict;                     // [n_reads]: a round's decision, under the unitig's head
   uint32_t* umap;                        // [n_reads]: (unitig << 1) | placed reversed, 0xFFFFFFFF for a removed read
-  unsigned long long* trim;              // TRIM_WORDS u64, zeroed before round 1: the TRIM_C_* counters (trim_slot), the lifted records at
+  unsigned long long* trim;              // TRIM_WORDS u64, zeroed before round 1: the TRIM_C_* counters (counter_slot), the lifted records at
                                          // TRIM_LIFTED, and at TRIM_ROUND0 + r whether round r removed something
   uint32_t round;                        // 1 .. max_rounds: a trim round; 0: the pass that writes the result
   uint32_t min_branch_length, min_branch_coverage;
@@ -303,10 +303,13 @@ struct UnitigTrimArgs : UnitigArgs {
   unsigned long long* epartial;          // scan_partials_needed(n_edges) u64
 };
 // A trim counter is TRIM_SLOTS partial sums 256 bytes apart, a wave adding to the slot of its number: where most unitigs go
-// in a round nearly every wave adds, and adds to one address serialise.
-enum { TRIM_C_ISLANDS = 0, TRIM_C_DEAD_ENDS = 1, TRIM_C_READS = 2, TRIM_C_DROPPED = 3, TRIM_COUNTERS = 4, TRIM_SLOTS = 32, TRIM_STRIDE = 32,
-       TRIM_LIFTED = TRIM_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, TRIM_ROUND0 = TRIM_LIFTED + 8, TRIM_MAX_ROUNDS = 64,
-       TRIM_WORDS = TRIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
+// in a round nearly every wave adds, and adds to one address serialise.  Every counter block of the unitig, pairs
+// and scaffold calls is laid out so: counter_words(n) words of n counters (counter_slot and counter_total of sigax_device.h), then
+// the block's own tail; a step of the rounds keeps one flag per round there, at X_ROUND0 + r.
+enum { TRIM_SLOTS = 32, TRIM_STRIDE = 32, TRIM_MAX_ROUNDS = 64 };
+constexpr int counter_words(int n) { return n * TRIM_SLOTS * TRIM_STRIDE; }
+enum { TRIM_C_ISLANDS = 0, TRIM_C_DEAD_ENDS = 1, TRIM_C_READS = 2, TRIM_C_DROPPED = 3, TRIM_COUNTERS = 4,
+       TRIM_LIFTED = counter_words(TRIM_COUNTERS), TRIM_ROUND0 = TRIM_LIFTED + 8, TRIM_WORDS = TRIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
 static const uint32_t TRIM_NO_COVERAGE = 0xFFFFFFFFu;
 // non-maximal overlap cutting (sigax_unitigs_prune_*): the trim block and what a round's cut step needs.  Again a block of its
 // own: the kernels of the two older entry points keep theirs.
@@ -325,7 +328,7 @@ struct UnitigPruneArgs : UnitigTrimArgs {
   unsigned long long num_reads, genome_size;
   double uniq_threshold;
 };
-enum { PRUNE_C_CUT = 0, PRUNE_C_UNIQUE = 1, PRUNE_COUNTERS = 2, PRUNE_ROUND0 = PRUNE_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+enum { PRUNE_C_CUT = 0, PRUNE_C_UNIQUE = 1, PRUNE_COUNTERS = 2, PRUNE_ROUND0 = counter_words(PRUNE_COUNTERS),
        PRUNE_WORDS = PRUNE_ROUND0 + TRIM_MAX_ROUNDS + 8 };
 unsigned unitig_rounds(unsigned long long n_reads);  // ceil(log2 n_reads) + 1: the pointer-jumping launches of one ranking
 void launch_unitigs(const UnitigArgs& a, hipStream_t st);
@@ -359,7 +362,7 @@ struct UnitigChimericArgs : UnitigPruneArgs {
   uint32_t min_chimeric_length, min_chimeric_coverage, chimeric_delta;
   double chimeric_threshold;
 };
-enum { CHIM_C_UNITIGS = 0, CHIM_C_READS = 1, CHIM_COUNTERS = 2, CHIM_ROUND0 = CHIM_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+enum { CHIM_C_UNITIGS = 0, CHIM_C_READS = 1, CHIM_COUNTERS = 2, CHIM_ROUND0 = counter_words(CHIM_COUNTERS),
        CHIM_WORDS = CHIM_ROUND0 + TRIM_MAX_ROUNDS + 8 };
 static const uint32_t REMOVED_CHIMERIC = 0x80000000u;
 // one round's chimeric step (a.round >= 1, a.maxlen = NULL), after launch_prune_trim_round: the graph of the live records, every
@@ -388,7 +391,7 @@ struct UnitigBubbleArgs : UnitigChimericArgs {
                                          // the appended losers at BUB_APPENDED; at BUB_ROUND0 + r whether round r's step removed something
   uint32_t max_bubble_span, max_divergence_permille;
 };
-enum { BUB_C_POPPED = 0, BUB_C_READS = 1, BUB_C_KEPT = 2, BUB_COUNTERS = 3, BUB_APPENDED = BUB_COUNTERS * TRIM_SLOTS * TRIM_STRIDE,
+enum { BUB_C_POPPED = 0, BUB_C_READS = 1, BUB_C_KEPT = 2, BUB_COUNTERS = 3, BUB_APPENDED = counter_words(BUB_COUNTERS),
        BUB_ROUND0 = BUB_APPENDED + 8, BUB_WORDS = BUB_ROUND0 + TRIM_MAX_ROUNDS + 8, BUB_COMPARE_WAVES = 8192 };
 static const uint32_t REMOVED_BUBBLE = 0x40000000u;
 static const uint32_t BUBBLE_NO_BASES = 0xFFFFFFFFu;
@@ -407,7 +410,7 @@ struct UnitigIndelArgs : UnitigBubbleArgs {
   uint32_t max_edits, max_edit_permille;
 };
 enum { IND_C_POPPED = 0, IND_C_READS = 1, IND_C_KEPT = 2, IND_C_SKIPPED = 3, IND_COUNTERS = 4,
-       IND_APPENDED = IND_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, IND_ROUND0 = IND_APPENDED + 8, IND_WORDS = IND_ROUND0 + TRIM_MAX_ROUNDS + 8,
+       IND_APPENDED = counter_words(IND_COUNTERS), IND_ROUND0 = IND_APPENDED + 8, IND_WORDS = IND_ROUND0 + TRIM_MAX_ROUNDS + 8,
        IND_MAX_SPAN = 4096, IND_MAX_EDITS = 31 };
 static const uint32_t REMOVED_INDEL = 0x20000000u;
 // one round's indel step (a.round >= 1, a.maxlen = NULL, 0 < a.max_bubble_span <= IND_MAX_SPAN, 0 < a.max_edits <= IND_MAX_EDITS), after
@@ -433,7 +436,7 @@ struct UnitigReduceArgs : UnitigIndelArgs {
   unsigned long long red_cap;            // a power of two, at least 4 n_edges
   uint32_t red_prev;                     // the round before this pass (0: none); the pass is idle when that round changed nothing
 };
-enum { RED_C_FLAGGED = 0, RED_C_PART = 1, RED_COUNTERS = 2, RED_FIRST = RED_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, RED_LAST = RED_FIRST + 1,
+enum { RED_C_FLAGGED = 0, RED_C_PART = 1, RED_COUNTERS = 2, RED_FIRST = counter_words(RED_COUNTERS), RED_LAST = RED_FIRST + 1,
        RED_PASSES = RED_FIRST + 2, RED_LAST_PART = RED_FIRST + 3, RED_WORDS = RED_FIRST + 8 };
 static const uint32_t CUT_TRANSITIVE = 0x80000000u;
 // One reduction pass over the records as removed[] and the low bits of cut[] stand (a.maxlen = NULL, n_edges < 2^32): bit 31 of every
@@ -473,7 +476,7 @@ struct PairArgs {
   void* sort_tmp;                        // pairs_sort_bytes(cap) bytes
   unsigned long long sort_tmp_bytes;
 };
-enum { PAIR_COUNTERS = 22, PAIR_APPENDED = PAIR_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, PAIR_WORDS = PAIR_APPENDED + 8, PAIR_HIST_MAX = 8192,
+enum { PAIR_COUNTERS = 22, PAIR_APPENDED = counter_words(PAIR_COUNTERS), PAIR_WORDS = PAIR_APPENDED + 8, PAIR_HIST_MAX = 8192,
        PAIR_READS_PER_BLOCK = 1024 };
 // bytes of scratch the device sort of `cap` (key, value) entries asks for: a size query, launches nothing
 hipError_t pairs_sort_bytes(unsigned long long cap, unsigned long long* bytes);
@@ -516,7 +519,7 @@ struct ScaffoldArgs {
   unsigned long long* plen;              // [max_unitigs]: its bases
 };
 // counters 2-14 are status entries; SCAF_C_CLOSING_GAPS sums the gaps of the joins that close cycles
-enum { SCAF_C_CLOSING_GAPS = 0, SCAF_COUNTERS = 16, SCAF_ANY_CUT = SCAF_COUNTERS * TRIM_SLOTS * TRIM_STRIDE, SCAF_WORDS = SCAF_ANY_CUT + 8 };
+enum { SCAF_C_CLOSING_GAPS = 0, SCAF_COUNTERS = 16, SCAF_ANY_CUT = counter_words(SCAF_COUNTERS), SCAF_WORDS = SCAF_ANY_CUT + 8 };
 hipError_t launch_scaffold(const ScaffoldArgs& a, hipStream_t st);
 void launch_scaffold_bases(const ScaffoldArgs& a, hipStream_t st);  // the last phase alone, over what launch_scaffold left
 

@@ -8,7 +8,7 @@
 //                    layout, so whatever it holds names a readable placement and a readable unitig.
 //   k_pair_classify  1024 reads per workgroup, four per lane.  The smaller id of a pair classifies it.  Counts are taken with one
 //                    ballot per class and read, after the loop; the sums are per-lane, then per-wave; lane 0 adds what is not zero to
-//                    the wave's slot of each counter (the trim_slot pattern: 32 slots 256 bytes apart).  The 128-bit sums of
+//                    the wave's slot of each counter (counter_slot, sigax_device.h: 32 slots 256 bytes apart).  The 128-bit sums of
 //                    squares add their low word and carry from the value that add returns.  The histogram is an LDS
 //                    sub-histogram per workgroup, flushed with one global add per non-zero bin: spans of one library pile into a
 //                    handful of bins.  A pair that joins a link appends (key, s) to a list -- one counter add per wave -- whose
@@ -24,12 +24,10 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "sigax_device.h"
 #include "sigax_kernels.h"
 
 namespace {
-typedef unsigned long long u64;
-typedef uint32_t u32;
-
 constexpr u64 EMPTY = ~0ull;
 // status entries that are counts of reads or pairs (one ballot each); 21 is the appended entries, 22 the scan's total
 enum { ST_ENTRY = 0, ST_BAD = 1, ST_PAIRS = 2, ST_UNPLACED = 3, ST_SAME = 4, ST_INWARD = 5, ST_OUTWARD = 6, ST_TANDEM = 7, ST_RING = 8,
@@ -37,14 +35,6 @@ enum { ST_ENTRY = 0, ST_BAD = 1, ST_PAIRS = 2, ST_UNPLACED = 3, ST_SAME = 4, ST_
        ST_LINKED = 21, ST_RECORDS = 22 };
 constexpr u32 BALLOTED = 0x1C47FFu;  // bits 0-10, 14, 18-20
 
-__device__ __forceinline__ u64 wave_total(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ u64* pair_slot(const PairArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.cnt + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
 // the unitigs and the placements that can be read
 __device__ __forceinline__ void pair_bounds(const PairArgs& A, u64& nu, u64& P) {
   nu = *A.n_unitigs;
@@ -58,7 +48,7 @@ __global__ __launch_bounds__(256) void k_pair_where(PairArgs A) {
   u64 nu, P;
   pair_bounds(A, nu, P);
   if (p >= P) return;
-  u64 lo = 0, hi = nu;
+  u64 lo = 0, hi = nu;  // (last_at_most, written out: through the helper the kernel's one 64-bit add swaps its operands)
   for (int step = 0; step < 32 && hi - lo > 1; ++step) {
     const u64 mid = (lo + hi) >> 1;
     if (A.lay_offs[mid] <= p)
@@ -76,10 +66,10 @@ __device__ __forceinline__ void add_squares(const PairArgs& A, u32 c, u64 L, u64
   const u64 part = (H & 0xFFFFFFFFull) << 32, lo = L + part;
   hi += lo < L;
   if (lo) {
-    const u64 old = atomicAdd(pair_slot(A, c), lo);
+    const u64 old = atomicAdd(counter_slot(A.cnt, c), lo);
     hi += old + lo < old;
   }
-  if (hi) atomicAdd(pair_slot(A, c + 1u), hi);
+  if (hi) atomicAdd(counter_slot(A.cnt, c + 1u), hi);
 }
 
 __global__ __launch_bounds__(256) void k_pair_classify(PairArgs A) {
@@ -181,19 +171,19 @@ __global__ __launch_bounds__(256) void k_pair_classify(PairArgs A) {
       }
     }
   }
-  const u64 t_sd = wave_total(sd), t_sd2l = wave_total(sd2l), t_sd2h = wave_total(sd2h);
-  const u64 t_ss = wave_total(ss), t_ss2l = wave_total(ss2l), t_ss2h = wave_total(ss2h);
+  const u64 t_sd = wave_sum(sd), t_sd2l = wave_sum(sd2l), t_sd2h = wave_sum(sd2h);
+  const u64 t_ss = wave_sum(ss), t_ss2l = wave_sum(ss2l), t_ss2h = wave_sum(ss2h);
 #pragma unroll
   for (int c = 0; c < 21; ++c)
     if ((BALLOTED >> c) & 1u) {  // one ballot per class and read: the wave's count, one add when it is not zero
       u32 tot = 0;
 #pragma unroll
       for (u32 it = 0; it < PAIR_READS_PER_BLOCK / 256u; ++it) tot += (u32)__popcll(__ballot((fs[it] >> c) & 1u));
-      if (lane == 0u && tot) atomicAdd(pair_slot(A, (u32)c), (u64)tot);
+      if (lane == 0u && tot) atomicAdd(counter_slot(A.cnt, (u32)c), (u64)tot);
     }
   if (lane == 0u) {
-    if (t_sd) atomicAdd(pair_slot(A, ST_SD), t_sd);
-    if (t_ss) atomicAdd(pair_slot(A, ST_SS), t_ss);
+    if (t_sd) atomicAdd(counter_slot(A.cnt, ST_SD), t_sd);
+    if (t_ss) atomicAdd(counter_slot(A.cnt, ST_SS), t_ss);
     if (t_sd2l | t_sd2h) add_squares(A, ST_SD2, t_sd2l, t_sd2h);
     if (t_ss2l | t_ss2h) add_squares(A, ST_SS2, t_ss2l, t_ss2h);
   }
@@ -237,8 +227,8 @@ __global__ __launch_bounds__(256) void k_pair_reduce(PairArgs A, const u64* __re
   u32 mn = s > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)s;
   const u64 r0 = __shfl(r, 0, 64);
   if (__all(valid && r == r0)) {  // the whole wave in one run
-    const u64 sum = wave_total(s);
-    for (int o = 32; o > 0; o >>= 1) {
+    const u64 sum = wave_sum(s);
+    for (int o = 32; o > 0; o >>= 1) {  // (not wave_min32: its shuffle of an int compiles to other code here)
       const u32 other = __shfl_xor(mn, o, 64);
       mn = other < mn ? other : mn;
     }
@@ -270,7 +260,7 @@ __global__ void k_pair_status(PairArgs A) {
       ++c;
       continue;
     }
-    u64 v = 0;
+    u64 v = 0;  // (counter_total, through the lambda the 128-bit sums need)
     for (u32 s = 0; s < TRIM_SLOTS; ++s) v += slot(c, s);
     A.status[c] = v;
   }
@@ -293,14 +283,14 @@ hipError_t pairs_sort_bytes(u64 cap, u64* bytes) {
 
 hipError_t launch_pairs(const PairArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  const unsigned per_read = (unsigned)((n + 255) / 256), per_block = (unsigned)((n + PAIR_READS_PER_BLOCK - 1) / PAIR_READS_PER_BLOCK);
+  const unsigned per_read = blocks_of(n), per_block = (unsigned)((n + PAIR_READS_PER_BLOCK - 1) / PAIR_READS_PER_BLOCK);
   hipLaunchKernelGGL(k_pair_where, dim3(per_read), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_pair_classify, dim3(per_block), dim3(256), 0, st, a);
   if (a.cap) {
     size_t tb = (size_t)a.sort_tmp_bytes;
     const hipError_t e = rocprim::radix_sort_pairs(a.sort_tmp, tb, (const u64*)a.keys[0], a.keys[1], (const u64*)a.vals[0], a.vals[1], (size_t)a.cap, 0u, 64u, st);
     if (e != hipSuccess) return e;
-    const unsigned per_entry = (unsigned)((a.cap + 255) / 256);
+    const unsigned per_entry = blocks_of(a.cap);
     hipLaunchKernelGGL(k_pair_heads, dim3(per_entry), dim3(256), 0, st, a, (const u64*)a.keys[1]);
     launch_scan(a.head, a.cap, a.partial, a.scan, a.scan_total, st);
     hipLaunchKernelGGL(k_pair_init, dim3(per_entry), dim3(256), 0, st, a, (const u64*)a.keys[1]);

@@ -1,6 +1,7 @@
 // siga_amd/csrc/sigax_rank.h -- what the kernels that walk the forward strand symbol by symbol share (sigax_match.hip,
 // sigax_spectrum.hip, sigax_locate.hip), each piece once:
-//   leaves    byte -> rank, Occ out of a one-step granule, the pair counts of a two-step line (fm_layout.h), wave reductions
+//   leaves    byte -> rank, Occ out of a one-step granule, the pair counts of a two-step line (fm_layout.h); the wave sum is
+//             sigax_device.h's
 //   search    the workgroup's constants (SearchSh, search_sh_fill), a chain's start from C[] or from the corrector's prefix
 //             table (search_init, ptab_start), one backward-search step (search_step), interval_valid
 //   chains    a wave's reservation of chain numbers from a global counter (ChainGrab, grab_chains)
@@ -12,11 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "fm_layout.h"
+#include "sigax_device.h"
 
 namespace {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
 
 template <bool WIDE> struct PosOf { typedef u32 type; };
 template <> struct PosOf<true> { typedef u64 type; };
@@ -36,10 +35,6 @@ __device__ __forceinline__ T sel4(u32 i, T v0, T v1, T v2, T v3) {  // v[i], i i
   return (i & 2u) ? t23 : t01;
 }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ u64 first_lane64(u64 v) {
   return (u64)__builtin_amdgcn_readfirstlane((u32)v) | ((u64)__builtin_amdgcn_readfirstlane((u32)(v >> 32)) << 32);
 }

@@ -25,39 +25,24 @@
 //                    pdst and keeps the 64 descriptors from there on in LDS; a lane finds its own among them in at most 6 LDS
 //                    steps (beyond them: the bisection again).  Then a run of N, one 16-byte load and store (forward), the
 //                    mirrored 16 bytes complemented in registers (reverse), or bytes where the piece crosses a boundary
-// Counters are per-wave sums into 32 slots 256 bytes apart (the trim_slot pattern).  Every loop has a bound the host knows and
+// Counters are per-wave sums into 32 slots 256 bytes apart (counter_slot, sigax_device.h).  Every loop has a bound the host knows and
 // every access is bounds-checked.  Plain vector stores and atomics only; integer work, no LDS beyond those descriptors.
 #include <hip/hip_runtime.h>
 
+#include "sigax_device.h"
 #include "sigax_kernels.h"
 
 namespace {
-typedef unsigned long long u64;
-typedef uint32_t u32;
-
 constexpr u32 NIL = 0xFFFFFFFFu;
 // status entries
 enum { ST_SCAFFOLDS = 0, ST_BASES = 1, ST_LINKS = 2, ST_MALFORMED = 3, ST_SELF = 4, ST_CIRCULAR = 5, ST_SHORT = 6, ST_THIN = 7, ST_WEAK = 8,
        ST_AMBIGUOUS = 9, ST_JOINS = 10, ST_CYCLES = 11, ST_GAP_BASES = 12, ST_BELOW = 13, ST_CLAMPED = 14, ST_NO_ROOM = 15 };
 constexpr u32 CANDIDATE = 0u;  // a class that is no status entry
 
-__device__ __forceinline__ u64 wave_total(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ u64* scaf_slot(const ScaffoldArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.cnt + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 scaf_count(const ScaffoldArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.cnt[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
-}
 // this wave's lanes with `on` set, added once to counter c
 __device__ __forceinline__ void count_lanes(const ScaffoldArgs& A, u32 c, bool on) {
   const u64 m = __ballot(on);
-  if (m && (threadIdx.x & 63u) == 0u) atomicAdd(scaf_slot(A, c), (u64)__popcll(m));
+  if (m && (threadIdx.x & 63u) == 0u) atomicAdd(counter_slot(A.cnt, c), (u64)__popcll(m));
 }
 __device__ __forceinline__ u64 n_unitigs(const ScaffoldArgs& A) {
   const u64 nu = *A.n_unitigs;
@@ -183,8 +168,7 @@ __global__ __launch_bounds__(256) void k_scaf_joins(ScaffoldArgs A) {
   count_lanes(A, ST_JOINS, join);
   count_lanes(A, ST_BELOW, below);
   count_lanes(A, ST_CLAMPED, clamped);
-  const u64 tg = wave_total(gap);
-  if (tg && (threadIdx.x & 63u) == 0u) atomicAdd(scaf_slot(A, ST_GAP_BASES), tg);
+  wave_add(counter_slot(A.cnt, ST_GAP_BASES), gap);
 }
 
 // rk[s] = {successor or NIL, state reached so far, hops so far, smallest unitig id so far}; dist[s] = bases so far: a hop into
@@ -242,13 +226,8 @@ __global__ __launch_bounds__(256) void k_scaf_cut(ScaffoldArgs A, const uint4* _
     }
   }
   count_lanes(A, ST_CYCLES, cut);
-  const u64 tg = wave_total(gap);
-  if (tg && (threadIdx.x & 63u) == 0u) atomicAdd(scaf_slot(A, SCAF_C_CLOSING_GAPS), tg);
+  wave_add(counter_slot(A.cnt, SCAF_C_CLOSING_GAPS), gap);
 }
-
-// the direction of unitig u that leads to its scaffold's head: the terminal with the smaller id (a unitig on its own: B, so
-// that it is entered through B and placed forward)
-__device__ __forceinline__ u32 head_dir(const uint4 a0, const uint4 a1) { return (a0.y >> 1) <= (a1.y >> 1) ? 0u : 1u; }
 
 __global__ __launch_bounds__(256) void k_scaf_heads(ScaffoldArgs A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -316,7 +295,7 @@ __global__ __launch_bounds__(64) void k_scaf_status(ScaffoldArgs A) {
   const u32 c = threadIdx.x;
   if (blockIdx.x != 0u) return;
   const u64 n = A.max_unitigs;
-  const u64 v = c < SCAF_COUNTERS ? scaf_count(A, c) : 0ull;
+  const u64 v = c < SCAF_COUNTERS ? counter_total(A.cnt, c) : 0ull;
   const u64 closing_gaps = __shfl(v, SCAF_C_CLOSING_GAPS, 64), joins = __shfl(v, ST_JOINS, 64), cycles = __shfl(v, ST_CYCLES, 64);
   const u64 bases = A.scan[2 * (n + 1) + n] + (A.scan[3 * (n + 1) + n] << 32);
   u64 out = v;
@@ -327,10 +306,6 @@ __global__ __launch_bounds__(64) void k_scaf_status(ScaffoldArgs A) {
   if (c == ST_GAP_BASES) out = v - closing_gaps;
   if (c == ST_NO_ROOM) out = bases > A.sseqs_capacity ? 1ull : 0ull;
   if (c < 16u) A.status[c] = out;
-}
-
-__device__ __forceinline__ u32 comp_byte(u32 b) {
-  return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
 }
 
 // what a wave keeps in LDS of the placements its 1024 output bytes begin in: 64 descriptors from the first byte's placement on
@@ -354,18 +329,8 @@ __global__ __launch_bounds__(256) void k_scaf_bases(ScaffoldArgs A) {
   const u64 wb = ((u64)blockIdx.x * 4u + wave) * 1024ull;  // the wave's first output byte
   const u64 b = wb + 16ull * lane;
   const u64* __restrict__ D = A.pdst;
-  // the placement of output byte p: the last k with D[k] <= p (at most 32 steps: P < 2^31)
-  auto find = [&](u64 p) -> u64 {
-    u64 lo = 0, hi = P;
-    for (int step = 0; step < 32 && hi - lo > 1; ++step) {
-      const u64 mid = (lo + hi) >> 1;
-      if (D[mid] <= p)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    return lo;
-  };
+  // the placement of output byte p: the last k with D[k] <= p
+  auto find = [&](u64 p) -> u64 { return last_at_most(D, P, p); };
   // one bisection per wave (its operands are the wave's alone), then 64 descriptors side by side
   u64 k0 = 0;
   u32 cnt = 0;
@@ -382,7 +347,8 @@ __global__ __launch_bounds__(256) void k_scaf_bases(ScaffoldArgs A) {
   __syncthreads();
   if (!live || b >= total) return;
   const u64* Dw = sh.dst[wave];
-  // the placement of byte p >= wb: in the window by at most 6 LDS steps, beyond it by the bisection over the whole table
+  // the placement of byte p >= wb: in the window by at most 6 LDS steps, beyond it by the bisection over the whole table.  (Not
+  // last_at_most: the window is in LDS, indexed in 32 bits, and its search ends with the test whether p lies beyond it.)
   auto locate = [&](u64 p) -> u64 {
     u32 lo = 0, hi = cnt;
     while (hi - lo > 1u) {
@@ -443,7 +409,8 @@ __global__ __launch_bounds__(256) void k_scaf_bases(ScaffoldArgs A) {
       else
         __builtin_memcpy(&w, A.useqs + from, 16);  // (no alignment: the compiler picks the access)
       if (rev) {
-        // byte j of the piece = complement of byte 15 - j of the load
+        // byte j of the piece = complement of byte 15 - j of the load (written out in each bases kernel: as a shared
+        // function it compiles to other code, and these kernels stay as they are)
         const u32 x[4] = {w.w, w.z, w.y, w.x};
         u32 y[4];
 #pragma unroll
@@ -468,7 +435,6 @@ __global__ __launch_bounds__(256) void k_scaf_bases(ScaffoldArgs A) {
   }
 }
 
-unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 void launch_scaffold_bases(const ScaffoldArgs& a, hipStream_t st) {

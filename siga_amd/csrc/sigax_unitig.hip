@@ -29,10 +29,12 @@
 // kernels above as <TRIM = true> skip reads with removed[r] != 0 and the records that touch one, and
 //   k_trim_decide one lane per read: a head judges its unitig by its two end degrees, its bases and its reads (what
 //                 k_uni_heads left) and writes the verdict under its own id; islands and dead ends are counted
-//   k_trim_mark   one lane per read: it finds its head through the final rank entry and takes the verdict into removed[]
+//   k_step_mark<TrimStep>   one lane per read: it finds its head through the final rank entry and takes the verdict into removed[]
 //   k_lift_flag / k_lift_write   one lane per record: a live record that is no link of the final graph is flagged, launch_scan
 //                 gives it its place, and it is written over unitig ids and unitig ends (one 16-byte load, one 16-byte store)
 // A round's launches leave at once when the round before it removed nothing (idle_round).
+// What a removing step of a round must provide is written down at `Step`; every step begins with launch_step_graph and ends with
+// k_step_mark, and the wave reductions, counter slots and base helpers are sigax_device.h's.
 // Non-maximal overlap cutting (sigax_unitigs_prune_*; tests/prune_cases.py::expected_prune): the kernels above as
 // <TRIM = 2> also skip the records with cut[i] != 0, k_uni_degree<2> takes the longest participant per read end (atomicMax), and
 //   k_prune_clear  the step's scratch emptied: the maxima and, careful mode, the table (a kernel: idle rounds write nothing)
@@ -47,25 +49,26 @@
 //                  degree >= 2 takes the smallest (bases, head) and (reads, head) over the unitigs its participants lead to
 //                  (64-bit atomicMin behind a plain compare), then the smallest among those not of the first one's unitig
 //   k_chim_decide  one lane per read: a head judges its unitig from its two end degrees, its neighbours' degrees, scores and minima
-//   k_chim_mark    one lane per read: removed[r] = round | 0x80000000 under a chimeric head
+//   k_step_mark<ChimStep>   one lane per read: removed[r] = round | 0x80000000 under a chimeric head
 // Bubble popping (sigax_unitigs_bubble_*; tests/bubble_cases.py::expected_bubble): a step between the trim and the
 // chimeric step of a round, over the <TRIM = 2> kernels, and
-//   k_bub_clear    the step's scratch emptied (a kernel: idle rounds write nothing)
+//   k_arm_clear<BubStep>   the step's scratch emptied (a kernel: idle rounds write nothing)
 //   k_bub_ends     one lane per record: an end of degree 1 learns the read end at its record's other side and the record's length
 //   k_bub_place    one lane per read: the step's own layout, where in its unitig the bases a read adds begin (bases test only)
 //   k_bub_arms     one lane per read: a head judges whether its unitig is an arm that takes part, and with which (lo, hi, span)
-//   k_bub_group    one lane per read: an arm finds its group's slot in an open-addressing table and offers (K << 32) | ~head
+//   k_arm_group<.., true>   one lane per read: an arm finds its group's slot in an open-addressing table under the key (lo, hi, span)
+//                  and offers (K << 32) | ~head
 //   k_bub_losers   one lane per read: an arm that is not its group's maximum is popped (no bases test) or appended to a list
 //   k_bub_compare  one wave per appended loser: lanes stride over the window, each base found by bisecting the placements
-//   k_bub_mark     one lane per read: removed[r] = round | 0x40000000 under a popped head
+//   k_step_mark<BubStep>   one lane per read: removed[r] = round | 0x40000000 under a popped head
 // Indel bubble popping (sigax_unitigs_indel_*; tests/indel_cases.py::expected_indel): a step between the bubble and the
 // chimeric step of a round, over the <TRIM = 2> kernels, k_bub_ends, k_bub_place and k_bub_arms as they are, and
-//   k_ind_clear    k_bub_clear's work, and no pair appended
-//   k_ind_group    one lane per read: k_bub_group under the key (lo, hi) alone
+//   k_arm_clear<IndStep>   the bubble step's clear, and no pair appended
+//   k_arm_group<.., false>  one lane per read: the bubble step's grouping under the key (lo, hi) alone
 //   k_ind_losers   one lane per read: a loser of the winner's span, or more than E bases from it, stays; another is appended to a list
 //   k_ind_compare  one wave per appended pair: both windows staged as bytes in LDS (at most 4096 + 4096), then the furthest-reaching
 //                  recurrence over the 2 E + 1 diagonals, one per lane, neighbours by shuffles, at most E + 1 turns
-//   k_ind_mark     one lane per read: removed[r] = round | 0x20000000 under a popped head
+//   k_step_mark<IndStep>   one lane per read: removed[r] = round | 0x20000000 under a popped head
 // Transitive reduction (sigax_unitigs_reduce_*; tests/reduce_cases.py::expected_reduce): a pass before the cut step of
 // every round and one more before the final unitigs.  It flags records in bit 31 of cut[], and every kernel above already takes a
 // record with cut[i] != 0 as not there, so none of them changed.  A record a-b of overlap len is explained through a third read's
@@ -92,12 +95,10 @@
 
 #include <type_traits>
 
+#include "sigax_device.h"
 #include "sigax_kernels.h"
 
 namespace {
-typedef unsigned long long u64;
-typedef uint32_t u32;
-
 constexpr u32 NIL = 0xFFFFFFFFu;
 
 // ---- phase 1, 2: records ----
@@ -128,11 +129,6 @@ __device__ __forceinline__ RecClass classify(const uint4 rec, const UnitigArgs& 
   return c;
 }
 
-__device__ __forceinline__ u64 wave_total(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // TRIM = 1: the kernels of sigax_unitigs_trim_*: reads with removed[r] != 0 are not there, nor are the records that touch one.
 // They take the longer argument block; TRIM = 0 is sigax_unitigs_device's code as it was, over the block it had.  TRIM = 2: the
 // kernels of sigax_unitigs_prune_*, as 1 and without the records that were cut, over a block of their own again.
@@ -143,16 +139,6 @@ template <int TRIM>
 __device__ __forceinline__ bool idle_round(const ArgsOf<TRIM>& A) {
   if constexpr (TRIM != 0) return A.round > 1u && A.trim[TRIM_ROUND0 + A.round - 1u] == 0ull;
   return false;
-}
-// where this wave adds to trim counter c
-__device__ __forceinline__ u64* trim_slot(const UnitigTrimArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.trim + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 trim_count(const UnitigTrimArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.trim[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
 }
 // both reads of a kept record alive
 template <int TRIM>
@@ -198,14 +184,14 @@ __global__ __launch_bounds__(256) void k_uni_degree(ArgsOf<TRIM> A) {
       }
     }
   }
-  const u64 tb = wave_total(bad), tl = wave_total(low);
+  const u64 tb = wave_sum(bad), tl = wave_sum(low);
   if ((threadIdx.x & 63u) == 0u) {
     if (tb) atomicAdd(&A.counts[UNI_C_BAD], tb);
     if (tl) atomicAdd(&A.counts[UNI_C_LOW], tl);
   }
   if constexpr (TRIM != 0) {
-    const u64 td = wave_total(dropped);
-    if ((threadIdx.x & 63u) == 0u && td && A.round == 0u) atomicAdd(trim_slot(A, TRIM_C_DROPPED), td);
+    const u64 td = wave_sum(dropped);
+    if ((threadIdx.x & 63u) == 0u && td && A.round == 0u) atomicAdd(counter_slot(A.trim, TRIM_C_DROPPED), td);
   }
 }
 
@@ -223,7 +209,7 @@ __global__ __launch_bounds__(256) void k_uni_links(ArgsOf<TRIM> A) {
       simple = 1;
     }
   }
-  const u64 ts = wave_total(simple);
+  const u64 ts = wave_sum(simple);
   if ((threadIdx.x & 63u) == 0u && ts) atomicAdd(&A.counts[UNI_C_SIMPLE], ts);
 }
 
@@ -284,15 +270,12 @@ __global__ __launch_bounds__(256) void k_uni_cut(ArgsOf<TRIM> A, const uint4* __
       }
     }
   }
-  const u64 tc = wave_total(cut);
+  const u64 tc = wave_sum(cut);
   if ((threadIdx.x & 63u) == 0u && tc) atomicAdd(&A.counts[UNI_C_CYCLES], tc);
 }
 
 // ---- phase 5: heads ----
-// the direction of read r that leads to its unitig's head: the terminal with the smaller id (a read on its own: B, so that
-// it is entered through B and placed forward)
-__device__ __forceinline__ u32 head_dir(const uint4 a0, const uint4 a1) { return (a0.y >> 1) <= (a1.y >> 1) ? 0u : 1u; }
-
+// (head_dir, sigax_device.h: the direction of read r that leads to its unitig's head)
 template <int TRIM>
 __global__ __launch_bounds__(256) void k_uni_heads(ArgsOf<TRIM> A, const uint4* __restrict__ rk, const u64* __restrict__ dist) {
   if (idle_round<TRIM>(A)) return;
@@ -375,10 +358,6 @@ __global__ __launch_bounds__(256) void k_uni_place(ArgsOf<TRIM> A, const uint4* 
 }
 
 // ---- phase 7: bases ----
-__device__ __forceinline__ u32 comp_byte(u32 b) {
-  return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
-}
-
 struct BaseSh {
   u64 dst[4][65];
   u64 src[4][64];
@@ -421,7 +400,8 @@ __global__ __launch_bounds__(256) void k_uni_bases(ArgsOf<TRIM> A) {
     const u32 b = A.seqs[at];
     return rev ? comp_byte(b) : b;
   };
-  // stretch of destination byte p: the last k with D[k] <= p (D ascends over a wave's stretches)
+  // stretch of destination byte p: the last k with D[k] <= p (D ascends over a wave's stretches).  (Not last_at_most: D is the
+  // wave's window in LDS, indexed in 32 bits, and cnt <= 64 bounds the steps.)
   auto find = [&](u64 p) -> u32 {
     u32 a = 0, b = cnt;
     while (b - a > 1u) {  // at most 6 steps
@@ -451,7 +431,8 @@ __global__ __launch_bounds__(256) void k_uni_bases(ArgsOf<TRIM> A) {
           uint4 w;
           __builtin_memcpy(&w, A.seqs + from, 16);  // (no alignment promised: the compiler picks the access)
           if (rev) {
-            // byte j of the piece = complement of byte 15 - j of the load
+            // byte j of the piece = complement of byte 15 - j of the load (written out in each bases kernel: as a shared
+            // function it compiles to other code, and these kernels stay as they are)
             const u32 x[4] = {w.w, w.z, w.y, w.x};
             u32 y[4];
             for (u32 q = 0; q < 4; ++q) {
@@ -512,31 +493,65 @@ __global__ __launch_bounds__(256) void k_trim_decide(UnitigTrimArgs A, const uin
     }
     A.verdict[r] = v;
   }
-  const u64 ti = wave_total(island), td = wave_total(dead_end);
+  const u64 ti = wave_sum(island), td = wave_sum(dead_end);
   if ((threadIdx.x & 63u) == 0u) {
-    if (ti) atomicAdd(trim_slot(A, TRIM_C_ISLANDS), ti);
-    if (td) atomicAdd(trim_slot(A, TRIM_C_DEAD_ENDS), td);
+    if (ti) atomicAdd(counter_slot(A.trim, TRIM_C_ISLANDS), ti);
+    if (td) atomicAdd(counter_slot(A.trim, TRIM_C_DEAD_ENDS), td);
   }
 }
 
-// One lane per read: the verdict lies under its head, which the final rank entry names.
-__global__ __launch_bounds__(256) void k_trim_mark(UnitigTrimArgs A, const uint4* __restrict__ rk) {
+// ---- what a removing step of a round is ----
+// A step that takes reads out -- trim, bubble, indel, chimeric -- provides: its argument block (the block of the step before it,
+// extended); its own counter block in it, zeroed before round 1, with a "reads" counter and one flag per round at ROUND0 + r; its
+// bit in removed[] (0 for the trim step, whose block is `trim` itself); kernels of its own that leave verdict[head] for every
+// unitig (after launch_step_graph: the graph of the live records and k_uni_heads); a k_x_status that writes its status words with
+// rounds_ran.  k_step_mark<Step> then does what is common to them all.
+template <class ArgsT, u64* ArgsT::*BLOCK, u32 C_READS_, u32 ROUND0_, u32 BIT_, u32 APPENDED_ = 0u>
+struct Step {
+  typedef ArgsT Args;
+  static constexpr u32 C_READS = C_READS_, ROUND0 = ROUND0_, BIT = BIT_, APPENDED = APPENDED_;  // APPENDED: the word that counts a list
+  static __device__ __forceinline__ u64* block(const ArgsT& A) { return A.*BLOCK; }
+};
+using TrimStep = Step<UnitigTrimArgs, &UnitigTrimArgs::trim, TRIM_C_READS, TRIM_ROUND0, 0u>;
+using ChimStep = Step<UnitigChimericArgs, &UnitigChimericArgs::chim, CHIM_C_READS, CHIM_ROUND0, REMOVED_CHIMERIC>;
+using BubStep = Step<UnitigBubbleArgs, &UnitigBubbleArgs::bub, BUB_C_READS, BUB_ROUND0, REMOVED_BUBBLE, BUB_APPENDED>;
+using IndStep = Step<UnitigIndelArgs, &UnitigIndelArgs::ind, IND_C_READS, IND_ROUND0, REMOVED_INDEL, IND_APPENDED>;
+
+// the head of the unitig of state s (s < 2 n_reads), by the final rank entry; NIL where the entry names no read
+__device__ __forceinline__ u32 head_of(const UnitigArgs& A, const uint4* __restrict__ rk, u32 s) {
+  const u64 r = s >> 1;
+  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
+  const u32 h = (head_dir(a0, a1) ? a1 : a0).y >> 1;
+  return (u64)h < A.n_reads ? h : NIL;
+}
+// the rounds in which a step did something, from its block's flags
+__device__ __forceinline__ u64 rounds_ran(const u64* block, u32 round0) {
+  u64 rounds = 0;
+  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += block[round0 + r] != 0ull;
+  return rounds;
+}
+
+// One lane per read: the verdict lies under its head, which the final rank entry names; removed[r] = round | the step's bit.  The
+// wave's count goes to the trim block's reads and to the step's own, and the round is flagged in both.
+template <class S>
+__global__ __launch_bounds__(256) void k_step_mark(typename S::Args A, const uint4* __restrict__ rk) {
   if (idle_round<1>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   const u64 n = A.n_reads;
   u32 gone = 0;
   if (r < n && A.removed[r] == 0u) {
-    const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
-    const u64 h = (head_dir(a0, a1) ? a1 : a0).y >> 1;
-    if (h < n && A.verdict[h] != 0u) {
-      A.removed[r] = A.round;
+    const u32 h = head_of(A, rk, 2u * (u32)r);  // (a state fits 32 bits: the host refuses n_reads >= 2^31)
+    if (h != NIL && A.verdict[h] != 0u) {
+      A.removed[r] = A.round | S::BIT;
       gone = 1;
     }
   }
-  const u64 tg = wave_total(gone);
+  const u64 tg = wave_sum(gone);
   if ((threadIdx.x & 63u) == 0u && tg) {
-    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
+    atomicAdd(counter_slot(A.trim, TRIM_C_READS), tg);
+    if constexpr (S::BIT != 0u) atomicAdd(counter_slot(S::block(A), S::C_READS), tg);
     A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
+    if constexpr (S::BIT != 0u) S::block(A)[S::ROUND0 + A.round] = 1ull;
   }
 }
 
@@ -572,34 +587,15 @@ __global__ __launch_bounds__(256) void k_lift_write(UnitigTrimArgs A) {
 
 __global__ void k_trim_status(UnitigTrimArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-  u64 rounds = 0;
-  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.trim[TRIM_ROUND0 + r] != 0ull;
-  A.status[6] = rounds;
-  A.status[7] = trim_count(A, TRIM_C_ISLANDS);
-  A.status[8] = trim_count(A, TRIM_C_DEAD_ENDS);
-  A.status[9] = trim_count(A, TRIM_C_READS);
-  A.status[10] = trim_count(A, TRIM_C_DROPPED);
+  A.status[6] = rounds_ran(A.trim, TRIM_ROUND0);
+  A.status[7] = counter_total(A.trim, TRIM_C_ISLANDS);
+  A.status[8] = counter_total(A.trim, TRIM_C_DEAD_ENDS);
+  A.status[9] = counter_total(A.trim, TRIM_C_READS);
+  A.status[10] = counter_total(A.trim, TRIM_C_DROPPED);
   A.status[11] = A.uedges ? A.trim[TRIM_LIFTED] : 0ull;
 }
 
 // ---- non-maximal overlap cutting: one round's cut step (MaximumOverlapVisitor, src/bigraph_visitors.cpp:410-512) ----
-__device__ __forceinline__ u64* prune_slot(const UnitigPruneArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.prune + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 prune_count(const UnitigPruneArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.prune[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
-}
-// the head of the unitig of state s (s < 2 n_reads), by the final rank entry; NIL where the entry names no read
-__device__ __forceinline__ u32 head_of(const UnitigPruneArgs& A, const uint4* __restrict__ rk, u32 s) {
-  const u64 r = s >> 1;
-  const uint4 a0 = rk[2 * r], a1 = rk[2 * r + 1];
-  const u32 h = (head_dir(a0, a1) ? a1 : a0).y >> 1;
-  return (u64)h < A.n_reads ? h : NIL;
-}
-
 // Before a cut step: the longest participant per read end back to 0 and, careful mode, the longest self record and the key table
 // back to empty.  A kernel and no memset, so that the rounds after one that changed nothing do not write the table again.
 __global__ __launch_bounds__(256) void k_prune_clear(UnitigPruneArgs A) {
@@ -632,8 +628,8 @@ __global__ __launch_bounds__(256) void k_prune_unique(UnitigPruneArgs A) {
     }
     A.uniq[r] = u;
   }
-  const u64 tu = wave_total(u);
-  if ((threadIdx.x & 63u) == 0u && tu && A.round == 1u) atomicAdd(prune_slot(A, PRUNE_C_UNIQUE), tu);
+  const u64 tu = wave_sum(u);
+  if ((threadIdx.x & 63u) == 0u && tu && A.round == 1u) atomicAdd(counter_slot(A.prune, PRUNE_C_UNIQUE), tu);
 }
 
 // a participant of the cut step: live, and no containment -> its two read ends and its length
@@ -716,9 +712,9 @@ __global__ __launch_bounds__(256) void k_prune_cut(UnitigPruneArgs A, const uint
       }
     }
   }
-  const u64 tc = wave_total(cut);
+  const u64 tc = wave_sum(cut);
   if ((threadIdx.x & 63u) == 0u && tc) {
-    atomicAdd(prune_slot(A, PRUNE_C_CUT), tc);
+    atomicAdd(counter_slot(A.prune, PRUNE_C_CUT), tc);
     A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
     A.prune[PRUNE_ROUND0 + A.round] = 1ull;
   }
@@ -726,24 +722,13 @@ __global__ __launch_bounds__(256) void k_prune_cut(UnitigPruneArgs A, const uint
 
 __global__ void k_prune_status(UnitigPruneArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-  u64 rounds = 0;
-  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.prune[PRUNE_ROUND0 + r] != 0ull;
-  A.status[12] = prune_count(A, PRUNE_C_CUT);
-  A.status[13] = rounds;
-  A.status[14] = prune_count(A, PRUNE_C_UNIQUE);
+  A.status[12] = counter_total(A.prune, PRUNE_C_CUT);
+  A.status[13] = rounds_ran(A.prune, PRUNE_ROUND0);
+  A.status[14] = counter_total(A.prune, PRUNE_C_UNIQUE);
   A.status[15] = 0ull;
 }
 
 // ---- chimeric unitig removal: one round's chimeric step (ChimericVisitor, src/bigraph_visitors.cpp:83-198) ----
-__device__ __forceinline__ u64* chim_slot(const UnitigChimericArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.chim + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 chim_count(const UnitigChimericArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.chim[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
-}
 // reads and bases of the unitig under head h (h < n_reads), as k_uni_heads left them
 __device__ __forceinline__ u64 unit_reads(const UnitigArgs& A, u32 h) { return A.cnt[A.n_reads + 1 + h]; }
 __device__ __forceinline__ u64 unit_bases(const UnitigArgs& A, u32 h) {
@@ -835,55 +820,24 @@ __global__ __launch_bounds__(256) void k_chim_decide(UnitigChimericArgs A, const
     }
     A.verdict[r] = v;
   }
-  const u64 tv = wave_total(v);
-  if ((threadIdx.x & 63u) == 0u && tv) atomicAdd(chim_slot(A, CHIM_C_UNITIGS), tv);
-}
-
-// One lane per read, as k_trim_mark: the verdict lies under its head.
-__global__ __launch_bounds__(256) void k_chim_mark(UnitigChimericArgs A, const uint4* __restrict__ rk) {
-  if (idle_round<2>(A)) return;
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  const u64 n = A.n_reads;
-  u32 gone = 0;
-  if (r < n && A.removed[r] == 0u) {
-    const u32 h = head_of(A, rk, 2u * (u32)r);
-    if (h != NIL && A.verdict[h] != 0u) {
-      A.removed[r] = A.round | REMOVED_CHIMERIC;
-      gone = 1;
-    }
-  }
-  const u64 tg = wave_total(gone);
-  if ((threadIdx.x & 63u) == 0u && tg) {
-    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
-    atomicAdd(chim_slot(A, CHIM_C_READS), tg);
-    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
-    A.chim[CHIM_ROUND0 + A.round] = 1ull;
-  }
+  const u64 tv = wave_sum(v);
+  if ((threadIdx.x & 63u) == 0u && tv) atomicAdd(counter_slot(A.chim, CHIM_C_UNITIGS), tv);
 }
 
 __global__ void k_chim_status(UnitigChimericArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-  u64 rounds = 0;
-  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.chim[CHIM_ROUND0 + r] != 0ull;
-  A.status[16] = chim_count(A, CHIM_C_UNITIGS);
-  A.status[17] = chim_count(A, CHIM_C_READS);
-  A.status[18] = rounds;
+  A.status[16] = counter_total(A.chim, CHIM_C_UNITIGS);
+  A.status[17] = counter_total(A.chim, CHIM_C_READS);
+  A.status[18] = rounds_ran(A.chim, CHIM_ROUND0);
   A.status[19] = 0ull;
 }
 
 // ---- bubble popping: one round's bubble step (the reference declares SmoothingVisitor and leaves it empty: the rules are sigax.h's) ----
-__device__ __forceinline__ u64* bub_slot(const UnitigBubbleArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.bub + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 bub_count(const UnitigBubbleArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.bub[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
-}
 
-// Before a bubble step: neighbours, group table and maxima back to empty, no loser appended.  A kernel, as k_prune_clear.
-__global__ __launch_bounds__(256) void k_bub_clear(UnitigBubbleArgs A) {
+// Before a bubble or an indel step (S): neighbours, group table and maxima back to empty, nothing appended to the step's list.  A
+// kernel, as k_prune_clear.
+template <class S>
+__global__ __launch_bounds__(256) void k_arm_clear(typename S::Args A) {
   if (idle_round<2>(A)) return;
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
   if (i < 2 * A.n_reads) {
@@ -894,7 +848,7 @@ __global__ __launch_bounds__(256) void k_bub_clear(UnitigBubbleArgs A) {
     A.table[i] = NIL;
     A.best[i] = 0ull;
   }
-  if (i == 0) A.bub[BUB_APPENDED] = 0ull;
+  if (i == 0) S::block(A)[S::APPENDED] = 0ull;
 }
 
 // One lane per record, a participant in both directions a -> b: an end of degree 1 learns its neighbour and its record's length (its
@@ -964,22 +918,26 @@ __global__ __launch_bounds__(256) void k_bub_arms(UnitigBubbleArgs A, const uint
   A.gslot[r] = NIL;
 }
 
-// One lane per read.  An arm that takes part finds the slot of its group -- the first free one on the probe path of (lo, hi, span), or
-// the one an arm of that key opened -- and offers (K << 32) | ~head to the group's maximum.  arm[] is the kernel before's: stable.
-__global__ __launch_bounds__(256) void k_bub_group(UnitigBubbleArgs A) {
+// One lane per read.  An arm that takes part finds the slot of its group -- the first free one on the probe path of its key, or the
+// one an arm of that key opened -- and offers (K << 32) | ~head to the group's maximum.  arm[] is the kernel before's: stable.  The key
+// is (lo, hi, span) in the bubble step (SPAN) and (lo, hi) alone in the indel step, where arms of every span that takes part meet in
+// one group.
+template <class ArgsT, bool SPAN>
+__global__ __launch_bounds__(256) void k_arm_group(ArgsT A) {
   if (idle_round<2>(A)) return;
   const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
   if (r >= A.n_reads) return;
   const uint4 arm = A.arm[r];
   if (arm.z == 0u) return;
   const u64 mask = A.group_cap - 1ull;
-  u64 at = key_hash((((u64)arm.x << 32) | arm.y) ^ key_hash(arm.z)) & mask;
+  const u64 ends = ((u64)arm.x << 32) | arm.y;
+  u64 at = key_hash(SPAN ? ends ^ key_hash(arm.z) : ends) & mask;
   for (u64 p = 0; p < A.group_cap; ++p, at = (at + 1ull) & mask) {  // (never more than group_cap probes; at most half the table fills)
     const u32 was = atomicCAS(&A.table[at], NIL, (u32)r);
     bool mine = was == NIL || was == (u32)r;
     if (!mine && (u64)was < A.n_reads) {
       const uint4 o = A.arm[was];
-      mine = o.x == arm.x && o.y == arm.y && o.z == arm.z;
+      mine = o.x == arm.x && o.y == arm.y && (!SPAN || o.z == arm.z);
     }
     if (mine) {
       A.gslot[r] = (u32)at;
@@ -1006,7 +964,7 @@ __global__ __launch_bounds__(256) void k_bub_losers(UnitigBubbleArgs A) {
   const u64 losers = __ballot(loser);
   if (!losers) return;
   if (no_bases) {
-    if (lane == 0u) atomicAdd(bub_slot(A, BUB_C_POPPED), (u64)__popcll(losers));
+    if (lane == 0u) atomicAdd(counter_slot(A.bub, BUB_C_POPPED), (u64)__popcll(losers));
     return;
   }
   u64 base = 0;
@@ -1065,7 +1023,7 @@ __global__ __launch_bounds__(256) void k_bub_compare(UnitigBubbleArgs A) {
     const u64 span = al.z < A.max_bubble_span ? al.z : A.max_bubble_span;
     u64 mism = 0;
     for (u64 t = lane; t < span; t += 64) mism += arm_base(A, h, al, sl, t, src_end) != arm_base(A, w, aw, sw, t, src_end);
-    mism = wave_total(mism);
+    mism = wave_sum(mism);
     if (mism * 1000ull <= (u64)A.max_divergence_permille * span) {
       if (lane == 0u) A.verdict[h] = 1u;
       ++popped;
@@ -1074,92 +1032,20 @@ __global__ __launch_bounds__(256) void k_bub_compare(UnitigBubbleArgs A) {
     }
   }
   if (lane == 0u) {
-    if (popped) atomicAdd(bub_slot(A, BUB_C_POPPED), popped);
-    if (kept) atomicAdd(bub_slot(A, BUB_C_KEPT), kept);
-  }
-}
-
-// One lane per read, as k_chim_mark: the verdict lies under its head.
-__global__ __launch_bounds__(256) void k_bub_mark(UnitigBubbleArgs A, const uint4* __restrict__ rk) {
-  if (idle_round<2>(A)) return;
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  const u64 n = A.n_reads;
-  u32 gone = 0;
-  if (r < n && A.removed[r] == 0u) {
-    const u32 h = head_of(A, rk, 2u * (u32)r);
-    if (h != NIL && A.verdict[h] != 0u) {
-      A.removed[r] = A.round | REMOVED_BUBBLE;
-      gone = 1;
-    }
-  }
-  const u64 tg = wave_total(gone);
-  if ((threadIdx.x & 63u) == 0u && tg) {
-    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
-    atomicAdd(bub_slot(A, BUB_C_READS), tg);
-    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
-    A.bub[BUB_ROUND0 + A.round] = 1ull;
+    if (popped) atomicAdd(counter_slot(A.bub, BUB_C_POPPED), popped);
+    if (kept) atomicAdd(counter_slot(A.bub, BUB_C_KEPT), kept);
   }
 }
 
 __global__ void k_bub_status(UnitigBubbleArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-  u64 rounds = 0;
-  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.bub[BUB_ROUND0 + r] != 0ull;
-  A.status[20] = bub_count(A, BUB_C_POPPED);
-  A.status[21] = bub_count(A, BUB_C_READS);
-  A.status[22] = rounds;
-  A.status[23] = bub_count(A, BUB_C_KEPT);
+  A.status[20] = counter_total(A.bub, BUB_C_POPPED);
+  A.status[21] = counter_total(A.bub, BUB_C_READS);
+  A.status[22] = rounds_ran(A.bub, BUB_ROUND0);
+  A.status[23] = counter_total(A.bub, BUB_C_KEPT);
 }
 
 // ---- indel bubble popping: one round's indel step, after the bubble step (the rules are sigax.h's own, as the bubble step's) ----
-__device__ __forceinline__ u64* ind_slot(const UnitigIndelArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  return A.ind + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 ind_count(const UnitigIndelArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.ind[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
-}
-
-// Before an indel step: what k_bub_clear empties, and no pair appended.
-__global__ __launch_bounds__(256) void k_ind_clear(UnitigIndelArgs A) {
-  if (idle_round<2>(A)) return;
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < 2 * A.n_reads) {
-    A.bnbr[i] = NIL;
-    A.blen[i] = 0u;
-  }
-  if (i < A.group_cap) {
-    A.table[i] = NIL;
-    A.best[i] = 0ull;
-  }
-  if (i == 0) A.ind[IND_APPENDED] = 0ull;
-}
-
-// One lane per read, as k_bub_group with the key (lo, hi) alone: arms of every span that takes part meet in one group.
-__global__ __launch_bounds__(256) void k_ind_group(UnitigIndelArgs A) {
-  if (idle_round<2>(A)) return;
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (r >= A.n_reads) return;
-  const uint4 arm = A.arm[r];
-  if (arm.z == 0u) return;
-  const u64 mask = A.group_cap - 1ull;
-  u64 at = key_hash(((u64)arm.x << 32) | arm.y) & mask;
-  for (u64 p = 0; p < A.group_cap; ++p, at = (at + 1ull) & mask) {  // (never more than group_cap probes; at most half the table fills)
-    const u32 was = atomicCAS(&A.table[at], NIL, (u32)r);
-    bool mine = was == NIL || was == (u32)r;
-    if (!mine && (u64)was < A.n_reads) {
-      const uint4 o = A.arm[was];
-      mine = o.x == arm.x && o.y == arm.y;
-    }
-    if (mine) {
-      A.gslot[r] = (u32)at;
-      atomicMax(&A.best[at], (unit_reads(A, (u32)r) << 32) | (u64)(~(u32)r));
-      return;
-    }
-  }
-}
 
 // One lane per read.  An arm that is not its group's maximum is a loser: of the winner's span (the bubble step's business) or more
 // than max_edits bases from it, it stays and is counted; otherwise it is appended to the list k_ind_compare walks.
@@ -1182,7 +1068,7 @@ __global__ __launch_bounds__(256) void k_ind_losers(UnitigIndelArgs A) {
     }
   }
   const u64 skipped = __ballot(loser && !compared), listed = __ballot(compared);
-  if (lane == 0u && skipped) atomicAdd(ind_slot(A, IND_C_SKIPPED), (u64)__popcll(skipped));
+  if (lane == 0u && skipped) atomicAdd(counter_slot(A.ind, IND_C_SKIPPED), (u64)__popcll(skipped));
   if (!listed) return;
   u64 base = 0;
   if (lane == 0u) base = atomicAdd(A.ind + IND_APPENDED, (u64)__popcll(listed));
@@ -1262,42 +1148,18 @@ __global__ __launch_bounds__(64) void k_ind_compare(UnitigIndelArgs A) {
     }
   }
   if (lane == 0u) {
-    if (popped) atomicAdd(ind_slot(A, IND_C_POPPED), popped);
-    if (kept) atomicAdd(ind_slot(A, IND_C_KEPT), kept);
-  }
-}
-
-// One lane per read, as k_bub_mark: the verdict lies under its head.
-__global__ __launch_bounds__(256) void k_ind_mark(UnitigIndelArgs A, const uint4* __restrict__ rk) {
-  if (idle_round<2>(A)) return;
-  const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-  const u64 n = A.n_reads;
-  u32 gone = 0;
-  if (r < n && A.removed[r] == 0u) {
-    const u32 h = head_of(A, rk, 2u * (u32)r);
-    if (h != NIL && A.verdict[h] != 0u) {
-      A.removed[r] = A.round | REMOVED_INDEL;
-      gone = 1;
-    }
-  }
-  const u64 tg = wave_total(gone);
-  if ((threadIdx.x & 63u) == 0u && tg) {
-    atomicAdd(trim_slot(A, TRIM_C_READS), tg);
-    atomicAdd(ind_slot(A, IND_C_READS), tg);
-    A.trim[TRIM_ROUND0 + A.round] = 1ull;  // (every wave that writes here writes the same)
-    A.ind[IND_ROUND0 + A.round] = 1ull;
+    if (popped) atomicAdd(counter_slot<1>(A.ind, IND_C_POPPED), popped);
+    if (kept) atomicAdd(counter_slot<1>(A.ind, IND_C_KEPT), kept);
   }
 }
 
 __global__ void k_ind_status(UnitigIndelArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u) return;
-  u64 rounds = 0;
-  for (u32 r = 1; r <= TRIM_MAX_ROUNDS; ++r) rounds += A.ind[IND_ROUND0 + r] != 0ull;
-  A.status[24] = ind_count(A, IND_C_POPPED);
-  A.status[25] = ind_count(A, IND_C_READS);
-  A.status[26] = rounds;
-  A.status[27] = ind_count(A, IND_C_KEPT);
-  A.status[28] = ind_count(A, IND_C_SKIPPED);
+  A.status[24] = counter_total(A.ind, IND_C_POPPED);
+  A.status[25] = counter_total(A.ind, IND_C_READS);
+  A.status[26] = rounds_ran(A.ind, IND_ROUND0);
+  A.status[27] = counter_total(A.ind, IND_C_KEPT);
+  A.status[28] = counter_total(A.ind, IND_C_SKIPPED);
   A.status[29] = A.status[30] = A.status[31] = 0ull;
 }
 
@@ -1306,15 +1168,6 @@ __global__ void k_ind_status(UnitigIndelArgs A) {
 // a pass after a round that changed nothing has nothing to do: the flags of the pass before still hold
 __device__ __forceinline__ bool red_idle(const UnitigReduceArgs& A) {
   return A.red_prev >= 1u && A.red_prev <= (u32)TRIM_MAX_ROUNDS && A.trim[TRIM_ROUND0 + A.red_prev] == 0ull;
-}
-__device__ __forceinline__ u64* red_slot(const UnitigReduceArgs& A, u32 c) {
-  const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-  return A.red + ((u64)c * TRIM_SLOTS + (wave & (TRIM_SLOTS - 1u))) * TRIM_STRIDE;
-}
-__device__ __forceinline__ u64 red_count(const UnitigReduceArgs& A, u32 c) {
-  u64 v = 0;
-  for (u32 s = 0; s < TRIM_SLOTS; ++s) v += A.red[((u64)c * TRIM_SLOTS + s) * TRIM_STRIDE];
-  return v;
 }
 // a participant of a pass: kept, both reads alive, not cut in an earlier round (k_red_clear has taken bit 31 off), neither a
 // containment nor a self edge -> its two read ends and its length
@@ -1426,20 +1279,20 @@ __global__ __launch_bounds__(256) void k_red_walk(UnitigReduceArgs A) {
       flagged = 1;
     }
   }
-  const u64 tp = wave_total(part), tf = wave_total(flagged);
+  const u64 tp = wave_sum(part), tf = wave_sum(flagged);
   if ((threadIdx.x & 63u) == 0u) {
-    if (tp) atomicAdd(red_slot(A, RED_C_PART), tp);
-    if (tf) atomicAdd(red_slot(A, RED_C_FLAGGED), tf);
+    if (tp) atomicAdd(counter_slot(A.red, RED_C_PART), tp);
+    if (tf) atomicAdd(counter_slot(A.red, RED_C_FLAGGED), tf);
   }
 }
 
 // After a pass that ran: its counts become the call's "latest", and the call's "first" if none ran before.
 __global__ void k_red_note(UnitigReduceArgs A) {
   if (threadIdx.x != 0u || blockIdx.x != 0u || red_idle(A)) return;
-  const u64 f = red_count(A, RED_C_FLAGGED);
+  const u64 f = counter_total(A.red, RED_C_FLAGGED);
   if (A.red[RED_PASSES] == 0ull) A.red[RED_FIRST] = f;
   A.red[RED_LAST] = f;
-  A.red[RED_LAST_PART] = red_count(A, RED_C_PART);
+  A.red[RED_LAST_PART] = counter_total(A.red, RED_C_PART);
   A.red[RED_PASSES] += 1ull;
 }
 
@@ -1451,8 +1304,6 @@ __global__ void k_red_status(UnitigReduceArgs A) {
   A.status[35] = A.red[RED_LAST_PART];
   A.status[36] = A.status[37] = A.status[38] = A.status[39] = 0ull;
 }
-
-unsigned blocks_of(u64 n) { return (unsigned)((n + 255) / 256); }
 
 // degrees, links, ranking, ring cut, ranking again -> which of the two ranking buffers holds the result
 template <int TRIM>
@@ -1486,18 +1337,40 @@ void launch_unitigs_t(const ArgsOf<TRIM>& a, hipStream_t st) {
   if (a.useqs) hipLaunchKernelGGL(k_uni_bases<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a);
 }
 
+// what every step of a round asks of its block: reads, removed[], and a round the flags have a word for
+bool step_ok(const UnitigTrimArgs& a) { return a.n_reads != 0 && a.removed && a.round != 0u && a.round <= TRIM_MAX_ROUNDS; }
+
+// how every step of a round begins: the graph of the live records and the heads of its unitigs -> the final rank buffer and the
+// distances that go with it
+struct StepGraph {
+  const uint4* rk;
+  const u64* dist;
+};
+template <int TRIM>
+StepGraph launch_step_graph(const ArgsOf<TRIM>& a, hipStream_t st) {
+  const unsigned f = launch_graph<TRIM>(a, st);
+  const StepGraph g = {reinterpret_cast<const uint4*>(a.rank[f]), a.dist[f]};
+  hipLaunchKernelGGL(k_uni_heads<TRIM>, dim3(blocks_of(a.n_reads)), dim3(256), 0, st, a, g.rk, g.dist);
+  return g;
+}
+
 // a round's trim step: TRIM = 1 over the trim block, TRIM = 2 over the records that are not cut (never with a.maxlen set: that is a cut step)
 template <int TRIM>
 void launch_trim_round_t(const ArgsOf<TRIM>& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  if (!step_ok(a)) return;
   if constexpr (TRIM == 2)
     if (a.maxlen) return;
-  const unsigned f = launch_graph<TRIM>(a, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<TRIM>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  const uint4* fin = launch_step_graph<TRIM>(a, st).rk;
   hipLaunchKernelGGL(k_trim_decide, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
-  hipLaunchKernelGGL(k_trim_mark, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+  hipLaunchKernelGGL(k_step_mark<TrimStep>, dim3(blocks_of(n)), dim3(256), 0, st, static_cast<const UnitigTrimArgs&>(a), fin);
+}
+
+// a step's status words, by its one-lane kernel
+template <class K, class ArgsT>
+void launch_status(K kernel, const ArgsT& a, hipStream_t st) {
+  if (a.n_reads == 0 || !a.removed) return;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, a);
 }
 
 // the lifted records and status[6 .. 11]; TRIM = 2: without the cut records, and status[12 .. 15]
@@ -1538,12 +1411,10 @@ void launch_unitig_lift(const UnitigTrimArgs& a, hipStream_t st) { launch_lift_t
 
 void launch_prune_cut_round(const UnitigPruneArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || !a.maxlen || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  if (!step_ok(a) || !a.maxlen) return;
   const u64 lanes = a.careful && a.key_cap > 2 * n ? a.key_cap : 2 * n;
   hipLaunchKernelGGL(k_prune_clear, dim3(blocks_of(lanes)), dim3(256), 0, st, a);
-  const unsigned f = launch_graph<2>(a, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+  const uint4* fin = launch_step_graph<2>(a, st).rk;
   hipLaunchKernelGGL(k_prune_unique, dim3(blocks_of(n)), dim3(256), 0, st, a);
   if (a.n_edges == 0) return;  // (unitigs are scored and counted all the same)
   if (a.careful) hipLaunchKernelGGL(k_prune_keys, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin);
@@ -1560,13 +1431,10 @@ void launch_unitig_prune_lift(const UnitigPruneArgs& a, hipStream_t st) { launch
 
 void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.maxlen || !a.nbr || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
+  if (!step_ok(a) || a.maxlen || !a.nbr) return;
   hipLaunchKernelGGL(k_chim_clear, dim3(blocks_of(2 * n)), dim3(256), 0, st, a);
-  const UnitigPruneArgs& pa = a;
-  const unsigned f = launch_graph<2>(pa, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
-  UnitigPruneArgs score = pa;  // the cut step's scoring kernel, under the chimeric threshold, counting aside
+  const uint4* fin = launch_step_graph<2>(a, st).rk;
+  UnitigPruneArgs score = a;  // the cut step's scoring kernel, under the chimeric threshold, counting aside
   score.uniq_threshold = a.chimeric_threshold;
   score.prune = a.prune_aside;
   hipLaunchKernelGGL(k_prune_unique, dim3(blocks_of(n)), dim3(256), 0, st, score);
@@ -1575,67 +1443,56 @@ void launch_chimeric_round(const UnitigChimericArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_chim_minima, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a, fin, 1);
   }
   hipLaunchKernelGGL(k_chim_decide, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
-  hipLaunchKernelGGL(k_chim_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_step_mark<ChimStep>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
 }
 
-void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed) return;
-  hipLaunchKernelGGL(k_chim_status, dim3(1), dim3(64), 0, st, a);
-}
+void launch_chimeric_status(const UnitigChimericArgs& a, hipStream_t st) { launch_status(k_chim_status, a, st); }
 
 void launch_bubble_round(const UnitigBubbleArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.maxlen || !a.bnbr || !a.where || a.max_bubble_span == 0u || a.round == 0u || a.round > TRIM_MAX_ROUNDS) return;
-  hipLaunchKernelGGL(k_bub_clear, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
-  const UnitigPruneArgs& pa = a;
-  const unsigned f = launch_graph<2>(pa, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
+  if (!step_ok(a) || a.maxlen || !a.bnbr || !a.where || a.max_bubble_span == 0u) return;
+  hipLaunchKernelGGL(k_arm_clear<BubStep>, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
+  const StepGraph g = launch_step_graph<2>(a, st);
+  const uint4* fin = g.rk;
   if (a.n_edges) hipLaunchKernelGGL(k_bub_ends, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, a);
   const bool bases_test = a.max_divergence_permille != BUBBLE_NO_BASES;
   if (bases_test) {  // where each unitig's placements begin (the scan has no idle form: after an idle round nothing reads its result)
     launch_scan(a.cnt + (n + 1), n, a.partial, a.scan + (n + 1), a.scan_total, st);
-    hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, (const u64*)a.dist[f]);
+    hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, a, fin, g.dist);
   }
   hipLaunchKernelGGL(k_bub_arms, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
-  hipLaunchKernelGGL(k_bub_group, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_arm_group<UnitigBubbleArgs, true>), dim3(blocks_of(n)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_bub_losers, dim3(blocks_of(n)), dim3(256), 0, st, a);
   if (bases_test) {
     const u32 waves = (u32)(n < BUB_COMPARE_WAVES ? n : BUB_COMPARE_WAVES);
     hipLaunchKernelGGL(k_bub_compare, dim3((waves + 3u) / 4u), dim3(256), 0, st, a);
   }
-  hipLaunchKernelGGL(k_bub_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_step_mark<BubStep>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
 }
 
-void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed) return;
-  hipLaunchKernelGGL(k_bub_status, dim3(1), dim3(64), 0, st, a);
-}
+void launch_bubble_status(const UnitigBubbleArgs& a, hipStream_t st) { launch_status(k_bub_status, a, st); }
 
 void launch_indel_round(const UnitigIndelArgs& a, hipStream_t st) {
   const u64 n = a.n_reads;
-  if (n == 0 || !a.removed || a.maxlen || !a.bnbr || !a.where || !a.pairs || !a.ind || a.max_bubble_span == 0u ||
-      a.max_bubble_span > (u32)IND_MAX_SPAN || a.max_edits == 0u || a.max_edits > (u32)IND_MAX_EDITS || a.round == 0u || a.round > TRIM_MAX_ROUNDS)
+  if (!step_ok(a) || a.maxlen || !a.bnbr || !a.where || !a.pairs || !a.ind || a.max_bubble_span == 0u || a.max_bubble_span > (u32)IND_MAX_SPAN ||
+      a.max_edits == 0u || a.max_edits > (u32)IND_MAX_EDITS)
     return;
-  hipLaunchKernelGGL(k_ind_clear, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
-  const UnitigPruneArgs& pa = a;
+  hipLaunchKernelGGL(k_arm_clear<IndStep>, dim3(blocks_of(a.group_cap > 2 * n ? a.group_cap : 2 * n)), dim3(256), 0, st, a);
   const UnitigBubbleArgs& ba = a;  // the bubble step's own kernels, over the block they know
-  const unsigned f = launch_graph<2>(pa, st);
-  const uint4* fin = reinterpret_cast<const uint4*>(a.rank[f]);
-  hipLaunchKernelGGL(k_uni_heads<2>, dim3(blocks_of(n)), dim3(256), 0, st, pa, fin, (const u64*)a.dist[f]);
+  const StepGraph g = launch_step_graph<2>(a, st);
+  const uint4* fin = g.rk;
   if (a.n_edges) hipLaunchKernelGGL(k_bub_ends, dim3(blocks_of(a.n_edges)), dim3(256), 0, st, ba);
   launch_scan(a.cnt + (n + 1), n, a.partial, a.scan + (n + 1), a.scan_total, st);  // (no idle form, as in the bubble step)
-  hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, ba, fin, (const u64*)a.dist[f]);
+  hipLaunchKernelGGL(k_bub_place, dim3(blocks_of(n)), dim3(256), 0, st, ba, fin, g.dist);
   hipLaunchKernelGGL(k_bub_arms, dim3(blocks_of(n)), dim3(256), 0, st, ba, fin);
-  hipLaunchKernelGGL(k_ind_group, dim3(blocks_of(n)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_arm_group<UnitigIndelArgs, false>), dim3(blocks_of(n)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_ind_losers, dim3(blocks_of(n)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_ind_compare, dim3((unsigned)(n < BUB_COMPARE_WAVES ? n : BUB_COMPARE_WAVES)), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(k_ind_mark, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
+  hipLaunchKernelGGL(k_step_mark<IndStep>, dim3(blocks_of(n)), dim3(256), 0, st, a, fin);
 }
 
 void launch_indel_status(const UnitigIndelArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed || !a.ind) return;
-  hipLaunchKernelGGL(k_ind_status, dim3(1), dim3(64), 0, st, a);
+  if (a.ind) launch_status(k_ind_status, a, st);
 }
 
 void launch_reduce_pass(const UnitigReduceArgs& a, hipStream_t st) {
@@ -1656,6 +1513,5 @@ void launch_reduce_pass(const UnitigReduceArgs& a, hipStream_t st) {
 }
 
 void launch_reduce_status(const UnitigReduceArgs& a, hipStream_t st) {
-  if (a.n_reads == 0 || !a.removed || !a.red) return;
-  hipLaunchKernelGGL(k_red_status, dim3(1), dim3(64), 0, st, a);
+  if (a.red) launch_status(k_red_status, a, st);
 }

@@ -673,6 +673,33 @@ def random_case(seed):
     return case
 
 
+# ---- many small bubbles at once: every counter the sum of slots that more than one wave added to ----
+@functools.lru_cache(maxsize=None)
+def many_bubbles(indels=44, plain=40, fillers=420):
+    """-> (case, expected_indel's dict of it): `indels` bubbles apart by one deleted base and `plain` apart by one substitution, each
+    between two chains of its own, and `fillers` chains of four short reads, every fourth with a tip: more than 2048 reads, so the
+    256-lane kernels run more than 32 waves, and more than 32 pairs compared in round 1, one workgroup of one wave each"""
+    g = tc._Grow(4100)
+    pairs = [(g.chain(2, lens=[60] * 2, ovs=[22]), g.chain(2, lens=[60] * 2, ovs=[22])) for _ in range(indels + plain)]
+    fill = [g.chain(4, lens=[50] * 4, ovs=[22] * 3) for _ in range(fillers)]
+    case = _case(g, "many_bubbles", x=10, L=45, Lb=40, D=50, Ed=2, De=1000)
+    case["N"] = None  # (the reads given: the call refuses a smaller number)
+    rng = random.Random(4101)
+    for k, (a, c) in enumerate(pairs):
+        p, q = cc._end(g, a[1], E), cc._end(g, c[0], B)
+        mid = bases(rng, 30)
+        plant_arm(case, rng, p, q, mid, flip=k % 3 == 1)
+        plant_arm(case, rng, p, q, delete(mid, k % 30) if k < indels else mutate(rng, mid, (k % 30,)), flip=k % 2 == 1)
+    for chain in fill[::4]:
+        cc.plant(case, rng, cc._end(g, chain[1], E), o1=22, mid=18)
+    exp = run(expected_indel, case)
+    assert len(case["reads"]) == 4 * (indels + plain) + 2 * (indels + plain) + 4 * fillers + (fillers + 3) // 4 > 2048
+    assert sum(1 for e in exp["indel_log"] if e["round"] == 1 and e["ed"] is not None) >= 40
+    st = exp["status"]
+    assert st[8] == (fillers + 3) // 4 and st[20] == plain and st[24] == indels, st  # tips, bubbles, indel bubbles: all taken
+    return case, exp
+
+
 # ---- end to end: reads that tile two haplotypes of a small genome, apart by substitutions and short indels ----
 E2E_SEED, E2E_GENOME, E2E_READS, E2E_LEN, E2E_M, E2E_EVERY = 37, 6000, 2400, 100, 40, 1000
 E2E_X, E2E_L, E2E_LB, E2E_D, E2E_ED, E2E_DE = 10, 150, 100, 1000, 4, 1000

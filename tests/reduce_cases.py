@@ -366,6 +366,37 @@ def _wide_end():
             "claims": {"hub_degree": 300}}
 
 
+@functools.lru_cache(maxsize=None)
+def every_step():
+    """-> (case, expected_reduce's dict of it): one graph of a few dozen reads in which, in one call, every step of the rounds takes
+    something -- a transitive triple, a fork whose shorter overlap the cut step takes, a tip, a bubble apart by a substitution, one
+    apart by a deleted base and a bridge between two chains.  That each step does is asserted here, on the restatement's own output."""
+    g = tc._Grow(77)
+    abc = g.chain(3, lens=[50] * 3, ovs=[35] * 2)
+    g._record(abc[0], abc[2], 20)  # A's last 20 bases begin C
+    f = g.start(60)  # the fork: 45 bases against 33 at one end
+    g.grow(f, 1, lens=[60], ovs=[45])
+    g.grow(f, 1, lens=[60], ovs=[33])
+    chains = [g.chain(4, lens=[60] * 4, ovs=[22] * 3) for _ in range(7)]
+    case = ic._case(g, "every_step", x=10, L=45, Lb=40, D=50, Lc=60, Ed=2, De=1000)
+    case.update(delta=10, G=1000, reduce=True)
+    rng = random.Random(78)
+    end = lambda r, e: cc._end(g, r, e)  # noqa: E731
+    cc.plant(case, rng, end(chains[0][1], E), o1=22, mid=18)  # a tip of 40 bases
+    mid = ic.bases(rng, 30)
+    for edit, (a, c) in ((ic.mutate(rng, mid, (4,)), chains[1:3]), (ic.delete(mid, 7), chains[3:5])):
+        ic.plant_arm(case, rng, end(a[3], E), end(c[0], B), mid)
+        ic.plant_arm(case, rng, end(a[3], E), end(c[0], B), edit, flip=True)
+    cc.plant(case, rng, end(chains[5][1], E), end(chains[6][2], B), o1=25, o2=25, mid=10)  # a bridge of 60 bases
+    exp = run(expected_reduce, case)
+    marks = [x & ~ROUND_BITS for x in exp["removed"] if x]
+    assert all(marks.count(bit) >= 1 for bit in (0, ic.CHIMERIC, ic.BUBBLE, ic.INDEL)), marks
+    assert any(x & ~TRANSITIVE for x in exp["cut"]) and any(x & TRANSITIVE for x in exp["cut"]) and exp["first_flags"]
+    st = exp["status"]
+    assert st[8] >= 1 and st[12] >= 1 and st[16] >= 1 and st[20] >= 1 and st[24] >= 1 and st[33] >= 1, st
+    return case, exp
+
+
 def random_case(seed, want=None):
     """reads of 40 to 60 bases at random places of a random genome, either strand, and every overlap of 20 or more between them that is
     no containment; want: exactly that many records (the first `want` of a shuffle; every one of them is a participant)"""

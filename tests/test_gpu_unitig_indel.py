@@ -157,6 +157,15 @@ def test_second_round_round_by_round(rounds):
     _untouched(tails, "second_round")
 
 
+def test_counter_slots_wrap_with_both_block_shapes():
+    """indel_cases.many_bubbles (44 indel bubbles, 40 plain ones and 105 tips among 2289 reads, asserted there): the compare kernel runs more than 32 one-wave workgroups and the
+    256-lane kernels more than 32 waves, so every counter is the sum of slots that were added to more than once"""
+    case, exp = ic.many_bubbles()
+    res, tails = _device_call(case)
+    _same(res, exp, "many_bubbles")
+    _untouched(tails, "many_bubbles")
+
+
 def test_random_graphs():
     seen = {}
     for seed in range(0, 300, 3):

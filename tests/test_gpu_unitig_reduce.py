@@ -131,6 +131,15 @@ def test_revive_round_by_round(rounds):
     _untouched(tails, "revive")
 
 
+def test_every_step_removes_something_in_one_call():
+    """reduce, cut, trim, bubble, indel and chimeric all on, and each with something to take (reduce_cases.every_step asserts that on
+    the restatement): a mark or a counter wired to another step's block shows in removed[]'s flag bits or in a status word"""
+    case, exp = rc.every_step()
+    res, tails = _device_call(case)
+    _same(res, exp, "every_step")
+    _untouched(tails, "every_step")
+
+
 def test_revive_through_the_indel_call_without_the_record_stays_broken():
     import siga_amd
     case, irr = rc.case_named("revive"), rc.case_named("revive_irreducible")

@@ -11,8 +11,9 @@ same reads.  Two GPU steps, each a child process under a `timeout` of its own; t
               cut, bubble or chimeric removal to do that is its trim step plus one idle-free chimeric step), and with reduce = 1 at 10
             and, on the host, the records the pass left unflagged against the irreducible run's, as unordered (read end, read end,
             overlap) keys, with the containment records and the reads that occur twice (either strand) counted
-            with --ab-lib (the parent commit's library): sigax_unitigs_device and the trim, prune, chimeric, bubble and indel device calls
-            (10 rounds) over the irreducible records through that library and through this one, five runs each, alternating
+            with --ab-lib (the parent commit's library): sigax_unitigs_device and the trim, prune, chimeric, bubble, indel and reduce
+            device calls (10 rounds) over the irreducible records through that library and through this one, three runs each, in the
+            order parent, this, this, parent, parent, this; a call passes when this_over_parent <= 1 + the spread of the parent's medians
 One JSON document on stdout (and in --out; the A/B in --ab-out).  Needs a GPU; nothing but this repository.
 
     python tools/reduce_bench.py --out profiles/reduce_configs1.json
@@ -84,7 +85,7 @@ def step_measure(args):
         return spread(ms)
 
     OLD = ("sigax_unitigs_device", "sigax_unitigs_trim_device", "sigax_unitigs_prune_device", "sigax_unitigs_chimeric_device",
-           "sigax_unitigs_bubble_device", "sigax_unitigs_indel_device")
+           "sigax_unitigs_bubble_device", "sigax_unitigs_indel_device", "sigax_unitigs_reduce_device")
     P = None
     if args.ab_lib:
         P = C.CDLL(args.ab_lib)
@@ -192,12 +193,12 @@ def step_measure(args):
             "equal": bool(len(only_left) == 0 and len(only_irr) == 0)}
         if P:
             topts = _lib.TrimOpts(10, args.min_branch_length, _lib.SIGAX_TRIM_NO_COVERAGE, 0)
-            iopts = opts(10, 0, lb=150, edits=4, delta=10).indel
+            ropts = opts(10, 1, lb=150, edits=4, delta=10)
+            iopts = ropts.indel
             bopts = iopts.bubble
             copts, popts = bopts.chimeric, bopts.chimeric.prune
             runs = []
-            for order in range(10):
-                tree = "parent" if order % 2 == 0 else "this"
+            for order, tree in enumerate(("parent", "this", "this", "parent", "parent", "this")):
                 X = P if tree == "parent" else L
                 run = {"order": order + 1, "tree": tree}
                 run["unitigs_device"] = timed(lambda: X.sigax_unitigs_device(0, d_irr, ne_irr, d_len, d_seqs, d_offs, n, args.min_overlap, d_so, d_lo,
@@ -209,16 +210,21 @@ def step_measure(args):
                                     ("bubble", X.sigax_unitigs_bubble_device, bopts), ("indel", X.sigax_unitigs_indel_device, iopts)):
                     run[name + "_device_10_rounds"] = timed(lambda: fn(0, d_irr, ne_irr, d_len, d_seqs, d_offs, n, args.min_overlap, C.byref(o), d_so,
                                                                        d_lo, d_uf, d_lay, d_us, d_rm, d_ct, None, d_stat, d_work, wr.value, stream))
+                run["reduce_device_10_rounds"] = timed(lambda: X.sigax_unitigs_reduce_device(0, d_irr, ne_irr, d_len, d_seqs, d_offs, n, args.min_overlap,
+                                                                                             C.byref(ropts), d_so, d_lo, d_uf, d_lay, d_us, d_rm, d_ct,
+                                                                                             None, d_stat, d_work, wr.value, stream))
                 runs.append(run)
             summary = {}
             for call in [k for k in runs[0] if k not in ("order", "tree")]:
                 med = {tree: [r[call]["median_ms"] for r in runs if r["tree"] == tree] for tree in ("parent", "this")}
                 rng = {tree: [min(v), max(v)] for tree, v in med.items()}
-                summary[call] = {"range_of_medians_ms": rng, "this_over_parent_of_means": float(np.mean(med["this"]) / np.mean(med["parent"])),
-                                 "ranges_overlap": bool(rng["this"][0] <= rng["parent"][1] and rng["parent"][0] <= rng["this"][1])}
-            out["old_entry_ab"] = {"what": "the six older device entry points over the irreducible records through the parent commit's library and "
+                ratio = float(np.mean(med["this"]) / np.mean(med["parent"]))
+                margin = float((rng["parent"][1] - rng["parent"][0]) / np.mean(med["parent"]))
+                summary[call] = {"range_of_medians_ms": rng, "this_over_parent": ratio, "margin": margin, "passes": bool(ratio <= 1.0 + margin)}
+            out["old_entry_ab"] = {"what": "the seven device entry points over the irreducible records through the parent commit's library and "
                                            "through this tree's, over the same device buffers in one process, HIP events, median of %d calls after "
-                                           "%d, five runs each, alternating; the margin is the parent's own range of medians"
+                                           "%d, three runs each in the order parent, this, this, parent, parent, this; this_over_parent is the ratio "
+                                           "of the means of the medians, the margin the spread of the parent's own medians, (max - min) / mean"
                                            % (args.steps, args.warmup), "config": out["config"], "runs": runs, "summary": summary}
     finally:
         for q in held:

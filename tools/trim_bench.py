@@ -162,7 +162,7 @@ def step_measure(args, trace=False):
 def analyse(path):
     """a rocprofv3 kernel trace (CSV) of `--step trace` -> per kernel the microseconds of the second call without rounds, and of
     the second call with one round split into the round and the pass that writes the result; k_trim_status ends every call,
-    k_trim_mark the round"""
+    k_step_mark the round"""
     import csv
     with open(path) as f:
         rows = list(csv.DictReader(f))
@@ -183,7 +183,7 @@ def analyse(path):
                 "launches": hi - lo, "kernels": by}
 
     # (a call's first kernel follows the k_trim_status of the call before it)
-    mark = max(i for i in range(ends[2], ends[3]) if "k_trim_mark" in rows[i][kn])
+    mark = max(i for i in range(ends[2], ends[3]) if "k_step_mark" in rows[i][kn])
     return {"no_rounds": part(ends[0] + 1, ends[1] + 1), "round_1": part(ends[2] + 1, mark + 1), "result_pass_after_round_1": part(mark + 1, ends[3] + 1)}
 
 
