@@ -321,6 +321,80 @@ int  sigax_locate_batch(sigax_index*, const char* seqs, const uint64_t* offs, ui
                         uint32_t max_hits, uint32_t max_len, uint64_t** totals, uint32_t** qflags, uint64_t** hit_offs,
                         sigax_hit** hits);
 
+/* ---- `siga correct -a overlap`: pile-up correction of reads (csrc/sigax_pileup.hip) -------------------------------------------
+ * A read is lined up, without gaps, against the indexed reads that share a seed with it, and every column is put to the vote.
+ * The reference declares the algorithm and leaves it empty (OverlapCorrector::process, src/correct_processor.cpp:231-240); the
+ * rules are these.  Integer arithmetic throughout; no result depends on the order of hits, candidates or reads.
+ *
+ * Parameters (sigax_pile_params; CLI spelling and default in brackets), anything outside the range is SIGAX_E_ARG with the
+ * field named in sigax_last_error():
+ *   S seed_length 12..64 (--seed-length 24)    T seed_stride 1..S (--seed-stride 12)      H max_seed_hits 1..4096 (--max-seed-hits 256)
+ *   M min_overlap >= 1 (-m 45)                 P error_permille 0..250 (-e 40)            C conflict >= 1 (--conflict 5)
+ *   D min_depth >= 1 (--min-depth 2)           K max_candidates 1..4096 (--max-candidates 512)
+ *   max_read_len 1..SIGAX_PILE_MAX_LEN, 0 = SIGAX_PILE_MAX_LEN: the columns a wave's LDS is sized for (the host form sets it
+ *   from the batch's longest read); a longer read is "too long" below.
+ *
+ * The reference set is the reads of the index by read id, ref[t], ACGT only (locate's condition), each shorter than 2^30
+ * bases.  The query q is a read of n bytes.
+ *  1. n < S: unchanged, valid = 0.  n > max_read_len: unchanged, valid = 2 (as sigax_correct_device for reads it cannot take).
+ *  2. Seeds: the windows q[p, p+S) for p = 0, T, 2T, ... while p + S <= n, and p = n - S if it is not among them.  A seed with a
+ *     byte outside ACGT is skipped; every other seed is located on both strands (sigax_locate_device with SIGAX_RC); one whose
+ *     total exceeds H is skipped as a repeat.
+ *  3. Candidates: a forward hit (t, o) of the seed at p gives (t, +, d = o - p); a reverse hit (t, o) gives (t, -, d = len(t) -
+ *     o - S - p), read against revcomp(ref[t]).  The candidates are the DISTINCT triples (t, strand, d): one triple found through
+ *     several seeds counts once, one read at two diagonals twice.  The query gets no vote of its own; if it is in the index it
+ *     is a candidate like any read.  More than K distinct triples: unchanged, valid = 0, counted in status[2].
+ *  4. Acceptance: column x of q faces position x + d of the candidate's text; the overlap is the x for which both exist, l its
+ *     length, m its mismatches (a query byte outside ACGT is one).  Accepted iff l >= M and m <= floor(l * P / 1000).
+ *  5. Votes: cnt[x][A,C,G,T] over the accepted candidates that cover x.
+ *  6. Change: b = q[x], cnt[x][b] = 0 for a byte outside ACGT, c = the base of the unique largest count at x.  q'[x] = c iff
+ *     c != b and cnt[x][c] >= C and cnt[x][b] < C; a tie for the largest count changes nothing.  All columns from the same pile.
+ *  7. Validity: valid = 1 iff cnt[x][q'[x]] >= D for every x.  The output is q' for a valid read, q otherwise; changed = 1 iff
+ *     the output differs from q.
+ *  8. Rounds (host form): a further round runs 2-7 on the output; only reads that changed in the round before take part; the
+ *     loop ends when none did or after `rounds`.  The pile always comes from the index as it is.  valid comes from the last
+ *     round a read took part in, changed says whether any round changed it.
+ *
+ * Reference text.  sigax_reference_text_device builds ref[] on the device from the index alone, one BYTE per base (ASCII, read
+ * t at d_text[d_text_offs[t] .. d_text_offs[t+1])): rows 0 .. n_strings - 1 through the row walk of sigax_string_lengths_device
+ * / sigax_get_strings_device, filed under the read id sai[stretch].  Needs what locate needs (forward .sai, ACGT only),
+ * SIGAX_E_STATE otherwise.  *text_bytes of the workspace call = n_symbols - n_strings, exactly the bases; d_text_offs
+ * u64[n_strings + 1]; d_status4, written: {reads, bases, rows that gave no read (walk cut at 2^30 - 1 bases, stretch without a
+ * read id), slots of the wrong size}; the last two are 0 on an index that is in order.  Asynchronous, allocates nothing.
+ *
+ * sigax_pileup_device: one round, every buffer in device memory, asynchronous on `stream`, allocates nothing.  d_offs
+ * u64[n_reads + 1] (n_reads < 2^31), n_bases >= d_offs[n_reads] - d_offs[0] (it sizes the seed table), d_out_seqs in the layout
+ * of d_seqs and not overlapping it, d_valid and d_changed u8[n_reads], d_work = sigax_pileup_workspace(n_reads, n_bases,
+ * params, hits_cap) bytes, 16-byte aligned; the seeds' hits live in it.  Seeds go through sigax_locate_device.  d_status8,
+ * written (not added to): {hits listed, reads too long, reads over K, seeds located, seeds skipped as repeats, candidates tested,
+ * candidates accepted, bases changed}.  When the hits listed exceed hits_cap, no read, no valid[] and no changed[] is written,
+ * status[0] carries the number and status[1..7] are 0: the caller sizes its workspace from it and calls again.
+ *
+ * sigax_pile_ref: the reference text of an index, built once (synchronous) and kept on the device until it is destroyed.
+ * sigax_pileup_batch: host buffers, synchronous; loops the rounds (rule 8), sizes hits_cap itself and splits a batch that does
+ * not fit the device's free memory.  out_seqs has the layout of seqs (offs[0] need not be 0), valid and changed u8[n_reads],
+ * status8 (may be NULL) = the rounds' status words added up, *rounds_run (may be NULL) = the rounds that ran. */
+#define SIGAX_PILE_MAX_LEN 4096u
+typedef struct sigax_pile_params {
+  uint32_t seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, conflict, min_depth, max_candidates;
+  uint32_t max_read_len, reserved;  /* reserved = 0 */
+} sigax_pile_params;
+int  sigax_reference_text_workspace(sigax_index*, uint64_t* text_bytes, uint64_t* work_bytes);  /* host arithmetic only */
+int  sigax_reference_text_device(sigax_index*, void* d_text, uint64_t text_bytes, void* d_text_offs, void* d_status4, void* d_work,
+                                 uint64_t work_bytes, void* stream);
+int  sigax_pileup_workspace(uint64_t n_reads, uint64_t n_bases, const sigax_pile_params*, uint64_t hits_cap, uint64_t* bytes);
+int  sigax_pileup_device(sigax_index*, const void* d_seqs, const void* d_offs, uint64_t n_reads, uint64_t n_bases,
+                         const sigax_pile_params*, const void* d_ref_text, const void* d_ref_offs, void* d_out_seqs, void* d_valid,
+                         void* d_changed, void* d_status8, void* d_work, uint64_t work_bytes, uint64_t hits_cap, void* stream);
+typedef struct sigax_pile_ref sigax_pile_ref;
+int  sigax_pile_ref_create(sigax_index*, sigax_pile_ref** out);
+void sigax_pile_ref_destroy(sigax_pile_ref*);
+/* the device buffers of the text (for sigax_pileup_device) and its bytes; any of the three may be NULL */
+int  sigax_pile_ref_buffers(const sigax_pile_ref*, const void** d_text, const void** d_text_offs, uint64_t* text_bytes);
+int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, const uint64_t* offs, uint64_t n_reads,
+                        const sigax_pile_params*, uint32_t rounds, char* out_seqs, uint8_t* valid, uint8_t* changed,
+                        uint64_t status8[8], uint32_t* rounds_run);
+
 /* ---- `siga unitig`: unbranched chains of overlaps compacted (csrc/sigax_unitig.hip) ----------------------------------------------
  * The fixpoint of Bigraph::simplify (src/bigraph.cpp:341-414, Vertex::merge at :131-202) over the edge records of an overlap
  * run, without an index: every chain of reads joined by SIMPLE records becomes one unitig.

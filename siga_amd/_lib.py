@@ -149,6 +149,17 @@ class IndexInfo(C.Structure):
                 ("pred", C.c_uint64 * 5), ("device", C.c_int), ("wide", C.c_int)]
 
 
+class PileParams(C.Structure):
+    """sigax_pile_params (`siga correct -a overlap`); the defaults are the CLI's"""
+    _fields_ = [(n, C.c_uint32) for n in ("seed_length", "seed_stride", "max_seed_hits", "min_overlap", "error_permille", "conflict",
+                                          "min_depth", "max_candidates", "max_read_len", "reserved")]
+
+    def __init__(self, seed_length=24, seed_stride=12, max_seed_hits=256, min_overlap=45, error_permille=40, conflict=5, min_depth=2,
+                 max_candidates=512, max_read_len=0):
+        super().__init__(seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, conflict, min_depth, max_candidates,
+                         max_read_len, 0)
+
+
 class RunInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_sub", "find_per_sub", "two_step", "coop", "read_order", "cap", "worst_cap", "row_bits",
                                           "row_syms", "row_text", "row_direct", "deep_k")] + \
@@ -172,6 +183,8 @@ SYMBOLS = [
     "sigax_string_lengths_device", "sigax_get_strings_device", "sigax_get_strings", "sigax_kmer_spectrum_workspace",
     "sigax_kmer_spectrum_device", "sigax_kmer_spectrum_batch", "sigax_kmer_spectrum_rows", "sigax_kmer_spectrum_rows_hint",
     "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
+    "sigax_reference_text_workspace", "sigax_reference_text_device", "sigax_pileup_workspace", "sigax_pileup_device",
+    "sigax_pile_ref_create", "sigax_pile_ref_destroy", "sigax_pile_ref_buffers", "sigax_pileup_batch",
     "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
@@ -271,6 +284,18 @@ def lib():
     L.sigax_locate_workspace.argtypes = [u64, C.POINTER(u64)]
     L.sigax_locate_device.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp]
     L.sigax_locate_batch.argtypes = [vp, cp, vp, u64, u32, u32, u32, pvp, pvp, pvp, pvp]
+    pp = C.POINTER(PileParams)
+    L.sigax_reference_text_workspace.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.sigax_reference_text_device.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp]
+    L.sigax_pileup_workspace.argtypes = [u64, u64, pp, u64, C.POINTER(u64)]
+    L.sigax_pileup_device.argtypes = [vp, vp, vp, u64, u64, pp, vp, vp, vp, vp, vp, vp, vp, u64, u64, vp]
+    # (not in include/sigax.h: the measurement aid of tools/pileup_bench.py, sigax_pileup.h)
+    L.sigax_pileup_pile_device.argtypes = L.sigax_pileup_device.argtypes
+    L.sigax_pile_ref_create.argtypes = [vp, pvp]
+    L.sigax_pile_ref_destroy.argtypes = [vp]
+    L.sigax_pile_ref_destroy.restype = None
+    L.sigax_pile_ref_buffers.argtypes = [vp, pvp, pvp, C.POINTER(u64)]
+    L.sigax_pileup_batch.argtypes = [vp, vp, cp, vp, u64, pp, u32, vp, vp, vp, vp, C.POINTER(u32)]
     L.sigax_unitigs_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_unitigs_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(u64), pvp, pvp, pvp, pvp, pvp]

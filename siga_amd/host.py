@@ -33,6 +33,8 @@ def lib():
         L.sigah_write_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64]
         L.sigah_correct_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                          C.c_int, C.c_char_p, C.c_uint64]
+        L.sigah_correct_overlap_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                                 C.c_char_p, C.c_uint64]
         L.sigah_format_asqg.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int]
         L.sigah_format_asqg.restype = C.c_int64
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
@@ -124,11 +126,24 @@ def rmdup_file(reads_path, prefix, output, duplicates, device=0):
         raise RuntimeError("siga rmdup failed: " + err.value.decode())
 
 
-def correct_file(reads_path, prefix, output, k=31, threshold=3, rounds=10, offset=1, device=0):
-    """FMIndex::load + CorrectProcessor::process (k-mer algorithm) in the host C++ library (GPU compute)."""
+def correct_file(reads_path, prefix, output, k=31, threshold=3, rounds=None, offset=1, device=0, algorithm="kmer", **pile):
+    """FMIndex::load + CorrectProcessor::process in the host C++ library (GPU compute).  algorithm "kmer": the k-mer
+    corrector with k, threshold, rounds (default 10) and offset.  algorithm "overlap": the pile-up of include/sigax.h with
+    rounds (default 1) and the fields of sigax_pile_params as keywords (seed_length=..., min_overlap=..., ...); needs
+    <prefix>.sai; -> the eight status words added up over the batches."""
     err = C.create_string_buffer(512)
-    if lib().sigah_correct_file(reads_path.encode(), prefix.encode(), output.encode(), k, threshold, rounds, offset, device,
-                                err, 512) != 0:
+    if algorithm == "overlap":
+        from . import _lib as core
+        params = core.PileParams(**pile)
+        status = np.zeros(8, dtype=np.uint64)
+        if lib().sigah_correct_overlap_file(reads_path.encode(), prefix.encode(), output.encode(), C.addressof(params),
+                                            1 if rounds is None else int(rounds), device, status.ctypes.data, err, 512) != 0:
+            raise RuntimeError("siga correct failed: " + err.value.decode())
+        return status
+    if algorithm != "kmer" or pile:
+        raise ValueError("algorithm %r with %r" % (algorithm, sorted(pile)))
+    if lib().sigah_correct_file(reads_path.encode(), prefix.encode(), output.encode(), k, threshold, 10 if rounds is None else rounds,
+                                offset, device, err, 512) != 0:
         raise RuntimeError("siga correct failed: " + err.value.decode())
 
 

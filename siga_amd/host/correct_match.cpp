@@ -17,6 +17,19 @@ bool CorrectProcessor::process(const FMIndex& index, const std::string& input, c
     _error = "FMIndex not loaded";
     return false;
   }
+  // -a overlap: the reference text once, before any file is touched, then the k-mer path's batches through the pile-up
+  sigax_pile_ref* ref = nullptr;
+  struct RefGuard {
+    sigax_pile_ref** r;
+    ~RefGuard() { sigax_pile_ref_destroy(*r); }
+  } ref_guard{&ref};
+  for (int k = 0; k < 8; ++k) _pileStatus[k] = 0;
+  _readsIn = 0;
+  _readsOut = 0;
+  if (_options.overlap && sigax_pile_ref_create(index.handle(), &ref) != SIGAX_OK) {
+    _error = std::string("correct failed: ") + sigax_last_error();
+    return false;
+  }
   DNASeqList reads;
   if (!ReadDNASequences(input, reads)) {
     _error = "Failed to create DNASeqReader " + input;
@@ -28,9 +41,10 @@ bool CorrectProcessor::process(const FMIndex& index, const std::string& input, c
     return false;
   }
   const size_t n = reads.size(), per = 262144;
+  _readsIn = n;
   std::string seqs, quals, corrected, text;
   std::vector<uint64_t> offs;
-  std::vector<uint8_t> valid;
+  std::vector<uint8_t> valid, changed;
   for (size_t base = 0; base < n; base += per) {
     size_t cnt = std::min(per, n - base);
     seqs.clear();
@@ -49,7 +63,16 @@ bool CorrectProcessor::process(const FMIndex& index, const std::string& input, c
     }
     corrected.assign(seqs.size(), '\0');
     valid.assign(cnt, 0);
-    if (sigax_correct_batch(index.handle(), seqs.data(), anyQual ? quals.data() : nullptr, offs.data(), (uint32_t)cnt,
+    if (_options.overlap) {
+      changed.assign(cnt, 0);
+      uint64_t st[8];
+      if (sigax_pileup_batch(index.handle(), ref, seqs.data(), offs.data(), cnt, &_options.pile, (uint32_t)_options.rounds, &corrected[0],
+                             valid.data(), changed.data(), st, nullptr) != SIGAX_OK) {
+        _error = std::string("correct failed: ") + sigax_last_error();
+        return false;
+      }
+      for (int k = 0; k < 8; ++k) _pileStatus[k] += st[k];
+    } else if (sigax_correct_batch(index.handle(), seqs.data(), anyQual ? quals.data() : nullptr, offs.data(), (uint32_t)cnt,
                             (uint32_t)_options.kmerSize, (int32_t)_options.kmerThreshold, (uint32_t)_options.kmerRounds,
                             (uint32_t)_options.kmerCountOffset, &corrected[0], valid.data()) != SIGAX_OK) {
       _error = std::string("correct failed: ") + sigax_last_error();
@@ -58,6 +81,7 @@ bool CorrectProcessor::process(const FMIndex& index, const std::string& input, c
     text.clear();
     for (size_t i = 0; i < cnt; ++i) {  // PostCorrector (src/correct_processor.cpp:247-253) + DNASeq << (src/kseq.cpp:106-126)
       if (valid[i] != 1) continue;
+      ++_readsOut;
       const DNASeq& rd = reads[base + i];
       text += rd.quality.empty() ? '>' : '@';
       text += rd.name;

@@ -203,6 +203,29 @@ int sigah_correct_file(const char* reads_path, const char* prefix, const char* o
   return 0;
 }
 
+// `siga correct -a overlap`: FMIndex::loadForwardSai + CorrectProcessor::process with the pile-up; status8 (may be NULL) receives
+// the status words of sigax_pileup_batch added up over the batches
+int sigah_correct_overlap_file(const char* reads_path, const char* prefix, const char* output, const sigax_pile_params* params,
+                               uint64_t rounds, int device, uint64_t* status8, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {
+    if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
+    return -1;
+  }
+  sigah::CorrectProcessor::Options o;
+  o.overlap = true;
+  if (params) o.pile = *params;
+  o.rounds = rounds;
+  sigah::CorrectProcessor proc(o);
+  if (!proc.process(fmi, reads_path, output)) {
+    if (err && errcap) snprintf(err, errcap, "%s", proc.error().c_str());
+    return -1;
+  }
+  if (status8)
+    for (int k = 0; k < 8; ++k) status8[k] = proc.pileStatus()[k];
+  return 0;
+}
+
 // `siga match`: FMIndex::load(prefix.bwt) + Matcher::run over n_paths inputs; out_path "" = stdout; max_length ~0 = no limit;
 // batch_reads 0 = device batches sized from the free memory
 int sigah_match_files(const char* const* paths, uint64_t n_paths, const char* prefix, uint64_t max_length, int rc, int device,

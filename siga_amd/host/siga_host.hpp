@@ -125,20 +125,34 @@ class OverlapBuilder {
   bool _keep_reads = false;
 };
 
-// src/correct_processor.h:25-42 (k-mer algorithm only; the reference's "overlap" algorithm is an empty stub)
+// src/correct_processor.h:25-42.  The k-mer algorithm is the reference's; its "overlap" algorithm is an empty stub there and the
+// pile-up of include/sigax.h here (`siga correct -a overlap`).
 class CorrectProcessor {
  public:
   struct Options {
     size_t kmerSize, kmerThreshold, kmerRounds, kmerCountOffset;  // -k -x -i -O, defaults src/correct_processor.h:15-20
-    Options() : kmerSize(31), kmerThreshold(3), kmerRounds(10), kmerCountOffset(1) {}
+    bool overlap;               // -a overlap: the fields below, and `rounds` for -i
+    sigax_pile_params pile;     // --seed-length --seed-stride --max-seed-hits -m -e --conflict --min-depth --max-candidates
+    size_t rounds;
+    Options() : kmerSize(31), kmerThreshold(3), kmerRounds(10), kmerCountOffset(1), overlap(false), rounds(1) {
+      pile.seed_length = 24; pile.seed_stride = 12; pile.max_seed_hits = 256; pile.min_overlap = 45; pile.error_permille = 40;
+      pile.conflict = 5; pile.min_depth = 2; pile.max_candidates = 512; pile.max_read_len = 0; pile.reserved = 0;
+    }
   };
   explicit CorrectProcessor(const Options& options) : _options(options) {}
-  // reads that became all-solid are written to `output` in the input's format (FASTA/FASTQ), the rest are dropped
+  // k-mer: reads that became all-solid are written to `output` in the input's format (FASTA/FASTQ), the rest are dropped.
+  // overlap: the valid reads (rule 7) are written, qualities unchanged; the index needs its .sai table (FMIndex::loadForwardSai)
   bool process(const FMIndex& index, const std::string& input, const std::string& output, size_t threads = 1,
                size_t* processed = nullptr) const;
   const std::string& error() const { return _error; }
+  // overlap: the status words of sigax_pileup_batch added up over the batches, and the reads read and written
+  const uint64_t* pileStatus() const { return _pileStatus; }
+  uint64_t readsIn() const { return _readsIn; }
+  uint64_t readsOut() const { return _readsOut; }
 
  private:
+  mutable uint64_t _pileStatus[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  mutable uint64_t _readsIn = 0, _readsOut = 0;
   Options _options;
   mutable std::string _error;
 };

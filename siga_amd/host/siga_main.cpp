@@ -81,7 +81,7 @@ static int usage() {
          "  index     build the FM-index (.sai/.bwt/.rsai/.rbwt) of READSFILE\n"
          "  overlap   compute pairwise overlaps between all the sequences in READSFILE (GPU)\n"
          "  rmdup     remove duplicated reads (GPU)\n"
-         "  correct   k-mer based error correction (GPU)\n"
+         "  correct   k-mer or overlap based error correction (GPU)\n"
          "  match     count the occurrences of every read of READSFILE in the indexed reads (GPU)\n"
          "  locate    list where every sequence of QUERYFILE occurs in the indexed reads: read, offset, strand (GPU)\n"
          "  unitig    overlap READSFILE and compact every unbranched chain of overlaps into one sequence (GPU)\n"
@@ -314,47 +314,80 @@ static int correct_help() {
          "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
          "      -o, --outfile=FILE               write the corrected reads to FILE (default READFILE.ec.fa)\n"
          "      -t, --threads=NUM                use NUM threads for the computation (default: 1)\n"
-         "      -a, --algorithm=STR              specify the correction algorithm to use. Only kmer is built. (default: kmer)\n"
+         "      -a, --algorithm=STR              specify the correction algorithm to use. STR is one of kmer, overlap. (default: kmer)\n"
          "\n"
          "      -k, --kmer-size=N                the length of the kmer to user (default: 31)\n"
          "      -x, --kmer-threshold=N           attempt to correct kmers that are seen less than N times (default: 3)\n"
          "      -i, --kmer-rounds=N              perform up to N rounds of kmer correction (default: 10)\n"
          "      -O, --kmer-count-offset=N        when correcting a kmer, require the count of the new kmer is at least +N higher than the count of the old kmer. (default: 1)\n"
          "          --device=NUM                 GPU to use (default: 0)\n"
+         "\n"
+         "Overlap correction parameters (-a overlap; needs PREFIX.sai and reads of ACGT only in the index; -k, -x and -O do not apply):\n"
+         "      -i, --rounds=N                   perform up to N rounds of pile-up correction (default: 1)\n"
+         "      -m, --min-overlap=LEN            columns a read of the pile must share with the read (default: 45)\n"
+         "      -e, --error-permille=N           mismatches allowed per 1000 columns of an overlap, 0..250 (default: 40)\n"
+         "          --seed-length=N              length of the seeds that find the pile, 12..64 (default: 24)\n"
+         "          --seed-stride=N              distance between two seeds, 1..seed length (default: 12)\n"
+         "          --max-seed-hits=N            skip a seed that occurs more than N times, 1..4096 (default: 256)\n"
+         "          --conflict=N                 change a base when another has N votes and it has fewer (default: 5)\n"
+         "          --min-depth=N                write a read only if every base has N votes (default: 2)\n"
+         "          --max-candidates=N           leave a read with more than N reads in its pile alone, 1..4096 (default: 512)\n"
          "\n");
   return 256;
 }
 
 // src/correct.cpp:22-60
 static int run_correct(int argc, char** argv) {
-  enum { OPT_DEVICE = 1 };
+  enum { OPT_DEVICE = 1, OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_CONFLICT, OPT_MIN_DEPTH, OPT_MAX_CANDIDATES };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},   {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},    {"outfile", required_argument, nullptr, 'o'},
                                     {"threads", required_argument, nullptr, 't'},   {"algorithm", required_argument, nullptr, 'a'},
                                     {"kmer-size", required_argument, nullptr, 'k'}, {"kmer-threshold", required_argument, nullptr, 'x'},
                                     {"kmer-rounds", required_argument, nullptr, 'i'}, {"kmer-count-offset", required_argument, nullptr, 'O'},
+                                    {"rounds", required_argument, nullptr, 'i'},    {"min-overlap", required_argument, nullptr, 'm'},
+                                    {"error-permille", required_argument, nullptr, 'e'}, {"seed-length", required_argument, nullptr, OPT_SEED_LENGTH},
+                                    {"seed-stride", required_argument, nullptr, OPT_SEED_STRIDE},
+                                    {"max-seed-hits", required_argument, nullptr, OPT_MAX_SEED_HITS},
+                                    {"conflict", required_argument, nullptr, OPT_CONFLICT}, {"min-depth", required_argument, nullptr, OPT_MIN_DEPTH},
+                                    {"max-candidates", required_argument, nullptr, OPT_MAX_CANDIDATES},
                                     {"device", required_argument, nullptr, OPT_DEVICE}, {"help", no_argument, nullptr, 'h'},
                                     {nullptr, 0, nullptr, 0}};
   std::string prefix, outfile, algorithm = "kmer";
   sigah::CorrectProcessor::Options o;
   size_t threads = 1;
-  bool help = false;
+  bool help = false, rounds_given = false;
+  const char* kmer_only = nullptr;     // the first of -k, -x, -O on the line
+  const char* overlap_only = nullptr;  // the first option on the line that only -a overlap takes
   int device = 0, c;
+  // a number in 0 .. 2^32 - 1, or 2^32 - 1 for anything else: the library names the field that is out of range
+  auto num32 = [](const char* a) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(a, &end, 10);
+    return (uint32_t)((*a == '-' || end == a || *end || v > 0xFFFFFFFFull) ? 0xFFFFFFFFull : v);
+  };
   std::vector<std::string> ini_store;
   std::vector<char*> ini_argv;
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:p:o:t:a:k:x:i:O:h", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:p:o:t:a:k:x:i:O:m:e:h", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 'o': outfile = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
       case 'a': algorithm = optarg; break;
-      case 'k': o.kmerSize = strtoull(optarg, nullptr, 10); break;
-      case 'x': o.kmerThreshold = strtoull(optarg, nullptr, 10); break;
-      case 'i': o.kmerRounds = strtoull(optarg, nullptr, 10); break;
-      case 'O': o.kmerCountOffset = strtoull(optarg, nullptr, 10); break;
+      case 'k': o.kmerSize = strtoull(optarg, nullptr, 10); if (!kmer_only) kmer_only = "-k/--kmer-size"; break;
+      case 'x': o.kmerThreshold = strtoull(optarg, nullptr, 10); if (!kmer_only) kmer_only = "-x/--kmer-threshold"; break;
+      case 'i': o.kmerRounds = strtoull(optarg, nullptr, 10); o.rounds = num32(optarg); rounds_given = true; break;
+      case 'O': o.kmerCountOffset = strtoull(optarg, nullptr, 10); if (!kmer_only) kmer_only = "-O/--kmer-count-offset"; break;
+      case 'm': o.pile.min_overlap = num32(optarg); if (!overlap_only) overlap_only = "-m/--min-overlap"; break;
+      case 'e': o.pile.error_permille = num32(optarg); if (!overlap_only) overlap_only = "-e/--error-permille"; break;
+      case OPT_SEED_LENGTH: o.pile.seed_length = num32(optarg); if (!overlap_only) overlap_only = "--seed-length"; break;
+      case OPT_SEED_STRIDE: o.pile.seed_stride = num32(optarg); if (!overlap_only) overlap_only = "--seed-stride"; break;
+      case OPT_MAX_SEED_HITS: o.pile.max_seed_hits = num32(optarg); if (!overlap_only) overlap_only = "--max-seed-hits"; break;
+      case OPT_CONFLICT: o.pile.conflict = num32(optarg); if (!overlap_only) overlap_only = "--conflict"; break;
+      case OPT_MIN_DEPTH: o.pile.min_depth = num32(optarg); if (!overlap_only) overlap_only = "--min-depth"; break;
+      case OPT_MAX_CANDIDATES: o.pile.max_candidates = num32(optarg); if (!overlap_only) overlap_only = "--max-candidates"; break;
       case OPT_DEVICE: device = atoi(optarg); break;
       case 'h': help = true; break;
       default: break;
@@ -365,9 +398,43 @@ static int run_correct(int argc, char** argv) {
   std::string stem = sigah::Utils::stem(input);
   if (outfile.empty()) outfile = stem + ".ec.fa";
   if (prefix.empty()) prefix = stem;
-  if (algorithm != "kmer") {  // AbstractCorrector::create returns NULL / the overlap corrector is an empty stub
+  if (algorithm != "kmer" && algorithm != "overlap") {  // AbstractCorrector::create returns NULL
     fprintf(stderr, "Failed to do error correction for reads %s: algorithm %s is not built\n", input.c_str(), algorithm.c_str());
     return -1;
+  }
+  if (algorithm == "kmer" && overlap_only) fprintf(stderr, "siga correct: option %s applies to -a overlap only and is ignored\n", overlap_only);
+  if (algorithm == "overlap") {
+    if (kmer_only) {
+      fprintf(stderr, "siga correct: option %s applies to -a kmer only, not to -a overlap\n", kmer_only);
+      return 1;
+    }
+    o.overlap = true;
+    if (!rounds_given) o.rounds = 1;
+    if (o.rounds < 1 || o.rounds == 0xFFFFFFFFull) {
+      fprintf(stderr, "siga correct: -i/--rounds must be a number from 1\n");
+      return 1;
+    }
+    uint64_t probe = 0;
+    if (sigax_pileup_workspace(0, 0, &o.pile, 0, &probe) != SIGAX_OK) {  // the ranges are the library's
+      fprintf(stderr, "siga correct: %s\n", sigax_last_error());
+      return 1;
+    }
+    sigah::FMIndex fmi;
+    if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {  // (a missing .sai file is named in the text)
+      fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+      return 1;
+    }
+    sigah::CorrectProcessor proc(o);
+    if (!proc.process(fmi, input, outfile, threads)) {
+      fprintf(stderr, "Failed to do error correction for reads %s: %s\n", input.c_str(), proc.error().c_str());
+      return 1;
+    }
+    const uint64_t* st = proc.pileStatus();
+    fprintf(stderr, "siga correct -a overlap: %llu reads in, %llu written, %llu bases changed; %llu reads too long, %llu over --max-candidates, "
+            "%llu seeds located, %llu skipped as repeats, %llu candidates tested, %llu accepted\n",
+            (unsigned long long)proc.readsIn(), (unsigned long long)proc.readsOut(), (unsigned long long)st[7], (unsigned long long)st[1],
+            (unsigned long long)st[2], (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[5], (unsigned long long)st[6]);
+    return 0;
   }
   sigah::FMIndex fmi;
   if (!sigah::FMIndex::loadForward(prefix, fmi, device)) {

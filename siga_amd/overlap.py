@@ -629,6 +629,9 @@ class FMIndexPair:
 
     def close(self):
         if self._h:
+            if getattr(self, "_pile_ref", None) is not None:
+                _lib.lib().sigax_pile_ref_destroy(self._pile_ref)
+                self._pile_ref = None
             _lib.lib().sigax_index_close(self._h)
             self._h = None
 
@@ -726,6 +729,29 @@ class FMIndexPair:
             for p in (t, f, o, h):
                 _lib.lib().sigax_free(p)
         return totals, qflags, hit_offs, hits
+
+    def correct_overlap(self, seqs, rounds=1, **pile):
+        """`siga correct -a overlap` for a batch (sigax_pileup_batch, rules in include/sigax.h) -> (list of bytes: the corrected
+        read where valid is 1, else the read as it went into its last round; valid u8[n]; changed u8[n]; status u64[8], the
+        rounds' words added up; rounds run).  The fields of sigax_pile_params as keywords, the CLI's defaults otherwise.  The
+        reference text is built from the index at the first call and kept.  Needs the .sai table and reads of ACGT only."""
+        L = _lib.lib()
+        if getattr(self, "_pile_ref", None) is None:
+            ref = C.c_void_p()
+            _check(L.sigax_pile_ref_create(self._h, C.byref(ref)), "sigax_pile_ref_create")
+            self._pile_ref = ref
+        params = _lib.PileParams(**pile)
+        buf, offs = pack_reads(seqs)
+        n = len(offs) - 1
+        if isinstance(buf, np.ndarray):
+            buf = C.c_char_p(buf.ctypes.data) if buf.size else b""
+        out = np.zeros(int(offs[-1]) + 1, dtype=np.uint8)
+        valid, changed = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        status, run = np.zeros(8, dtype=np.uint64), C.c_uint32()
+        _check(L.sigax_pileup_batch(self._h, self._pile_ref, buf, offs.ctypes.data, n, C.byref(params), int(rounds), out.ctypes.data,
+                                    valid.ctypes.data, changed.ctypes.data, status.ctypes.data, C.byref(run)), "sigax_pileup_batch")
+        text = out.tobytes()
+        return [text[int(offs[i]):int(offs[i + 1])] for i in range(n)], valid, changed, status, int(run.value)
 
     def get_strings(self, rows, which=0, max_len=MAX_STRING_LEN, stretch=False):
         """FMIndex::getString (src/fmindex.cpp:292-313, sigax_get_strings) for many BWT rows of strand `which` -> list of
