@@ -395,6 +395,85 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
                         const sigax_pile_params*, uint32_t rounds, char* out_seqs, uint8_t* valid, uint8_t* changed,
                         uint64_t status8[8], uint32_t* rounds_run);
 
+/* ---- `siga overlap -e`: overlaps with mismatches, seed and verify (csrc/sigax_mmoverlap.hip) ------------------------------------
+ * Every read of the index is lined up, without gaps, against the indexed reads that share a seed with it; an overlap of at least
+ * M columns with at most P mismatches per mille is kept, a dovetail as an edge record with its mismatch count, a containment as
+ * a flag.  The reference finds exact overlaps only (OverlapBlockFinder, src/overlap_builder.cpp:838-912), although Match::numDiff
+ * is part of its format (src/coord.cpp:67); the rules are these.  Integer arithmetic throughout; no result depends on the order
+ * of hits, candidates, reads or batches.
+ *
+ * The read set is the reads of the index by id, ref[t]: ACGT only with the forward .sai loaded (locate's condition), and
+ * sigax_index_set_reads called (lengths, name ranks); SIGAX_E_STATE otherwise.  A query is itself a read of the index, q = ref[i],
+ * n = len(q).
+ *
+ * Parameters (sigax_mmo_params; CLI spelling and default in brackets), range errors as in sigax_pile_params:
+ *   S seed_length 12..64 (--seed-length 24)    T seed_stride 1..S (--seed-stride 12)      H max_seed_hits 1..4096 (--max-seed-hits 256)
+ *   M min_overlap >= 1 (-m 45)                 P error_permille 0..250 (-e, no default: its presence selects this path)
+ *   K max_candidates 1..4096 (--max-candidates 512)                                       max_read_len 1..4096, 0 = 4096
+ *
+ *  1. n < S or n > max_read_len: the read emits nothing from its side, and status[1] counts it.
+ *  2. Seeds and candidates are exactly rules 2-3 of the pile-up block: the windows q[p, p+S) for p = 0, T, 2T, ... and n - S, each
+ *     located on both strands, one with more than H occurrences skipped; the candidates are the distinct triples (t, strand, d), a
+ *     forward hit (t, o) giving d = o - p, a reverse hit d = len(t) - o - S - p, read against revcomp(ref[t]).  More than K distinct
+ *     triples: the read emits nothing from its side and status[2] counts it.
+ *  3. A candidate with name_rank[t] == name_rank[i] is skipped: the read itself and reads of the same name, as
+ *     src/overlap_builder.cpp:358 does.  It counts towards K but is not "tested".
+ *  4. Geometry: text = ref[t] or its reverse complement, L = len(text), x0 = max(0, -d), x1 = min(n, L - d), l = x1 - x0, m = the
+ *     columns x in [x0, x1) with q[x] != text[x + d].  Accepted iff l >= M and m <= floor(l * P / 1000).
+ *  5. Class of an accepted candidate: l == n == L DUP; else l == n Q_IN_T; else l == L T_IN_Q; else d < 0 SUFFIX (q's suffix on
+ *     text's prefix, l = n + d); otherwise PREFIX (q's prefix on text's suffix, l = L - d).
+ *  6. Containment flags, contained[], one byte per read of the index: Q_IN_T sets contained[i], T_IN_Q sets contained[t], DUP sets
+ *     the flag of the read with the LARGER name rank (`rmdup` keeps the smaller name).  A flag is set from whichever side finds the
+ *     alignment.  Containments give no record.
+ *  7. Dovetail records: sigax_mm_edge {query, target, length = l, af, num_diff = m, reserved = 0}; af has the meaning it has in
+ *     sigax_edge, so the ED coordinates follow from (length, af, read lengths): SUFFIX + 0, SUFFIX - 6 (TARGETREV|QUERYCOMP),
+ *     PREFIX + 3 (QUERYREV|TARGETREV), PREFIX - 5 (QUERYREV|QUERYCOMP).  Canonical form: the read with the larger name rank is
+ *     `query` (the pair src/overlap_builder.cpp:365 keeps); when i has the smaller rank the record is written swapped, (t, i, l,
+ *     af', m) with af' = af if af & 4, else af ^ 3.
+ *  8. Both reads of a pair emit what their own seeds find.  The result is the SET of canonical records, each (query, target, af,
+ *     length) once, ascending in (query, target, af, length) by read id: a pair is there if either side's seeds find it.  Where
+ *     every accepted alignment holds a run of S + T - 1 matching columns -- min over l >= M of ceil((l - m) / (m + 1)) >= S + T - 1
+ *     with m = floor(l P / 1000) -- and neither H is reached nor K on both sides, the set equals the one a search over every read,
+ *     strand and diagonal gives.
+ *
+ * sigax_mmoverlap_device: reads first_read .. first_read + n_reads of the index as queries, every buffer in device memory,
+ * asynchronous on `stream`, allocates nothing.  d_ref_text / d_ref_offs: the reference text (sigax_reference_text_device,
+ * sigax_pile_ref_buffers); n_bases >= d_ref_offs[first_read + n_reads] - d_ref_offs[first_read] (it sizes the seed table, as in
+ * sigax_pileup_device); d_work = sigax_mmoverlap_workspace(n_reads, n_bases, params, hits_cap) bytes, 16-byte aligned; the seeds'
+ * hits live in it.  The call APPENDS its raw canonical records to d_edges[edges_cap] at *d_cursor (u64, the records held so far)
+ * and moves the cursor, and sets bytes to 1 in d_contained (u8 per read of the index, zeroed once by the caller).  d_status8,
+ * written: {hits listed, reads too short or too long, reads over K, seeds located, seeds skipped as repeats, candidates tested
+ * (rule 4 reached), candidates accepted, records emitted by this call}.  Hits over hits_cap: locate's protocol as
+ * sigax_pileup_device passes it through -- status[0] carries the number, status[1..7] are 0, nothing is written.  Records over
+ * edges_cap - *d_cursor: the cursor is left where it was, no record and no flag of this call is written, status[7] carries the
+ * number needed and status[0..6] are as counted.  Raw records are in no particular order and a pair may be there twice.
+ *
+ * sigax_mmoverlap_finish_device: orders n_raw raw records (below 2^32) by (query, target, af, length), drops repeats, leaves the
+ * result at the front of d_edges and its count in *d_n_unique (u64).  Asynchronous, allocates nothing; d_work =
+ * sigax_mmoverlap_finish_workspace(n_raw) bytes, 16-byte aligned.  Run it once over the records of all calls.
+ *
+ * sigax_mmoverlap_batch: synchronous; every read of the index in pieces, hits_cap and edges_cap sized from the status words, a
+ * piece that does not fit half the free device memory halved, finish once.  *edges (malloc'd; release with sigax_free) holds
+ * *n_edges records, contained u8[n_strings] is the caller's, status8 (may be NULL) = the pieces' status words added up.
+ *
+ * Not held: read sets beyond 2^32 bases are untested.  Out of scope: gapped overlaps (indels); transitive reduction or
+ * irreducible output inside this path; feeding these records to `siga unitig` (af and length were chosen so that it can be done);
+ * more than one GPU; quality values; seeds chosen by content. */
+typedef struct sigax_mmo_params {
+  uint32_t seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates;
+  uint32_t max_read_len, reserved;  /* reserved = 0 */
+} sigax_mmo_params;
+typedef struct sigax_mm_edge { uint32_t query, target, length, af, num_diff, reserved; } sigax_mm_edge;  /* 24 bytes */
+int  sigax_mmoverlap_workspace(uint64_t n_reads, uint64_t n_bases, const sigax_mmo_params*, uint64_t hits_cap, uint64_t* bytes);
+int  sigax_mmoverlap_device(sigax_index*, const void* d_ref_text, const void* d_ref_offs, uint64_t first_read, uint64_t n_reads,
+                            uint64_t n_bases, const sigax_mmo_params*, sigax_mm_edge* d_edges, uint64_t edges_cap, void* d_cursor,
+                            void* d_contained, void* d_status8, void* d_work, uint64_t work_bytes, uint64_t hits_cap, void* stream);
+int  sigax_mmoverlap_finish_workspace(uint64_t n_raw, uint64_t* bytes);
+int  sigax_mmoverlap_finish_device(sigax_mm_edge* d_edges, uint64_t n_raw, void* d_n_unique, void* d_work, uint64_t work_bytes,
+                                   void* stream);
+int  sigax_mmoverlap_batch(sigax_index*, const sigax_pile_ref*, const sigax_mmo_params*, sigax_mm_edge** edges, uint64_t* n_edges,
+                           uint8_t* contained, uint64_t status8[8]);
+
 /* ---- `siga unitig`: unbranched chains of overlaps compacted (csrc/sigax_unitig.hip) ----------------------------------------------
  * The fixpoint of Bigraph::simplify (src/bigraph.cpp:341-414, Vertex::merge at :131-202) over the edge records of an overlap
  * run, without an index: every chain of reads joined by SIMPLE records becomes one unitig.

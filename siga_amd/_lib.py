@@ -21,6 +21,8 @@ BLOCK_DTYPE = np.dtype([
 EDGE_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("length", "<u4"), ("af", "<u4")])
 HIT_DTYPE = np.dtype([("query", "<u4"), ("read", "<u4"), ("offset", "<u4"), ("flags", "<u4")])  # sigax_hit
 PLACEMENT_DTYPE = np.dtype([("read", "<u4"), ("flags", "<u4"), ("offset", "<u8")])  # sigax_placement
+MM_EDGE_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("length", "<u4"), ("af", "<u4"), ("num_diff", "<u4"), ("reserved", "<u4")])  # sigax_mm_edge
+assert MM_EDGE_DTYPE.itemsize == 24
 assert BLOCK_DTYPE.itemsize == 80 and EDGE_DTYPE.itemsize == 16 and HIT_DTYPE.itemsize == 16 and PLACEMENT_DTYPE.itemsize == 16
 SIGAX_HIT_REV = 1
 SIGAX_HIT_CUT = 2
@@ -160,6 +162,15 @@ class PileParams(C.Structure):
                          max_read_len, 0)
 
 
+class MmoParams(C.Structure):
+    """sigax_mmo_params (`siga overlap -e`); the defaults are the CLI's, error_permille has none"""
+    _fields_ = [(n, C.c_uint32) for n in ("seed_length", "seed_stride", "max_seed_hits", "min_overlap", "error_permille", "max_candidates",
+                                          "max_read_len", "reserved")]
+
+    def __init__(self, error_permille, seed_length=24, seed_stride=12, max_seed_hits=256, min_overlap=45, max_candidates=512, max_read_len=0):
+        super().__init__(seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates, max_read_len, 0)
+
+
 class RunInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_sub", "find_per_sub", "two_step", "coop", "read_order", "cap", "worst_cap", "row_bits",
                                           "row_syms", "row_text", "row_direct", "deep_k")] + \
@@ -185,6 +196,8 @@ SYMBOLS = [
     "sigax_locate_workspace", "sigax_locate_device", "sigax_locate_batch",
     "sigax_reference_text_workspace", "sigax_reference_text_device", "sigax_pileup_workspace", "sigax_pileup_device",
     "sigax_pile_ref_create", "sigax_pile_ref_destroy", "sigax_pile_ref_buffers", "sigax_pileup_batch",
+    "sigax_mmoverlap_workspace", "sigax_mmoverlap_device", "sigax_mmoverlap_finish_workspace", "sigax_mmoverlap_finish_device",
+    "sigax_mmoverlap_batch",
     "sigax_unitigs_workspace", "sigax_unitigs_device", "sigax_unitigs_host", "sigax_unitigs_last_status",
     "sigax_unitigs_trim_workspace", "sigax_unitigs_trim_device", "sigax_unitigs_trim_host",
     "sigax_unitigs_prune_workspace", "sigax_unitigs_prune_device", "sigax_unitigs_prune_host",
@@ -296,6 +309,14 @@ def lib():
     L.sigax_pile_ref_destroy.restype = None
     L.sigax_pile_ref_buffers.argtypes = [vp, pvp, pvp, C.POINTER(u64)]
     L.sigax_pileup_batch.argtypes = [vp, vp, cp, vp, u64, pp, u32, vp, vp, vp, vp, C.POINTER(u32)]
+    mp = C.POINTER(MmoParams)
+    L.sigax_mmoverlap_workspace.argtypes = [u64, u64, mp, u64, C.POINTER(u64)]
+    L.sigax_mmoverlap_device.argtypes = [vp, vp, vp, u64, u64, u64, mp, vp, u64, vp, vp, vp, vp, u64, u64, vp]
+    # (not in include/sigax.h: the measurement aid of tools/mmoverlap_bench.py, sigax_mmoverlap.h)
+    L.sigax_mmoverlap_stages_device.argtypes = L.sigax_mmoverlap_device.argtypes + [ci]
+    L.sigax_mmoverlap_finish_workspace.argtypes = [u64, C.POINTER(u64)]
+    L.sigax_mmoverlap_finish_device.argtypes = [vp, u64, vp, vp, u64, vp]
+    L.sigax_mmoverlap_batch.argtypes = [vp, vp, mp, pvp, C.POINTER(u64), vp, vp]
     L.sigax_unitigs_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_unitigs_device.argtypes = [ci, vp, u64, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(u64), pvp, pvp, pvp, pvp, pvp]

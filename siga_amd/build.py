@@ -12,8 +12,8 @@ SOURCES = ["sigax_kernels.hip", "sigax_api.cpp", "sigax_index.cpp", "sigax_table
            "sigax_comm.cpp", "sigax_keys.hip", "sigax_match.hip", "sigax_match.cpp", "sigax_order.hip", "sigax_spectrum.hip", "sigax_spectrum.cpp",
            "sigax_locate.hip", "sigax_locate.cpp", "sigax_unitig.hip", "sigax_unitig.cpp", "sigax_pairs.hip", "sigax_pairs.cpp",
            "sigax_scaffold.hip", "sigax_scaffold.cpp", "sigax_gapfill.hip", "sigax_gapfill.cpp", "sigax_join.hip", "sigax_join.cpp",
-           "sigax_pileup.hip", "sigax_pileup.cpp"]
-HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", "sigax_rank.h", "sigax_device.h", "sigax_pileup.h", os.path.join(ROOT, "include", "sigax.h")]
+           "sigax_pileup.hip", "sigax_pileup.cpp", "sigax_mmoverlap.hip", "sigax_mmoverlap.cpp"]
+HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", "sigax_rank.h", "sigax_device.h", "sigax_pileup.h", "sigax_mmoverlap.h", os.path.join(ROOT, "include", "sigax.h")]
 
 
 def _stale(target, deps):
@@ -43,7 +43,7 @@ HOST = os.path.join(HERE, "host")
 HOSTLIB = os.path.join(HERE, "lib", "libsiga_host.so")
 CLI = os.path.join(HERE, "lib", "siga")
 CXX = os.environ.get("CXX", "g++")
-HOST_SOURCES = ["reads.cpp", "strand_index.cpp", "out_file.cpp", "asqg_text.cpp", "overlap_builder.cpp", "correct_match.cpp", "locate.cpp", "kmer_spectrum.cpp", "unitig.cpp", "pairs.cpp", "host_capi.cpp"]
+HOST_SOURCES = ["reads.cpp", "strand_index.cpp", "out_file.cpp", "asqg_text.cpp", "overlap_builder.cpp", "mismatch_overlap.cpp", "correct_match.cpp", "locate.cpp", "kmer_spectrum.cpp", "unitig.cpp", "pairs.cpp", "host_capi.cpp"]
 HOST_HEADERS = ["siga_host.hpp", "host_util.hpp", "reads.hpp", "out_file.hpp", "asqg_text.hpp", "sais.hpp", "line_deflate.hpp", "pairs.hpp"]
 
 

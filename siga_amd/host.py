@@ -35,6 +35,8 @@ def lib():
                                          C.c_int, C.c_char_p, C.c_uint64]
         L.sigah_correct_overlap_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                                  C.c_char_p, C.c_uint64]
+        L.sigah_overlap_mismatch_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                                  C.c_char_p, C.c_uint64]
         L.sigah_format_asqg.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int]
         L.sigah_format_asqg.restype = C.c_int64
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
@@ -110,9 +112,25 @@ def index_file_sais(reads_path, prefix, threads=2):
         raise RuntimeError("siga index -a sais failed: " + err.value.decode())
 
 
-def overlap_file(reads_path, prefix, min_overlap, output, irreducible=True, rc=True, threads=1, batch=10000, device=0, gpus=1):
-    """FMIndex::load + OverlapBuilder::build in the host C++ library (GPU compute), reads sharded over `gpus` GPUs."""
+def overlap_file(reads_path, prefix, min_overlap, output, irreducible=True, rc=True, threads=1, batch=10000, device=0, gpus=1,
+                 error_permille=None, **seed):
+    """FMIndex::load + OverlapBuilder::build in the host C++ library (GPU compute), reads sharded over `gpus` GPUs.
+    error_permille given (`siga overlap -e`): FMIndex::loadForwardSai + MismatchOverlapper::run instead -- every overlap of
+    min_overlap columns with that many mismatches per mille at most, the rules of include/sigax.h, with seed_length, seed_stride,
+    max_seed_hits and max_candidates as keywords; one GPU, both strands; -> the eight status words."""
     err = C.create_string_buffer(512)
+    if error_permille is not None:
+        if gpus != 1 or not rc:
+            raise ValueError("error_permille with gpus=%r, rc=%r" % (gpus, rc))
+        from . import _lib as core
+        params = core.MmoParams(int(error_permille), min_overlap=int(min_overlap), **seed)
+        status = np.zeros(8, dtype=np.uint64)
+        if lib().sigah_overlap_mismatch_file(reads_path.encode(), prefix.encode(), output.encode(), C.addressof(params), threads, device,
+                                             status.ctypes.data, err, 512) != 0:
+            raise RuntimeError("siga overlap failed: " + err.value.decode())
+        return status
+    if seed:
+        raise ValueError("%r without error_permille" % sorted(seed))
     r = lib().sigah_overlap_file_gpus(reads_path.encode(), prefix.encode(), min_overlap, output.encode(), int(irreducible), int(rc),
                                       threads, batch, device, gpus, err, 512)
     if r != 0:

@@ -77,7 +77,7 @@ static void write_vertex(std::string& o, std::string_view name, std::string_view
 
 // EdgeRecord << (src/asqg.cpp:228-237, src/coord.cpp:4-80) with OverlapBlock::overlap's coordinates
 // (src/overlap_builder.cpp:158-175)
-// ... written through a raw pointer: the caller has room for the two names and 3 + 2 + 6 x 21 + 4 bytes more (22 M lines at
+// ... written through a raw pointer: the caller has room for the two names and 3 + 2 + 7 x 21 + 3 bytes more (22 M lines at
 // BASELINE configs[2]: the capacity check of every append was a third of the formatting)
 static inline char* put_u64(char* p, uint64_t v) {
   char tmp[24];
@@ -89,8 +89,9 @@ static inline char* put_u64(char* p, uint64_t v) {
   while (n) *p++ = tmp[--n];
   return p;
 }
-static const size_t kEdgeLineExtra = 3 + 2 + 6 * 21 + 4;
-static inline char* write_edge_line(char* p, const sigax_edge& e, const std::string_view qn, const std::string_view tn, uint64_t ql, uint64_t tl) {
+static const size_t kEdgeLineExtra = 3 + 2 + 7 * 21 + 3;
+static inline char* write_edge_line(char* p, const sigax_edge& e, const std::string_view qn, const std::string_view tn, uint64_t ql, uint64_t tl,
+                                    uint64_t num_diff = 0) {  // Match::numDiff (src/coord.cpp:67): 0 for the exact overlaps
   const uint64_t len = e.length;
   uint64_t s0 = ql - len, e0 = ql - 1, s1 = 0, e1 = len - 1;
   if (e.af & 1u) { uint64_t t = s0; s0 = ql - e0 - 1; e0 = ql - t - 1; }
@@ -109,11 +110,13 @@ static inline char* write_edge_line(char* p, const sigax_edge& e, const std::str
   p = put_u64(p, e1); *p++ = ' ';
   p = put_u64(p, tl); *p++ = ' ';
   *p++ = (e.af & 4u) ? '1' : '0';
-  *p++ = ' '; *p++ = '0'; *p++ = '\n';
+  *p++ = ' ';
+  p = put_u64(p, num_diff);
+  *p++ = '\n';
   return p;
 }
-static char* write_edge(char* p, const sigax_edge& e, const ReadStore& reads, const uint32_t* lengths) {
-  return write_edge_line(p, e, reads.name(e.query), reads.name(e.target), lengths[e.query], lengths[e.target]);
+static char* write_edge(char* p, const sigax_edge& e, const ReadStore& reads, const uint32_t* lengths, uint64_t num_diff) {
+  return write_edge_line(p, e, reads.name(e.query), reads.name(e.target), lengths[e.query], lengths[e.target], num_diff);
 }
 void append_edge_line(std::string& o, const sigax_edge& e, std::string_view qn, std::string_view tn, uint64_t ql, uint64_t tl) {
   const size_t at = o.size();
@@ -124,8 +127,9 @@ void append_edge_line(std::string& o, const sigax_edge& e, std::string_view qn, 
 
 // ED text of `cnt` edge records in chunks of ed_chunk lines, one string per chunk, on nt threads: every chunk gets room for
 // the longest lines there can be (two names of max_name bytes + kEdgeLineExtra) and is written through a raw pointer.
-static void format_edge_text(const ReadStore& reads, const uint32_t* read_len, const sigax_edge* e, uint64_t cnt, unsigned nt, uint32_t max_name,
-                             size_t ed_chunk, std::vector<std::string>* parts) {
+// num_diff: the records' mismatch counts, or nullptr for 0 everywhere.
+static void format_edge_text(const ReadStore& reads, const uint32_t* read_len, const sigax_edge* e, const uint32_t* num_diff, uint64_t cnt, unsigned nt,
+                             uint32_t max_name, size_t ed_chunk, std::vector<std::string>* parts) {
   parts->assign((cnt + ed_chunk - 1) / ed_chunk, std::string());
   parallel_for(parts->size(), nt, [&](size_t c) {
     const uint64_t cb = c * ed_chunk, ce = std::min<uint64_t>(cnt, cb + ed_chunk);
@@ -142,7 +146,7 @@ static void format_edge_text(const ReadStore& reads, const uint32_t* read_len, c
         __builtin_prefetch(&read_len[t]);
       }
       if (i + 8 < ce) __builtin_prefetch(reads.file.data() + reads.head_off[e[i + 8].target]);
-      w = write_edge(w, e[i], reads, read_len);
+      w = write_edge(w, e[i], reads, read_len, num_diff ? num_diff[i] : 0);
     }
     o.resize((size_t)(w - &o[0]));
     o.shrink_to_fit();  // the text may be held until the last batch is through: not with three times its size in reserve
@@ -393,6 +397,7 @@ AsqgWriter::AsqgWriter(OutFile& out, const ReadStore& reads, const std::vector<u
   for (uint32_t l : lengths) _maxLen = std::max(_maxLen, l);
   for (uint32_t l : reads.name_len) _max_name = std::max(_max_name, l);
   if (_ahead) _sub_all.assign(reads.size(), 0);
+  _num_diff.reserve(nbatch);
   _edges.reserve(nbatch);    // (the edge-text job of a batch keeps its slots while the next batch is taken)
   _ed_text.reserve(nbatch);
 }
@@ -404,10 +409,11 @@ AsqgWriter::~AsqgWriter() {
 }
 
 void AsqgWriter::format_edges(size_t k) {
-  format_edge_text(_reads, _read_len, _edges[k].first, _edges[k].second, _nt, _max_name, _ed_chunk, &_ed_text[k]);
+  format_edge_text(_reads, _read_len, _edges[k].first, _num_diff[k], _edges[k].second, _nt, _max_name, _ed_chunk, &_ed_text[k]);
 }
 
-void AsqgWriter::add_batch(size_t lo, size_t cnt, const uint8_t* substring, const sigax_edge* edges, uint64_t n_edges, double wait_s) {
+void AsqgWriter::add_batch(size_t lo, size_t cnt, const uint8_t* substring, const sigax_edge* edges, uint64_t n_edges, double wait_s,
+                           const uint32_t* num_diff) {
   const size_t b = _edges.size(), n = _reads.size();
   PhaseTimer clock(false);
   double vt_s = 0;
@@ -441,6 +447,7 @@ void AsqgWriter::add_batch(size_t lo, size_t cnt, const uint8_t* substring, cons
   }
   if (_timing) fprintf(stderr, "[siga]   batch %zu: VT text %.3f s, deflate + write %.3f s\n", b, vt_s, clock.split());
   _edges.emplace_back(edges, n_edges);
+  _num_diff.push_back(num_diff);
   _ed_text.emplace_back();
   join_ed();  // (one batch's edge text at a time; ed_held is the job's to update, ours to read after the join)
   if (_timing) fprintf(stderr, "[siga]   batch %zu: waited %.3f s for the batch, %.3f s for the ED text before it\n", b, wait_s, clock.split());

@@ -92,8 +92,10 @@ class AsqgWriter {
   AsqgWriter& operator=(const AsqgWriter&) = delete;
   // The VT lines of reads [lo, lo + cnt) (substring: their flags, or nullptr for none set); the batch's edge records are taken
   // over and, under the hold limit, their ED text is started.  Batches come in input order.  wait_s: how long the caller
-  // waited for the batch (for the SIGA_TIMING line).
-  void add_batch(size_t lo, size_t cnt, const uint8_t* substring, const sigax_edge* edges, uint64_t n_edges, double wait_s = 0);
+  // waited for the batch (for the SIGA_TIMING line).  num_diff: the last column of the records' ED lines (`siga overlap -e`), the
+  // caller's until finish() has returned; nullptr: 0, as for every exact overlap.
+  void add_batch(size_t lo, size_t cnt, const uint8_t* substring, const sigax_edge* edges, uint64_t n_edges, double wait_s = 0,
+                 const uint32_t* num_diff = nullptr);
   // ED lines in hits order (Hit2OverlapConverter, src/overlap_builder.cpp:345-375 + :474-483), then the file is closed; false: a
   // write failed
   bool finish();
@@ -114,6 +116,7 @@ class AsqgWriter {
   size_t _ahead_from = 0;
   std::vector<std::string> _vt_parts;
   std::vector<std::pair<const sigax_edge*, uint64_t>> _edges;
+  std::vector<const uint32_t*> _num_diff;  // per batch, or nullptr
   std::vector<std::vector<std::string>> _ed_text;
   size_t _ed_held = 0;
   const size_t _ed_hold_max, _ed_chunk;

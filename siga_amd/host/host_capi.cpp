@@ -175,6 +175,29 @@ int sigah_overlap_file(const char* reads_path, const char* prefix, uint64_t min_
   return sigah_overlap_file_gpus(reads_path, prefix, min_overlap, output, irreducible, rc, threads, batch, device, 1, err, errcap);
 }
 
+// `siga overlap -e`: FMIndex::loadForwardSai + MismatchOverlapper::run; status8 (may be NULL) receives the status words of
+// sigax_mmoverlap_batch
+int sigah_overlap_mismatch_file(const char* reads_path, const char* prefix, const char* output, const sigax_mmo_params* params, uint64_t threads,
+                                int device, uint64_t* status8, char* err, uint64_t errcap) {
+  sigah::FMIndex fmi;
+  if (!params) {
+    if (err && errcap) snprintf(err, errcap, "params is NULL");
+    return -1;
+  }
+  if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {
+    if (err && errcap) snprintf(err, errcap, "Failed to load FMIndex from %s: %s", prefix, sigax_last_error());
+    return -1;
+  }
+  sigah::MismatchOverlapper finder(*params);
+  if (!finder.run(fmi, reads_path, output, (size_t)threads)) {
+    if (err && errcap) snprintf(err, errcap, "%s", finder.error().c_str());
+    return -1;
+  }
+  if (status8)
+    for (int k = 0; k < 8; ++k) status8[k] = finder.status()[k];
+  return 0;
+}
+
 // `siga rmdup`: FMIndex::load + OverlapBuilder::rmdup
 int sigah_rmdup_file(const char* reads_path, const char* prefix, const char* output, const char* duplicates, int device,
                      char* err, uint64_t errcap) {

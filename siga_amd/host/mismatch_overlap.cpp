@@ -1,0 +1,92 @@
+// siga_amd/host/mismatch_overlap.cpp -- MismatchOverlapper (`siga overlap -e`): the reads for names and lengths, the read
+// metadata into the index, the reference text once, sigax_mmoverlap_batch, and the ASQG text through the writer of
+// OverlapBuilder::build.
+#include <algorithm>
+
+#include "asqg_text.hpp"
+#include "host_util.hpp"
+#include "out_file.hpp"
+#include "reads.hpp"
+#include "siga_host.hpp"
+
+namespace sigah {
+
+bool MismatchOverlapper::run(const FMIndex& index, const std::string& input, const std::string& output, size_t threads) const {
+  for (int k = 0; k < 8; ++k) _status[k] = 0;
+  _records = 0;
+  // the reference text once, before any file is touched: an index that cannot serve is refused here
+  sigax_pile_ref* ref = nullptr;
+  struct RefGuard {
+    sigax_pile_ref** r;
+    ~RefGuard() { sigax_pile_ref_destroy(*r); }
+  } ref_guard{&ref};
+  if (sigax_pile_ref_create(index.handle(), &ref) != SIGAX_OK) {
+    _error = sigax_last_error();
+    return false;
+  }
+  const HostSettings hs;
+  const unsigned nt = (unsigned)std::max<size_t>(threads, 1);
+  ReadStore rs;
+  if (!LoadReads(input, &rs, nt, hs)) {
+    _error = "cannot read " + input;
+    return false;
+  }
+  const size_t n = rs.size();
+  sigax_index_info info;
+  if (sigax_index_info_get(index.handle(), &info) != SIGAX_OK) {
+    _error = sigax_last_error();
+    return false;
+  }
+  if (info.n_strings != n) {
+    _error = input + " holds " + std::to_string(n) + " reads, the index " + std::to_string(info.n_strings);
+    return false;
+  }
+  std::vector<uint32_t> lengths, ranks;
+  name_ranks(rs, nt, &lengths, &ranks);
+  if (sigax_index_set_reads(index.handle(), lengths.data(), ranks.data(), n) != SIGAX_OK) {
+    _error = sigax_last_error();
+    return false;
+  }
+  sigax_mm_edge* found = nullptr;
+  struct Found {
+    sigax_mm_edge** p;
+    ~Found() { sigax_free(*p); }
+  } found_guard{&found};
+  uint64_t n_found = 0;
+  std::vector<uint8_t> contained(std::max<size_t>(n, 1), 0);
+  if (sigax_mmoverlap_batch(index.handle(), ref, &_params, &found, &n_found, contained.data(), _status) != SIGAX_OK) {
+    _error = sigax_last_error();
+    return false;
+  }
+  _records = n_found;
+  // the writer takes sigax_edge records; the mismatch counts go beside them
+  std::vector<sigax_edge> edges((size_t)n_found);
+  std::vector<uint32_t> num_diff((size_t)n_found);
+  parallel_for(((size_t)n_found + 65535) / 65536, nt, [&](size_t c) {
+    const size_t b = c * 65536, e = std::min<size_t>((size_t)n_found, b + 65536);
+    for (size_t i = b; i < e; ++i) {
+      edges[i].query = found[i].query;
+      edges[i].target = found[i].target;
+      edges[i].length = found[i].length;
+      edges[i].af = found[i].af;
+      num_diff[i] = found[i].num_diff;
+    }
+  });
+  sigax_free(found);
+  found = nullptr;
+  OutFile out(output, nt);
+  if (!out.ok()) {
+    _error = "cannot write " + output;
+    return false;
+  }
+  out.write(asqg_header((size_t)_params.min_overlap));
+  AsqgWriter writer(out, rs, lengths, nt, hs, nullptr, 1000, nullptr, 1);  // (the records are this function's)
+  writer.add_batch(0, n, contained.data(), edges.data(), n_found, 0, num_diff.data());
+  if (!writer.finish()) {
+    _error = "cannot write " + output;
+    return false;
+  }
+  return true;
+}
+
+}  // namespace sigah

@@ -125,6 +125,33 @@ class OverlapBuilder {
   bool _keep_reads = false;
 };
 
+// `siga overlap -e`: every overlap of at least min_overlap columns with at most error_permille mismatches per mille, without gaps,
+// found by seeds and verified on the GPU (sigax_mmoverlap_batch; the rules in include/sigax.h).  No counterpart in the reference,
+// whose finder is exact.  OverlapBuilder::build is not involved.  The index needs its forward .sai table and reads of ACGT only
+// (FMIndex::loadForwardSai will do); `input` must be the reads it was built from.
+class MismatchOverlapper {
+ public:
+  static sigax_mmo_params defaults(uint32_t error_permille) {  // the CLI's
+    sigax_mmo_params p;
+    p.seed_length = 24; p.seed_stride = 12; p.max_seed_hits = 256; p.min_overlap = 45; p.error_permille = error_permille;
+    p.max_candidates = 512; p.max_read_len = 0; p.reserved = 0;
+    return p;
+  }
+  explicit MismatchOverlapper(const sigax_mmo_params& params) : _params(params) {}
+  // HT, VT (input order, SS:i:1 where the read is contained in another or is a duplicate of a smaller name), ED (the records'
+  // order: query, target, strand and end, length; the mismatches in the last column) to `output` (gz when the name ends with .gz).
+  bool run(const FMIndex& index, const std::string& input, const std::string& output, size_t threads = 1) const;
+  const std::string& error() const { return _error; }
+  const uint64_t* status() const { return _status; }  // the status words of sigax_mmoverlap_batch
+  uint64_t records() const { return _records; }
+
+ private:
+  sigax_mmo_params _params;
+  mutable uint64_t _status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  mutable uint64_t _records = 0;
+  mutable std::string _error;
+};
+
 // src/correct_processor.h:25-42.  The k-mer algorithm is the reference's; its "overlap" algorithm is an empty stub there and the
 // pile-up of include/sigax.h here (`siga correct -a overlap`).
 class CorrectProcessor {

@@ -126,6 +126,15 @@ static int overlap_help() {
          "          --no-opposite-strand         treat all reads as forward strand\n"
          "          --device=NUM                 first GPU to use (default: 0)\n"
          "          --gpus=NUM                   shard the reads over NUM GPUs of this node, index replicated on each (default: 1)\n"
+         "\n"
+         "Overlaps with mismatches (needs PREFIX.sai and reads of ACGT only; one GPU, both strands):\n"
+         "      -e, --error-permille=N           output every overlap of at least -m columns (default with -e: 45) with at most N\n"
+         "                                       mismatches per mille of its columns, 0..250, without gaps, as -x does for exact ones;\n"
+         "                                       found by seeds and verified, the mismatches in the last column of the ED lines\n"
+         "          --seed-length=N              length of the seeds that find the candidates, 12..64 (default: 24)\n"
+         "          --seed-stride=N              distance between two seeds of a read, 1..seed length (default: 12)\n"
+         "          --max-seed-hits=N            skip a seed that occurs more than N times, 1..4096 (default: 256)\n"
+         "          --max-candidates=N           a read with more than N candidates reports nothing itself, 1..4096 (default: 512)\n"
          "\n");
   return 256;
 }
@@ -189,8 +198,12 @@ static int run_index(int argc, char** argv) {
 }
 
 static int run_overlap(int argc, char** argv) {
-  enum { OPT_BATCH_SIZE = 1, OPT_NO_RC, OPT_DEVICE, OPT_GPUS };
+  enum { OPT_BATCH_SIZE = 1, OPT_NO_RC, OPT_DEVICE, OPT_GPUS, OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
+                                    {"error-permille", required_argument, nullptr, 'e'}, {"seed-length", required_argument, nullptr, OPT_SEED_LENGTH},
+                                    {"seed-stride", required_argument, nullptr, OPT_SEED_STRIDE},
+                                    {"max-seed-hits", required_argument, nullptr, OPT_MAX_SEED_HITS},
+                                    {"max-candidates", required_argument, nullptr, OPT_MAX_CANDIDATES},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"batch-size", required_argument, nullptr, OPT_BATCH_SIZE},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, 'x'},
@@ -201,16 +214,31 @@ static int run_overlap(int argc, char** argv) {
   size_t threads = 1, batch = 10000, minOverlap = 10;  // code defaults of src/overlap.cpp:44
   bool exhaustive = false, norc = false, help = false;
   int device = 0, gpus = 1, c;
+  // -e: overlaps with mismatches (MismatchOverlapper); the seed options are its own
+  sigax_mmo_params mmo = sigah::MismatchOverlapper::defaults(0);
+  bool mismatches = false;
+  const char* seed_option = nullptr;  // the first option on the line that only -e takes
+  // a number in 0 .. 2^32 - 1, or 2^32 - 1 for anything else: the library names the field that is out of range
+  auto num32 = [](const char* a) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(a, &end, 10);
+    return (uint32_t)((*a == '-' || end == a || *end || v > 0xFFFFFFFFull) ? 0xFFFFFFFFull : v);
+  };
   std::vector<std::string> ini_store;
   std::vector<char*> ini_argv;
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:xh", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:e:xh", longopts, nullptr)) != -1) {
     switch (c) {
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
-      case 'm': minOverlap = strtoull(optarg, nullptr, 10); break;
+      case 'm': minOverlap = strtoull(optarg, nullptr, 10); mmo.min_overlap = num32(optarg); break;
+      case 'e': mmo.error_permille = num32(optarg); mismatches = true; break;
+      case OPT_SEED_LENGTH: mmo.seed_length = num32(optarg); if (!seed_option) seed_option = "--seed-length"; break;
+      case OPT_SEED_STRIDE: mmo.seed_stride = num32(optarg); if (!seed_option) seed_option = "--seed-stride"; break;
+      case OPT_MAX_SEED_HITS: mmo.max_seed_hits = num32(optarg); if (!seed_option) seed_option = "--max-seed-hits"; break;
+      case OPT_MAX_CANDIDATES: mmo.max_candidates = num32(optarg); if (!seed_option) seed_option = "--max-candidates"; break;
       case 'x': exhaustive = true; break;
       case OPT_BATCH_SIZE: batch = strtoull(optarg, nullptr, 10); break;
       case OPT_NO_RC: norc = true; break;
@@ -223,6 +251,37 @@ static int run_overlap(int argc, char** argv) {
   if (help || argc - optind != 1) return overlap_help();
   std::string input = argv[optind];
   if (prefix.empty()) prefix = sigah::Utils::stem(input);
+  if (!mismatches && seed_option) {
+    fprintf(stderr, "siga overlap: option %s applies to -e/--error-permille only\n", seed_option);
+    return 1;
+  }
+  if (mismatches) {
+    if (norc || gpus > 1) {
+      fprintf(stderr, "siga overlap: option %s cannot be combined with -e/--error-permille\n", norc ? "--no-opposite-strand" : "--gpus");
+      return 1;
+    }
+    uint64_t probe = 0;
+    if (sigax_mmoverlap_workspace(0, 0, &mmo, 0, &probe) != SIGAX_OK) {  // the ranges are the library's
+      fprintf(stderr, "siga overlap: %s\n", sigax_last_error());
+      return 1;
+    }
+    sigah::FMIndex fmi;
+    if (!sigah::FMIndex::loadForwardSai(prefix, fmi, device)) {  // (a missing .sai file is named in the text)
+      fprintf(stderr, "Failed to load FMIndex from %s: %s\n", prefix.c_str(), sigax_last_error());
+      return 1;
+    }
+    sigah::MismatchOverlapper finder(mmo);
+    if (!finder.run(fmi, input, prefix + ".asqg.gz", threads)) {
+      fprintf(stderr, "Failed to build overlaps from reads %s: %s\n", input.c_str(), finder.error().c_str());
+      return 1;
+    }
+    const uint64_t* st = finder.status();
+    fprintf(stderr, "siga overlap -e: %llu overlaps; %llu reads too short or too long, %llu over --max-candidates, %llu seeds located, "
+            "%llu skipped as repeats, %llu candidates tested, %llu accepted\n",
+            (unsigned long long)finder.records(), (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3],
+            (unsigned long long)st[4], (unsigned long long)st[5], (unsigned long long)st[6]);
+    return 0;
+  }
   // (not destroyed: the process ends when this command returns, and handing tens of GB of tables back to the driver one
   // hipFree at a time was 0.2 s of a 2 s run at BASELINE configs[2])
   sigah::FMIndex& fmi = *new sigah::FMIndex;

@@ -753,6 +753,30 @@ class FMIndexPair:
         text = out.tobytes()
         return [text[int(offs[i]):int(offs[i + 1])] for i in range(n)], valid, changed, status, int(run.value)
 
+    def overlap_mismatch(self, error_permille, min_overlap=45, **seed):
+        """`siga overlap -e` over every read of the index (sigax_mmoverlap_batch, rules in include/sigax.h) -> (edges, a structured
+        array of _lib.MM_EDGE_DTYPE: the canonical dovetail records with num_diff, each once, in (query, target, af, length) order;
+        contained u8[n_strings]; status u64[8], the pieces' words added up).  seed: seed_length, seed_stride, max_seed_hits,
+        max_candidates, max_read_len as keywords, the CLI's defaults otherwise.  The reference text is built from the index at the
+        first call and kept.  Needs the .sai table, reads of ACGT only and set_reads()."""
+        L = _lib.lib()
+        params = _lib.MmoParams(int(error_permille), min_overlap=int(min_overlap), **seed)
+        if getattr(self, "_pile_ref", None) is None:
+            ref = C.c_void_p()
+            _check(L.sigax_pile_ref_create(self._h, C.byref(ref)), "sigax_pile_ref_create")
+            self._pile_ref = ref
+        n = self.info()["n_strings"]
+        contained = np.zeros(n, dtype=np.uint8)
+        status = np.zeros(8, dtype=np.uint64)
+        ptr, count = C.c_void_p(), C.c_uint64()
+        _check(L.sigax_mmoverlap_batch(self._h, self._pile_ref, C.byref(params), C.byref(ptr), C.byref(count), contained.ctypes.data,
+                                       status.ctypes.data), "sigax_mmoverlap_batch")
+        try:
+            edges = _copy_records(ptr, int(count.value), _lib.MM_EDGE_DTYPE)
+        finally:
+            L.sigax_free(ptr)
+        return edges, contained, status
+
     def get_strings(self, rows, which=0, max_len=MAX_STRING_LEN, stretch=False):
         """FMIndex::getString (src/fmindex.cpp:292-313, sigax_get_strings) for many BWT rows of strand `which` -> list of
         bytes, the text in front of each row's suffix; with stretch=True -> (that list, u64 array of the strings' stretch
