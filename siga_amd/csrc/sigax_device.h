@@ -1,7 +1,7 @@
 // siga_amd/csrc/sigax_device.h -- the small pieces the kernels of `siga unitig` and of the assembly behind it share
 // (sigax_unitig.hip, sigax_pairs.hip, sigax_scaffold.hip, sigax_gapfill.hip, sigax_join.hip; sigax_rank.h takes its wave sum from
-// here), each piece once:
-//   waves       wave_sum, wave_min32, wave_max32; wave_add: a wave's sum added once, by lane 0, when it is not zero
+// here, sigax_seeded.h its 64-bit shuffle), each piece once:
+//   waves       wave_sum, wave_min32, wave_max32; wave_add: a wave's sum added once, by lane 0, when it is not zero; shfl64
 //   counters    a counter block is TRIM_SLOTS partial sums per counter, TRIM_STRIDE words apart (sigax_kernels.h): counter_slot,
 //               counter_total
 //   bases       comp_byte
@@ -44,6 +44,10 @@ __device__ __forceinline__ u32 wave_max32(u32 v) {
 __device__ __forceinline__ void wave_add(u64* at, u64 v) {
   const u64 t = wave_sum(v);
   if (t && (threadIdx.x & 63u) == 0u) atomicAdd(at, t);
+}
+// v of lane `lane` of the wave
+__device__ __forceinline__ u64 shfl64(u64 v, u32 lane) {
+  return (u64)(u32)__shfl((int)(u32)v, (int)lane, 64) | ((u64)(u32)__shfl((int)(u32)(v >> 32), (int)lane, 64) << 32);
 }
 
 // ---- counter blocks -----------------------------------------------------------------------------------------------------------------

@@ -144,9 +144,6 @@ __device__ __forceinline__ Win4 win_shift(const Win4& w, u32 k, u32 b) {
   return x;
 }
 __device__ __forceinline__ u32 win_code(const Win4& w, u32 i) { return (u32)(sel4<u64>(i >> 5, w.a, w.b, w.c, w.d) >> (2u * (i & 31u))) & 3u; }
-__device__ __forceinline__ u64 shfl64(u64 v, u32 lane) {
-  return (u64)(u32)__shfl((int)(u32)v, (int)lane, 64) | ((u64)(u32)__shfl((int)(u32)(v >> 32), (int)lane, 64) << 32);
-}
 
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_gap_walk(GapfillArgs A) {

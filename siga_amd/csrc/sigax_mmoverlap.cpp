@@ -3,19 +3,12 @@
 
 #include "sigax_internal.h"
 #include "sigax_mmoverlap.h"
-#include "sigax_pileup.h"
 
 namespace {
 
-#define MMO_REF_MAX_LEN 0x3FFFFFFFu  // reference reads are shorter than 2^30 bases (the diagonal's 31 bits, sigax_mmoverlap.hip)
-
-u64 up16(u64 v) { return (v + 15) & ~15ull; }
-
 int mmo_usable(const sigax_index* ix) {
-  if (!ix->d_sai[0] || ix->n_sai != ix->n_strings)
-    return sigax_fail(SIGAX_E_STATE, "the index was opened without its forward .sai table: overlaps with mismatches need it to name the reads");
-  if (ix->st[0].C[1] != ix->n_strings)
-    return sigax_fail(SIGAX_E_STATE, "reads with non-ACGT bases in the index: stretches are not reads, no overlap can be verified against them");
+  const int rc = seeded_usable(ix, "overlaps with mismatches need", "no overlap can be verified against");
+  if (rc != SIGAX_OK) return rc;
   if (!ix->d_read_len || !ix->d_name_rank || ix->n_meta != ix->n_strings)
     return sigax_fail(SIGAX_E_STATE, "sigax_index_set_reads has not been called: overlaps with mismatches need the reads' name ranks");
   return SIGAX_OK;
@@ -23,124 +16,43 @@ int mmo_usable(const sigax_index* ix) {
 
 int check_params(const sigax_mmo_params* p) {
   if (!p) return sigax_fail(SIGAX_E_ARG, "params is NULL");
-  if (p->seed_length < 12 || p->seed_length > 64) return sigax_fail(SIGAX_E_ARG, "seed_length %u: 12..64", p->seed_length);
-  if (p->seed_stride < 1 || p->seed_stride > p->seed_length) return sigax_fail(SIGAX_E_ARG, "seed_stride %u: 1..seed_length", p->seed_stride);
-  if (p->max_seed_hits < 1 || p->max_seed_hits > 4096) return sigax_fail(SIGAX_E_ARG, "max_seed_hits %u: 1..4096", p->max_seed_hits);
-  if (p->min_overlap < 1) return sigax_fail(SIGAX_E_ARG, "min_overlap 0: from 1");
-  if (p->error_permille > 250) return sigax_fail(SIGAX_E_ARG, "error_permille %u: 0..250", p->error_permille);
-  if (p->max_candidates < 1 || p->max_candidates > 4096) return sigax_fail(SIGAX_E_ARG, "max_candidates %u: 1..4096", p->max_candidates);
-  if (p->max_read_len > SIGAX_PILE_MAX_LEN) return sigax_fail(SIGAX_E_ARG, "max_read_len %u: 0..%u", p->max_read_len, SIGAX_PILE_MAX_LEN);
-  if (p->reserved != 0) return sigax_fail(SIGAX_E_ARG, "reserved must be 0");
-  return SIGAX_OK;
+  return seeded_check_params(p->seed_length, p->seed_stride, p->max_seed_hits, p->min_overlap, p->error_permille, p->max_candidates,
+                             p->max_read_len, p->reserved);
 }
 
-sigax_mmo_params with_len(const sigax_mmo_params& p) {
-  sigax_mmo_params q = p;
-  if (q.max_read_len == 0) q.max_read_len = SIGAX_PILE_MAX_LEN;
-  return q;
-}
-
-struct MmoWork {
-  u64 seed_cap;
-  u64 seed_cnt, seed_start, partial, words, n_rec, n_flag, rec_offs, seed_bytes, seed_offs, totals, qflags, hit_offs, loc_work, loc_work_bytes,
-      hits, bytes;
+// the middle of the workspace: n_rec and n_flag, zeroed by the seeding stage (a read that ends early has none), then rec_offs;
+// words[1] = the records of the call
+struct MmoMiddle {
+  u64 n_rec, n_flag, rec_offs, bytes;
 };
-int mmo_work(u64 n, u64 n_bases, const sigax_mmo_params& p, u64 hits_cap, MmoWork* out) {
-  MmoWork w;
-  // a read of n bases has at most n / T + 1 seeds: (n - S) / T + 2 <= n / T + 1 with S >= T
-  w.seed_cap = n_bases / p.seed_stride + n;
-  if (w.seed_cap == 0) w.seed_cap = 1;
-  if (w.seed_cap > 0xFFFFFFFFull) return sigax_fail(SIGAX_E_ARG, "%llu seed slots: a hit names its seed in 32 bits", w.seed_cap);
-  if (hits_cap > LOCATE_MAX_SLOTS) return sigax_fail(SIGAX_E_ARG, "hits_cap above the %llu hits one call walks", LOCATE_MAX_SLOTS);
-  u64 at = 0;
-  w.seed_cnt = at;
-  at += up16(n * 4);
-  w.seed_start = at;
-  at += up16((n + 1) * 8);
-  w.partial = at;
-  at += up16(scan_partials_needed(n) * 8);
-  w.words = at;  // [0] seeds, [1] records of the call, [4..7] locate's status, [8..15] the call's counters
-  at += 128;
-  w.n_rec = at;
-  at += up16(n * 4);
-  w.n_flag = at;
-  at += up16(n * 4);
-  w.rec_offs = at;
-  at += up16((n + 1) * 8);
-  w.seed_bytes = at;
-  at += up16(w.seed_cap * p.seed_length + 16);
-  w.seed_offs = at;
-  at += up16((w.seed_cap + 1) * 8);
-  w.totals = at;
-  at += up16(w.seed_cap * 8);
-  w.qflags = at;
-  at += up16(w.seed_cap * 4);
-  w.hit_offs = at;
-  at += up16((w.seed_cap + 1) * 8);
-  w.loc_work = at;
-  uint64_t lw = 0;
-  const int rc = sigax_locate_workspace(w.seed_cap, &lw);
-  if (rc != SIGAX_OK) return rc;
-  w.loc_work_bytes = lw;
-  at += up16(lw);
-  w.hits = at;
-  at += hits_cap * 16;
-  w.bytes = at + 16;
-  *out = w;
-  return SIGAX_OK;
+MmoMiddle mmo_middle(u64 n) { return {0, up16(n * 4), 2 * up16(n * 4), 2 * up16(n * 4) + up16((n + 1) * 8)}; }
+int mmo_work(u64 n, u64 n_bases, const sigax_mmo_params& p, u64 hits_cap, SeedWork* out) {
+  return seed_work(n, n_bases, p.seed_length, p.seed_stride, hits_cap, mmo_middle(n).bytes, out);
 }
 
 // stages: 1 the seeds and their hits, 2 and k_mmo, 3 and the commit (the whole call)
 int mmo_enqueue(sigax_index* ix, const unsigned char* d_ref_text, const u64* d_ref_offs, u64 first, u64 n, const sigax_mmo_params& p,
-                sigax_mm_edge* d_edges, u64 edges_cap, u64* d_cursor, unsigned char* d_contained, u64* d_status, void* d_work, const MmoWork& w,
+                sigax_mm_edge* d_edges, u64 edges_cap, u64* d_cursor, unsigned char* d_contained, u64* d_status, void* d_work, const SeedWork& w,
                 u64 hits_cap, hipStream_t st, int stages = 3) {
   char* base = (char*)d_work;
   u64* words = (u64*)(base + w.words);
-  // the seeds of the pile-up: its two kernels over the reference text, reads first .. first + n
-  PileArgs s;
-  memset(&s, 0, sizeof(s));
-  s.seqs = d_ref_text;
-  s.offs = d_ref_offs + first;
-  s.n_reads = n;
-  s.p.seed_length = p.seed_length;
-  s.p.seed_stride = p.seed_stride;
-  s.p.max_read_len = p.max_read_len;
-  s.seed_cnt = (uint32_t*)(base + w.seed_cnt);
-  s.seed_start = (u64*)(base + w.seed_start);
-  s.seed_total = words;
-  s.seed_cap = w.seed_cap;
-  s.seed_bytes = (unsigned char*)(base + w.seed_bytes);
-  s.seed_offs = (u64*)(base + w.seed_offs);
-  HIP_TRY(hipMemsetAsync(words, 0, 128, st));
-  HIP_TRY(hipMemsetAsync(base + w.n_rec, 0, (size_t)(w.rec_offs - w.n_rec), st));  // n_rec and n_flag: a read that ends early has none
-  launch_pile_seed_count(s, st);
-  launch_scan(s.seed_cnt, n, (u64*)(base + w.partial), s.seed_start, s.seed_total, st);
-  launch_pile_seed_fill(s, st);
-  HIP_TRY(hipGetLastError());
-  const int rc = sigax_locate_device(ix, s.seed_bytes, s.seed_offs, w.seed_cap, SIGAX_RC, p.max_seed_hits, MMO_REF_MAX_LEN, base + w.totals,
-                                     base + w.qflags, base + w.hit_offs, base + w.hits, nullptr, hits_cap, words + 4, base + w.loc_work,
-                                     w.loc_work_bytes, st);
+  const MmoMiddle m = mmo_middle(n);
+  // the seeds of the reference text's reads first .. first + n
+  const int rc = seed_enqueue(ix, d_ref_text, d_ref_offs + first, n, p.seed_length, p.seed_stride, p.max_read_len, p.max_seed_hits, d_work, w,
+                              m.rec_offs, hits_cap, st);
   if (rc != SIGAX_OK) return rc;
   if (stages < 2) return SIGAX_OK;
   MmoArgs a;
-  a.ref_text = d_ref_text;
-  a.ref_offs = d_ref_offs;
-  a.n_ref = ix->n_strings;
+  a.R = {d_ref_text, d_ref_offs, ix->n_strings};
   a.name_rank = ix->d_name_rank;
   a.first_read = first;
   a.n_reads = n;
   a.p = p;
-  a.tab_cap = pile_tab_cap(p.max_candidates);
-  a.seed_start = s.seed_start;
-  a.seed_cap = w.seed_cap;
-  a.qflags = (const uint32_t*)(base + w.qflags);
-  a.hit_offs = (const u64*)(base + w.hit_offs);
-  a.hits = (uint4*)(base + w.hits);
-  a.hits_cap = hits_cap;
-  a.loc_status = words + 4;
-  a.n_rec = (uint32_t*)(base + w.n_rec);
-  a.n_flag = (uint32_t*)(base + w.n_flag);
-  a.rec_offs = (u64*)(base + w.rec_offs);
+  a.tab_cap = cand_tab_cap(p.max_candidates);
+  a.L = seed_hits<uint4>(d_work, w, hits_cap);
+  a.n_rec = (uint32_t*)(base + w.middle + m.n_rec);
+  a.n_flag = (uint32_t*)(base + w.middle + m.n_flag);
+  a.rec_offs = (u64*)(base + w.middle + m.rec_offs);
   a.rec_total = words + 1;
   a.edges = d_edges;
   a.edges_cap = edges_cap;
@@ -183,8 +95,9 @@ int mmoverlap_device(sigax_index* ix, const void* d_ref_text, const void* d_ref_
     return sigax_fail(SIGAX_E_ARG, "NULL where a buffer is required");
   if (((uintptr_t)d_work & 15) || ((uintptr_t)d_ref_offs & 7) || ((uintptr_t)d_cursor & 7) || ((uintptr_t)d_edges & 7))
     return sigax_fail(SIGAX_E_ARG, "d_work must be 16-byte aligned, d_ref_offs, d_cursor and d_edges 8-byte aligned");
-  MmoWork w;
-  const sigax_mmo_params p = with_len(*params);
+  SeedWork w;
+  sigax_mmo_params p = *params;
+  p.max_read_len = seeded_max_len(p.max_read_len);
   const int rw = mmo_work(n_reads, n_bases, p, hits_cap, &w);
   if (rw != SIGAX_OK) return rw;
   if (work_bytes < w.bytes) return sigax_fail(SIGAX_E_ARG, "workspace of %llu bytes, %llu needed (sigax_mmoverlap_workspace)", (u64)work_bytes, w.bytes);
@@ -254,7 +167,7 @@ extern "C" int sigax_mmoverlap_workspace(uint64_t n_reads, uint64_t n_bases, con
   if (!bytes) return sigax_fail(SIGAX_E_ARG, "bad argument");
   const int rc = check_params(params);
   if (rc != SIGAX_OK) return rc;
-  MmoWork w;
+  SeedWork w;
   const int rw = mmo_work(n_reads, n_bases, *params, hits_cap, &w);
   if (rw != SIGAX_OK) return rw;
   *bytes = w.bytes;
@@ -299,17 +212,8 @@ extern "C" int sigax_mmoverlap_finish_device(sigax_mm_edge* d_edges, uint64_t n_
   return finish_enqueue(d_edges, n_raw, (u64*)d_n_unique, d_work, w, (hipStream_t)stream);
 }
 
-namespace {
-
-// test hooks, read per call: reads a piece holds at most, the hits the first try of a piece has room for, the records the
-// first buffer has room for
-u64 env_u64(const char* name, u64 dflt) {
-  const char* v = getenv(name);
-  return v ? strtoull(v, nullptr, 10) : dflt;
-}
-
-}  // namespace
-
+// Test hooks, read per call: the reads a piece holds at most, the hits its first try has room for, the records the first buffer
+// has room for.
 extern "C" int sigax_mmoverlap_batch(sigax_index* ix, const sigax_pile_ref* ref, const sigax_mmo_params* params, sigax_mm_edge** edges,
                                      uint64_t* n_edges, uint8_t* contained, uint64_t status8[8]) {
   if (!ix || !ref || !edges || !n_edges) return sigax_fail(SIGAX_E_ARG, "bad argument");
@@ -335,11 +239,7 @@ extern "C" int sigax_mmoverlap_batch(sigax_index* ix, const sigax_pile_ref* ref,
   std::vector<u64> offs((size_t)n + 1);
   HIP_TRY(hipMemcpy(offs.data(), d_offs, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
   sigax_mmo_params p = *params;
-  if (p.max_read_len == 0) {
-    u64 longest = 1;
-    for (u64 i = 0; i < n; ++i) longest = std::max<u64>(longest, offs[i + 1] - offs[i]);
-    p.max_read_len = (uint32_t)std::min<u64>(longest, SIGAX_PILE_MAX_LEN);
-  }
+  p.max_read_len = seeded_max_len(p.max_read_len, offs.data(), n);
   const u64 piece_max = std::max<u64>(1, env_u64("SIGAX_TEST_MMO_PIECE", 1ull << 18));
   const u64 first_hits = env_u64("SIGAX_TEST_MMO_HITS_CAP", ~0ull);
   hipStream_t st = (hipStream_t)0;
@@ -368,11 +268,10 @@ extern "C" int sigax_mmoverlap_batch(sigax_index* ix, const sigax_pile_ref* ref,
     size_t mfree = 0, mtotal = 0;
     HIP_TRY(hipMemGetInfo(&mfree, &mtotal));
     const u64 budget = (u64)mfree / 2;
-    // the first try: room for 16 hits a base (some 20-fold cover at the default stride), no more than the budget holds
-    u64 hits_cap = first_hits != ~0ull ? first_hits : std::min<u64>(std::max<u64>(nb * 16, 4096), budget / 16);
+    u64 hits_cap = seeded_first_hits_cap(first_hits, nb, budget);
     bool done = false, split = false;
     for (int attempt = 0; attempt < 3 && !done && !split; ++attempt) {
-      MmoWork w;
+      SeedWork w;
       const int rw = mmo_work(cnt, nb, p, hits_cap, &w);
       if (rw != SIGAX_OK) return rw;
       if (w.bytes > budget && cnt > 1) {
@@ -387,13 +286,9 @@ extern "C" int sigax_mmoverlap_batch(sigax_index* ix, const sigax_pile_ref* ref,
       u64 status[8];
       HIP_TRY(hipMemcpyAsync(status, d_status, 64, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      if (status[0] > hits_cap) {  // nothing was written: size the hits from what the seeds list, or take fewer reads
-        if (status[0] > LOCATE_MAX_SLOTS || status[0] * 16 > budget) {
-          if (cnt == 1) return sigax_fail(SIGAX_E_CAPACITY, "one read lists %llu hits: they do not fit the device", status[0]);
-          split = true;
-        } else {
-          hits_cap = status[0];
-        }
+      if (status[0] > hits_cap) {
+        const int ro = seeded_hits_overflow(status[0], budget, cnt, &hits_cap, &split);
+        if (ro != SIGAX_OK) return ro;
         continue;
       }
       if (status[7] > edges_cap - cursor) {  // nothing was written: room for these and, at this rate, for the reads to come

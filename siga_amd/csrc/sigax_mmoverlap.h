@@ -1,5 +1,5 @@
 // siga_amd/csrc/sigax_mmoverlap.h -- argument blocks and launch wrappers shared by sigax_mmoverlap.hip and sigax_mmoverlap.cpp
-// (`siga overlap -e`).  The seeds and their hits come from sigax_pileup.h and sigax_locate_device.
+// (`siga overlap -e`).  The seeds, their hits and the reference text come from sigax_seeded.h.
 #ifndef SIGA_AMD_SIGAX_MMOVERLAP_H_
 #define SIGA_AMD_SIGAX_MMOVERLAP_H_
 
@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/sigax.h"
+#include "sigax_seeded.h"
 
 // counters of a call, in the caller's scratch (u64 each, zeroed before the call)
 enum { MMO_C_LENGTH = 0, MMO_C_OVER, MMO_C_LOCATED, MMO_C_REPEATS, MMO_C_TESTED, MMO_C_ACCEPTED, MMO_C_COUNT = 8 };
@@ -14,21 +15,12 @@ enum { MMO_C_LENGTH = 0, MMO_C_OVER, MMO_C_LOCATED, MMO_C_REPEATS, MMO_C_TESTED,
 // What k_mmo finds is on its way to k_mmo_commit in the place of the read's own hits, 16 bytes each: a record as {canonical query,
 // target, length, af | num_diff << 8}, a read to flag as {read id, 0, 0, 0}.
 struct MmoArgs {
-  const unsigned char* ref_text;         // the indexed reads by id: queries and candidates alike
-  const unsigned long long* ref_offs;    // [n_ref + 1]
-  unsigned long long n_ref;
+  RefText R;                             // the indexed reads by id: queries and candidates alike
   const uint32_t* name_rank;             // [n_ref]
   unsigned long long first_read, n_reads;
   sigax_mmo_params p;                    // max_read_len filled in
-  uint32_t tab_cap;                      // slots of a wave's table of candidates, a power of two (pile_tab_cap)
-  // seeds, and what locate left
-  const unsigned long long* seed_start;  // [n_reads + 1]
-  unsigned long long seed_cap;
-  const uint32_t* qflags;                // [seed_cap]
-  const unsigned long long* hit_offs;    // [seed_cap + 1]
-  uint4* hits;                           // [hits_cap]: read by k_mmo, then a read's own stretch holds what it found
-  unsigned long long hits_cap;
-  const unsigned long long* loc_status;  // 4 u64: [0] = hits listed
+  uint32_t tab_cap;                      // slots of a wave's table of candidates, a power of two (cand_tab_cap)
+  SeedHits<uint4> L;                     // the seeds' hits: read by k_mmo, then a read's own stretch holds what it found
   // found, per read of the call
   uint32_t* n_rec;                       // [n_reads]: records, from the front of the read's stretch of hits
   uint32_t* n_flag;                      // [n_reads]: read ids to flag, from the back of it

@@ -9,6 +9,9 @@
 //   k_mmo_status   the eight status words, and the cursor moved
 //   k_mmo_keys, k_mmo_keys2, k_mmo_gather, k_mmo_compact   the finish: two stable radix passes, repeats dropped
 //
+// The pieces k_mmo shares with k_pile (the table of candidate keys: cand_collect, cand_slot, cand_decode, cand_code; seed_span,
+// seed_flags) are sigax_seeded.h's.
+//
 // Shape of k_mmo.  A workgroup is one wave.  (1) As k_pile: the read's hits are taken 64 at a time, one per lane, and go as keys
 // {read, diagonal, strand} into an open-addressed table in dynamic LDS with a 64-bit compare-and-swap, which makes the triples
 // distinct; more than K ends the read.  (2) The read's own codes are held in registers, 2 bits a column: lane l has the columns
@@ -23,42 +26,10 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "sigax_device.h"
-#include "sigax_mmoverlap.h"
 #include "sigax_rank.h"
+#include "sigax_mmoverlap.h"
 
 namespace {
-
-#define MMO_EMPTY (~0ull)
-#define MMO_D_BIAS (1ll << 30)  // diagonals are kept as d + 2^30 in 31 bits: reference reads are shorter than 2^30 bases
-
-__device__ __forceinline__ u64 mmo_shfl64(u64 v, int src) {
-  return (u64)(u32)__shfl((int)(u32)v, src, 64) | ((u64)(u32)__shfl((int)(u32)(v >> 32), src, 64) << 32);
-}
-
-__device__ __forceinline__ u32 mmo_hash(u64 k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 29;
-  return (u32)k;
-}
-
-// the stretch of the hit list that belongs to read r of the call, and its seeds: all clamped to what the buffers hold
-struct MmoSpan {
-  u64 s0, s1, h0, h1;
-};
-__device__ __forceinline__ MmoSpan mmo_span(const MmoArgs& A, u64 r, u64 total_hits) {
-  MmoSpan sp;
-  sp.s0 = A.seed_start[r];
-  sp.s1 = A.seed_start[r + 1];
-  sp.s1 = sp.s1 < A.seed_cap ? sp.s1 : A.seed_cap;
-  sp.s0 = sp.s0 < sp.s1 ? sp.s0 : sp.s1;
-  sp.h0 = A.hit_offs[sp.s0];
-  sp.h1 = A.hit_offs[sp.s1];
-  sp.h1 = sp.h1 < total_hits ? sp.h1 : total_hits;
-  sp.h0 = sp.h0 < sp.h1 ? sp.h0 : sp.h1;
-  return sp;
-}
 
 __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
   extern __shared__ __align__(16) unsigned char mmo_lds[];
@@ -66,13 +37,13 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
 
   const u32 lane = threadIdx.x;
   const u64 r = blockIdx.x;
-  const u64 total_hits = A.loc_status[0];
-  if (total_hits > A.hits_cap) return;  // the caller's hits did not fit: nothing is written (sigax.h)
+  const u64 total_hits = A.L.loc_status[0];
+  if (total_hits > A.L.hits_cap) return;  // the caller's hits did not fit: nothing is written (sigax.h)
 
   const u32 S = A.p.seed_length, T = A.p.seed_stride;
   const u64 i = A.first_read + r;  // below n_ref (the host checks the range)
-  const u64 b0 = A.ref_offs[i], n64 = A.ref_offs[i + 1] - b0;
-  const unsigned char* q = A.ref_text + b0;
+  const u64 b0 = A.R.ref_offs[i], n64 = A.R.ref_offs[i + 1] - b0;
+  const unsigned char* q = A.R.ref_text + b0;
 
   // ---- rule 1 ----
   if (n64 < S || n64 > A.p.max_read_len) {
@@ -92,58 +63,14 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
       else q1 |= code << (2u * (c - 32u));
     }
   }
-  for (u32 s = lane; s < A.tab_cap; s += 64) tab[s] = MMO_EMPTY;
+  for (u32 s = lane; s < A.tab_cap; s += 64) tab[s] = CAND_EMPTY;
   __syncthreads();
 
   // ---- rule 2: the seeds' flags, and the hits into the table of distinct triples ----
-  const MmoSpan sp = mmo_span(A, r, total_hits);
-  u32 located = 0, repeats = 0;
-  for (u64 s = sp.s0 + lane; s < sp.s1; s += 64) {
-    const u32 f = A.qflags[s];
-    if (!(f & SIGAX_LOCATE_SKIPPED)) {
-      located += 1u;
-      if (f & SIGAX_LOCATE_OVER) repeats += 1u;
-    }
-  }
-  const u32 n_reg = (n - S) / T + 1u, n_seeds = (u32)(sp.s1 - sp.s0), tmask = A.tab_cap - 1u;
-  u32 n_dist = 0;
-  bool over = false;
-  for (u64 base = sp.h0; base < sp.h1; base += 64) {
-    const u64 at = base + lane;
-    u32 ins = 0;
-    if (at < sp.h1) {
-      const uint4 h = A.hits[at];  // {seed, read, offset, flags}
-      const u32 j = h.x - (u32)sp.s0;
-      if (!(h.w & SIGAX_HIT_CUT) && (u64)h.y < A.n_ref && j < n_seeds) {
-        const long long p = j < n_reg ? (long long)j * T : (long long)(n - S);
-        long long d;
-        if (h.w & SIGAX_HIT_REV) {
-          const long long len_t = (long long)(A.ref_offs[(u64)h.y + 1] - A.ref_offs[h.y]);
-          d = len_t - (long long)h.z - (long long)S - p;
-        } else {
-          d = (long long)h.z - p;
-        }
-        if (d >= -MMO_D_BIAS && d < MMO_D_BIAS) {
-          const u64 key = ((u64)h.y << 32) | ((u64)(u32)(d + MMO_D_BIAS) << 1) | ((h.w & SIGAX_HIT_REV) ? 1ull : 0ull);
-          u32 slot = mmo_hash(key) & tmask;
-          for (u32 probe = 0; probe < A.tab_cap; ++probe) {  // the table is never full: at most K + 64 keys in (K + 64) 4/3 slots
-            const u64 old = atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot]), MMO_EMPTY, key);
-            if (old == MMO_EMPTY) {
-              ins = 1u;
-              break;
-            }
-            if (old == key) break;
-            slot = (slot + 1u) & tmask;
-          }
-        }
-      }
-    }
-    n_dist += (u32)wave_sum((u64)ins);
-    if (n_dist > A.p.max_candidates) {
-      over = true;
-      break;
-    }
-  }
+  const SeedSpan sp = seed_span(A.L, r, total_hits);
+  u32 located, repeats;
+  seed_flags(A.L, sp, lane, located, repeats);
+  const bool over = cand_collect(tab, A.tab_cap, A.L, sp, A.R, n, S, T, A.p.max_candidates, lane);
   wave_add(&A.counters[MMO_C_LOCATED], (u64)located);
   wave_add(&A.counters[MMO_C_REPEATS], (u64)repeats);
   if (over) {
@@ -156,41 +83,30 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
   const u64 room = sp.h1 - sp.h0;  // results fit: a candidate gives at most one and comes from at least one hit
   u32 tested = 0, taken = 0, n_rec = 0, n_flag = 0;
   for (u32 base = 0; base < A.tab_cap; base += 64) {
-    const u64 key = tab[base + lane];
-    const bool has = key != MMO_EMPTY;
-    u64 rb = 0;
-    u32 len_t = 0, rank_t = 0;
-    if (has) {  // (a key's read is below n_ref)
-      const u64 t = key >> 32;
-      rb = A.ref_offs[t];
-      len_t = (u32)(A.ref_offs[t + 1] - rb);
-      rank_t = A.name_rank[t];
-    }
+    u64 key, rb;
+    u32 len_t, rank_t = 0;
+    const bool has = cand_slot(tab, base + lane, A.R, key, rb, len_t, [&](u64 t) { rank_t = A.name_rank[t]; });
     u64 mask = __ballot(has && rank_t != rank_q);  // rule 3
     uint4 my_rec = make_uint4(0, 0, 0, 0);
     u32 my_flag = 0, s_rec = 0, s_flag = 0;  // this sweep's results: the k-th of a kind with lane k
     while (mask) {
       const int src = __ffsll((long long)mask) - 1;
       mask &= mask - 1ull;
-      const u64 k = mmo_shfl64(key, src), crb = mmo_shfl64(rb, src);
-      const long long clen = (long long)(u32)__shfl((int)len_t, src, 64);
-      const u32 crank = (u32)__shfl((int)rank_t, src, 64);
-      const u32 t = (u32)(k >> 32);
-      const bool rev = (k & 1ull) != 0ull;
-      const long long d = (long long)(((u32)k) >> 1) - MMO_D_BIAS;
-      const long long x0 = d < 0 ? -d : 0, x1 = (clen - d) < (long long)n ? (clen - d) : (long long)n;
+      const Cand k = cand_decode(key, rb, len_t, src, n);
+      const u32 crank = (u32)__shfl((int)rank_t, src, 64), t = k.t;
+      const bool rev = k.rev;
+      const long long d = k.d, x0 = k.x0, x1 = k.x1, clen = k.clen;
       if (x1 <= x0) continue;  // (a hit's window lies in both texts: there is an overlap)
       const u32 ell = (u32)(x1 - x0);
       tested += 1u;
       if (ell < A.p.min_overlap) continue;
-      const unsigned char* text = A.ref_text + crb;
+      const unsigned char* text = A.R.ref_text + k.rb;
       u32 mism = 0;
       for (u32 c = (u32)x0 >> 6; c <= ((u32)x1 - 1u) >> 6; ++c) {  // x0 < x1 <= n <= 4096
         const long long x = (long long)(c * 64u + lane);
         if (x >= x0 && x < x1) {
           const long long pos = x + d;  // in [0, clen)
-          u32 code = (base_rank(rev ? text[clen - 1 - pos] : text[pos]) - 1u) & 3u;
-          code = rev ? 3u - code : code;
+          const u32 code = cand_code(text, clen, pos, rev);
           const u32 mine = (u32)((c < 32u ? q0 >> (2u * c) : q1 >> (2u * (c - 32u))) & 3ull);
           mism += code != mine ? 1u : 0u;
         }
@@ -217,8 +133,8 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
         s_rec += 1u;
       }
     }
-    if (lane < s_rec && (u64)(n_rec + lane) < room) A.hits[sp.h0 + n_rec + lane] = my_rec;
-    if (lane < s_flag && (u64)(n_flag + lane) < room) A.hits[sp.h1 - 1 - (n_flag + lane)] = make_uint4(my_flag, 0, 0, 0);
+    if (lane < s_rec && (u64)(n_rec + lane) < room) A.L.hits[sp.h0 + n_rec + lane] = my_rec;
+    if (lane < s_flag && (u64)(n_flag + lane) < room) A.L.hits[sp.h1 - 1 - (n_flag + lane)] = make_uint4(my_flag, 0, 0, 0);
     n_rec += s_rec;
     n_flag += s_flag;
   }
@@ -234,7 +150,7 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
 __device__ __forceinline__ bool mmo_fits(const MmoArgs& A, u64* cursor0) {
   const u64 c = *A.cursor;
   *cursor0 = c;
-  return A.loc_status[0] <= A.hits_cap && c <= A.edges_cap && *A.rec_total <= A.edges_cap - c;
+  return A.L.loc_status[0] <= A.L.hits_cap && c <= A.edges_cap && *A.rec_total <= A.edges_cap - c;
 }
 
 __global__ __launch_bounds__(256) void k_mmo_commit(MmoArgs A) {
@@ -243,14 +159,14 @@ __global__ __launch_bounds__(256) void k_mmo_commit(MmoArgs A) {
   if (r >= A.n_reads) return;
   u64 cursor0;
   if (!mmo_fits(A, &cursor0)) return;
-  const MmoSpan sp = mmo_span(A, r, A.loc_status[0]);
+  const SeedSpan sp = seed_span(A.L, r, A.L.loc_status[0]);
   const u64 room = sp.h1 - sp.h0;
   u64 n_rec = A.n_rec[r], n_flag = A.n_flag[r];
   n_rec = n_rec < room ? n_rec : room;
   n_flag = n_flag < room - n_rec ? n_flag : room - n_rec;
   const u64 out0 = cursor0 + A.rec_offs[r];
   for (u64 k = lane; k < n_rec; k += 64) {
-    const uint4 v = A.hits[sp.h0 + k];
+    const uint4 v = A.L.hits[sp.h0 + k];
     sigax_mm_edge e;
     e.query = v.x;
     e.target = v.y;
@@ -261,15 +177,15 @@ __global__ __launch_bounds__(256) void k_mmo_commit(MmoArgs A) {
     if (out0 + k < A.edges_cap) A.edges[out0 + k] = e;  // (it is: the total fits)
   }
   for (u64 k = lane; k < n_flag; k += 64) {
-    const u32 id = A.hits[sp.h1 - 1 - k].x;
-    if ((u64)id < A.n_ref) A.contained[id] = 1;
+    const u32 id = A.L.hits[sp.h1 - 1 - k].x;
+    if ((u64)id < A.R.n_ref) A.contained[id] = 1;
   }
 }
 
 __global__ void k_mmo_status(MmoArgs A) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const u64 hits = A.loc_status[0];
-  const bool listed = hits <= A.hits_cap;
+  const u64 hits = A.L.loc_status[0];
+  const bool listed = hits <= A.L.hits_cap;
   u64 cursor0;
   const bool fits = mmo_fits(A, &cursor0);
   A.status[0] = hits;
@@ -335,16 +251,7 @@ __global__ __launch_bounds__(256) void k_mmo_compact(MmoFinishArgs A) {
 
 uint32_t mmo_lds_bytes(uint32_t tab_cap) { return tab_cap * 8u; }
 
-int launch_mmo(const MmoArgs& a, hipStream_t st) {
-  if (a.n_reads == 0) return (int)hipSuccess;
-  const uint32_t lds = mmo_lds_bytes(a.tab_cap);
-  if (lds > 32768u) {  // above what a launch gets unasked: up to the 160 KiB of a CDNA4 compute unit
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mmo), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(k_mmo, dim3((unsigned)a.n_reads), dim3(64), lds, st, a);
-  return (int)hipSuccess;
-}
+int launch_mmo(const MmoArgs& a, hipStream_t st) { return launch_wave_lds(k_mmo, a, a.n_reads, mmo_lds_bytes(a.tab_cap), st); }
 
 void launch_mmo_commit(const MmoArgs& a, hipStream_t st) {
   if (a.n_reads) hipLaunchKernelGGL(k_mmo_commit, dim3((unsigned)((a.n_reads + 3) / 4)), dim3(256), 0, st, a);

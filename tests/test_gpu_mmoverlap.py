@@ -78,13 +78,20 @@ class _Calls:
         self.d_cursor = self.dev.buf(8, np.zeros(1, dtype=np.uint64))
         self.d_contained = self.dev.buf(len(refs), np.zeros(len(refs), dtype=np.uint8))
 
-    def call(self, p, first, count, hits_cap):
-        """-> status8"""
+    def workspace(self, p, count, nb, hits_cap):
+        """-> (d_work, its bytes) for calls of at most these sizes"""
+        wb = C.c_uint64()
+        assert self.L.sigax_mmoverlap_workspace(count, nb, C.byref(_params(p)), hits_cap, C.byref(wb)) == 0, self._lib.last_error()
+        return self.dev.buf(wb.value), wb.value
+
+    def call(self, p, first, count, hits_cap, work=None):
+        """-> status8; work: a workspace() to run in, as whatever ran there before has left it, in place of fresh memory"""
         nb = sum(len(r) for r in self.refs[first:first + count])
         params = _params(p)
         wb = C.c_uint64()
         assert self.L.sigax_mmoverlap_workspace(count, nb, C.byref(params), hits_cap, C.byref(wb)) == 0, self._lib.last_error()
-        d_stat, d_work = self.dev.buf(64), self.dev.buf(wb.value)
+        d_stat, d_work = self.dev.buf(64), work[0] if work else self.dev.buf(wb.value)
+        assert not work or wb.value <= work[1]
         assert self.dev.hip.hipDeviceSynchronize() == 0
         assert self.L.sigax_mmoverlap_device(self.pair.handle, self.d_text, self.d_toffs, first, count, nb, C.byref(params), self.d_edges,
                                              self.edges_cap, self.d_cursor, self.d_contained, d_stat, d_work, wb.value, hits_cap,
@@ -175,6 +182,18 @@ def test_every_boundary_set():
         assert want[0] == records and [i for i, c in enumerate(want[1]) if c] == flagged, name
 
 
+def test_query_columns_from_2048_on():
+    """a read of 4096 bases whose partners lie at its columns 2048 and above, where its codes are in the second register: a
+    forward and a reverse-complemented read that dovetail with its last 60 columns, the first with a mismatch among them, and a
+    read wholly inside"""
+    g = pc.random_genome(4300, 23)
+    fwd = pc.mutate(g[4036:4156], [30])
+    refs = [g[0:4096], fwd, pc.revcomp(g[4036:4096] + pc.random_genome(54, 24)), g[3000:3120]]
+    names = ["d", "c", "b", "a"]
+    want = _check_forms(refs, names, mc.params())
+    assert want[0] == [(0, 1, 60, 0, 1), (0, 2, 60, 6, 0)] and want[1] == [0, 0, 0, 1]
+
+
 def test_seeded_equals_brute_force_on_the_device():
     refs, names = mc.noisy_case()
     p = mc.params(S=12, T=4, M=45, P=40, H=4096, K=4096)
@@ -199,6 +218,7 @@ def test_read_over_k_and_seed_over_h():
 
 
 def test_two_calls_at_one_cursor_equal_one():
+    """... the second one, of fewer reads, in the workspace the first one has used"""
     refs, names, ranks = _mixed()
     p = mc.params()
     whole = mc.expected_mm_overlaps(refs, ranks, p)
@@ -209,9 +229,11 @@ def test_two_calls_at_one_cursor_equal_one():
     pair = _open(refs, names)
     calls = _Calls(pair, refs, whole[2][7])
     try:
-        assert calls.call(p, 0, half, a[2][0]) == a[2]
+        assert len(refs) - half < half
+        work = calls.workspace(p, half, sum(len(r) for r in refs), max(a[2][0], b[2][0]))
+        assert calls.call(p, 0, half, a[2][0], work) == a[2]
         assert calls.cursor() == a[2][7]
-        assert calls.call(p, half, len(refs) - half, b[2][0]) == b[2]  # first_read not 0
+        assert calls.call(p, half, len(refs) - half, b[2][0], work) == b[2]  # first_read not 0
         assert calls.cursor() == whole[2][7] and calls.contained() == whole[1]
         assert calls.finish() == whole[0]
     finally:

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 FIELDS = dict(S="seed_length", T="seed_stride", H="max_seed_hits", M="min_overlap", P="error_permille", C="conflict", D="min_depth",
               K="max_candidates", max_len="max_read_len")
 G = pc.random_genome(400, 77)
+REF_TEXT_SIZES = (300, 30239, 9680)  # (reads, text bytes, workspace bytes) of _random()'s reference set
 
 
 def _kw(p, max_len=False):
@@ -76,9 +77,10 @@ class _Device:
             self.hip.hipFree(q)
 
 
-def _device_round(pair, queries, p, hits_cap, lead=b"", max_len=False):
+def _device_round(pair, queries, p, hits_cap, lead=b"", max_len=False, then=None):
     """one sigax_pileup_device call on a stream -> (sequences as one bytes object, valid, changed, status8); `lead`: bytes in
-    front of the first read, so that the offsets do not start at 0"""
+    front of the first read, so that the offsets do not start at 0; then = (queries, hits_cap): a second call over the same d_work,
+    as the first one has left it, and the result is the second call's"""
     from siga_amd import _lib
     L = _lib.lib()
     dev = _Device()
@@ -89,22 +91,29 @@ def _device_round(pair, queries, p, hits_cap, lead=b"", max_len=False):
     try:
         d_text, d_toffs = C.c_void_p(), C.c_void_p()
         assert L.sigax_pile_ref_buffers(ref, C.byref(d_text), C.byref(d_toffs), None) == 0
-        buf, offs = po.pack_reads(queries)
-        buf = np.frombuffer(lead + buf, dtype=np.uint8)
-        offs = offs + np.uint64(len(lead))
-        n, nb = len(queries), int(offs[-1] - offs[0])
-        params = _lib.PileParams(**_kw(p, max_len))
-        wb = C.c_uint64()
-        assert L.sigax_pileup_workspace(n, nb, C.byref(params), hits_cap, C.byref(wb)) == 0, _lib.last_error()
-        d_seqs, d_offs = dev.buf(buf.nbytes, buf), dev.buf(offs.nbytes, offs)
-        d_out, d_valid, d_changed = dev.buf(buf.nbytes), dev.buf(n), dev.buf(n)
-        d_stat, d_work = dev.buf(64), dev.buf(wb.value)
-        assert dev.hip.hipDeviceSynchronize() == 0
-        assert L.sigax_pileup_device(pair.handle, d_seqs, d_offs, n, nb, C.byref(params), d_text, d_toffs, d_out, d_valid, d_changed, d_stat,
-                                     d_work, wb.value, hits_cap, stream) == 0, _lib.last_error()
-        assert dev.hip.hipStreamSynchronize(stream) == 0
-        return (dev.get(d_out, np.uint8, buf.nbytes).tobytes(), dev.get(d_valid, np.uint8, n), dev.get(d_changed, np.uint8, n),
-                dev.get(d_stat, np.uint64, 8))
+        d_work, work_bytes = None, 0
+        for queries, hits_cap in [(queries, hits_cap)] + ([then] if then else []):
+            buf, offs = po.pack_reads(queries)
+            buf = np.frombuffer(lead + buf, dtype=np.uint8)
+            offs = offs + np.uint64(len(lead))
+            n, nb = len(queries), int(offs[-1] - offs[0])
+            params = _lib.PileParams(**_kw(p, max_len))
+            wb = C.c_uint64()
+            assert L.sigax_pileup_workspace(n, nb, C.byref(params), hits_cap, C.byref(wb)) == 0, _lib.last_error()
+            if d_work is None:
+                d_work, work_bytes = dev.buf(wb.value), wb.value
+            assert wb.value <= work_bytes
+            d_seqs, d_offs = dev.buf(buf.nbytes, buf), dev.buf(offs.nbytes, offs)
+            d_out, d_valid, d_changed = dev.buf(buf.nbytes), dev.buf(n), dev.buf(n)
+            d_stat = dev.buf(64)
+            assert dev.hip.hipDeviceSynchronize() == 0
+            assert L.sigax_pileup_device(pair.handle, d_seqs, d_offs, n, nb, C.byref(params), d_text, d_toffs, d_out, d_valid, d_changed, d_stat,
+                                         d_work, wb.value, hits_cap, stream) == 0, _lib.last_error()
+            assert dev.hip.hipStreamSynchronize(stream) == 0
+            got = (dev.get(d_out, np.uint8, buf.nbytes).tobytes(), dev.get(d_valid, np.uint8, n), dev.get(d_changed, np.uint8, n),
+                   dev.get(d_stat, np.uint64, 8))
+            assert not then or got[3][0] <= hits_cap  # with a second call to come, the first one ran through
+        return got
     finally:
         L.sigax_pile_ref_destroy(ref)
         dev.free()
@@ -180,6 +189,38 @@ def test_reference_text_is_the_reads():
         assert L.sigax_reference_text_device(pair.handle, None, tb.value, d_offs, d_stat, d_work, wb.value, None) == _lib.SIGAX_E_ARG
     finally:
         dev.free()
+        pair.close()
+
+
+def test_reference_text_workspace_sizes():
+    """the two sizes for _random()'s reference set, as recorded before the reference text moved to sigax_seeded.cpp"""
+    from siga_amd import _lib
+    refs, _ = _random()
+    pair = _open(refs)
+    try:
+        tb, wb = C.c_uint64(), C.c_uint64()
+        assert _lib.lib().sigax_reference_text_workspace(pair.handle, C.byref(tb), C.byref(wb)) == 0
+        assert (len(refs), tb.value, wb.value) == REF_TEXT_SIZES
+    finally:
+        pair.close()
+
+
+def test_two_calls_in_one_workspace():
+    """a call with fewer reads over the d_work of an earlier one gives what it gives in fresh memory: the seeding stage zeroes
+    what the kernels behind it take as zero"""
+    refs, queries = _random()
+    p = pc.params(C=3)
+    few = queries[5:40:3]
+    outs, valid, changed, st = pc.expected_round(refs, few, p)
+    pair = _open(refs)
+    try:
+        fresh = _device_round(pair, few, p, st[0], max_len=True)
+        again = _device_round(pair, queries, p, 1 << 18, max_len=True, then=(few, st[0]))
+        for got in (fresh, again):
+            assert got[0].decode() == "".join(outs)
+            assert got[1].tolist() == valid and got[2].tolist() == changed and got[3].tolist() == st
+        assert st[5] > st[6] > 0 and 1 in changed
+    finally:
         pair.close()
 
 
@@ -276,6 +317,17 @@ def test_longest_read_and_one_above():
     want = _check_forms(refs, [q, g[100:101 + top], g[300:400]], p)
     assert want["valid"] == [1, 2, 1] and want["seqs"][0] == g[100:100 + top] and want["status"][1] == 1
     assert want["status"][7] == 3
+
+
+def test_reverse_candidates_across_column_2048():
+    """a read of 4096 bases under 200-base reads of which every second one is reverse-complemented, with substitutions below
+    and from column 2048 on: the second held word of a candidate together with the reversed text"""
+    g = pc.random_genome(5000, 3)
+    refs = [g[o:o + 200] if k % 2 else pc.revcomp(g[o:o + 200]) for k, o in enumerate(range(0, 4800, 50))]
+    top = pc.PILE_MAX_LEN
+    q = pc.mutate(g[100:100 + top], [7, 1000, 2047, 2048, 2111, 4000, 4090])
+    want = _check_forms(refs, [q], pc.params(C=3, D=1))
+    assert want["valid"] == [1] and want["seqs"] == [g[100:100 + top]] and want["status"][7] == 7
 
 
 def test_rounds():

@@ -10,7 +10,8 @@ substitutions tools/e2e_aux.py and tools/pileup_bench.py draw.
   1 % set     recall at the default seeds (24, 12) and at (16, 4): records found over the true overlaps the reads' places in the
               genome imply (length >= M, mismatches within P, neither read inside the other), and the seconds each setting takes
               through the batch call
-One JSON document on stdout (and in --out).  Needs a GPU; nothing but this repository.
+One JSON document on stdout (and in --out).  Needs a GPU; nothing but this repository.  --device-only measures the device
+section of the 1 % set alone (for A/B runs of two builds of the library, SIGAX_LIB selecting one).
 
     python tools/mmoverlap_bench.py --out profiles/mmoverlap_configs1.json
 """
@@ -204,6 +205,15 @@ def true_overlaps(noisy, pos, rev, K, M, P):
     return np.unique(np.concatenate(keys)) if keys else np.zeros(0, dtype=np.uint64)
 
 
+def emit(result, out):
+    text = json.dumps(result, indent=1)
+    print(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1000000)
@@ -215,6 +225,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--device-only", action="store_true")
     args = ap.parse_args()
 
     import siga_amd
@@ -233,6 +244,14 @@ def main():
                          "error_permille": P, "steps": args.steps, "warmup": args.warmup}}
 
     with tempfile.TemporaryDirectory() as d:
+        if args.device_only:
+            prefix = os.path.join(d, "noisy")
+            host.index_build_gpu(noisy.reshape(-1), offs, prefix)
+            pair = siga_amd.FMIndexPair.load_forward(prefix, device=0)
+            pair.set_reads(lengths, ranks)
+            result["noisy_defaults"] = device_times(hip, L, pair, N, N * K, _lib.MmoParams(P, min_overlap=M, max_read_len=K), args.steps, args.warmup)[0]
+            pair.close()
+            return emit(result, args.out)
         # ---- error-free, -e 0 ----
         prefix = os.path.join(d, "clean")
         host.index_build_gpu(reads.reshape(-1), offs, prefix)
@@ -273,12 +292,7 @@ def main():
                            "status8": [int(v) for v in st]})
         pair.close()
         result["noisy_recall"] = recall
-    text = json.dumps(result, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    return emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@ the set tools/e2e_aux.py draws; the index is built from the noisy reads, and the
   accuracy    through the command line: reads written and wrong bases before and after for `-a kmer`, `-a overlap`, and `-a kmer`
               followed by `-a overlap` over the reads the k-mer path dropped; reads over --max-candidates and seeds over
               --max-seed-hits at the defaults
-One JSON document on stdout (and in --out).  Needs a GPU; nothing but this repository.
+One JSON document on stdout (and in --out).  Needs a GPU; nothing but this repository.  --device-only ends after the device
+section (for A/B runs of two builds of the library, SIGAX_LIB selecting one).
 
     python tools/pileup_bench.py --out profiles/pileup_configs1.json
 """
@@ -146,6 +147,15 @@ def parse(path, length):
     return ids, np.frombuffer(b"".join(seqs[:len(ids)]), dtype=np.uint8).reshape(-1, length)
 
 
+def emit(result, out):
+    text = json.dumps(result, indent=1)
+    print(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1000000)
@@ -156,6 +166,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--device-only", action="store_true")
     args = ap.parse_args()
 
     import siga_amd
@@ -194,6 +205,8 @@ def main():
         pair = siga_amd.FMIndexPair.load_forward(prefix, device=0)
         result["device"] = device_times(hip, L, pair.handle, noisy.reshape(-1), offs, params, args.steps, args.warmup)
         pair.close()
+        if args.device_only:
+            return emit(result, args.out)
         t, note = run(["-a", "kmer", "-k", "31", "-p", prefix, "-o", "kmer.fa", "noisy.fa"], d)
         kmer, kept = score(os.path.join(d, "kmer.fa"), "kmer", t, note)
         t, note = run(["-a", "overlap", "-i", str(args.rounds), "-p", prefix, "-o", "overlap.fa", "noisy.fa"], d)
@@ -209,12 +222,7 @@ def main():
         result["kmer_dropped"] = int(len(dropped))
     st = result["device"]["status8"]
     result["caps_at_defaults"] = {"reads_over_max_candidates": st[2], "seeds_located": st[3], "seeds_over_max_seed_hits": st[4]}
-    text = json.dumps(result, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    return emit(result, args.out)
 
 
 if __name__ == "__main__":
