@@ -1,6 +1,6 @@
 // siga_amd/csrc/sigax_device.h -- the small pieces the kernels of `siga unitig` and of the assembly behind it share
-// (sigax_unitig.hip, sigax_pairs.hip, sigax_scaffold.hip, sigax_gapfill.hip, sigax_join.hip; sigax_rank.h takes its wave sum from
-// here, sigax_seeded.h its 64-bit shuffle), each piece once:
+// (sigax_unitig.hip, sigax_pairs.hip, sigax_scaffold.hip, sigax_gapfill.hip, sigax_join.hip; sigax_fm.h, and through it sigax_rank.h
+// and the kernels of sigax_kernels.hip, take the typedefs and the wave sum from here, sigax_seeded.h its 64-bit shuffle), each piece once:
 //   waves       wave_sum, wave_min32, wave_max32; wave_add: a wave's sum added once, by lane 0, when it is not zero; shfl64
 //   counters    a counter block is TRIM_SLOTS partial sums per counter, TRIM_STRIDE words apart (sigax_kernels.h): counter_slot,
 //               counter_total

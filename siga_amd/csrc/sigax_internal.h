@@ -80,7 +80,8 @@ extern "C" int sigax_scaffold_bases_device(int device, const void* d_n_unitigs, 
 // ------------------------------------------------------------------------------------------------------
 // The SIGAX_* switches of the host code, read once, at the first settings() call: nothing sets one in-process after the
 // library has loaded.  Read elsewhere: SIGAX_BUILD_GROUP (sigax_index_build.hip, per call: a test changes it between
-// calls) and the launch switches of sigax_kernels.hip.  INTEGRATION.md lists them all.
+// calls) and the launch switches of sigax_kernels.hip (finder and filter/extract; sigax_tables.hip and sigax_tail.hip have
+// none).  INTEGRATION.md lists them all.
 // ------------------------------------------------------------------------------------------------------
 struct Settings {
   static bool set(const char* v) { return v != nullptr; }     // present, whatever its value

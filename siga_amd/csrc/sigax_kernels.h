@@ -1,4 +1,6 @@
-// siga_amd/csrc/sigax_kernels.h -- argument blocks and launch wrappers shared by sigax_kernels.hip and sigax_api.cpp
+// siga_amd/csrc/sigax_kernels.h -- argument blocks and launch wrappers that the kernel files (sigax_kernels.hip: finder,
+// filter/extract, corrector; sigax_tables.hip: index tables; sigax_tail.hip: scan, ordered copy, edge records; and the files of
+// the later commands) share with the host code that launches them
 #ifndef SIGA_AMD_SIGAX_KERNELS_H_
 #define SIGA_AMD_SIGAX_KERNELS_H_
 
@@ -37,7 +39,7 @@ enum {
 };
 #define SIGAX_MAX_SUB 8
 
-struct Ent;  // defined in sigax_kernels.hip (48 bytes)
+struct Ent;  // defined in sigax_kernels.hip, with filter/extract (48 bytes)
 #define SIGAX_ENT_BYTES 48
 
 struct FindArgs {

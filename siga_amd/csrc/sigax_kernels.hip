@@ -4,195 +4,31 @@
 //   k_filter_extract  SubMaximalBlockFilter + ContainmentBlockRemover + IrreducibleBlockListExtractor +
 //                     the list plumbing of OverlapBuilder::overlap           (src/overlap_builder.cpp:706-836,
 //                                                                             914-1182)
-//   k_order_*         ordered compaction of the per-read block lists (replaces the hits text round trip,
-//                     src/overlap_builder.cpp:234-254,269-280)
-//   k_edge_*          Hit2OverlapConverter::convert                          (src/overlap_builder.cpp:345-375)
-//   k_occ_batch       FMIndex::getOcc                                        (src/fmindex.cpp:188-231,320-323)
-//   k_kmer_count      FMIndex::Interval::occurrences                         (src/fmindex.h:67-86)
+//   k_prefix_build, k_correct   KmerCorrector::process of `siga correct`     (src/correct_processor.cpp:81-229)
+// with their launch wrappers, size functions and getenv switches (sigax_kernels.h).
+//
+// What is where:
+//   sigax_fm.h        how device code reads an index, each piece once: rank views (FmRef, fm_rank*), the readers of the row,
+//                     text and deep start tables, the candidate record (Cand), SIGAX_NT, nblk
+//   sigax_kernels.hip this file: finder (k_find_n, _n2, _c2, _c2w, _w, and what only they share: Gran, Gran2, rank2_from,
+//                     find_step_loads*, fm_rank4p_from), filter/extract in its general and lane-group forms (k_filter_extract,
+//                     k_filter_extract_fast, k_fx_route; Ent), corrector
+//   sigax_tables.hip  the kernels that build the index's tables, k_occ_batch, k_kmer_count; launch_build2
+//   sigax_tail.hip    scan, ordered copy (k_order_scatter), edge records (k_edges_stage, k_edges_emit)
+//
+// The finder, filter/extract and the corrector stay in THIS file: bench.py hashes it (kernels_sha: this file and fm_layout.h)
+// and keys the traffic figures of k_find, k_filter_extract_fast and k_correct in profiles/traffic.json to that hash.  Moving
+// one of them out, k_correct next to sigax_correct.cpp for instance, would leave its figure stamped valid for sources the
+// hash no longer sees: not before the hash can follow (tests/test_build_lists.py holds the three definitions here).
 //
 // Integer / index work only: HBM- and latency-bound gathers of 64-byte rank granules (fm_layout.h); no MFMA.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "sigax_kernels.h"
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-// Non-temporal hints on data that passes through once -- the finder's candidate records on their way out (bit 2), the
-// records on their way into filter/extract (4), the row-table line a block looks up (1): they leave more of the caches to
-// the finder's tables.  Measured at BASELINE configs[1] (gpurun_out/r3w/): 118.6 M reads/s without, 119.4-120.5 M with one
-// of them, 121.0 M with all three; nothing at the configs[2] shape.  -DSIGAX_NT=0 turns them off.
-#ifndef SIGAX_NT
-#define SIGAX_NT 7
-#endif
-
-// -------------------------------------------------------------------------------------------------------
-// rank: number of A,C,G,T in BWT[0, p)   == FMIndex::getOcc(p - 1) without the '$' column
-// -------------------------------------------------------------------------------------------------------
-struct Cnt4 {
-  u64 a, c, g, t;
-};
-
-// Position type of an index: u32 while the BWT has fewer than 2^32 symbols (half the registers and ALU work), else u64.
-template <bool WIDE> struct PosOf { typedef u32 type; };
-template <> struct PosOf<true> { typedef u64 type; };
-template <typename P> struct Cnt4P {
-  P a, c, g, t;
-};
-
-// A candidate block as the finder leaves it in the arena: one naturally aligned record (32 B with u32 positions, 64 B
-// with u64) = one or two 16-byte stores per half instead of the five scattered ones of an 80-byte sigax_block.
-//   capped[0] = [c0lo, c0lo + d - 1], capped[1] = [c1lo, c1lo + d - 1]   (both intervals of a pair have one size)
-//   raw[0]    = [r0lo, r0lo + sz - 1], raw[1]   = [r1lo, r1lo + sz - 1]
-template <bool WIDE> struct Cand;
-template <> struct __attribute__((aligned(32))) Cand<false> {
-  u32 c0lo, d, c1lo, r0lo, r1lo, sz, len, af;
-};
-template <> struct __attribute__((aligned(64))) Cand<true> {
-  u64 c0lo, d, c1lo, r0lo, r1lo, sz;
-  u32 len, af;
-  u64 pad;
-};
-static_assert(sizeof(Cand<false>) == 32 && sizeof(Cand<true>) == 64, "candidate record sizes");
-
-__device__ __forceinline__ void cand_store(Cand<false>* dst, u32 c0lo, u32 d, u32 c1lo, u32 r0lo, u32 r1lo, u32 sz, u32 len, u32 af) {
-  uint4* q = reinterpret_cast<uint4*>(dst);
-  q[0] = make_uint4(c0lo, d, c1lo, r0lo);
-  q[1] = make_uint4(r1lo, sz, len, af);
-}
-__device__ __forceinline__ void cand_store(Cand<true>* dst, u64 c0lo, u64 d, u64 c1lo, u64 r0lo, u64 r1lo, u64 sz, u32 len, u32 af) {
-  ulonglong2* q = reinterpret_cast<ulonglong2*>(dst);
-  q[0] = make_ulonglong2(c0lo, d);
-  q[1] = make_ulonglong2(c1lo, r0lo);
-  q[2] = make_ulonglong2(r1lo, sz);
-  q[3] = make_ulonglong2((u64)len | ((u64)af << 32), 0ull);
-}
-template <bool WIDE>
-__device__ __forceinline__ Cand<WIDE> cand_load(const Cand<WIDE>* src);
-template <>
-__device__ __forceinline__ Cand<false> cand_load<false>(const Cand<false>* src) {
-  const uint4* q = reinterpret_cast<const uint4*>(src);
-#if (SIGAX_NT & 4)
-  typedef u32 nt4 __attribute__((ext_vector_type(4)));
-  const nt4 na = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(q)), nb = __builtin_nontemporal_load(reinterpret_cast<const nt4*>(q) + 1);
-  uint4 a = make_uint4(na.x, na.y, na.z, na.w), b = make_uint4(nb.x, nb.y, nb.z, nb.w);
-#else
-  uint4 a = q[0], b = q[1];
-#endif
-  Cand<false> c;
-  c.c0lo = a.x; c.d = a.y; c.c1lo = a.z; c.r0lo = a.w; c.r1lo = b.x; c.sz = b.y; c.len = b.z; c.af = b.w;
-  return c;
-}
-template <>
-__device__ __forceinline__ Cand<true> cand_load<true>(const Cand<true>* src) {
-  const ulonglong2* q = reinterpret_cast<const ulonglong2*>(src);
-  ulonglong2 a = q[0], b = q[1], c2 = q[2], d = q[3];
-  Cand<true> c;
-  c.c0lo = a.x; c.d = a.y; c.c1lo = b.x; c.r0lo = b.y; c.r1lo = c2.x; c.sz = c2.y; c.len = (u32)d.x; c.af = (u32)(d.x >> 32);
-  c.pad = 0;
-  return c;
-}
-
-__device__ __forceinline__ void chunk_count(const uint4& k, int take, u32& a, u32& c, u32& g, u32& t) {
-  u32 m = take >= 32 ? 0xFFFFFFFFu : (take <= 0 ? 0u : ((1u << take) - 1u));
-  u32 x0 = k.y & m, x1 = k.z & m, x2 = k.w & m;
-  a += __popc(x0 & ~x1);
-  c += __popc(x1 & ~x0);
-  g += __popc(x0 & x1);
-  t += __popc(x2);
-}
-
-// By-value view of one strand: granule table, superblock table, length, and which LDS row holds its C[]/totals.
-struct FmRef {
-  const uint4* g;
-  const u64* super;
-  u64 n;
-  u32 which;
-};
-__device__ __forceinline__ FmRef fm_ref(const FmStrand& s, u32 which) {
-  FmRef r;
-  r.g = reinterpret_cast<const uint4*>(s.granules);
-  r.super = s.super;
-  r.n = s.n;
-  r.which = which;
-  return r;
-}
-__device__ __forceinline__ FmRef fm_pick(bool first, const FmRef& a, const FmRef& b) {
-  FmRef r;
-  r.g = first ? a.g : b.g;
-  r.super = first ? a.super : b.super;
-  r.n = first ? a.n : b.n;
-  r.which = first ? a.which : b.which;
-  return r;
-}
-// C[] and symbol totals of both strands staged in LDS: [which][rank]
-struct FmTables {
-  u64 C[2][5];
-  u64 T[2][5];
-};
-__device__ __forceinline__ void fm_tables_load(FmTables& t, const FmStrand& fwd, const FmStrand& rev) {
-  if (threadIdx.x < 5) {
-    t.C[0][threadIdx.x] = fwd.C[threadIdx.x];
-    t.C[1][threadIdx.x] = rev.C[threadIdx.x];
-    t.T[0][threadIdx.x] = fwd.total[threadIdx.x];
-    t.T[1][threadIdx.x] = rev.total[threadIdx.x];
-  }
-  __syncthreads();
-}
-
-template <bool WIDE>
-__device__ __forceinline__ Cnt4 fm_rank(const FmRef& s, u64 p) {
-  p = p > s.n ? s.n : p;  // never leave the table, whatever an invalid interval holds
-  u64 gi = p >> 7;
-  int r = (int)(p & 127u);
-  const uint4* q = s.g + gi * 4;
-  uint4 k0 = q[0], k1 = q[1], k2 = q[2], k3 = q[3];
-  u32 a = k0.x, c = k1.x, g = k2.x, t = k3.x;
-  chunk_count(k0, r, a, c, g, t);
-  chunk_count(k1, r - 32, a, c, g, t);
-  chunk_count(k2, r - 64, a, c, g, t);
-  chunk_count(k3, r - 96, a, c, g, t);
-  Cnt4 o;
-  o.a = a; o.c = c; o.g = g; o.t = t;
-  if (WIDE) {
-    const u64* sb = s.super + (p >> SIGAX_SUPER_SHIFT) * 4;
-    o.a += sb[0]; o.c += sb[1]; o.g += sb[2]; o.t += sb[3];
-  }
-  return o;
-}
-
-// all five columns; v[0] = '$'
-template <bool WIDE>
-__device__ __forceinline__ void fm_rank5(const FmRef& s, u64 p, u64 v[5]) {
-  u64 pc = p > s.n ? s.n : p;
-  Cnt4 k = fm_rank<WIDE>(s, pc);
-  v[1] = k.a; v[2] = k.c; v[3] = k.g; v[4] = k.t;
-  v[0] = pc - (k.a + k.c + k.g + k.t);
-}
-
-// A,C,G,T counts of BWT[0, p) in the index's position type
-template <bool WIDE>
-__device__ __forceinline__ Cnt4P<typename PosOf<WIDE>::type> fm_rank4p(const FmRef& s, typename PosOf<WIDE>::type p) {
-  typedef typename PosOf<WIDE>::type P;
-  u64 pc = (u64)p > s.n ? s.n : (u64)p;
-  const uint4* q = s.g + (pc >> 7) * 4;
-  int r = (int)(pc & 127u);
-  uint4 k0 = q[0], k1 = q[1], k2 = q[2], k3 = q[3];
-  u32 a = k0.x, c = k1.x, g = k2.x, t = k3.x;
-  chunk_count(k0, r, a, c, g, t);
-  chunk_count(k1, r - 32, a, c, g, t);
-  chunk_count(k2, r - 64, a, c, g, t);
-  chunk_count(k3, r - 96, a, c, g, t);
-  Cnt4P<P> o;
-  o.a = a; o.c = c; o.g = g; o.t = t;
-  if (WIDE) {
-    const u64* sb = s.super + (pc >> SIGAX_SUPER_SHIFT) * 4;
-    o.a += (P)sb[0]; o.c += (P)sb[1]; o.g += (P)sb[2]; o.t += (P)sb[3];
-  }
-  return o;
-}
+#include "sigax_fm.h"
 
 // The finder's loads of one step, issued back to back and waited for once: both rank granules (4 x 16 B each; the
 // pieces of a granule share a line) and the read's base for this step.  Left to the compiler, the conditional record
@@ -295,504 +131,12 @@ __device__ __forceinline__ Cnt4P<typename PosOf<WIDE>::type> fm_rank4p_from(cons
   return o;
 }
 
-// BWT symbol at position i (FMIndex::getChar, src/fmindex.cpp:233-246)
-__device__ __forceinline__ u32 fm_char(const FmRef& s, u64 i) {
-  const u32* q = reinterpret_cast<const u32*>(s.g) + (i >> 7) * 16 + ((i >> 5) & 3) * 4;
-  u32 b = (u32)i & 31u;
-  return ((q[1] >> b) & 1u) | (((q[2] >> b) & 1u) << 1) | (((q[3] >> b) & 1u) << 2);
-}
-
-// alphabet.h:19-39 and kseq.cpp:18-27: byte -> rank; complement in rank space (non-ACGT -> 0 either way)
-// Branch-free (a chain of equality tests on one value is lowered to a divergent branch tree): bits 1-2 of 'A','C','T','G'
-// are 0,1,2,3; the byte expected at that index and its rank come out of two constants.
-__device__ __forceinline__ u32 base_rank(u32 ch) {
-  const u32 i = (ch >> 1) & 3u;
-  const u32 expect = (0x47544341u >> (i * 8)) & 0xFFu;  // "ACTG"
-  const u32 rank = (0x3421u >> (i * 4)) & 0xFu;         // 1, 2, 4, 3
-  return expect == ch ? rank : 0u;
-}
-// v[r] for r in 0..4 out of registers, as a select tree on the bits of r (again: no equality chain, no branches)
-template <typename T>
-__device__ __forceinline__ T sel5(u32 r, T v0, T v1, T v2, T v3, T v4) {
-  const bool b0 = (r & 1u) != 0, b1 = (r & 2u) != 0, b2 = (r & 4u) != 0;
-  const T t01 = b0 ? v1 : v0, t23 = b0 ? v3 : v2;
-  const T t = b1 ? t23 : t01;
-  return b2 ? v4 : t;
-}
-__device__ __forceinline__ u32 comp_rank(u32 r) { return r ? 5u - r : 0u; }
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// -------------------------------------------------------------------------------------------------------
-// k_occ_batch / k_kmer_count
-// -------------------------------------------------------------------------------------------------------
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_occ_batch(FmStrand s, const u64* pos, u64 n, u64* out) {
-  u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  u64 v[5];
-  fm_rank5<WIDE>(fm_ref(s, 0), pos[i] + 1, v);  // fmindex.cpp:191: ++i, so 2^64-1 wraps to the empty prefix
-  for (int k = 0; k < 5; ++k) out[i * 5 + k] = v[k];
-}
-
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_kmer_count(FmStrand s, const unsigned char* kmers, u32 k, u64 n, u64* out) {
-  u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const unsigned char* w = kmers + i * k;
-  FmRef f = fm_ref(s, 0);
-  u64 C[5] = {s.C[0], s.C[1], s.C[2], s.C[3], s.C[4]};
-  u64 T[5] = {s.total[0], s.total[1], s.total[2], s.total[3], s.total[4]};
-  auto sel = [](const u64 v[5], u32 r) { return r == 0 ? v[0] : r == 1 ? v[1] : r == 2 ? v[2] : r == 3 ? v[3] : v[4]; };
-  // Interval::get (fmindex.h:67-79): init with the last symbol, update while valid
-  u32 r = base_rank(w[k - 1]);
-  u64 lo = sel(C, r), hi = lo + sel(T, r) - 1;
-  for (u32 j = k - 1; j > 0; --j) {
-    if (!(hi != ~0ull && hi >= lo)) break;
-    r = base_rank(w[j - 1]);
-    u64 l[5], u[5];
-    fm_rank5<WIDE>(f, lo, l);       // getOcc(c, lower - 1)
-    fm_rank5<WIDE>(f, hi + 1, u);   // getOcc(c, upper)
-    lo = sel(C, r) + sel(l, r);
-    hi = sel(C, r) + sel(u, r) - 1;
-  }
-  out[i] = (hi != ~0ull && hi >= lo) ? hi - lo + 1 : 0;
-}
-
-// -------------------------------------------------------------------------------------------------------
-// Row table + stretch text of fm_layout.h.  One lane per symbol of rank 0 in the text (a read's terminator, or a non-ACGT
-// base, which the index stores as rank 0 too: alphabet.h:19-39): from the row of the suffix that starts there (rows
-// 0 .. C['A']-1) walk backwards (LF) to the row whose BWT symbol has rank 0.  k_stretch_scan learns the distance and
-// Occ('$') there (and the longest distance of the index, which sizes the entries); k_rows_fill walks again and writes
-// (steps still to go, that Occ) at every row passed and the symbols passed into the stretch's text row.  Every row lies on
-// exactly one such walk.
-// -------------------------------------------------------------------------------------------------------
-template <bool WIDE>
-__device__ __forceinline__ u32 lf_row(const FmRef& f, const u64* C, u64 p, u64* next) {
-  const u32 c = fm_char(f, p);
-  const Cnt4 k = fm_rank<WIDE>(f, p);
-  if (c == 0) *next = p - (k.a + k.c + k.g + k.t);  // Occ('$', p - 1)
-  else *next = C[c] + (c == 1 ? k.a : c == 2 ? k.c : c == 3 ? k.g : k.t);
-  return c;
-}
-#define STRETCH_BAD (~0ull)  // not a BWT of '$'-terminated reads: the walk did not end
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_stretch_scan(FmStrand s, u64 n_stretch, u64* info, u32* maxlen) {
-  const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
-  u32 mine = 0;
-  if (j < n_stretch) {
-    const FmRef f = fm_ref(s, 0);
-    const u64 C[5] = {s.C[0], s.C[1], s.C[2], s.C[3], s.C[4]};
-    u64 p = j, len = 0, v = STRETCH_BAD;
-    for (;;) {
-      u64 q;
-      if (lf_row<WIDE>(f, C, p, &q) == 0) { v = (len << 32) | (q & 0xFFFFFFFFull); break; }
-      p = q;
-      if (++len >= s.n || len >= (1ull << 28)) { len = 0; break; }
-    }
-    info[j] = v;
-    mine = (u32)len;
-  }
-  for (int off = 32; off > 0; off >>= 1) mine = max(mine, (u32)__shfl_xor((int)mine, off, 64));
-  if ((threadIdx.x & 63u) == 0 && mine) atomicMax(maxlen, mine);
-}
-// entry p of a bit-packed table of `bits`-bit values (zeroed before): set / get
-__device__ __forceinline__ void packed_or(unsigned char* tab, u64 p, u32 bits, u64 v) {
-  const u64 B = p * bits;
-  u64* w = reinterpret_cast<u64*>(tab) + (B >> 6);
-  const u32 sh = (u32)B & 63u;
-  atomicOr(w, v << sh);
-  if (sh + bits > 64u) atomicOr(w + 1, v >> (64u - sh));
-}
-__device__ __forceinline__ u64 packed_get(const unsigned char* tab, u64 p, u32 bits) {
-  const u64 B = p * bits;
-  u64 v;
-#if (SIGAX_NT & 1)
-  {  // the row-table line is used once
-    typedef u64 __attribute__((aligned(1))) u64u;
-    v = __builtin_nontemporal_load(reinterpret_cast<const u64u*>(tab + (B >> 3)));
-  }
-#else
-  __builtin_memcpy(&v, tab + (B >> 3), 8);  // one unaligned 8-byte load (the table is padded by 8 bytes)
-#endif
-  return (v >> ((u32)B & 7u)) & ((1ull << bits) - 1ull);
-}
-// (stretch, offset) of the suffix at `row` of a strand that has the row table; returns the entry's symbols (fm_layout.h)
-__device__ __forceinline__ u64 row_lookup(const FmStrand& st, u64 row, u32& ld, u32& t) {
-  const u64 v = packed_get(st.sa, row < st.n ? row : 0ull, st.sa_bits);  // never leave the table, whatever a block holds
-  ld = (u32)(v & ((1ull << st.ld_bits) - 1ull));
-  t = (u32)(v >> st.ld_bits) & ((1u << st.t_bits) - 1u);
-  return v >> (st.ld_bits + st.t_bits);
-}
-// The symbols on the backward path from offset t of stretch ld, 2 bits each (rank - 1), next one in the top two bits:
-// offsets t-1, t-2, ... -- at least SIGAX_TEXT_WINDOW of them, or all t (the caller knows from t where the read ends).
-__device__ __forceinline__ u64 text_window(const FmStrand& st, u32 ld, u32 t) {
-  if (t == 0) return 0ull;
-  const u32 end = 2u * t;                                  // the row's bits [0, end) hold offsets 0 .. t-1
-  const u32 b = end > 64u ? (end - 64u + 7u) >> 3 : 0u;  // first byte of the 8 that end at or past bit `end`
-  u64 w;
-  __builtin_memcpy(&w, st.text + (u64)ld * st.text_stride + b, 8);  // rows are padded (fm_layout.h)
-  return w << (64u - (end - 8u * b));
-}
-// -------------------------------------------------------------------------------------------------------
-// Self-check of an index against the order of record (sigax_index_check_order): the row table IS the suffix array, the
-// stretch text IS the reads, so whether the BWT rows are in suffix order can be seen on the device without a second
-// suffix sort: one lane per pair of adjacent rows compares the two suffixes of r0 $ r1 $ ... r(n-1) $ -- one '$' smaller
-// than A, C, G, T, comparisons running on past a '$' into the next read, the end of the text smallest (the order `siga
-// index` produces: SURVEY.md App. C model B; src/suffix_array_builder.cpp:472-674).  28 symbols per 8-byte load.
-// -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 text_bits(const FmStrand& st, u32 ld, u32 off) {  // symbols off, off+1, ... lowest first
-  u64 w;
-  __builtin_memcpy(&w, st.text + (u64)ld * st.text_stride + (off >> 2), 8);
-  return w >> (2u * (off & 3u));
-}
-// direct map of strand X as extension index (fm_layout.h): sai_y = the other strand's .sai ids, isai_x = inverse of X's
-__global__ __launch_bounds__(256) void k_xmap(const u32* sai_y, const u32* isai_x, const u32* slen_x, u64 n, u64* xmap) {
-  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const u32 ldx = isai_x[sai_y[i]];
-  xmap[i] = (u64)ldx | ((u64)slen_x[ldx] << 32);
-}
-__global__ __launch_bounds__(256) void k_isai(const u32* sai, u64 n, u32* isai) {
-  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) isai[sai[i]] = (u32)i;
-}
-__global__ __launch_bounds__(256) void k_suffix_order_check(FmStrand st, const u32* sai, const u32* isai, const u32* read_len, u64 n_strings,
-                                                            u64* bad) {
-  const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (p + 1 >= st.n) return;
-  u32 la, ta, lb, tb;
-  row_lookup(st, p, la, ta);
-  row_lookup(st, p + 1, lb, tb);
-  int verdict = -1;  // 1: suffix(p) < suffix(p + 1); 0: not
-  for (u32 hops = 0; verdict < 0 && hops < 4096u; ++hops) {
-    const u32 ida = sai[la], idb = sai[lb];
-    const u32 ra = read_len[ida] - ta, rb = read_len[idb] - tb;  // symbols left in each read
-    const u32 m = ra < rb ? ra : rb;
-    for (u32 k = 0; k < m && verdict < 0;) {
-      const u32 c = m - k < 28u ? m - k : 28u;
-      const u64 x = (text_bits(st, la, ta + k) ^ text_bits(st, lb, tb + k)) & ((1ull << (2u * c)) - 1ull);
-      if (x) {
-        const u32 d = (u32)__builtin_ctzll(x) >> 1;
-        const u32 sa = (u32)(text_bits(st, la, ta + k + d) & 3ull), sb = (u32)(text_bits(st, lb, tb + k + d) & 3ull);
-        verdict = sa < sb ? 1 : 0;
-      }
-      k += c;
-    }
-    if (verdict >= 0) break;
-    if (ra != rb) { verdict = ra < rb ? 1 : 0; break; }  // a '$' against a base
-    // both reads end here: '$' against '$', on into the reads that follow them in the text (the end of the text is smallest)
-    if ((u64)ida + 1 >= n_strings || (u64)idb + 1 >= n_strings) { verdict = ((u64)ida + 1 >= n_strings && (u64)idb + 1 < n_strings) ? 1 : 0; break; }
-    la = isai[ida + 1]; ta = 0;
-    lb = isai[idb + 1]; tb = 0;
-  }
-  if (verdict == 0) {
-    atomicAdd(&bad[0], 1ull);
-    atomicMin(&bad[1], p);
-  } else if (verdict < 0) {
-    atomicAdd(&bad[2], 1ull);  // undecided after 4096 reads' worth of ties (thousands of identical reads in a row)
-  }
-}
-
-#define ROWS_KMAX 14  // most symbols an entry can carry (fm_layout.h)
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_rows_fill(FmStrand s, u64 n_stretch, const u64* info, unsigned char* sa, u32 sa_bits, u32 ld_bits, u32 t_bits,
-                                                   unsigned char* text, u32 text_stride, u32* slen) {
-  const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n_stretch) return;
-  const u64 v = info[j];
-  if (v == STRETCH_BAD) return;  // rows of such a walk keep entry 0: "ends here, stretch 0" is never consulted then
-  const FmRef f = fm_ref(s, 0);
-  const u64 C[5] = {s.C[0], s.C[1], s.C[2], s.C[3], s.C[4]};
-  const u64 ld = v & 0xFFFFFFFFull;
-  if (slen != nullptr) slen[ld] = (u32)(v >> 32);  // the stretch's length, by its rank among the '$' rows
-  const u32 K = sa != nullptr ? (sa_bits - ld_bits - t_bits) >> 1 : 0u;  // symbols carried by an entry
-  u64 p = j;
-  unsigned char* trow = text ? text + ld * text_stride : nullptr;
-  // A window of the last ROWS_KMAX rows slides along: when the K-th symbol after a row has been seen its entry is complete
-  // (R[ROWS_KMAX - 1] = the newest row; wsym = the symbols seen as rank - 1, newest in the lowest two bits, so the K
-  // symbols that follow the row K places back read first-symbol-highest: the order text_window() hands them out in).
-  u64 R[ROWS_KMAX];
-  u32 wsym = 0, vm = 0;
-#pragma unroll
-  for (int i = 0; i < ROWS_KMAX; ++i) R[i] = 0;
-  auto insert = [&](u64 row, u32 c, bool real, u64 t_of_row) {
-#pragma unroll
-    for (int i = 0; i + 1 < ROWS_KMAX; ++i) R[i] = R[i + 1];
-    R[ROWS_KMAX - 1] = row;
-    wsym = (wsym << 2) | ((c - 1u) & 3u);
-    vm = (vm << 1) | (real ? 1u : 0u);
-    if (K == 0 || sa == nullptr) return;
-    u64 r0 = R[0];
-#pragma unroll
-    for (int i = 1; i < ROWS_KMAX; ++i)
-      if ((u32)(ROWS_KMAX - i) == K) r0 = R[i];
-    if ((vm >> (K - 1u)) & 1u) {
-      const u64 syms = (u64)wsym & ((1ull << (2u * K)) - 1ull);
-      packed_or(sa, r0, sa_bits, (syms << (ld_bits + t_bits)) | ((t_of_row + (K - 1u)) << ld_bits) | ld);
-    }
-  };
-  for (u64 t = v >> 32;; --t) {
-    if (K == 0 && sa != nullptr) packed_or(sa, p, sa_bits, (t << ld_bits) | ld);
-    u64 q;
-    const u32 c = lf_row<WIDE>(f, C, p, &q);  // the symbol at offset t - 1; rank 0 exactly when t == 0
-    insert(p, c, true, t);
-    if (t == 0) break;
-    if (trow) packed_or(trow, t - 1, 2u, (u64)((c - 1u) & 3u));  // offset t - 1 at bits 2 (t - 1) .. of the stretch's own (zeroed) row
-    p = q;
-  }
-  // the rows whose K symbols run past the read's first base: rank 0 from there on (t counts on below zero for the formula)
-  for (u32 i = 1; i < K; ++i) insert(0, 0, false, 0ull - i);
-}
-
-// -------------------------------------------------------------------------------------------------------
-// Start table of the block finder (fm_layout.h): one lane per 12-mer walks IntervalPair::init + eleven updateL steps
-// (src/overlap_builder.cpp:91-122) with `prim` as the primary index.
-// -------------------------------------------------------------------------------------------------------
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_start_build(FmStrand prim, FmStrand other, void* tab) {
-  typedef typename PosOf<WIDE>::type P;
-  const u32 code = blockIdx.x * 256 + threadIdx.x;
-  if (code >= (1u << (2 * SIGAX_START_K))) return;
-  const FmRef f = fm_ref(prim, 0);
-  u32 r = 1u + ((code >> (2 * (SIGAX_START_K - 1))) & 3u);
-  P lo0 = (P)prim.C[r], sz = (P)prim.total[r], lo1 = (P)other.C[r];
-  u32 s = 1;
-  for (int i = 1; i < SIGAX_START_K && sz != 0; ++i, ++s) {
-    r = 1u + ((code >> (2 * (SIGAX_START_K - 1 - i))) & 3u);
-    const u64 n = prim.n;
-    const u64 pl = (u64)lo0 > n ? n : (u64)lo0, pu0 = (u64)(P)(lo0 + sz), pu = pu0 > n ? n : pu0;
-    const Cnt4P<P> l = fm_rank4p<WIDE>(f, (P)pl), u = fm_rank4p<WIDE>(f, (P)pu);
-    const P da = u.a - l.a, dc = u.c - l.c, dg = u.g - l.g, dt = u.t - l.t;
-    const P dd = sz - (da + dc + dg + dt);
-    const P acc = r == 1 ? dd : r == 2 ? dd + da : r == 3 ? dd + da + dc : dd + da + dc + dg;
-    const P lc = r == 1 ? l.a : r == 2 ? l.c : r == 3 ? l.g : l.t;
-    const P dcur = r == 1 ? da : r == 2 ? dc : r == 3 ? dg : dt;
-    lo1 += acc;
-    lo0 = (P)prim.C[r] + lc;
-    sz = dcur;
-  }
-  if (WIDE) {
-    ulonglong2* q = reinterpret_cast<ulonglong2*>(tab) + 2ull * code;
-    q[0] = make_ulonglong2((u64)lo0, (u64)lo1);
-    q[1] = make_ulonglong2((u64)sz, (u64)s);
-  } else {
-    reinterpret_cast<uint4*>(tab)[code] = make_uint4((u32)lo0, (u32)lo1, (u32)sz, s);
-  }
-}
-
-// -------------------------------------------------------------------------------------------------------
-// Deep start table of the block finder (fm_layout.h): the distinct K-mers of a strand's text are the runs of equal
-// K-symbol prefixes among adjacent rows of its row table (k_deep_scan counts them, then lists each run's first row); one
-// lane per distinct K-mer then walks IntervalPair::init + K - 1 updateL steps (src/overlap_builder.cpp:91-122) with that
-// strand as primary index -- the arithmetic of k_start_build and of the finder itself -- and puts the state into the hash
-// table (k_deep_fill).  The walk must come out at the run's own first row: anything else (an index whose rows are not in
-// suffix order, a row table of a walk that did not end) raises *err and the host throws the table away.
-// -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 deep_slot(u64 k0, u64 k1, u64 nslots) {
-  u64 h = (k0 ^ (k1 * 0x9E3779B97F4A7C15ull)) * 0xBF58476D1CE4E5B9ull;
-  h ^= h >> 31;
-  h *= 0x94D049BB133111EBull;
-  h ^= h >> 29;
-  return __umul64hi(h, nslots);
-}
-// the first K symbols of the suffix at row p in text order, symbol j at bits 2 j of f0 (j < 28) / 2 (j - 28) of f1; false
-// when the row's stretch ends before that
-__device__ __forceinline__ bool deep_row_kmer(const FmStrand& st, const u32* slen, u64 n_stretch, u64 p, u32 K, u64& f0, u64& f1) {
-  u32 ld, t;
-  row_lookup(st, p, ld, t);
-  f0 = f1 = 0;
-  if ((u64)ld >= n_stretch) return false;
-  if ((u64)t + K > (u64)slen[ld]) return false;
-  const u64 m56 = (1ull << 56) - 1ull;
-  f0 = text_bits(st, ld, t) & (K >= 28u ? m56 : ((1ull << (2u * K)) - 1ull));
-  if (K > 28u) f1 = text_bits(st, ld, t + 28u) & (K >= 56u ? m56 : ((1ull << (2u * (K - 28u))) - 1ull));
-  return true;
-}
-__global__ __launch_bounds__(256) void k_deep_scan(FmStrand st, const u32* slen, u64 n_stretch, u32 K, u64* count, u64* list, u64 list_cap) {
-  const u32 lane = threadIdx.x & 63u;
-  // waves walk the rows in strides of the grid (a launch holds fewer than 2^32 threads; BASELINE configs[4] has 1.3e10 rows)
-  for (u64 p0 = (u64)blockIdx.x * 256; p0 < st.n; p0 += (u64)gridDim.x * 256) {
-    const u64 p = p0 + threadIdx.x;
-    u64 f0 = 0, f1 = 0;
-    bool v = false;
-    if (p < st.n) v = deep_row_kmer(st, slen, n_stretch, p, K, f0, f1);
-    // the row before: the lane below has it, except for the wave's first lane
-    u64 g0 = __shfl_up(f0, 1, 64), g1 = __shfl_up(f1, 1, 64);
-    bool pv = __shfl_up((int)v, 1, 64) != 0;
-    if (lane == 0) {
-      pv = false;
-      if (p > 0 && p < st.n) pv = deep_row_kmer(st, slen, n_stretch, p - 1, K, g0, g1);
-    }
-    const bool first = v && (!pv || g0 != f0 || g1 != f1);
-    const u64 m = __ballot(first);
-    if (!m) continue;
-    u64 base = 0;
-    if (lane == 0) base = atomicAdd(count, (u64)__popcll(m));
-    base = __shfl(base, 0, 64);
-    if (list != nullptr && first) {
-      const u64 i = base + (u32)__popcll(m & ((1ull << lane) - 1ull));
-      if (i < list_cap) list[i] = p;
-    }
-  }
-}
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_deep_fill(FmStrand prim, FmStrand other, const u32* slen, u64 n_stretch, u32 K, const u64* list, u64 n_list,
-                                                   u64* tab, u64 nslots, u64* err) {
-  typedef typename PosOf<WIDE>::type P;
-  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;  // (fewer than 2^32 distinct K-mers: the host checks)
-  if (i >= n_list) return;
-  const u64 p = list[i];
-  u64 f0, f1;
-  if (!deep_row_kmer(prim, slen, n_stretch, p, K, f0, f1)) {
-    atomicAdd(err, 1ull);
-    return;
-  }
-  auto sym = [&](u32 j) -> u32 { return (u32)((j < 28u ? f0 >> (2u * j) : f1 >> (2u * (j - 28u))) & 3ull); };
-  const FmRef f = fm_ref(prim, 0);
-  // the chain consumes the K-mer from its last symbol backwards
-  u32 r = 1u + sym(K - 1u);
-  P lo0 = (P)prim.C[r], sz = (P)prim.total[r], lo1 = (P)other.C[r];
-  u64 k0 = (u64)(r - 1u), k1 = 0;
-  for (u32 c = 1; c < K; ++c) {
-    r = 1u + sym(K - 1u - c);
-    if (c < 32u) k0 |= (u64)(r - 1u) << (2u * c);
-    else k1 |= (u64)(r - 1u) << (2u * (c - 32u));
-    if (sz == 0) continue;
-    const u64 n = prim.n;
-    const u64 pl = (u64)lo0 > n ? n : (u64)lo0, pu0 = (u64)(P)(lo0 + sz), pu = pu0 > n ? n : pu0;
-    const Cnt4P<P> l = fm_rank4p<WIDE>(f, (P)pl), u = fm_rank4p<WIDE>(f, (P)pu);
-    const P da = u.a - l.a, dc = u.c - l.c, dg = u.g - l.g, dt = u.t - l.t;
-    const P dd = sz - (da + dc + dg + dt);
-    const P acc = r == 1 ? dd : r == 2 ? dd + da : r == 3 ? dd + da + dc : dd + da + dc + dg;
-    const P lc = r == 1 ? l.a : r == 2 ? l.c : r == 3 ? l.g : l.t;
-    const P dcur = r == 1 ? da : r == 2 ? dc : r == 3 ? dg : dt;
-    lo1 += acc;
-    lo0 = (P)prim.C[r] + lc;
-    sz = dcur;
-  }
-  if (sz == 0 || (u64)lo0 != p || (WIDE && (((u64)lo0 | (u64)lo1 | (u64)sz) >> 40) != 0)) {
-    atomicAdd(err, 1ull);
-    return;
-  }
-  k1 |= (u64)(0x8000u | K) << 48;
-  u64 slot = deep_slot(k0, k1, nslots);
-  for (u64 tries = 0; tries < nslots; ++tries) {
-    if (atomicCAS(&tab[slot * 4 + 1], 0ull, k1) == 0ull) {
-      tab[slot * 4] = k0;
-      if (WIDE) {
-        tab[slot * 4 + 2] = (u64)lo0 | ((u64)lo1 << 40);
-        tab[slot * 4 + 3] = ((u64)lo1 >> 24) | ((u64)sz << 16);
-      } else {
-        tab[slot * 4 + 2] = (u64)(u32)lo0 | ((u64)(u32)lo1 << 32);
-        tab[slot * 4 + 3] = (u64)(u32)sz;
-      }
-      return;
-    }
-    slot = slot + 1 == nslots ? 0 : slot + 1;
-  }
-  atomicAdd(err, 1ull);
-}
-// the chain's state after the K-mer (k0, k1 = its code with the tag of fm_layout.h), or false: not a K-mer of the text
-template <bool WIDE>
-__device__ __forceinline__ bool deep_lookup(const void* tab, u64 nslots, u64 k0, u64 k1, typename PosOf<WIDE>::type& lo0,
-                                            typename PosOf<WIDE>::type& lo1, typename PosOf<WIDE>::type& sz) {
-  typedef typename PosOf<WIDE>::type P;
-  const ulonglong2* q = reinterpret_cast<const ulonglong2*>(tab);
-  u64 slot = deep_slot(k0, k1, nslots);
-  for (;;) {
-    const ulonglong2 key = q[2 * slot], pay = q[2 * slot + 1];
-    if (key.y == 0ull) return false;  // an empty slot ends the probe sequence (the table is never full)
-    if (key.x == k0 && key.y == k1) {
-      if (WIDE) {
-        const u64 m40 = (1ull << 40) - 1ull;
-        lo0 = (P)(pay.x & m40);
-        lo1 = (P)((pay.x >> 40) | ((pay.y & 0xFFFFull) << 24));
-        sz = (P)((pay.y >> 16) & m40);
-      } else {
-        lo0 = (P)(u32)pay.x;
-        lo1 = (P)(u32)(pay.x >> 32);
-        sz = (P)(u32)pay.y;
-      }
-      return true;
-    }
-    slot = slot + 1 == nslots ? 0 : slot + 1;
-  }
-}
-
 // -------------------------------------------------------------------------------------------------------
 // k_find: one lane per (read, orientation) chain; the four waves of a workgroup are the four chains of 64 reads.  Per step: two rank granules on the chain's primary index
 // (positions lower-1 and upper of IntervalPair::updateL, src/overlap_builder.cpp:95-122); the '$' probe of
 // src/overlap_builder.cpp:861-871 reuses them.  Blocks go to the chain's slots of the candidate arena in
 // increasing overlap length = the reference's push order.
 // -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void store_block(sigax_block* dst, u64 c0lo, u64 c0hi, u64 c1lo, u64 c1hi, u64 r0lo, u64 r0hi,
-                                            u64 r1lo, u64 r1hi, u32 len, u32 af) {
-  ulonglong2* d = reinterpret_cast<ulonglong2*>(dst);
-  d[0] = make_ulonglong2(c0lo, c0hi);
-  d[1] = make_ulonglong2(c1lo, c1hi);
-  d[2] = make_ulonglong2(r0lo, r0hi);
-  d[3] = make_ulonglong2(r1lo, r1hi);
-  d[4] = make_ulonglong2((u64)len | ((u64)af << 32), 0ull);
-}
-
-// ---- two-step table (fm_layout.h) -------------------------------------------------------------------------------
-// built on the device from the one-step granules: one wave per 64 rows
-template <bool WIDE>
-__global__ __launch_bounds__(256) void k_build2_a(FmStrand s, u32* gran2, u32* cnt, u64 ng2) {
-  const FmRef F = fm_ref(s, 0);
-  const u32 lane = threadIdx.x & 63u;
-  const u64 wave = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6, nw = (u64)gridDim.x * 4;
-  for (u64 g = wave; g < ng2; g += nw) {
-    const u64 p = g * 64 + lane;
-    u32 c1 = 0, c2 = 0;
-    if (p < s.n) {
-      c1 = fm_char(F, p);
-      if (c1 >= 1 && c1 <= 4) {
-        const Cnt4 k = fm_rank<WIDE>(F, p);
-        const u64 rk = c1 == 1 ? k.a : c1 == 2 ? k.c : c1 == 3 ? k.g : k.t;
-        c2 = fm_char(F, s.C[c1] + rk);  // BWT[LF(p)]
-      } else {
-        c1 = c1 > 4 ? 0 : c1;
-      }
-    }
-    const u64 y1 = __ballot((c1 & 1u) != 0), z1 = __ballot((c1 & 2u) != 0), w1 = __ballot((c1 & 4u) != 0);
-    const u64 y2 = __ballot((c2 & 1u) != 0), z2 = __ballot((c2 & 2u) != 0), w2 = __ballot((c2 & 4u) != 0);
-    u32 mine = 0;  // lane t < 20 ends up with the granule's count for header word t
-    for (u32 b = 1; b <= 4; ++b) {
-      const u32 v = (u32)__popcll(__ballot(c1 == b));
-      if (lane == b - 1) mine = v;
-    }
-    for (u32 c = 1; c <= 4; ++c)
-      for (u32 x = 1; x <= 4; ++x) {
-        const u32 v = (u32)__popcll(__ballot(c1 == c && c2 == x));
-        if (lane == 4 + (c - 1) * 4 + (x - 1)) mine = v;
-      }
-    if (lane < 20) cnt[(u64)lane * ng2 + g] = mine;
-    if (lane == 0) {
-      u32* q = gran2 + g * SIGAX_GRAN2_WORDS + 20;
-      q[0] = (u32)y1; q[1] = (u32)(y1 >> 32); q[2] = (u32)z1; q[3] = (u32)(z1 >> 32); q[4] = (u32)w1; q[5] = (u32)(w1 >> 32);
-      q[6] = (u32)y2; q[7] = (u32)(y2 >> 32); q[8] = (u32)z2; q[9] = (u32)(z2 >> 32); q[10] = (u32)w2; q[11] = (u32)(w2 >> 32);
-    }
-  }
-}
-// counter `col` of every line; with 64-bit positions relative to the line's superblock, whose base goes to super2
-__global__ __launch_bounds__(256) void k_build2_b(const u64* offs, u32* gran2, u32 col, u64 ng2, u64* super2) {
-  const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (g >= ng2) return;
-  u64 base = 0;
-  if (super2) {
-    const u32 sh = SIGAX_SUPER_SHIFT - 6;  // lines per superblock = 2^sh
-    const u64 first = (g >> sh) << sh;
-    base = offs[first];
-    if (g == first) super2[(g >> sh) * 20 + col] = base;
-  }
-  gran2[g * SIGAX_GRAN2_WORDS + col] = (u32)(offs[g] - base);
-}
-
 #ifndef SIGAX_FIND_POLICY
 #define SIGAX_FIND_POLICY ""  // cache-policy bits of the finder's table loads (A/B builds: " nt", " sc1", " sc0 sc1")
 #endif
@@ -3926,267 +3270,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LMAX <= 512
 }
 
 // -------------------------------------------------------------------------------------------------------
-// exclusive scan of u32 counts into u64 offsets (two small kernels), ordered scatter of the final blocks
-// -------------------------------------------------------------------------------------------------------
-#define SCAN_ITEMS 2048  // per workgroup of 256 threads
-
-__device__ __forceinline__ u64 block_exclusive_scan(u64 v, u64* total) {
-  __shared__ u64 wsum[4];
-  u32 lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  u64 x = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    u64 y = __shfl_up(x, off, 64);
-    if (lane >= (u32)off) x += y;
-  }
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  u64 base = 0;
-  for (u32 w = 0; w < wid; ++w) base += wsum[w];
-  u64 tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
-
-__global__ __launch_bounds__(256) void k_scan_partials(const u32* cnt, u64 n, u64* partial) {
-  u64 base = (u64)blockIdx.x * SCAN_ITEMS + (u64)threadIdx.x * 8;
-  u64 s = 0;
-  for (int k = 0; k < 8; ++k)
-    if (base + k < n) s += cnt[base + k];
-  u64 tot;
-  block_exclusive_scan(s, &tot);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-// Each workgroup sums the totals of the workgroups before it itself (at most a few thousand u64 values, from L2) instead
-// of waiting for a one-workgroup launch that scanned them.  even_out (or NULL): even_out[i] = offs[2i], i <= n / 2 -- the
-// per-read offsets of a per-(read, side) scan (n even).
-__global__ __launch_bounds__(256) void k_scan_apply(const u32* cnt, u64 n, const u64* partial, u64* offs, u64* total_out, u64* even_out) {
-  u64 before = 0;
-  for (u64 i = threadIdx.x; i < blockIdx.x; i += 256) before += partial[i];
-  u64 carry;
-  block_exclusive_scan(before, &carry);
-  u64 base = (u64)blockIdx.x * SCAN_ITEMS + (u64)threadIdx.x * 8;
-  u64 v[8], s = 0;
-  for (int k = 0; k < 8; ++k) {
-    v[k] = (base + k < n) ? cnt[base + k] : 0;
-    s += v[k];
-  }
-  u64 tot;
-  u64 ex = block_exclusive_scan(s, &tot) + carry;
-  for (int k = 0; k < 8; ++k) {
-    if (base + k < n) {
-      offs[base + k] = ex;
-      if (even_out != nullptr && !(k & 1)) even_out[(base + k) >> 1] = ex;  // base is a multiple of 8
-    }
-    ex += v[k];
-  }
-  if (base <= n && n < base + 8) {  // the thread owning position n writes the grand total
-    offs[n] = ex;
-    *total_out = ex;
-    if (even_out != nullptr) even_out[n >> 1] = ex;
-  }
-}
-
-// one lane per (read, side) item: copy its blocks from the unordered arena to their place in the ordered output; blocks
-// written by the lane-group kernels get their raw pair, length and flags from the candidate record here
-template <bool WIDE>
-__device__ __forceinline__ void order_fill_from_cand(const OrderArgs& A, u64 item, u32 src, ulonglong2& v2, ulonglong2& v3, ulonglong2& v4) {
-  const Cand<WIDE>* rec = reinterpret_cast<const Cand<WIDE>*>(A.arena) + (item >> 1) * 4 * A.cap + (src & 0x3FFFFFFFu);
-  const Cand<WIDE> b = cand_load<WIDE>(rec);
-  v2 = make_ulonglong2((u64)b.r0lo, (u64)b.r0lo + b.sz - 1);
-  v3 = make_ulonglong2((u64)b.r1lo, (u64)b.r1lo + b.sz - 1);
-  v4 = make_ulonglong2((u64)b.len | ((u64)b.af << 32), 0ull);
-}
-// Hit2OverlapConverter::convert's test for one (query, target) pair (src/overlap_builder.cpp:358,365); nq, lq: the query's
-// name rank and length, which an item loads once for all its targets
-__device__ __forceinline__ bool edge_kept(const uint32_t* name_rank, const uint32_t* read_len, u32 nq, u32 lq, u32 t, u32 len, u32 af) {
-  u32 nt = name_rank[t];
-  if (nq == nt) return false;                       // query.name != target.name (:358)
-  bool contained = (len == lq) || (len == read_len[t]);  // Match::isContainment (coord.h:150-152)
-  if (nq < nt || (contained && (af & 1u))) return false;              // dedup rule (:365)
-  return true;
-}
-// The ordered copy: what a run without edge records ends with, and what a run with them does only when somebody asks for
-// its blocks (sigax_batch_download, sigax_batch_device_outputs with d_blocks).  bad_ids (or NULL): out-of-range read ids
-// are counted here in a run without edge records.
-__global__ __launch_bounds__(256) void k_order_scatter(OrderArgs A) {
-  u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (w >= A.n_items) return;
-  u32 cnt = A.fin_cnt[w];
-  if (A.read_ids != nullptr && A.bad_ids != nullptr && A.read_ids[w >> 1] >= A.n_index_reads) atomicAdd(A.bad_ids, 1ull);
-  if (!cnt) return;
-  u64 srcb = A.item_base[w], dstb = A.offs2[w];
-  for (u32 i = 0; i < cnt; ++i) {
-    if (srcb + i >= A.fin_cap || dstb + i >= A.out_cap) break;  // only after an overflow, whose results the host discards
-    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + srcb + i);
-    ulonglong2* d = reinterpret_cast<ulonglong2*>(A.out + dstb + i);
-    ulonglong2 v0 = s[0], v1 = s[1], v4 = s[4];
-    ulonglong2 v2, v3;
-    if (v4.y >> 63) {
-      if (A.wide) order_fill_from_cand<true>(A, w, (u32)v4.y, v2, v3, v4);
-      else order_fill_from_cand<false>(A, w, (u32)v4.y, v2, v3, v4);
-    } else {
-      v2 = s[2]; v3 = s[3];
-    }
-    d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4;
-  }
-}
-
-// -------------------------------------------------------------------------------------------------------
-// edges: Hit2OverlapConverter::convert (overlap_builder.cpp:345-375) in two passes with the scan of the per-item counts
-// between them, one lane per (read, side) item: its blocks are consecutive in the ordered output, its records consecutive
-// in the edge list (hits order = the ED order at -t 1).  The ordered blocks themselves are not needed for it.
-//   stage: reads each block where filter/extract left it (fin + item_base) -- its capped0 range, and length and flags from
-//          the block or, for a lane-group block, from the half of its candidate record that holds them --, tests the
-//          block's one target and leaves a 16-byte record at the block's ORDERED index (neighbouring items write
-//          neighbouring records): the final sigax_edge, or EDGE_ST_DROPPED; a block whose range holds several targets
-//          (duplicates, repeats, exhaustive mode) is counted by walking it and left as EDGE_ST_WALK
-//   emit:  copies the staged records that were kept to their places and walks the EDGE_ST_WALK blocks again, from fin
-// `af` of a record holds the three AlignFlags bits, so the two markers are no record's af.
-// -------------------------------------------------------------------------------------------------------
-static_assert(sizeof(sigax_edge) == 16, "a staged record is a sigax_edge");
-#define EDGE_ST_DROPPED 0xFFFFFFFFu
-#define EDGE_ST_WALK 0xFFFFFFFEu
-
-// length | af << 32 of the block at fin[at]; v4 = its last 16 bytes
-__device__ __forceinline__ u64 edge_len_af(const EdgeArgs& A, u64 item, const ulonglong2& v4) {
-  if (!(v4.y >> 63)) return v4.x;
-  const u64 rec = (item >> 1) * 4 * A.cap + ((u32)v4.y & 0x3FFFFFFFu);
-  if (A.wide) return reinterpret_cast<const ulonglong2*>(reinterpret_cast<const Cand<true>*>(A.arena) + rec)[3].x;
-  const uint4 h = reinterpret_cast<const uint4*>(reinterpret_cast<const Cand<false>*>(A.arena) + rec)[1];
-  return (u64)h.z | ((u64)h.w << 32);
-}
-
-__global__ __launch_bounds__(256) void k_edges_stage(EdgeArgs A) {
-  const u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (w >= A.n_items) return;
-  const u32 cnt = A.fin_cnt[w];
-  u32 kept = 0;
-  u32 q = A.read_base + (u32)(w >> 1);
-  bool known = true;  // the read is one of the index's
-  if (A.read_ids != nullptr) {
-    q = A.read_ids[w >> 1];
-    known = q < A.n_index_reads;
-    if (!known) atomicAdd(A.bad_ids, 1ull);
-  }
-  if (cnt && known) {
-    const u64 srcb = A.item_base[w], dstb = A.offs2[w];
-    const u32 nq = A.name_rank[q], lq = A.read_len[q];
-    uint4* stage = reinterpret_cast<uint4*>(A.stage);
-    for (u32 i = 0; i < cnt; ++i) {
-      if (srcb + i >= A.fin_cap || dstb + i >= A.stage_cap) break;  // only after an overflow, whose results the host discards
-      const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + srcb + i);
-      const ulonglong2 v0 = s[0], v4 = s[4];
-      const u64 la = edge_len_af(A, w, v4);
-      const u32 len = (u32)la, af = (u32)(la >> 32);
-      const u32* sa = (af & 2u) ? A.rsai : A.sai;
-      uint4 rec = make_uint4(q, 0u, len, EDGE_ST_DROPPED);
-      if (v0.x == v0.y) {
-        if (v0.x < A.n_sai) {
-          rec.y = sa[v0.x];
-          if (edge_kept(A.name_rank, A.read_len, nq, lq, rec.y, len, af)) {
-            rec.w = af;
-            ++kept;
-          }
-        }
-      } else if (v0.x < v0.y) {
-        rec.w = EDGE_ST_WALK;
-        for (u64 j = v0.x; j <= v0.y && j < A.n_sai; ++j)
-          if (edge_kept(A.name_rank, A.read_len, nq, lq, sa[j], len, af)) ++kept;
-      }
-      stage[dstb + i] = rec;
-    }
-  }
-  A.item_edges[w] = kept;
-}
-
-__global__ __launch_bounds__(256) void k_edges_emit(EdgeArgs A) {
-  const u64 w = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (w >= A.n_items) return;
-  const u32 cnt = A.fin_cnt[w];
-  if (!cnt) return;
-  u64 e = A.edge_offs[w];
-  const u64 e_end = A.edge_offs[w + 1];
-  if (e_end == e) return;  // no record from this item (most items: the self-containment blocks)
-  const u64 first = A.offs2[w];
-  const uint4* stage = reinterpret_cast<const uint4*>(A.stage);
-  uint4* edges = reinterpret_cast<uint4*>(A.edges);  // sigax_edge = (query, target, length, af)
-  for (u32 i = 0; i < cnt && e < e_end; ++i) {
-    if (first + i >= A.stage_cap) return;  // only after an overflow, whose results the host discards
-    const uint4 rec = stage[first + i];
-    if (rec.w == EDGE_ST_DROPPED) continue;
-    if (rec.w != EDGE_ST_WALK) {
-      if (e < A.edge_cap) edges[e] = rec;
-      ++e;
-      continue;
-    }
-    const u64 at = A.item_base[w] + i;
-    if (at >= A.fin_cap) return;
-    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(A.fin + at);
-    const ulonglong2 v0 = s[0], v4 = s[4];
-    const u64 la = edge_len_af(A, w, v4);
-    const u32 len = (u32)la, af = (u32)(la >> 32);
-    const u32* sa = (af & 2u) ? A.rsai : A.sai;
-    // (not rec.x: after an overflow the staged record may be a stale one)
-    const u32 q = A.read_ids != nullptr ? A.read_ids[w >> 1] : A.read_base + (u32)(w >> 1);
-    const u32 nq = A.name_rank[q], lq = A.read_len[q];
-    for (u64 j = v0.x; j <= v0.y && j < A.n_sai; ++j) {
-      const u32 t = sa[j];
-      if (edge_kept(A.name_rank, A.read_len, nq, lq, t, len, af)) {
-        if (e < A.edge_cap) edges[e] = make_uint4(q, t, len, af);
-        ++e;
-      }
-    }
-  }
-}
-
-// -------------------------------------------------------------------------------------------------------
 // launch wrappers
 // -------------------------------------------------------------------------------------------------------
-static inline unsigned nblk(u64 n, u64 per) { return (unsigned)((n + per - 1) / per); }
-
-void launch_occ_batch(const FmStrand& s, bool wide, const u64* pos, u64 n, u64* out, hipStream_t st) {
-  if (n == 0) return;
-  if (wide) hipLaunchKernelGGL(k_occ_batch<true>, dim3(nblk(n, 256)), dim3(256), 0, st, s, pos, n, out);
-  else hipLaunchKernelGGL(k_occ_batch<false>, dim3(nblk(n, 256)), dim3(256), 0, st, s, pos, n, out);
-}
-
-void launch_kmer_count(const FmStrand& s, bool wide, const unsigned char* kmers, u32 k, u64 n, u64* out, hipStream_t st) {
-  if (n == 0) return;
-  if (wide) hipLaunchKernelGGL(k_kmer_count<true>, dim3(nblk(n, 256)), dim3(256), 0, st, s, kmers, k, n, out);
-  else hipLaunchKernelGGL(k_kmer_count<false>, dim3(nblk(n, 256)), dim3(256), 0, st, s, kmers, k, n, out);
-}
-
 unsigned long long prefix_table_bytes(bool wide, u32 pk) { return (1ull << (2 * pk)) * (wide ? 16u : 8u); }
 void launch_prefix_build(const FmStrand& s, bool wide, void* tab, u32 pk, hipStream_t st) {
   const unsigned g = (1u << (2 * pk)) / 256u;
   if (wide) hipLaunchKernelGGL(k_prefix_build<true>, dim3(g), dim3(256), 0, st, s, tab, pk);
   else hipLaunchKernelGGL(k_prefix_build<false>, dim3(g), dim3(256), 0, st, s, tab, pk);
-}
-
-unsigned long long start_table_bytes(bool wide) { return (1ull << (2 * SIGAX_START_K)) * (wide ? 32u : 16u); }
-void launch_start_build(const FmStrand& prim, const FmStrand& other, bool wide, void* tab, hipStream_t st) {
-  const unsigned g = (1u << (2 * SIGAX_START_K)) / 256u;
-  if (wide) hipLaunchKernelGGL(k_start_build<true>, dim3(g), dim3(256), 0, st, prim, other, tab);
-  else hipLaunchKernelGGL(k_start_build<false>, dim3(g), dim3(256), 0, st, prim, other, tab);
-}
-
-unsigned long long deep_entry_bytes() { return 32; }
-void launch_deep_scan(const FmStrand& s, const u32* slen, u64 n_stretch, u32 K, u64* count, u64* list, u64 list_cap, hipStream_t st) {
-  if (s.n == 0) return;
-  hipLaunchKernelGGL(k_deep_scan, dim3((unsigned)std::min<u64>((s.n + 255) / 256, 1u << 22)), dim3(256), 0, st, s, slen, n_stretch, K, count, list, list_cap);
-}
-void launch_deep_fill(const FmStrand& prim, const FmStrand& other, bool wide, const u32* slen, u64 n_stretch, u32 K, const u64* list, u64 n_list,
-                      void* tab, u64 nslots, u64* err, hipStream_t st) {
-  if (n_list == 0) return;
-  if (wide) hipLaunchKernelGGL(k_deep_fill<true>, dim3(nblk(n_list, 256)), dim3(256), 0, st, prim, other, slen, n_stretch, K, list, n_list, (u64*)tab, nslots, err);
-  else hipLaunchKernelGGL(k_deep_fill<false>, dim3(nblk(n_list, 256)), dim3(256), 0, st, prim, other, slen, n_stretch, K, list, n_list, (u64*)tab, nslots, err);
-}
-void launch_suffix_order_check(const FmStrand& s, const u32* sai, u32* isai_tmp, const u32* read_len, u64 n_strings, u64* bad3, hipStream_t st) {
-  if (n_strings == 0 || s.n < 2) return;
-  hipLaunchKernelGGL(k_isai, dim3(nblk(n_strings, 256)), dim3(256), 0, st, sai, n_strings, isai_tmp);
-  hipLaunchKernelGGL(k_suffix_order_check, dim3(nblk(s.n - 1, 256)), dim3(256), 0, st, s, sai, (const u32*)isai_tmp, read_len, n_strings, bad3);
 }
 
 void launch_correct(const CorrectArgs& a0, bool wide, hipStream_t st) {
@@ -4343,56 +3433,4 @@ void launch_filter_extract(const FxArgs& a, bool wide, unsigned grid, hipStream_
   if (a.n_work == 0 && !a.n_work_ptr) return;
   if (wide) hipLaunchKernelGGL(k_filter_extract<true>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_filter_extract<false>, dim3(grid), dim3(256), 0, st, a);
-}
-
-void launch_scan(const u32* cnt, u64 n, u64* partial, u64* offs, u64* total_out, hipStream_t st, u64* even_out) {
-  // offs has n+1 entries; offs[n] = total.  Two launches: per-workgroup totals, then the scan itself (k_scan_apply)
-  unsigned g = nblk(n + 1, SCAN_ITEMS);
-  hipLaunchKernelGGL(k_scan_partials, dim3(g), dim3(256), 0, st, cnt, n, partial);
-  hipLaunchKernelGGL(k_scan_apply, dim3(g), dim3(256), 0, st, cnt, n, (const u64*)partial, offs, total_out, even_out);
-}
-
-void launch_build2(const FmStrand& s, bool wide, u32* gran2, u64* super2, u32* cnt, u64* offs, u64* partial, u64* total, hipStream_t st) {
-  const u64 ng2 = s.n / SIGAX_GRAN2_SYMS + 1;
-  const unsigned g = (unsigned)std::min<u64>(nblk(ng2, 4), 65536);
-  if (wide) hipLaunchKernelGGL(k_build2_a<true>, dim3(g), dim3(256), 0, st, s, gran2, cnt, ng2);
-  else hipLaunchKernelGGL(k_build2_a<false>, dim3(g), dim3(256), 0, st, s, gran2, cnt, ng2);
-  for (u32 col = 0; col < 20; ++col) {
-    launch_scan(cnt + (u64)col * ng2, ng2, partial, offs, total, st);
-    hipLaunchKernelGGL(k_build2_b, dim3(nblk(ng2, 256)), dim3(256), 0, st, (const u64*)offs, gran2, col, ng2, wide ? super2 : (u64*)nullptr);
-  }
-}
-
-void launch_stretch_scan(const FmStrand& s, bool wide, u64 n_stretch, u64* info, u32* maxlen, hipStream_t st) {
-  if (n_stretch == 0) return;
-  if (wide) hipLaunchKernelGGL(k_stretch_scan<true>, dim3(nblk(n_stretch, 256)), dim3(256), 0, st, s, n_stretch, info, maxlen);
-  else hipLaunchKernelGGL(k_stretch_scan<false>, dim3(nblk(n_stretch, 256)), dim3(256), 0, st, s, n_stretch, info, maxlen);
-}
-void launch_rows_fill(const FmStrand& s, bool wide, u64 n_stretch, const u64* info, unsigned char* sa, u32 sa_bits, u32 ld_bits, u32 t_bits,
-                      unsigned char* text, u32 text_stride, u32* slen, hipStream_t st) {
-  if (n_stretch == 0) return;
-  if (wide) hipLaunchKernelGGL(k_rows_fill<true>, dim3(nblk(n_stretch, 256)), dim3(256), 0, st, s, n_stretch, info, sa, sa_bits, ld_bits, t_bits, text, text_stride, slen);
-  else hipLaunchKernelGGL(k_rows_fill<false>, dim3(nblk(n_stretch, 256)), dim3(256), 0, st, s, n_stretch, info, sa, sa_bits, ld_bits, t_bits, text, text_stride, slen);
-}
-void launch_xmap(const u32* sai_y, const u32* sai_x, u32* isai_tmp, const u32* slen_x, u64 n, u64* xmap, hipStream_t st) {
-  if (n == 0) return;
-  hipLaunchKernelGGL(k_isai, dim3(nblk(n, 256)), dim3(256), 0, st, sai_x, n, isai_tmp);
-  hipLaunchKernelGGL(k_xmap, dim3(nblk(n, 256)), dim3(256), 0, st, sai_y, (const u32*)isai_tmp, slen_x, n, xmap);
-}
-
-u64 scan_partials_needed(u64 n) { return (n + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1; }
-
-void launch_order_scatter(const OrderArgs& a, hipStream_t st) {
-  if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_order_scatter, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
-}
-
-void launch_edges_stage(const EdgeArgs& a, hipStream_t st) {
-  if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_edges_stage, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
-}
-
-void launch_edges_emit(const EdgeArgs& a, hipStream_t st) {
-  if (a.n_items == 0) return;
-  hipLaunchKernelGGL(k_edges_emit, dim3(nblk(a.n_items, 256)), dim3(256), 0, st, a);
 }

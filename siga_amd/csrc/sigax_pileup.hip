@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64) void k_pile(PileArgs A) {
     while (mask) {
       const int src = __ffsll((long long)mask) - 1;
       mask &= mask - 1ull;
-      const Cand k = cand_decode(key, rb, len_t, src, n);
+      const SeedCand k = cand_decode(key, rb, len_t, src, n);
       const bool rev = k.rev;
       const long long d = k.d, x0 = k.x0, x1 = k.x1, clen = k.clen;
       if (x1 <= x0) continue;  // (a hit's window lies in both texts: there is an overlap)

@@ -1,7 +1,7 @@
 // siga_amd/csrc/sigax_rank.h -- what the kernels that walk the forward strand symbol by symbol share (sigax_match.hip,
 // sigax_spectrum.hip, sigax_locate.hip), each piece once:
-//   leaves    byte -> rank, Occ out of a one-step granule, the pair counts of a two-step line (fm_layout.h); the wave sum is
-//             sigax_device.h's
+//   leaves    Occ out of a one-step granule (Gran1, gran_rank), the pair counts of a two-step line (Gran2, rank2; fm_layout.h);
+//             PosOf, byte -> rank, chunk_count, sel4 and first_lane64 are sigax_fm.h's, the wave sum is sigax_device.h's
 //   search    the workgroup's constants (SearchSh, search_sh_fill), a chain's start from C[] or from the corrector's prefix
 //             table (search_init, ptab_start), one backward-search step (search_step), interval_valid
 //   chains    a wave's reservation of chain numbers from a global counter (ChainGrab, grab_chains)
@@ -13,44 +13,14 @@
 #include <hip/hip_runtime.h>
 
 #include "fm_layout.h"
-#include "sigax_device.h"
+#include "sigax_fm.h"
 
 namespace {
-
-template <bool WIDE> struct PosOf { typedef u32 type; };
-template <> struct PosOf<true> { typedef u64 type; };
-
-// alphabet.h:19-39: byte -> rank, branch-free (as base_rank of sigax_kernels.hip); complement in rank space
-__device__ __forceinline__ u32 base_rank(u32 ch) {
-  const u32 i = (ch >> 1) & 3u;
-  const u32 expect = (0x47544341u >> (i * 8)) & 0xFFu;  // "ACTG"
-  const u32 rank = (0x3421u >> (i * 4)) & 0xFu;         // 1, 2, 4, 3
-  return expect == ch ? rank : 0u;
-}
-__device__ __forceinline__ u32 comp_rank(u32 r) { return r ? 5u - r : 0u; }
-
-template <typename T>
-__device__ __forceinline__ T sel4(u32 i, T v0, T v1, T v2, T v3) {  // v[i], i in 0..3, out of registers
-  const T t01 = (i & 1u) ? v1 : v0, t23 = (i & 1u) ? v3 : v2;
-  return (i & 2u) ? t23 : t01;
-}
-
-__device__ __forceinline__ u64 first_lane64(u64 v) {
-  return (u64)__builtin_amdgcn_readfirstlane((u32)v) | ((u64)__builtin_amdgcn_readfirstlane((u32)(v >> 32)) << 32);
-}
 
 // ---- one-step granule (fm_layout.h): A, C, G, T among BWT[0, p) ---------------------------------------------------
 struct Gran1 {
   uint4 k0, k1, k2, k3;
 };
-__device__ __forceinline__ void chunk_count(const uint4& k, int take, u32& a, u32& c, u32& g, u32& t) {
-  const u32 m = take >= 32 ? 0xFFFFFFFFu : (take <= 0 ? 0u : ((1u << take) - 1u));
-  const u32 x0 = k.y & m, x1 = k.z & m, x2 = k.w & m;
-  a += __popc(x0 & ~x1);
-  c += __popc(x1 & ~x0);
-  g += __popc(x0 & x1);
-  t += __popc(x2);
-}
 // Occ(rank r, p - 1) for the clamped position pc out of its granule; r = 0: the '$' column (fm_layout.h)
 template <bool WIDE>
 __device__ __forceinline__ u64 gran_rank(const FmStrand& s, const Gran1& q, u64 pc, u32 r) {

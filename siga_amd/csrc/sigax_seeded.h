@@ -234,14 +234,14 @@ __device__ __forceinline__ bool cand_slot(const u64* tab, u32 slot, const RefTex
 
 // lane src's slot for the whole wave, facing a query of n columns: candidate t on strand rev at diagonal d, its text of clen
 // bases at ref_text + rb, the columns [x0, x1) in both (x1 <= x0: none)
-struct Cand {
+struct SeedCand {
   u64 rb;
   u32 t;
   bool rev;
   long long d, x0, x1, clen;
 };
-__device__ __forceinline__ Cand cand_decode(u64 key, u64 rb, u32 len_t, int src, u32 n) {
-  Cand c;
+__device__ __forceinline__ SeedCand cand_decode(u64 key, u64 rb, u32 len_t, int src, u32 n) {
+  SeedCand c;
   const u64 k = shfl64(key, (u32)src);
   c.rb = shfl64(rb, (u32)src);
   c.clen = (long long)(u32)__shfl((int)len_t, src, 64);
