@@ -457,8 +457,8 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
  * *n_edges records, contained u8[n_strings] is the caller's, status8 (may be NULL) = the pieces' status words added up.
  *
  * Not held: read sets beyond 2^32 bases are untested.  Out of scope: gapped overlaps (indels); transitive reduction or
- * irreducible output inside this path; feeding these records to `siga unitig` (af and length were chosen so that it can be done);
- * more than one GPU; quality values; seeds chosen by content. */
+ * irreducible output inside this path (`siga unitig -e --reduce` reduces these records on the graph side); more than one GPU;
+ * quality values; seeds chosen by content. */
 typedef struct sigax_mmo_params {
   uint32_t seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates;
   uint32_t max_read_len, reserved;  /* reserved = 0 */
@@ -937,6 +937,68 @@ int  sigax_unitigs_reduce_host(int device, const sigax_edge* edges, uint64_t n_e
                                uint64_t* n_unitigs, uint64_t** seq_offs, uint64_t** lay_offs, uint32_t** uflags,
                                sigax_placement** layout, char** useqs, uint32_t** removed, uint32_t** cut, sigax_edge** uedges,
                                uint64_t status40[40]);
+/* ---- `siga unitig -e`: the consensus pass, every unitig column by majority vote (csrc/sigax_consensus.hip) -------------------------
+ * A unitig's bases are a copy: the first read whole, then of every next read its last L - overlap bytes.  With exact overlaps
+ * every read that covers a column agrees and the copy is the truth; with the mismatch overlaps of `siga overlap -e` a column holds
+ * whatever the one copied read holds there, error included.  The layout already says which reads lie over which column; this pass
+ * takes the vote.  The reference has nothing like it (Vertex::merge, src/bigraph.cpp:131-202, appends label bytes); the rules are
+ * these.  Integer arithmetic throughout; no vote depends on the order of placements, reads or lanes.  DESIGN.md 9r; the serial
+ * restatement the tests hold this against is tests/consensus_cases.py::expected_consensus.
+ *
+ * Input: the outputs of any unitig call -- the number of unitigs, seq_offs, lay_offs, layout, and useqs, which on entry holds what
+ * the call wrote (the OWN bases) -- and the reads (lengths, seqs, offs, n_reads).  For unitig u with U = seq_offs[u+1] - seq_offs[u]
+ * columns:
+ *  1. A placement (r, flags, o) of layout[lay_offs[u] .. lay_offs[u+1]) is valid iff r < n_reads and o + L[r] <= U (no wrap: o <= U
+ *     and L[r] <= U - o).  An invalid one is skipped and counted; a valid one covers the columns [o, o + L[r]).
+ *  2. The placed byte at column x is seqs[offs[r] + x - o] when the read lies forward, and the complement (A<->T, C<->G, every other
+ *     byte as it is) of seqs[offs[r] + L[r] - 1 - (x - o)] when flags & SIGAX_PLACED_REV.
+ *  3. c[A], c[C], c[G], c[T] are the numbers of valid placements whose placed byte at x is that letter.  Any other byte -- N, lower
+ *     case, anything else -- does not vote.  depth = the sum of the four.
+ *  4. The winner w is the letter with the most votes, a tie going to the earliest in the order A, C, G, T.
+ *  5. own = the byte of useqs at x on entry, c_own = c[own] if it is one of the four letters, else 0.  The column becomes w iff
+ *     c[w] > c_own and c[w] >= min_votes; otherwise it stays.  An own base that ties for first place stays, so with exact overlaps
+ *     nothing ever changes.
+ *  6. A ring is treated as a line: a placement votes on the columns it covers and on nothing else; the closing overlap of a
+ *     SIGAX_UNITIG_CIRCULAR unitig is not wrapped round.
+ *
+ * Output: useqs rewritten in place (every column is written by one lane, and that lane reads nothing of useqs but its own byte);
+ * changed u32 per unitig, the columns replaced; support u8 per column, optional (NULL: not wanted): min(255, votes for the byte the
+ * column holds on return), 0 where that byte is no letter.  status8 = 8 u64, written: 0 unitigs seen, 1 columns, 2 columns changed,
+ * 3 columns of depth below 2, 4 columns where the own base stayed on a tie with another letter (own is a letter with at least one
+ * vote, no letter has more, another has as many), 5 columns held back by min_votes (c[w] > c_own but c[w] < min_votes), 6 the
+ * largest depth, 7 placements skipped as invalid.
+ *
+ * sigax_consensus_opts: min_votes >= 1 (CLI --consensus-min-votes, default 1), reserved = 0.
+ *
+ * sigax_consensus_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the device,
+ * so it can be enqueued straight behind a unitig call.  d_n_unitigs points at a u64 ON THE DEVICE -- entry 0 of the unitig call's
+ * status block; a value above n_reads or above max_unitigs is taken as that.  d_seq_offs and d_lay_offs u64[max_unitigs + 1],
+ * d_layout sigax_placement[n_reads], d_lengths u32[n_reads], d_offs u64[n_reads + 1], d_seqs indexed by d_offs; d_useqs and
+ * d_support (or NULL) offs[n_reads] - offs[0] bytes as the unitig call's, d_changed u32[max_unitigs], of which entries 0 ..
+ * n_unitigs - 1 are counts and the rest zero; d_work = sigax_consensus_workspace bytes (counters: some 48 KiB whatever the sizes).
+ * d_layout, d_useqs, d_support and d_work 16-byte aligned, d_n_unitigs, d_seq_offs, d_lay_offs, d_offs and d_status8 8-byte aligned,
+ * d_lengths and d_changed 4-byte aligned.  A NULL where a buffer is required, a misaligned buffer, a short workspace, min_votes =
+ * 0, a non-zero reserved word and n_reads >= 2^31: SIGAX_E_ARG.  n_reads = 0 (or max_unitigs = 0): SIGAX_OK, status zeros.
+ * Whatever layout, lay_offs and seq_offs hold -- read ids that are too large, offsets beyond the unitig, tables that do not ascend
+ * -- nothing outside the buffers is touched, and every loop has a bound the host knows.  The pass finds the placements over a
+ * column by bisection: the rules above are met exactly where seq_offs and lay_offs ascend and, within each unitig, the offsets
+ * of its placements ascend, as every unitig call writes them (invalid placements among them or not); elsewhere some placements
+ * may get no vote or no count.  Needs no index.
+ * Not held: read sets beyond 2^32 bases are untested.  Out of scope: votes of contained reads (they have no placement); gapped
+ * alignment; quality-weighted votes; wrapping a ring's closing overlap; consensus inside the scaffold, gapfill and join passes. */
+typedef struct sigax_consensus_opts { uint32_t min_votes; uint32_t reserved[3]; } sigax_consensus_opts;
+int  sigax_consensus_workspace(uint64_t n_reads, uint64_t n_unitigs_max, uint64_t* bytes);  /* host arithmetic only */
+int  sigax_consensus_device(int device, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_lay_offs,
+                            const sigax_placement* d_layout, const void* d_lengths, const void* d_seqs, const void* d_offs,
+                            uint64_t n_reads, const sigax_consensus_opts* opts, void* d_useqs, void* d_changed, void* d_support,
+                            void* d_status8, void* d_work, uint64_t work_bytes, void* stream);
+/* Host buffers, synchronous.  seq_offs and lay_offs u64[n_unitigs + 1], layout sigax_placement[lay_offs[n_unitigs]], useqs
+ * seq_offs[n_unitigs] bytes, in and out; offs[0] need not be 0.  n_unitigs or lay_offs[n_unitigs] above n_reads, or more unitig
+ * bases than read bases: SIGAX_E_ARG.  *changed u32[n_unitigs] and *support u8[seq_offs[n_unitigs]] (support = NULL: not wanted)
+ * are malloc'd; release with sigax_free.  status8 is filled. */
+int  sigax_consensus_host(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint64_t* lay_offs, const sigax_placement* layout,
+                          const uint32_t* lengths, const char* seqs, const uint64_t* offs, uint64_t n_reads,
+                          const sigax_consensus_opts* opts, char* useqs, uint32_t** changed, uint8_t** support, uint64_t status8[8]);
 /* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
  * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
  * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain

@@ -49,6 +49,8 @@ SIGAX_PAIRS_OUTWARD = 1
 SIGAX_PAIRS_MAX_BINS = 8192
 PAIR_LINK_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("count", "<u4"), ("min_span", "<u4"), ("sum_span", "<u8")])  # sigax_pair_link
 assert PAIR_LINK_DTYPE.itemsize == 24
+# the entries of sigax_consensus_*'s status8, by name
+CONSENSUS_STATUS = ("unitigs", "columns", "changed", "shallow", "ties", "held_back", "max_depth", "invalid_placements")
 # the entries of sigax_unitigs_pairs_*'s status24, by name
 PAIRS_STATUS = ("mate_entries", "malformed", "pairs", "unplaced", "same", "inward", "outward", "tandem", "ring", "far", "d_n", "d_sum",
                 "d_sq_low", "d_sq_high", "span_n", "span_sum", "span_sq_low", "span_sq_high", "across", "ring_links_dropped", "over_max_span",
@@ -108,6 +110,10 @@ class IndelOpts(C.Structure):  # sigax_indel_opts
 
 class ReduceOpts(C.Structure):  # sigax_reduce_opts
     _fields_ = [("indel", IndelOpts), ("reduce", C.c_uint32), ("reserved5", C.c_uint32 * 3)]
+
+
+class ConsensusOpts(C.Structure):  # sigax_consensus_opts
+    _fields_ = [("min_votes", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class PairsOpts(C.Structure):  # sigax_pairs_opts
@@ -205,6 +211,7 @@ SYMBOLS = [
     "sigax_unitigs_bubble_workspace", "sigax_unitigs_bubble_device", "sigax_unitigs_bubble_host",
     "sigax_unitigs_indel_workspace", "sigax_unitigs_indel_device", "sigax_unitigs_indel_host",
     "sigax_unitigs_reduce_workspace", "sigax_unitigs_reduce_device", "sigax_unitigs_reduce_host",
+    "sigax_consensus_workspace", "sigax_consensus_device", "sigax_consensus_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
@@ -350,6 +357,9 @@ def lib():
                                               vp, u64, vp]
     L.sigax_unitigs_reduce_host.argtypes = [ci, vp, u64, vp, cp, vp, u64, u32, C.POINTER(ReduceOpts), C.POINTER(u64), pvp, pvp, pvp, pvp,
                                             pvp, pvp, pvp, pvp, vp]
+    L.sigax_consensus_workspace.argtypes = [u64, u64, C.POINTER(u64)]
+    L.sigax_consensus_device.argtypes = [ci, vp, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(ConsensusOpts), vp, vp, vp, vp, vp, u64, vp]
+    L.sigax_consensus_host.argtypes = [ci, u64, vp, vp, vp, vp, cp, vp, u64, C.POINTER(ConsensusOpts), vp, pvp, pvp, vp]
     L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]

@@ -65,6 +65,12 @@ def lib():
                                               C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
                                               C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_char_p,
                                               C.c_uint64]
+        L.sigah_unitig_consensus_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                  C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
+                                                  C.c_uint64, C.c_uint64, C.c_double, C.c_char_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_double,
+                                                  C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64,
+                                                  C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p,
+                                                  C.c_char_p, C.c_uint64]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -191,7 +197,7 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
                 min_branch_length=150, min_branch_coverage=None, graph=None, removed=None, max_overlap_delta=0, max_overlap_carefully=False,
                 num_reads=None, genome_size=None, uniq_threshold=13.0, cut_edges=None, min_chimeric_length=0, min_chimeric_coverage=None,
                 max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None, max_bubble_span=0, bubble_divergence=50, bubbles=None,
-                bubble_edits=0, bubble_edit_permille=50):
+                bubble_edits=0, bubble_edit_permille=50, reduce=False, error_permille=None, consensus=None, min_votes=1, contained=None, **seed):
     """`siga unitig`: FMIndex::load + Unitigger::run; the FASTA goes to the file `out`, or to stdout, the placements to the file
     `layout` when one is named.  piece_reads: reads per overlap call (0: 2^20); the result does not depend on it.
     cut_terminal (-x), min_branch_length (-n), min_branch_coverage (-C, None: no coverage test): tip trimming, 0 rounds = none;
@@ -209,8 +215,40 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
     bubble_edits (--bubble-edits; 0: none; at most 31, with a span of at most 4096), bubble_edit_permille (--bubble-edit-permille):
     indel bubble popping between the bubble and the chimeric step of a round; `bubbles` then also lists the reads it removed, as
     "name<TAB>round<TAB>indel" lines behind the others.  With edits the dict also holds indels_popped, indel_reads, indels_kept and
-    indels_not_compared."""
+    indels_not_compared.
+    error_permille (-e; None: exact overlaps): mismatch overlaps in, found as `siga overlap -e` finds them with the seed options
+    seed_length, seed_stride, max_seed_hits and max_candidates (**seed); contained reads are set aside, their names go to the file
+    `contained`.  consensus (None: on exactly when error_permille is given), min_votes: the consensus pass behind the unitig call.
+    reduce (--reduce): the transitive reduction in the rounds.  With any of them -> the dict of bubble_edits plus reduced,
+    contained_reads, columns_changed and shallow_columns."""
     err = C.create_string_buffer(512)
+    if min_votes != 1 and not (consensus or (consensus is None and error_permille is not None)):
+        raise ValueError("min_votes needs the consensus pass")
+    if error_permille is not None or consensus or reduce or contained is not None or seed:
+        unknown = set(seed) - {"seed_length", "seed_stride", "max_seed_hits", "max_candidates"}
+        if unknown:
+            raise TypeError("unitig_file: unknown option %s" % ", ".join(sorted(unknown)))
+        if error_permille is None and (seed or contained is not None):
+            raise ValueError("the seed options and `contained` apply to error_permille only")
+        status = np.zeros(24, dtype=np.uint64)
+        if lib().sigah_unitig_consensus_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,
+                                             (out or "").encode(), (layout or "").encode(), piece_reads, int(cut_terminal), int(min_branch_length),
+                                             -1 if min_branch_coverage is None else int(min_branch_coverage), (graph or "").encode(),
+                                             (removed or "").encode(), int(max_overlap_delta), int(max_overlap_carefully), int(num_reads or 0),
+                                             int(genome_size or 0), float(uniq_threshold), (cut_edges or "").encode(), int(min_chimeric_length),
+                                             -1 if min_chimeric_coverage is None else int(min_chimeric_coverage), int(max_chimeric_delta),
+                                             float(chimeric_threshold), (chimeric or "").encode(), int(max_bubble_span),
+                                             -1 if bubble_divergence is None else int(bubble_divergence), (bubbles or "").encode(),
+                                             int(bubble_edits), int(bubble_edit_permille), int(bool(reduce)),
+                                             -1 if error_permille is None else int(error_permille), int(seed.get("seed_length", 24)),
+                                             int(seed.get("seed_stride", 12)), int(seed.get("max_seed_hits", 256)),
+                                             int(seed.get("max_candidates", 512)), -1 if consensus is None else int(bool(consensus)),
+                                             int(min_votes), (contained or "").encode(), status.ctypes.data, err, 512) != 0:
+            raise RuntimeError("siga unitig failed: " + err.value.decode())
+        return dict(zip(("unitigs", "bases", "merged", "circular", "rounds", "islands", "dead_ends", "reads_removed", "records_cut", "cut_rounds",
+                         "chimeric_unitigs", "chimeric_reads", "bubbles_popped", "bubble_reads", "bubbles_kept", "indels_popped", "indel_reads",
+                         "indels_kept", "indels_not_compared", "reduced", "contained_reads", "columns_changed", "shallow_columns"),
+                        (int(x) for x in status)))
     if bubble_edits:
         status = np.zeros(19, dtype=np.uint64)
         if lib().sigah_unitig_indel_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,

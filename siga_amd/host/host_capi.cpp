@@ -434,6 +434,65 @@ int sigah_unitig_indel_file(const char* reads_path, const char* prefix, uint64_t
   return r;
 }
 
+// ... and with the transitive reduction (reduce), mismatch overlaps in (error_permille >= 0: `siga unitig -e`; the four seed
+// options as `siga overlap -e` takes them; contained_path "" = none) and the consensus pass (consensus < 0: on exactly with
+// error_permille; min_votes); status24 (unless NULL) = status19, then {records transitive in the final graph, contained reads,
+// columns the vote changed, columns of depth below 2, 0}
+int sigah_unitig_consensus_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                                const char* fasta_path, const char* layout_path, uint64_t piece_reads, uint64_t cut_terminal,
+                                uint64_t min_branch_length, int64_t min_branch_coverage, const char* graph_path, const char* removed_path,
+                                uint64_t delta, int careful, uint64_t num_reads, uint64_t genome_size, double uniq_threshold,
+                                const char* cut_path, uint64_t min_chimeric_length, int64_t min_chimeric_coverage, uint64_t chimeric_delta,
+                                double chimeric_threshold, const char* chimeric_path, uint64_t max_bubble_span, int64_t bubble_divergence,
+                                const char* bubbles_path, uint64_t bubble_edits, uint64_t bubble_edit_permille, int reduce,
+                                int64_t error_permille, uint64_t seed_length, uint64_t seed_stride, uint64_t max_seed_hits,
+                                uint64_t max_candidates, int consensus, uint64_t min_votes, const char* contained_path, uint64_t* status24,
+                                char* err, uint64_t errcap) {
+  sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  unitigger.setTrim((size_t)cut_terminal, (size_t)min_branch_length, (long)min_branch_coverage);
+  unitigger.setGraph(graph_path ? graph_path : "");
+  unitigger.setRemoved(removed_path ? removed_path : "");
+  unitigger.setMaxOverlap((size_t)delta, careful != 0, (size_t)num_reads, (size_t)genome_size, uniq_threshold);
+  unitigger.setCutEdges(cut_path ? cut_path : "");
+  unitigger.setChimeric((size_t)min_chimeric_length, (long)min_chimeric_coverage, (size_t)chimeric_delta, chimeric_threshold);
+  unitigger.setChimericOut(chimeric_path ? chimeric_path : "");
+  unitigger.setBubble((size_t)max_bubble_span, (long)bubble_divergence);
+  unitigger.setBubbleOut(bubbles_path ? bubbles_path : "");
+  unitigger.setBubbleEdits((size_t)bubble_edits, (size_t)bubble_edit_permille);
+  unitigger.setReduce(reduce != 0);
+  const bool mismatches = error_permille >= 0;
+  auto u32 = [](uint64_t v) { return (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull); };  // (the library names the field out of range)
+  if (mismatches) {
+    sigax_mmo_params p = sigah::MismatchOverlapper::defaults(u32((uint64_t)error_permille));
+    p.seed_length = u32(seed_length);
+    p.seed_stride = u32(seed_stride);
+    p.max_seed_hits = u32(max_seed_hits);
+    p.max_candidates = u32(max_candidates);
+    p.min_overlap = u32(min_overlap);
+    uint64_t probe = 0;
+    if (sigax_mmoverlap_workspace(0, 0, &p, 0, &probe) != SIGAX_OK) {
+      if (err && errcap) snprintf(err, errcap, "%s", sigax_last_error());
+      return -1;
+    }
+    unitigger.setMismatch(p, contained_path ? contained_path : "");
+  } else if (contained_path && contained_path[0]) {
+    if (err && errcap) snprintf(err, errcap, "contained reads are only written with mismatch overlaps");
+    return -1;
+  }
+  unitigger.setConsensus(consensus < 0 ? mismatches : consensus != 0, (size_t)min_votes);
+  const int r = unitig_file(unitigger, reads_path, prefix, min_overlap, device, fasta_path, layout_path, piece_reads, err, errcap);
+  if (r == 0 && status24) {
+    const uint64_t s[24] = {unitigger.unitigs(),  unitigger.bases(),        unitigger.merged(),     unitigger.cycles(),    unitigger.trimRounds(),
+                            unitigger.islands(),  unitigger.deadEnds(),     unitigger.readsRemoved(), unitigger.recordsCut(), unitigger.cutRounds(),
+                            unitigger.chimericUnitigs(), unitigger.chimericReads(), unitigger.bubblesPopped(), unitigger.bubbleReads(),
+                            unitigger.bubblesKept(), unitigger.indelsPopped(), unitigger.indelReads(), unitigger.indelsKept(),
+                            unitigger.indelsNotCompared(), unitigger.reducedFinal(), unitigger.containedReads(), unitigger.consensusChanged(),
+                            unitigger.consensusStatus()[3], 0};
+    for (int k = 0; k < 24; ++k) status24[k] = s[k];
+  }
+  return r;
+}
+
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty
 int sigah_preqc(const char* prefix, uint64_t k, uint64_t samples, uint64_t seed, int all, uint64_t max_count, int device,
                 const char* out_path, uint64_t batch_rows, char* err, uint64_t errcap) {

@@ -11,19 +11,51 @@
 
 namespace sigah {
 
+MismatchRecords::~MismatchRecords() { sigax_pile_ref_destroy(_ref); }
+
+bool MismatchRecords::open(const FMIndex& index, std::string* error) {
+  if (sigax_pile_ref_create(index.handle(), &_ref) != SIGAX_OK) {
+    *error = sigax_last_error();
+    return false;
+  }
+  return true;
+}
+
+bool MismatchRecords::find(const FMIndex& index, const sigax_mmo_params& params, size_t n, unsigned nt, std::vector<sigax_edge>* edges,
+                           std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error) {
+  sigax_mm_edge* found = nullptr;
+  struct Found {
+    sigax_mm_edge** p;
+    ~Found() { sigax_free(*p); }
+  } found_guard{&found};
+  uint64_t n_found = 0;
+  contained->assign(std::max<size_t>(n, 1), 0);
+  if (sigax_mmoverlap_batch(index.handle(), _ref, &params, &found, &n_found, contained->data(), status8) != SIGAX_OK) {
+    *error = sigax_last_error();
+    return false;
+  }
+  // the writer and the unitig calls take sigax_edge records; the mismatch counts go beside them
+  edges->resize((size_t)n_found);
+  num_diff->resize((size_t)n_found);
+  parallel_for(((size_t)n_found + 65535) / 65536, nt, [&](size_t c) {
+    const size_t b = c * 65536, e = std::min<size_t>((size_t)n_found, b + 65536);
+    for (size_t i = b; i < e; ++i) {
+      (*edges)[i].query = found[i].query;
+      (*edges)[i].target = found[i].target;
+      (*edges)[i].length = found[i].length;
+      (*edges)[i].af = found[i].af;
+      (*num_diff)[i] = found[i].num_diff;
+    }
+  });
+  return true;
+}
+
 bool MismatchOverlapper::run(const FMIndex& index, const std::string& input, const std::string& output, size_t threads) const {
   for (int k = 0; k < 8; ++k) _status[k] = 0;
   _records = 0;
   // the reference text once, before any file is touched: an index that cannot serve is refused here
-  sigax_pile_ref* ref = nullptr;
-  struct RefGuard {
-    sigax_pile_ref** r;
-    ~RefGuard() { sigax_pile_ref_destroy(*r); }
-  } ref_guard{&ref};
-  if (sigax_pile_ref_create(index.handle(), &ref) != SIGAX_OK) {
-    _error = sigax_last_error();
-    return false;
-  }
+  MismatchRecords ref;
+  if (!ref.open(index, &_error)) return false;
   const HostSettings hs;
   const unsigned nt = (unsigned)std::max<size_t>(threads, 1);
   ReadStore rs;
@@ -47,33 +79,12 @@ bool MismatchOverlapper::run(const FMIndex& index, const std::string& input, con
     _error = sigax_last_error();
     return false;
   }
-  sigax_mm_edge* found = nullptr;
-  struct Found {
-    sigax_mm_edge** p;
-    ~Found() { sigax_free(*p); }
-  } found_guard{&found};
-  uint64_t n_found = 0;
-  std::vector<uint8_t> contained(std::max<size_t>(n, 1), 0);
-  if (sigax_mmoverlap_batch(index.handle(), ref, &_params, &found, &n_found, contained.data(), _status) != SIGAX_OK) {
-    _error = sigax_last_error();
-    return false;
-  }
+  std::vector<sigax_edge> edges;
+  std::vector<uint32_t> num_diff;
+  std::vector<uint8_t> contained;
+  if (!ref.find(index, _params, n, nt, &edges, &num_diff, &contained, _status, &_error)) return false;
+  const uint64_t n_found = edges.size();
   _records = n_found;
-  // the writer takes sigax_edge records; the mismatch counts go beside them
-  std::vector<sigax_edge> edges((size_t)n_found);
-  std::vector<uint32_t> num_diff((size_t)n_found);
-  parallel_for(((size_t)n_found + 65535) / 65536, nt, [&](size_t c) {
-    const size_t b = c * 65536, e = std::min<size_t>((size_t)n_found, b + 65536);
-    for (size_t i = b; i < e; ++i) {
-      edges[i].query = found[i].query;
-      edges[i].target = found[i].target;
-      edges[i].length = found[i].length;
-      edges[i].af = found[i].af;
-      num_diff[i] = found[i].num_diff;
-    }
-  });
-  sigax_free(found);
-  found = nullptr;
   OutFile out(output, nt);
   if (!out.ok()) {
     _error = "cannot write " + output;

@@ -314,6 +314,10 @@ std::string run_pairs(int device, const std::vector<uint32_t>& mate, const std::
   append_double(t, span_mean);
   t += ", \"span_sd\": ";
   append_double(t, span_sd);
+  if (rq.haveContainedMates) {
+    t += ", \"contained_mates\": ";
+    append_u64(t, rq.containedMates);
+  }
   t += ", \"hist_bins\": ";
   append_u64(t, rq.bins);
   t += ", \"hist_shift\": ";

@@ -21,6 +21,8 @@ struct PairsRequest {
   uint64_t maxSpan = 0;
   bool outward = false;
   uint32_t bins = 1024, shift = 0;
+  bool haveContainedMates = false;  // `siga unitig -e`: the JSON also gets "contained_mates"
+  uint64_t containedMates = 0;
 };
 struct ScaffoldRequest {
   std::string fasta, layout;  // files; fasta empty: no scaffolds; layout may be empty

@@ -129,6 +129,23 @@ class OverlapBuilder {
 // found by seeds and verified on the GPU (sigax_mmoverlap_batch; the rules in include/sigax.h).  No counterpart in the reference,
 // whose finder is exact.  OverlapBuilder::build is not involved.  The index needs its forward .sai table and reads of ACGT only
 // (FMIndex::loadForwardSai will do); `input` must be the reads it was built from.
+// The records of that path, shared by `siga overlap -e` and `siga unitig -e`: open() builds the reference text (an index that
+// cannot serve -- no forward .sai, reads with other bytes than ACGT -- is refused there, with the library's message), find() runs
+// sigax_mmoverlap_batch over every read of the index and hands the records on as sigax_edge with the mismatch counts beside them.
+class MismatchRecords {
+ public:
+  MismatchRecords() = default;
+  MismatchRecords(const MismatchRecords&) = delete;
+  MismatchRecords& operator=(const MismatchRecords&) = delete;
+  ~MismatchRecords();
+  bool open(const FMIndex& index, std::string* error);
+  bool find(const FMIndex& index, const sigax_mmo_params& params, size_t n, unsigned threads, std::vector<sigax_edge>* edges,
+            std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error);
+
+ private:
+  sigax_pile_ref* _ref = nullptr;
+};
+
 class MismatchOverlapper {
  public:
   static sigax_mmo_params defaults(uint32_t error_permille) {  // the CLI's
@@ -390,6 +407,30 @@ class Unitigger {
     _joinMismatches = mismatches;
     _joinMismatchPermille = permille;
   }
+  // Mismatch overlaps in (`-e`; the rules of the `siga overlap -e` block of include/sigax.h): the records come from
+  // MismatchRecords over every read of the index instead of the exact overlap stages, every record that touches a contained read
+  // is dropped before the unitig call, so that such a read ends up as a unitig of its own, and no output shows those unitigs;
+  // unitig numbers stay the call's.  The irreducible / rc flags of the constructor play no part.  `contained`, if not empty, gets
+  // the names of the contained reads, one per line, in input order.  With --pairs a pair with a contained mate is no pair.
+  // unitigs() counts the call's unitigs, the hidden ones among them (unitigsHidden()).  With trim rounds a contained read on
+  // its own is an island like any other: the trim step may remove it, and setRemoved's file then lists it with its round.
+  void setMismatch(const sigax_mmo_params& params, const std::string& contained = std::string()) {
+    _mismatch = true;
+    _mmo = params;
+    _containedOut = contained;
+  }
+  // The consensus pass (sigax_consensus_host; the rules in include/sigax.h) right behind the unitig call and before anything reads
+  // the bases: every column by majority vote over the reads laid over it; every FASTA header then ends in " changed=<columns>".
+  void setConsensus(bool on, size_t minVotes = 1) {
+    _consensus = on;
+    _minVotes = minVotes;
+  }
+  uint64_t containedReads() const { return _containedReads; }
+  uint64_t unitigsHidden() const { return _unitigsHidden; }    // unitigs of one contained read each, which no output shows
+  uint64_t containedMates() const { return _containedMates; }  // pairs left out because a mate is contained
+  uint64_t consensusChanged() const { return _consChanged; }   // columns the vote replaced
+  const uint64_t* consensusStatus() const { return _consStatus; }
+  const uint64_t* mismatchStatus() const { return _mmStatus; }
   uint64_t joinsApproximate() const { return _joinsApprox; }
   uint64_t joinCorrected() const { return _joinCorrected; }
   uint64_t gaps() const { return _gaps; }
@@ -464,6 +505,12 @@ class Unitigger {
   size_t _scMinPairs = 2, _scLinkRatio = 0, _scMinUnitigBases = 0, _scMinGap = 1, _scMaxGap = 1000000;
   long long _scInsertSize = -1;
   uint64_t _scaffolds = 0, _scJoins = 0, _scAmbiguous = 0, _scGapBases = 0;
+  bool _mismatch = false, _consensus = false;
+  sigax_mmo_params _mmo = {24, 12, 256, 45, 0, 512, 0, 0};
+  size_t _minVotes = 1;
+  std::string _containedOut;
+  uint64_t _containedReads = 0, _containedMates = 0, _consChanged = 0, _unitigsHidden = 0;
+  uint64_t _consStatus[8] = {0, 0, 0, 0, 0, 0, 0, 0}, _mmStatus[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool _gapfill = false;
   size_t _gapKmer = 31, _gapMinCount = 3, _gapSlack = 100, _gapMaxFill = 10000;
   std::string _gapsOut;

@@ -7,6 +7,7 @@
 
 #include <chrono>
 #include <thread>
+#include <algorithm>
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
@@ -649,6 +650,20 @@ static int unitig_help() {
          "      -p, --prefix=PREFIX              use PREFIX instead of prefix of READSFILE for the names of the index files\n"
          "      -o, --out=FILE                   write the unitigs to FILE (default: <prefix>.unitigs.fa)\n"
          "          --layout=FILE                also write one line per read to FILE: unitig, read name, + or -, offset\n"
+         "      -e, --error-permille=P           take the overlaps with at most P mismatches per mille, found by seeds and verified as\n"
+         "                                       `siga overlap -e` does, instead of the exact ones; a read contained in another is set\n"
+         "                                       aside (no output shows it; with -x it goes as an island and --removed lists it; the\n"
+         "                                       unitig count printed includes it), and every unitig column is then rewritten by vote\n"
+         "                                       over the reads laid over it (headers gain changed=<columns>).  These records are\n"
+         "                                       exhaustive: without --reduce nearly every read end is branched, as with --exhaustive.\n"
+         "                                       Needs the .sai of the index and reads of ACGT only; not with --exhaustive or\n"
+         "                                       --no-opposite-strand\n"
+         "          --seed-length=N, --seed-stride=N, --max-seed-hits=N, --max-candidates=N\n"
+         "                                       (need -e) the seeds, as in `siga overlap -e` (defaults: 24, 12, 256, 512)\n"
+         "          --contained=FILE             (needs -e) write the names of the contained reads to FILE, in input order\n"
+         "          --consensus, --no-consensus  the vote on or off (default: on exactly with -e); without -e it changes no base and\n"
+         "                                       adds changed=0 to every header\n"
+         "          --consensus-min-votes=N      replace a base only by one with at least N votes (default: 1)\n"
          "          --exhaustive                 overlap exhaustively, transitive edges included (they branch: fewer merges;\n"
          "                                       see --reduce)\n"
          "          --reduce                     flag the overlaps a third read explains exactly (transitive reduction) before the\n"
@@ -785,7 +800,8 @@ static int run_unitig(int argc, char** argv) {
          OPT_MIN_SCAFFOLD_UNITIG, OPT_INSERT_SIZE, OPT_MIN_GAP, OPT_MAX_GAP, OPT_BUBBLE_DIVERGENCE, OPT_NO_BUBBLE_BASES, OPT_BUBBLES,
          OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
          OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS,
-         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE, OPT_REDUCE, OPT_REDUCED_EDGES };
+         OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE, OPT_REDUCE, OPT_REDUCED_EDGES,
+         OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES, OPT_CONSENSUS, OPT_NO_CONSENSUS, OPT_CONSENSUS_MIN_VOTES, OPT_CONTAINED };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -825,9 +841,28 @@ static int run_unitig(int argc, char** argv) {
                                     {"join-min-count", required_argument, nullptr, OPT_JOIN_MIN_COUNT}, {"joins", required_argument, nullptr, OPT_JOINS},
                                     {"join-mismatches", required_argument, nullptr, OPT_JOIN_MISMATCHES},
                                     {"join-mismatch-permille", required_argument, nullptr, OPT_JOIN_MISMATCH_PERMILLE},
+                                    {"error-permille", required_argument, nullptr, 'e'}, {"seed-length", required_argument, nullptr, OPT_SEED_LENGTH},
+                                    {"seed-stride", required_argument, nullptr, OPT_SEED_STRIDE},
+                                    {"max-seed-hits", required_argument, nullptr, OPT_MAX_SEED_HITS},
+                                    {"max-candidates", required_argument, nullptr, OPT_MAX_CANDIDATES},
+                                    {"consensus", no_argument, nullptr, OPT_CONSENSUS}, {"no-consensus", no_argument, nullptr, OPT_NO_CONSENSUS},
+                                    {"consensus-min-votes", required_argument, nullptr, OPT_CONSENSUS_MIN_VOTES},
+                                    {"contained", required_argument, nullptr, OPT_CONTAINED},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut, reducedEdges;
+  // -e: mismatch overlaps in (the seed options are its own, as in `siga overlap -e`), consensus bases out
+  sigax_mmo_params mmo = sigah::MismatchOverlapper::defaults(0);
+  bool mismatches = false, votesTuned = false;
+  int consensus = -1;  // -1: on exactly when -e is given
+  size_t minVotes = 1;
+  std::string containedOut;
+  const char* seed_option = nullptr;  // the first option on the line that only -e takes
+  auto num32 = [](const char* a) {  // a number in 0 .. 2^32 - 1, or 2^32 - 1 for anything else: the library names the field out of range
+    char* end = nullptr;
+    const unsigned long long v = strtoull(a, &end, 10);
+    return (uint32_t)((*a == '-' || end == a || *end || v > 0xFFFFFFFFull) ? 0xFFFFFFFFull : v);
+  };
   bool reduce = false;
   size_t maxSpan = 0, pairsBins = 1024, pairsShift = 0;
   bool outward = false, pairsTuned = false;
@@ -856,8 +891,24 @@ static int run_unitig(int argc, char** argv) {
   if (apply_ini(argc, argv, longopts, &ini_store, &ini_argv) != 0) return 1;
   argc = (int)ini_argv.size();
   argv = ini_argv.data();
-  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:l:A:a:b:h", longopts, nullptr)) != -1) {
+  while ((c = getopt_long(argc, argv, "c:s:t:p:m:o:x:n:C:d:N:G:T:l:A:a:b:e:h", longopts, nullptr)) != -1) {
     switch (c) {
+      case 'e': mmo.error_permille = num32(optarg); mismatches = true; break;
+      case OPT_SEED_LENGTH: mmo.seed_length = num32(optarg); if (!seed_option) seed_option = "--seed-length"; break;
+      case OPT_SEED_STRIDE: mmo.seed_stride = num32(optarg); if (!seed_option) seed_option = "--seed-stride"; break;
+      case OPT_MAX_SEED_HITS: mmo.max_seed_hits = num32(optarg); if (!seed_option) seed_option = "--max-seed-hits"; break;
+      case OPT_MAX_CANDIDATES: mmo.max_candidates = num32(optarg); if (!seed_option) seed_option = "--max-candidates"; break;
+      case OPT_CONTAINED: containedOut = optarg; if (!seed_option) seed_option = "--contained"; break;
+      case OPT_CONSENSUS: consensus = 1; break;
+      case OPT_NO_CONSENSUS: consensus = 0; break;
+      case OPT_CONSENSUS_MIN_VOTES:
+        if (!unitig_number(optarg, "--consensus-min-votes", 0xFFFFFFFFull, &minVotes)) return 1;
+        if (minVotes == 0) {
+          fprintf(stderr, "siga unitig: --consensus-min-votes needs a number from 1 to 4294967295, got '0'\n");
+          return 1;
+        }
+        votesTuned = true;
+        break;
       case 'p': prefix = optarg; break;
       case 't': threads = strtoull(optarg, nullptr, 10); break;
       case 'm': minOverlap = strtoull(optarg, nullptr, 10); break;
@@ -945,6 +996,27 @@ static int run_unitig(int argc, char** argv) {
     }
   }
   if (help || argc - optind != 1) return unitig_help();
+  if (!mismatches && seed_option) {
+    fprintf(stderr, "siga unitig: option %s applies to -e/--error-permille only\n", seed_option);
+    return 1;
+  }
+  if (mismatches && (exhaustive || norc)) {
+    fprintf(stderr, "siga unitig: option %s cannot be combined with -e/--error-permille\n", exhaustive ? "--exhaustive" : "--no-opposite-strand");
+    return 1;
+  }
+  const bool vote = consensus < 0 ? mismatches : consensus != 0;
+  if (votesTuned && !vote) {
+    fprintf(stderr, "siga unitig: --consensus-min-votes needs --consensus or -e/--error-permille\n");
+    return 1;
+  }
+  if (mismatches) {
+    mmo.min_overlap = (uint32_t)std::min<size_t>(minOverlap, 0xFFFFFFFFull);
+    uint64_t probe = 0;
+    if (sigax_mmoverlap_workspace(0, 0, &mmo, 0, &probe) != SIGAX_OK) {  // the ranges are the library's
+      fprintf(stderr, "siga unitig: %s\n", sigax_last_error());
+      return 1;
+    }
+  }
   if (delta > 0 && cutTerminal == 0) {
     fprintf(stderr, "siga unitig: -d, --max-overlap-delta needs -x, --cut-terminal: the cutting runs in its rounds\n");
     return 1;
@@ -1052,12 +1124,22 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setGapfill(gapfill, gapKmer, gapMinCount, gapSlack, gapMaxFill, gapsOut);
   unitigger.setJoinOverlaps(joinOverlaps, joinMinOverlap, joinMaxOverlap, joinSlack, joinKmer, joinMinCount, joinsOut);
   unitigger.setJoinMismatches(joinMismatches, joinMismatchPermille);
+  if (mismatches) unitigger.setMismatch(mmo, containedOut);
+  unitigger.setConsensus(vote, minVotes);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
     return -1;
   }
   fprintf(stderr, "%llu unitigs, %llu bases, %llu overlaps merged, %llu circular\n", (unsigned long long)unitigger.unitigs(),
           (unsigned long long)unitigger.bases(), (unsigned long long)unitigger.merged(), (unsigned long long)unitigger.cycles());
+  if (mismatches)
+    fprintf(stderr, "%llu contained reads set aside; %llu of the unitigs counted above are such a read on its own, which no output shows%s\n",
+            (unsigned long long)unitigger.containedReads(), (unsigned long long)unitigger.unitigsHidden(),
+            cutTerminal ? " (the others went as islands in the trim rounds: --removed lists them)" : "");
+  if (vote)
+    fprintf(stderr, "%llu columns changed by the vote, %llu of depth below 2, %llu ties kept, largest depth %llu\n",
+            (unsigned long long)unitigger.consensusChanged(), (unsigned long long)unitigger.consensusStatus()[3],
+            (unsigned long long)unitigger.consensusStatus()[4], (unsigned long long)unitigger.consensusStatus()[6]);
   if (cutTerminal)
     fprintf(stderr, "%llu trim rounds, %llu islands and %llu dead ends removed, %llu reads\n", (unsigned long long)unitigger.trimRounds(),
             (unsigned long long)unitigger.islands(), (unsigned long long)unitigger.deadEnds(), (unsigned long long)unitigger.readsRemoved());

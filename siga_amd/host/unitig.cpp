@@ -40,7 +40,7 @@ bool write_all(FILE* f, const std::string& t) { return t.empty() || fwrite(t.dat
 
 // The unitig graph as ASQG: the header, one VT line per unitig, one ED line per lifted record (AsqgWriter's formatter over the
 // unitigs' names and lengths).
-static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t n_uedges, size_t minOverlap) {
+static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t n_uedges, size_t minOverlap, const std::vector<uint8_t>& hidden) {
   OutFile out(path);
   if (!out.ok()) return false;
   out.write(asqg_header(minOverlap));
@@ -49,6 +49,7 @@ static bool write_graph_file(const std::string& path, const Unitigs& u, uint64_t
   for (uint64_t k = 0; k < u.n; ++k) {
     names[k] = "unitig-";
     append_u64(names[k], k);
+    if (!hidden.empty() && hidden[k]) continue;  // (a contained read on its own: no record touches it)
     const uint64_t cnt = u.lay_offs[k + 1] - u.lay_offs[k];
     t += "VT\t";
     t += names[k];
@@ -89,8 +90,14 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _scaffolds = _scJoins = _scAmbiguous = _scGapBases = 0;
   _gaps = _gapsFilled = _gapFillBases = _gapBasesLeft = 0;
   _joinGaps = _joinsMade = _joinOverlapBases = _joinNRemoved = _joinsApprox = _joinCorrected = 0;
+  _containedReads = _containedMates = _consChanged = _unitigsHidden = 0;
+  for (int k = 0; k < 8; ++k) _consStatus[k] = _mmStatus[k] = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
+  if (!_mismatch && !_containedOut.empty()) return fail("contained reads are only written with mismatch overlaps");
+  if (_consensus && (_minVotes < 1 || _minVotes > 0xFFFFFFFFull)) return fail("consensus min-votes out of range");
+  MismatchRecords mm;  // the reference text once, before any file is touched: an index that cannot serve is refused here
+  if (_mismatch && !mm.open(index, &_error)) return false;
   const HostSettings hs;
   const unsigned nt = host_threads(threads, hs);
   ReadStore reads;
@@ -106,7 +113,21 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   std::vector<sigax_edge> edges;
   std::vector<uint64_t> offs;
   const size_t per = _piece ? _piece : (size_t)1 << 20;
-  for (size_t base = 0; base < n; base += per) {
+  std::vector<uint8_t> contained;  // -e: one byte per read
+  if (_mismatch) {
+    if (inf.n_strings != n) return fail(input + " holds " + std::to_string(n) + " reads, the index " + std::to_string(inf.n_strings));
+    sigax_mmo_params p = _mmo;
+    p.min_overlap = (uint32_t)std::min<size_t>(minOverlap, 0xFFFFFFFFull);
+    std::vector<uint32_t> num_diff;
+    if (!mm.find(index, p, n, nt, &edges, &num_diff, &contained, _mmStatus, &_error)) return false;
+    // a record that touches a contained read is dropped: the read stays a unitig of its own, which no output shows
+    size_t kept = 0;
+    for (size_t i = 0; i < edges.size(); ++i)
+      if (!contained[edges[i].query] && !contained[edges[i].target]) edges[kept++] = edges[i];
+    edges.resize(kept);
+    for (size_t r = 0; r < n; ++r) _containedReads += contained[r] ? 1 : 0;
+  }
+  for (size_t base = 0; base < n && !_mismatch; base += per) {
     const size_t cnt = std::min(per, n - base);
     offs.resize(cnt + 1);
     for (size_t i = 0; i <= cnt; ++i) offs[i] = reads.offs[base + i] - reads.offs[base];
@@ -238,6 +259,25 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _redFirst = status[32];
   _redFinal = status[33];
   _redPasses = status[34];
+  // -e: the unitigs of one contained read each, which no output shows; their numbers stay taken
+  std::vector<uint8_t> hidden;
+  if (_mismatch) {
+    hidden.assign((size_t)u.n, 0);
+    for (uint64_t k = 0; k < u.n; ++k)
+      _unitigsHidden += hidden[k] = u.lay_offs[k + 1] - u.lay_offs[k] == 1 && contained[u.layout[u.lay_offs[k]].read] ? 1 : 0;
+  }
+  // the vote, before anything reads the bases
+  struct Changed {
+    uint32_t* p = nullptr;
+    ~Changed() { sigax_free(p); }
+  } changed;
+  if (_consensus) {
+    const sigax_consensus_opts copts = {(uint32_t)_minVotes, {0, 0, 0}};
+    if (sigax_consensus_host(inf.device, u.n, u.seq_offs, u.lay_offs, u.layout, lengths.data(), reads.seqs.data(), reads.offs.data(), n, &copts,
+                             u.useqs, &changed.p, nullptr, _consStatus) != SIGAX_OK)
+      return fail(std::string("consensus failed: ") + sigax_last_error());
+    _consChanged = _consStatus[2];
+  }
   if (!_pairsOut.empty()) {  // over the unitigs as they stand, whichever call built them; the other outputs do not depend on it
     PairsRequest rq;
     rq.json = _pairsOut;
@@ -278,7 +318,21 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     uint64_t st24[24], st16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t gp24[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t jn24[24] = {0};
-    const std::string e = run_pairs(inf.device, mates_by_name(reads, ranks), lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
+    std::vector<uint32_t> mate = mates_by_name(reads, ranks);
+    if (_mismatch)  // a pair with a contained mate is no pair
+      for (size_t r = 0; r < n; ++r) {
+        const uint32_t m = mate[r];
+        if (m != SIGAX_NO_MATE && m < n && (contained[r] || contained[m])) {
+          if (mate[m] == r) {
+            mate[m] = SIGAX_NO_MATE;
+            ++_containedMates;
+          }
+          mate[r] = SIGAX_NO_MATE;
+        }
+      }
+    rq.haveContainedMates = _mismatch;
+    rq.containedMates = _containedMates;
+    const std::string e = run_pairs(inf.device, mate, lengths, u.n, u.seq_offs, u.lay_offs, u.uflags, u.layout, rq, st24,
                                     &_insertSize, &_insertDelta, &sq, u.useqs, st16, gp24, jn24);
     if (!e.empty()) return fail(e);
     _joinGaps = jn24[0];
@@ -307,6 +361,14 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   std::string t;
   bool ok = true;
   for (uint64_t k = 0; k < u.n && ok; ++k) {
+    const bool last = k + 1 == u.n;
+    if (!hidden.empty() && hidden[k]) {
+      if (last) {
+        ok = write_all(out, t);
+        t.clear();
+      }
+      continue;
+    }
     const uint64_t cnt = u.lay_offs[k + 1] - u.lay_offs[k];
     t += ">unitig-";
     append_u64(t, k);
@@ -317,6 +379,10 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (u.uflags[k] & SIGAX_UNITIG_CIRCULAR) {
       t += " circular=";
       append_u64(t, u.uflags[k] >> 1);
+    }
+    if (_consensus) {
+      t += " changed=";
+      append_u64(t, changed.p[k]);
     }
     t += '\n';
     t.append(u.useqs + u.seq_offs[k], u.seq_offs[k + 1] - u.seq_offs[k]);
@@ -329,7 +395,22 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   if (fflush(out) != 0) ok = false;
   if (out != stdout) fclose(out);
   if (!ok) return fail("Failed to write " + (fasta.empty() ? std::string("stdout") : fasta));
-  if (!_graph.empty() && !write_graph_file(_graph, u, status[11], minOverlap)) return fail("Failed to write " + _graph);
+  if (!_graph.empty() && !write_graph_file(_graph, u, status[11], minOverlap, hidden)) return fail("Failed to write " + _graph);
+  if (!_containedOut.empty()) {  // the names of the contained reads, in input order
+    FILE* rf = fopen(_containedOut.c_str(), "wb");
+    if (!rf) return fail("Failed to create " + _containedOut);
+    t.clear();
+    for (size_t r = 0; r < n; ++r)
+      if (contained[r]) {
+        const std::string_view name = reads.name(r);
+        t.append(name.data(), name.size());
+        t += '\n';
+      }
+    ok = write_all(rf, t);
+    if (fclose(rf) != 0) ok = false;
+    if (!ok) return fail("Failed to write " + _containedOut);
+    t.clear();
+  }
   if (!_removed.empty()) {
     FILE* rf = fopen(_removed.c_str(), "wb");
     if (!rf) return fail("Failed to create " + _removed);
@@ -443,7 +524,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   if (!lf) return fail("Failed to create " + layout);
   t.clear();
   for (uint64_t k = 0; k < u.n && ok; ++k) {
-    for (uint64_t p = u.lay_offs[k]; p < u.lay_offs[k + 1]; ++p) {
+    for (uint64_t p = u.lay_offs[k]; p < u.lay_offs[k + 1] && (hidden.empty() || !hidden[k]); ++p) {
       const sigax_placement& pl = u.layout[p];
       const std::string_view name = reads.name(pl.read);
       t += "unitig-";

@@ -328,6 +328,42 @@ def pairs_estimate(status):
     return int(ins.value), int(dl.value), float(sm.value), float(sd.value)
 
 
+def unitigs_consensus(res, lengths, seqs, offs, min_votes=1, support=False, device=0):
+    """The consensus pass (sigax_consensus_host, the rules in include/sigax.h) over the dict `res` any `unitigs*` call returned
+    with its bases, and the reads that call was given: every unitig column by majority vote over the reads the layout lays over
+    it -> dict(useqs uint8 array, changed u32[U] columns replaced per unitig, support u8 array (votes for the byte a column
+    holds, at most 255) or None, status u64[8] (named by _lib.CONSENSUS_STATUS)).  `res` is not modified."""
+    _, lengths, buf, offs, n = _unitig_arrays(np.zeros(0, dtype=EDGE_DTYPE), lengths, seqs, offs)
+    if res.get("useqs") is None:
+        raise ValueError("the unitig call's bases are needed (bases=True)")
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    lo = np.ascontiguousarray(res["lay_offs"], dtype=np.uint64)
+    lay = np.ascontiguousarray(res["layout"], dtype=PLACEMENT_DTYPE)
+    u = len(so) - 1
+    if u < 0 or len(lo) != u + 1:
+        raise ValueError("seq_offs and lay_offs must have one entry more than there are unitigs")
+    if len(lay) < int(lo[u]):
+        raise ValueError("layout shorter than lay_offs says")
+    us = np.array(res["useqs"], dtype=np.uint8)  # (a copy: the call rewrites it in place)
+    if len(us) < int(so[u]):
+        raise ValueError("useqs shorter than seq_offs says")
+    L = _lib.lib()
+    opts = _lib.ConsensusOpts(int(min_votes), (0, 0, 0))
+    cp, sp = C.c_void_p(), C.c_void_p()
+    status = np.zeros(8, dtype=np.uint64)
+    _check(L.sigax_consensus_host(device, u, so.ctypes.data, lo.ctypes.data, lay.ctypes.data if len(lay) else None,
+                                  lengths.ctypes.data if n else None, buf[0], offs.ctypes.data, n, C.byref(opts),
+                                  us.ctypes.data if len(us) else None, C.byref(cp), C.byref(sp) if support else None, status.ctypes.data),
+           "sigax_consensus_host")
+    try:
+        out = {"useqs": us, "changed": _copy_records(cp, u, np.dtype(np.uint32)),
+               "support": _copy_records(sp, int(so[u]), np.dtype(np.uint8)) if support else None, "status": status}
+    finally:
+        L.sigax_free(cp)
+        L.sigax_free(sp)
+    return out
+
+
 def unitigs_pairs(res, lengths, mate, hist_bins=1024, hist_shift=0, max_span=0, outward=False, device=0):
     """Mate-pair statistics and the links between unitig ends (sigax_unitigs_pairs_host, the rules in include/sigax.h) over the
     dict `res` any `unitigs*` call returned: lengths u32[n], mate u32[n] (`mates_by_name`; SIGAX_NO_MATE = none) -> dict(status
