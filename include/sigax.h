@@ -424,7 +424,7 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
  *     text's prefix, l = n + d); otherwise PREFIX (q's prefix on text's suffix, l = L - d).
  *  6. Containment flags, contained[], one byte per read of the index: Q_IN_T sets contained[i], T_IN_Q sets contained[t], DUP sets
  *     the flag of the read with the LARGER name rank (`rmdup` keeps the smaller name).  A flag is set from whichever side finds the
- *     alignment.  Containments give no record.
+ *     alignment.  Containments give no record unless params.flags asks for them (rule 9).
  *  7. Dovetail records: sigax_mm_edge {query, target, length = l, af, num_diff = m, reserved = 0}; af has the meaning it has in
  *     sigax_edge, so the ED coordinates follow from (length, af, read lengths): SUFFIX + 0, SUFFIX - 6 (TARGETREV|QUERYCOMP),
  *     PREFIX + 3 (QUERYREV|TARGETREV), PREFIX - 5 (QUERYREV|QUERYCOMP).  Canonical form: the read with the larger name rank is
@@ -435,6 +435,15 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
  *     every accepted alignment holds a run of S + T - 1 matching columns -- min over l >= M of ceil((l - m) / (m + 1)) >= S + T - 1
  *     with m = floor(l P / 1000) -- and neither H is reached nor K on both sides, the set equals the one a search over every read,
  *     strand and diagonal gives.
+ *
+ *  9. flags = SIGAX_MMO_CONTAINMENTS: every accepted candidate of class Q_IN_T, T_IN_Q or DUP also gives one record in the same
+ *     stream, counted by status[7] and subject to edges_cap like the others: query = the contained read (the one rule 6 flags),
+ *     target = its container, length = len(contained), af = SIGAX_MM_CONTAINMENT | (4 if the contained read lies
+ *     reverse-complemented in the container), num_diff = m, reserved = o, the first column of the container's FORWARD text that the
+ *     contained read covers: Q_IN_T found from q = contained gives o = d forward and o = L - d - n reverse, T_IN_Q found from q =
+ *     container gives o = -d on either strand, DUP gives 0; both sides of a pair thus give the same record.  Every set byte of
+ *     contained[] then has at least one record.  flags = 0: no such record, every output as without this rule.  Other values:
+ *     SIGAX_E_ARG.  Two containments of one pair on different diagonals are two records.
  *
  * sigax_mmoverlap_device: reads first_read .. first_read + n_reads of the index as queries, every buffer in device memory,
  * asynchronous on `stream`, allocates nothing.  d_ref_text / d_ref_offs: the reference text (sigax_reference_text_device,
@@ -448,8 +457,10 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
  * edges_cap - *d_cursor: the cursor is left where it was, no record and no flag of this call is written, status[7] carries the
  * number needed and status[0..6] are as counted.  Raw records are in no particular order and a pair may be there twice.
  *
- * sigax_mmoverlap_finish_device: orders n_raw raw records (below 2^32) by (query, target, af, length), drops repeats, leaves the
- * result at the front of d_edges and its count in *d_n_unique (u64).  Asynchronous, allocates nothing; d_work =
+ * sigax_mmoverlap_finish_device: orders n_raw raw records (below 2^32) by (query, target, af, length, reserved), drops repeats,
+ * leaves the result at the front of d_edges and its count in *d_n_unique (u64).  reserved is ordered in full width -- a
+ * containment's offset is as wide as its container is long, and a read longer than max_read_len can be one -- and length by its
+ * low 13 bits: an overlap of this path has at most 4096 columns.  Asynchronous, allocates nothing; d_work =
  * sigax_mmoverlap_finish_workspace(n_raw) bytes, 16-byte aligned.  Run it once over the records of all calls.
  *
  * sigax_mmoverlap_batch: synchronous; every read of the index in pieces, hits_cap and edges_cap sized from the status words, a
@@ -461,8 +472,10 @@ int  sigax_pileup_batch(sigax_index*, const sigax_pile_ref*, const char* seqs, c
  * quality values; seeds chosen by content. */
 typedef struct sigax_mmo_params {
   uint32_t seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates;
-  uint32_t max_read_len, reserved;  /* reserved = 0 */
+  uint32_t max_read_len, flags;  /* flags: 0 or SIGAX_MMO_CONTAINMENTS */
 } sigax_mmo_params;
+#define SIGAX_MMO_CONTAINMENTS 1u  /* sigax_mmo_params.flags: containment records too (rule 9) */
+#define SIGAX_MM_CONTAINMENT   8u  /* sigax_mm_edge.af of a containment record; bit 2 (4): reverse-complemented in the container */
 typedef struct sigax_mm_edge { uint32_t query, target, length, af, num_diff, reserved; } sigax_mm_edge;  /* 24 bytes */
 int  sigax_mmoverlap_workspace(uint64_t n_reads, uint64_t n_bases, const sigax_mmo_params*, uint64_t hits_cap, uint64_t* bytes);
 int  sigax_mmoverlap_device(sigax_index*, const void* d_ref_text, const void* d_ref_offs, uint64_t first_read, uint64_t n_reads,
@@ -512,6 +525,7 @@ int  sigax_mmoverlap_batch(sigax_index*, const sigax_pile_ref*, const sigax_mmo_
  * SIGAX_OK, status zeros (when d_status6 is given).  Needs no index. */
 typedef struct sigax_placement { uint32_t read, flags; uint64_t offset; } sigax_placement; /* 16 bytes */
 #define SIGAX_PLACED_REV      1u   /* the read lies reverse-complemented in its unitig */
+#define SIGAX_PLACED_CONTAINED 2u  /* a contained read placed by sigax_contained_place_*: no unitig call sets it */
 #define SIGAX_UNITIG_CIRCULAR 1u   /* unitig flag, bit0; the closing overlap is uflags >> 1 */
 int  sigax_unitigs_workspace(uint64_t n_reads, uint64_t n_edges, uint64_t* bytes);  /* host arithmetic only */
 int  sigax_unitigs_device(int device, const sigax_edge* d_edges, uint64_t n_edges, const void* d_lengths, const void* d_seqs,
@@ -984,8 +998,9 @@ int  sigax_unitigs_reduce_host(int device, const sigax_edge* edges, uint64_t n_e
  * column by bisection: the rules above are met exactly where seq_offs and lay_offs ascend and, within each unitig, the offsets
  * of its placements ascend, as every unitig call writes them (invalid placements among them or not); elsewhere some placements
  * may get no vote or no count.  Needs no index.
- * Not held: read sets beyond 2^32 bases are untested.  Out of scope: votes of contained reads (they have no placement); gapped
- * alignment; quality-weighted votes; wrapping a ring's closing overlap; consensus inside the scaffold, gapfill and join passes. */
+ * Not held: read sets beyond 2^32 bases are untested.  Votes of contained reads: a contained read votes once
+ * sigax_contained_place_device has given it a placement, and this pass is run over that call's lay_offs2 and layout2.  Out of
+ * scope: gapped alignment; quality-weighted votes; wrapping a ring's closing overlap; consensus inside the scaffold, gapfill and join passes. */
 typedef struct sigax_consensus_opts { uint32_t min_votes; uint32_t reserved[3]; } sigax_consensus_opts;
 int  sigax_consensus_workspace(uint64_t n_reads, uint64_t n_unitigs_max, uint64_t* bytes);  /* host arithmetic only */
 int  sigax_consensus_device(int device, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_lay_offs,
@@ -999,6 +1014,74 @@ int  sigax_consensus_device(int device, const void* d_n_unitigs, uint64_t max_un
 int  sigax_consensus_host(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint64_t* lay_offs, const sigax_placement* layout,
                           const uint32_t* lengths, const char* seqs, const uint64_t* offs, uint64_t n_reads,
                           const sigax_consensus_opts* opts, char* useqs, uint32_t** changed, uint8_t** support, uint64_t status8[8]);
+
+/* ---- `siga unitig -e --place-contained`: contained reads placed in the layout (csrc/sigax_contained.hip) ---------------------------
+ * `siga unitig -e` sets every contained read aside: it becomes a unitig of its own that is not written, and has no placement in
+ * the unitig that holds its bases.  This pass takes the containment records of the mismatch overlap path (SIGAX_MMO_CONTAINMENTS)
+ * and gives such a read the placement its container implies, so that it votes in the consensus pass and pairs.  The reference drops
+ * contained reads before its graph is built (src/bigraph.cpp); the rules are these.  Integer arithmetic throughout; no result
+ * depends on the order of records, reads or lanes.  DESIGN.md 9s; the serial restatement the tests hold this against is
+ * tests/contained_cases.py::expected_placement.
+ *
+ * Input: a unitig call's number of unitigs, seq_offs, lay_offs and layout; lengths and n_reads; contained u8[n_reads]; n_conts
+ * containment records in any order.  Unitig u holds the placements lay_offs[u] .. lay_offs[u+1] when lay_offs[u] <= lay_offs[u+1] <=
+ * n_reads, none otherwise; placement j belongs to the last u with lay_offs[u] <= j if that unitig holds it, to none otherwise; a
+ * read's placement is the first one that belongs to a unitig and names it.
+ *  1. A record is VALID iff query and target are below n_reads, query != target, af & SIGAX_MM_CONTAINMENT, contained[query] is
+ *     set and reserved + L[query] <= L[target].  Others are skipped and counted.
+ *  2. CHOICE(c) is the valid record of c that is smallest in (contained[target] != 0, num_diff, target, af & 4, reserved): a
+ *     container that is placed directly first, then the fewest mismatches.
+ *  3. ROOT: the choices are followed from c while the current read is contained and has a choice.  c at (o, v) in r, r of length Lr
+ *     at (o2, v2) in q: c lies in q at (o2 + o, v) if v2 = 0, at (o2 + Lr - o - Lc, v ^ 1) otherwise.  Records of rule 1 cannot
+ *     form a cycle (the length grows or the name rank falls); the chain is resolved by pointer doubling in ceil(log2 n_reads) + 1
+ *     rounds, and one that has not reached a read that is not contained by then -- a cycle in foreign tables, or a contained read
+ *     without a choice at its end -- is NO_ROOT.  A contained read without a valid record is NO_RECORD.
+ *  4. The root's placement (u, flags, offset) composes in the same way with (offset, flags & SIGAX_PLACED_REV) to c's placement
+ *     in u; a root without a placement (a trim round took it) gives ROOT_REMOVED, an offset with o + Lc > U (U the bases of u;
+ *     foreign tables only) INVALID.
+ *  5. lay_offs2 / layout2: per unitig its placements less those whose read is a PLACED contained read -- the hidden unitig of such
+ *     a read keeps its number and its bases and has no placement -- plus the placed contained reads with SIGAX_PLACED_CONTAINED
+ *     or'ed into flags, ascending in (offset, kind: 0 chain read, 1 contained, read id): what the consensus pass's bisection needs.
+ *     The chain placements keep their order among themselves (every unitig call writes them ascending).  A contained read that is
+ *     not placed keeps what it had.
+ *  6. place_class u8 per read: SIGAX_CP_*.  status8, written: {contained reads, records read, records invalid, placed, no record
+ *     or no root, root removed, the longest chain in steps among the reads whose walk reached a root, placements in layout2}.
+ *
+ * sigax_contained_place_device: every buffer in device memory, asynchronous on `stream`, allocates nothing, never waits for the
+ * device.  d_n_unitigs points at a u64 ON THE DEVICE -- entry 0 of the unitig call's status block; a value above n_reads or above
+ * max_unitigs is taken as that.  d_seq_offs, d_lay_offs and d_lay_offs2 u64[max_unitigs + 1] (lay_offs2: entries 0 .. min(max_unitigs, n_reads)
+ * written, those behind n_unitigs with the total), d_layout and d_layout2 sigax_placement[n_reads] (layout2: 0xFF behind the total), d_lengths
+ * u32[n_reads], d_contained and d_place_class u8[n_reads], d_conts sigax_mm_edge[n_conts] (NULL when n_conts = 0), d_work =
+ * sigax_contained_place_workspace bytes (some 120 bytes a read and the sort's scratch: the placed contained reads are ordered by
+ * two radix passes over one slot a read, because only the device knows how many there are).  d_layout, d_layout2 and d_work
+ * 16-byte aligned, d_n_unitigs, d_seq_offs, d_lay_offs, d_lay_offs2, d_conts and d_status8 8-byte aligned, d_lengths 4-byte aligned.
+ * A NULL where a buffer is required, a misaligned buffer, a short workspace, a non-zero reserved word, n_reads >= 2^31 and n_conts
+ * >= 2^32: SIGAX_E_ARG.  n_reads = 0 (or max_unitigs = 0): SIGAX_OK, status zeros, nothing else written.  Whatever the tables hold
+ * -- read ids that are too large, cycles among the choices, offsets beyond the container, tables that do not ascend -- nothing
+ * outside the buffers is touched and every loop has a bound the host knows; rules 1-4 and 6 hold for any tables, rule 5 where
+ * lay_offs ascends, no read is placed twice and every unitig's offsets ascend.  Needs no index.
+ * Not held: read sets beyond 2^32 bases are untested.  Out of scope: gapped containments; placing contained reads into
+ * scaffolds; more than one GPU. */
+typedef struct sigax_contained_opts { uint32_t reserved[4]; } sigax_contained_opts;  /* all 0 */
+#define SIGAX_CP_NOT_CONTAINED 0u
+#define SIGAX_CP_PLACED        1u
+#define SIGAX_CP_NO_RECORD     2u
+#define SIGAX_CP_NO_ROOT       3u
+#define SIGAX_CP_ROOT_REMOVED  4u
+#define SIGAX_CP_INVALID       5u
+int  sigax_contained_place_workspace(uint64_t n_reads, uint64_t max_unitigs, uint64_t n_conts, uint64_t* bytes);
+int  sigax_contained_place_device(int device, const void* d_n_unitigs, uint64_t max_unitigs, const void* d_seq_offs, const void* d_lay_offs,
+                                  const sigax_placement* d_layout, const void* d_lengths, uint64_t n_reads, const void* d_contained,
+                                  const sigax_mm_edge* d_conts, uint64_t n_conts, const sigax_contained_opts* opts, void* d_lay_offs2,
+                                  sigax_placement* d_layout2, void* d_place_class, void* d_status8, void* d_work, uint64_t work_bytes,
+                                  void* stream);
+/* Host buffers, synchronous.  seq_offs and lay_offs u64[n_unitigs + 1], layout sigax_placement[lay_offs[n_unitigs]].  n_unitigs or
+ * lay_offs[n_unitigs] above n_reads: SIGAX_E_ARG.  *lay_offs2 u64[n_unitigs + 1], *layout2 sigax_placement[n_reads] (status8[7] of
+ * them written) and *place_class u8[n_reads] are malloc'd; release with sigax_free.  status8 is filled. */
+int  sigax_contained_place_host(int device, uint64_t n_unitigs, const uint64_t* seq_offs, const uint64_t* lay_offs, const sigax_placement* layout,
+                                const uint32_t* lengths, uint64_t n_reads, const uint8_t* contained, const sigax_mm_edge* conts,
+                                uint64_t n_conts, const sigax_contained_opts* opts, uint64_t** lay_offs2, sigax_placement** layout2,
+                                uint8_t** place_class, uint64_t status8[8]);
 /* ---- `siga unitig --pairs`: mate-pair statistics and the links between unitig ends (csrc/sigax_pairs.hip) --------------------------
  * The data-parallel part of the reference's paired-end `assemble` (--pe-mode=1, src/assembler.cpp:75-90): InsertSizeEstimateVisitor
  * (src/bigraph_visitors.cpp:517-663) walks every unbranched chain of the read graph, notes each read's distance along the chain

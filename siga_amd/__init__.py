@@ -5,4 +5,4 @@ This package is the thin Python side used by tests and bench.py: ctypes bindings
 mirror of the reference's OverlapBuilder interface (`overlap`).  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
-from .overlap import FMIndexPair, OverlapBuilder, SigaxError, mates_by_name, pairs_estimate, scaffolds_gapfill, scaffolds_join, unitigs, unitigs_bubble, unitigs_chimeric, unitigs_consensus, unitigs_indel, unitigs_pairs, unitigs_prune, unitigs_reduce, unitigs_scaffold, unitigs_trim  # noqa: F401
+from .overlap import FMIndexPair, OverlapBuilder, SigaxError, mates_by_name, pairs_estimate, scaffolds_gapfill, scaffolds_join, unitigs, unitigs_bubble, unitigs_chimeric, unitigs_consensus, unitigs_indel, unitigs_pairs, unitigs_place_contained, unitigs_prune, unitigs_reduce, unitigs_scaffold, unitigs_trim  # noqa: F401

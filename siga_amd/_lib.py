@@ -112,6 +112,16 @@ class ReduceOpts(C.Structure):  # sigax_reduce_opts
     _fields_ = [("indel", IndelOpts), ("reduce", C.c_uint32), ("reserved5", C.c_uint32 * 3)]
 
 
+class ContainedOpts(C.Structure):  # sigax_contained_opts
+    _fields_ = [("reserved", C.c_uint32 * 4)]
+
+
+# sigax_contained_place_*: place_class values and the entries of status8, by name
+CP_CLASSES = ("not_contained", "placed", "no_record", "no_root", "root_removed", "invalid")
+CONTAINED_STATUS = ("contained", "records", "records_invalid", "placed", "no_chain", "root_removed", "longest_chain", "placements")
+PLACED_CONTAINED = 2  # SIGAX_PLACED_CONTAINED
+
+
 class ConsensusOpts(C.Structure):  # sigax_consensus_opts
     _fields_ = [("min_votes", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
@@ -168,13 +178,18 @@ class PileParams(C.Structure):
                          max_read_len, 0)
 
 
+MMO_CONTAINMENTS = 1  # SIGAX_MMO_CONTAINMENTS
+MM_CONTAINMENT = 8    # SIGAX_MM_CONTAINMENT
+
+
 class MmoParams(C.Structure):
     """sigax_mmo_params (`siga overlap -e`); the defaults are the CLI's, error_permille has none"""
     _fields_ = [(n, C.c_uint32) for n in ("seed_length", "seed_stride", "max_seed_hits", "min_overlap", "error_permille", "max_candidates",
-                                          "max_read_len", "reserved")]
+                                          "max_read_len", "flags")]
 
-    def __init__(self, error_permille, seed_length=24, seed_stride=12, max_seed_hits=256, min_overlap=45, max_candidates=512, max_read_len=0):
-        super().__init__(seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates, max_read_len, 0)
+    def __init__(self, error_permille, seed_length=24, seed_stride=12, max_seed_hits=256, min_overlap=45, max_candidates=512, max_read_len=0,
+                 flags=0):
+        super().__init__(seed_length, seed_stride, max_seed_hits, min_overlap, error_permille, max_candidates, max_read_len, flags)
 
 
 class RunInfo(C.Structure):
@@ -212,6 +227,7 @@ SYMBOLS = [
     "sigax_unitigs_indel_workspace", "sigax_unitigs_indel_device", "sigax_unitigs_indel_host",
     "sigax_unitigs_reduce_workspace", "sigax_unitigs_reduce_device", "sigax_unitigs_reduce_host",
     "sigax_consensus_workspace", "sigax_consensus_device", "sigax_consensus_host",
+    "sigax_contained_place_workspace", "sigax_contained_place_device", "sigax_contained_place_host",
     "sigax_unitigs_pairs_workspace", "sigax_unitigs_pairs_device", "sigax_unitigs_pairs_host", "sigax_pairs_estimate",
     "sigax_scaffold_workspace", "sigax_scaffold_device", "sigax_scaffold_host",
     "sigax_gapfill_workspace", "sigax_gapfill_device", "sigax_gapfill_host",
@@ -360,6 +376,9 @@ def lib():
     L.sigax_consensus_workspace.argtypes = [u64, u64, C.POINTER(u64)]
     L.sigax_consensus_device.argtypes = [ci, vp, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(ConsensusOpts), vp, vp, vp, vp, vp, u64, vp]
     L.sigax_consensus_host.argtypes = [ci, u64, vp, vp, vp, vp, cp, vp, u64, C.POINTER(ConsensusOpts), vp, pvp, pvp, vp]
+    L.sigax_contained_place_workspace.argtypes = [u64, u64, u64, C.POINTER(u64)]
+    L.sigax_contained_place_device.argtypes = [ci, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(ContainedOpts), vp, vp, vp, vp, vp, u64, vp]
+    L.sigax_contained_place_host.argtypes = [ci, u64, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(ContainedOpts), pvp, pvp, pvp, vp]
     L.sigax_unitigs_pairs_workspace.argtypes = [ci, u64, C.POINTER(u64)]
     L.sigax_unitigs_pairs_device.argtypes = [ci, vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(PairsOpts), vp, vp, vp, vp, u64, vp]
     L.sigax_unitigs_pairs_host.argtypes = [ci, vp, vp, u64, u64, vp, vp, vp, vp, C.POINTER(PairsOpts), pvp, pvp, vp]

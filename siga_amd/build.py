@@ -13,8 +13,8 @@ SOURCES = ["sigax_kernels.hip", "sigax_tables.hip", "sigax_tail.hip", "sigax_api
            "sigax_locate.hip", "sigax_locate.cpp", "sigax_unitig.hip", "sigax_unitig.cpp", "sigax_pairs.hip", "sigax_pairs.cpp",
            "sigax_scaffold.hip", "sigax_scaffold.cpp", "sigax_gapfill.hip", "sigax_gapfill.cpp", "sigax_join.hip", "sigax_join.cpp",
            "sigax_seeded.hip", "sigax_seeded.cpp", "sigax_pileup.hip", "sigax_pileup.cpp", "sigax_mmoverlap.hip", "sigax_mmoverlap.cpp",
-           "sigax_consensus.hip", "sigax_consensus.cpp"]
-HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", "sigax_fm.h", "sigax_rank.h", "sigax_device.h", "sigax_seeded.h", "sigax_pileup.h", "sigax_mmoverlap.h", "sigax_consensus.h", os.path.join(ROOT, "include", "sigax.h")]
+           "sigax_consensus.hip", "sigax_consensus.cpp", "sigax_contained.hip", "sigax_contained.cpp"]
+HEADERS = ["sigax_kernels.h", "fm_layout.h", "sigax_internal.h", "sigax_fm.h", "sigax_rank.h", "sigax_device.h", "sigax_seeded.h", "sigax_pileup.h", "sigax_mmoverlap.h", "sigax_consensus.h", "sigax_contained.h", os.path.join(ROOT, "include", "sigax.h")]
 
 
 def _stale(target, deps):

@@ -16,8 +16,9 @@ int mmo_usable(const sigax_index* ix) {
 
 int check_params(const sigax_mmo_params* p) {
   if (!p) return sigax_fail(SIGAX_E_ARG, "params is NULL");
+  if (p->flags > SIGAX_MMO_CONTAINMENTS) return sigax_fail(SIGAX_E_ARG, "flags %u: 0 or SIGAX_MMO_CONTAINMENTS", p->flags);
   return seeded_check_params(p->seed_length, p->seed_stride, p->max_seed_hits, p->min_overlap, p->error_permille, p->max_candidates,
-                             p->max_read_len, p->reserved);
+                             p->max_read_len, 0);
 }
 
 // the middle of the workspace: n_rec and n_flag, zeroed by the seeding stage (a read that ends early has none), then rec_offs;

@@ -13,7 +13,8 @@
 enum { MMO_C_LENGTH = 0, MMO_C_OVER, MMO_C_LOCATED, MMO_C_REPEATS, MMO_C_TESTED, MMO_C_ACCEPTED, MMO_C_COUNT = 8 };
 
 // What k_mmo finds is on its way to k_mmo_commit in the place of the read's own hits, 16 bytes each: a record as {canonical query,
-// target, length, af | num_diff << 8}, a read to flag as {read id, 0, 0, 0}.
+// target, length, af | num_diff << 8}, a read to flag as its containment record {read id, container, o, af |
+// num_diff << 8 | length << 19}.
 struct MmoArgs {
   RefText R;                             // the indexed reads by id: queries and candidates alike
   const uint32_t* name_rank;             // [n_ref]
@@ -38,7 +39,7 @@ uint32_t mmo_lds_bytes(uint32_t tab_cap);  // the dynamic LDS of a wave: the tab
 int launch_mmo(const MmoArgs& a, hipStream_t st);  // hipSuccess or the error of raising the LDS limit
 void launch_mmo_commit(const MmoArgs& a, hipStream_t st);  // k_mmo_commit, then k_mmo_status
 
-// finish: the raw records in (query, target, af, length) order, each once
+// finish: the raw records in (query, target, af, length, reserved) order, each once
 struct MmoFinishArgs {
   sigax_mm_edge* edges;                  // [n]
   unsigned long long n;

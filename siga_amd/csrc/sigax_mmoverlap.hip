@@ -5,7 +5,8 @@
 //
 //   k_mmo          one wave per read: the distinct candidates of its hits, each verified, what is accepted left in the read's own
 //                  stretch of the hit list
-//   k_mmo_commit   one wave per read: when the call's records fit, they go behind the cursor and the flags are set
+//   k_mmo_commit   one wave per read: when the call's records fit, they go behind the cursor and the flags are set; with
+//                  SIGAX_MMO_CONTAINMENTS every flag gives a containment record behind the read's dovetail records
 //   k_mmo_status   the eight status words, and the cursor moved
 //   k_mmo_keys, k_mmo_keys2, k_mmo_gather, k_mmo_compact   the finish: two stable radix passes, repeats dropped
 //
@@ -21,8 +22,11 @@
 // the reverse strand, and the mismatches are summed over the wave.  (3) What a sweep accepts is collected one result a lane and
 // written by neighbouring lanes, 16 bytes each, over the read's own hits, which nobody reads any more: records from the front of
 // the stretch, read ids to flag from its back.  A candidate gives at most one of the two and comes from at least one hit, so they
-// fit.  No atomic is taken on the record cursor: the call's records are counted per read and scanned, and k_mmo_commit writes
-// them only if all of them fit -- the rule that an overflowing call writes nothing needs the count before the first write.
+// fit.  A flag's 16 bytes hold its whole containment record {contained, container, o, af | num_diff << 8 | len << 19}, whether
+// or not the call asks for it: o in full width, since a container may be longer than any query (rule 1 stops it as a query, not
+// as a candidate); the contained read is a query or lies within one, so len <= 4096 takes 13 bits, and num_diff <= len / 4 takes
+// 11.  No atomic is taken on the record cursor: the call's records are counted per read and scanned, and k_mmo_commit writes them
+// only if all of them fit -- the rule that an overflowing call writes nothing needs the count before the first write.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -87,8 +91,8 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
     u32 len_t, rank_t = 0;
     const bool has = cand_slot(tab, base + lane, A.R, key, rb, len_t, [&](u64 t) { rank_t = A.name_rank[t]; });
     u64 mask = __ballot(has && rank_t != rank_q);  // rule 3
-    uint4 my_rec = make_uint4(0, 0, 0, 0);
-    u32 my_flag = 0, s_rec = 0, s_flag = 0;  // this sweep's results: the k-th of a kind with lane k
+    uint4 my_rec = make_uint4(0, 0, 0, 0), my_flag = make_uint4(0, 0, 0, 0);
+    u32 s_rec = 0, s_flag = 0;  // this sweep's results: the k-th of a kind with lane k
     while (mask) {
       const int src = __ffsll((long long)mask) - 1;
       mask &= mask - 1ull;
@@ -117,8 +121,14 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
       // rules 5-7, the same in every lane
       const bool q_in = ell == n, t_in = (long long)ell == clen;
       if (q_in || t_in) {
-        const u32 id = (q_in && t_in) ? (rank_q > crank ? (u32)i : t) : (q_in ? (u32)i : t);
-        if (lane == s_flag) my_flag = id;
+        // the contained read is the query (for DUP: the larger name rank) or the candidate; o = the first column of the
+        // container's forward text that it covers: d (reverse: L - d - n) for the query, -d for the candidate
+        const bool q_is = (q_in && t_in) ? rank_q > crank : q_in;
+        const u32 o = q_is ? (u32)(rev ? clen - d - (long long)n : d) : (u32)(-d);
+        const u32 af = SIGAX_MM_CONTAINMENT | (rev ? 4u : 0u);
+        const u32 packed = af | (m << 8) | ((q_is ? n : ell) << 19);  // m <= 1024, the contained read's length <= 4096
+        const uint4 flag = q_is ? make_uint4((u32)i, t, o, packed) : make_uint4(t, (u32)i, o, packed);
+        if (lane == s_flag) my_flag = flag;
         s_flag += 1u;
       } else {
         u32 af = d < 0 ? (rev ? 6u : 0u) : (rev ? 5u : 3u);
@@ -134,12 +144,12 @@ __global__ __launch_bounds__(64) void k_mmo(MmoArgs A) {
       }
     }
     if (lane < s_rec && (u64)(n_rec + lane) < room) A.L.hits[sp.h0 + n_rec + lane] = my_rec;
-    if (lane < s_flag && (u64)(n_flag + lane) < room) A.L.hits[sp.h1 - 1 - (n_flag + lane)] = make_uint4(my_flag, 0, 0, 0);
+    if (lane < s_flag && (u64)(n_flag + lane) < room) A.L.hits[sp.h1 - 1 - (n_flag + lane)] = my_flag;
     n_rec += s_rec;
     n_flag += s_flag;
   }
   if (lane == 0) {
-    A.n_rec[r] = n_rec;
+    A.n_rec[r] = n_rec + ((A.p.flags & SIGAX_MMO_CONTAINMENTS) ? n_flag : 0u);  // the records the commit writes for this read
     A.n_flag[r] = n_flag;
     if (tested) atomicAdd(&A.counters[MMO_C_TESTED], (u64)tested);
     if (taken) atomicAdd(&A.counters[MMO_C_ACCEPTED], (u64)taken);
@@ -161,7 +171,9 @@ __global__ __launch_bounds__(256) void k_mmo_commit(MmoArgs A) {
   if (!mmo_fits(A, &cursor0)) return;
   const SeedSpan sp = seed_span(A.L, r, A.L.loc_status[0]);
   const u64 room = sp.h1 - sp.h0;
+  const bool conts = (A.p.flags & SIGAX_MMO_CONTAINMENTS) != 0;
   u64 n_rec = A.n_rec[r], n_flag = A.n_flag[r];
+  if (conts) n_rec = n_rec >= n_flag ? n_rec - n_flag : 0;  // the dovetail records alone
   n_rec = n_rec < room ? n_rec : room;
   n_flag = n_flag < room - n_rec ? n_flag : room - n_rec;
   const u64 out0 = cursor0 + A.rec_offs[r];
@@ -177,8 +189,18 @@ __global__ __launch_bounds__(256) void k_mmo_commit(MmoArgs A) {
     if (out0 + k < A.edges_cap) A.edges[out0 + k] = e;  // (it is: the total fits)
   }
   for (u64 k = lane; k < n_flag; k += 64) {
-    const u32 id = A.L.hits[sp.h1 - 1 - k].x;
-    if ((u64)id < A.R.n_ref) A.contained[id] = 1;
+    const uint4 v = A.L.hits[sp.h1 - 1 - k];
+    if ((u64)v.x < A.R.n_ref) A.contained[v.x] = 1;
+    if (conts) {
+      sigax_mm_edge e;
+      e.query = v.x;
+      e.target = v.y;
+      e.length = v.w >> 19;
+      e.af = v.w & 0xFFu;
+      e.num_diff = (v.w >> 8) & 0x7FFu;
+      e.reserved = v.z;
+      if (out0 + n_rec + k < A.edges_cap) A.edges[out0 + n_rec + k] = e;  // (it is: the total fits)
+    }
   }
 }
 
@@ -204,11 +226,11 @@ __global__ __launch_bounds__(256) void k_mmo_keys(MmoFinishArgs A) {
   const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n) return;
   const sigax_mm_edge e = A.edges[i];
-  A.keys[0][i] = ((u64)e.af << 32) | (u64)e.length;
+  A.keys[0][i] = ((u64)(e.af & 15u) << 45) | ((u64)(e.length & 0x1FFFu) << 32) | (u64)e.reserved;
   A.vals[0][i] = i;
 }
 
-// the first pass has left the records' places in (af, length) order in vals[1]: their (query, target) in that order
+// the first pass has left the records' places in (af, length, reserved) order in vals[1]: their (query, target) in that order
 __global__ __launch_bounds__(256) void k_mmo_keys2(MmoFinishArgs A) {
   const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
   if (i >= A.n) return;
@@ -222,7 +244,7 @@ __global__ __launch_bounds__(256) void k_mmo_keys2(MmoFinishArgs A) {
 }
 
 __device__ __forceinline__ bool mmo_same(const sigax_mm_edge& a, const sigax_mm_edge& b) {
-  return a.query == b.query && a.target == b.target && a.af == b.af && a.length == b.length;
+  return a.query == b.query && a.target == b.target && a.af == b.af && a.length == b.length && a.reserved == b.reserved;
 }
 
 // the second pass has left the places in full order in vals[0]: the records in that order, and which of them open a run
@@ -272,8 +294,10 @@ hipError_t launch_mmo_finish(const MmoFinishArgs& a, hipStream_t st) {
   const unsigned grid = blocks_of(a.n);
   size_t tb = (size_t)a.sort_tmp_bytes;
   hipLaunchKernelGGL(k_mmo_keys, dim3(grid), dim3(256), 0, st, a);
-  // stable passes, the minor key first: (af, length) in 35 bits, then (query, target)
-  hipError_t e = rocprim::radix_sort_pairs(a.sort_tmp, tb, (const u64*)a.keys[0], a.keys[1], (const u64*)a.vals[0], a.vals[1], (size_t)a.n, 0u, 35u, st);
+  // stable passes, the minor key first: (af, length, reserved) in 49 bits (4 + 13 + 32: an overlap has at most 4096 columns, a
+  // containment's offset is as wide as its container is long), then
+  // (query, target)
+  hipError_t e = rocprim::radix_sort_pairs(a.sort_tmp, tb, (const u64*)a.keys[0], a.keys[1], (const u64*)a.vals[0], a.vals[1], (size_t)a.n, 0u, 49u, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_mmo_keys2, dim3(grid), dim3(256), 0, st, a);
   tb = (size_t)a.sort_tmp_bytes;

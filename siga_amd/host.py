@@ -37,6 +37,8 @@ def lib():
                                                  C.c_char_p, C.c_uint64]
         L.sigah_overlap_mismatch_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                                   C.c_char_p, C.c_uint64]
+        L.sigah_overlap_mismatch_containments_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int,
+                                                               C.c_void_p, C.c_char_p, C.c_uint64]
         L.sigah_format_asqg.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int]
         L.sigah_format_asqg.restype = C.c_int64
         L.sigah_rmdup_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
@@ -71,6 +73,8 @@ def lib():
                                                   C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int64,
                                                   C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_char_p, C.c_void_p,
                                                   C.c_char_p, C.c_uint64]
+        a = L.sigah_unitig_consensus_file.argtypes
+        L.sigah_unitig_placed_file.argtypes = a[:-3] + [C.c_int] + a[-3:]
         L.sigah_preqc.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                   C.c_uint64, C.c_char_p, C.c_uint64]
         _lib = L
@@ -119,11 +123,13 @@ def index_file_sais(reads_path, prefix, threads=2):
 
 
 def overlap_file(reads_path, prefix, min_overlap, output, irreducible=True, rc=True, threads=1, batch=10000, device=0, gpus=1,
-                 error_permille=None, **seed):
+                 error_permille=None, containments=None, **seed):
     """FMIndex::load + OverlapBuilder::build in the host C++ library (GPU compute), reads sharded over `gpus` GPUs.
     error_permille given (`siga overlap -e`): FMIndex::loadForwardSai + MismatchOverlapper::run instead -- every overlap of
     min_overlap columns with that many mismatches per mille at most, the rules of include/sigax.h, with seed_length, seed_stride,
-    max_seed_hits and max_candidates as keywords; one GPU, both strands; -> the eight status words."""
+    max_seed_hits and max_candidates as keywords; one GPU, both strands; -> the eight status words.  containments: a path
+    (`--containments FILE`, with error_permille only) for one line per containment record -- contained name, container name,
+    offset, + or -, mismatches; status[7] then counts those records too."""
     err = C.create_string_buffer(512)
     if error_permille is not None:
         if gpus != 1 or not rc:
@@ -131,12 +137,13 @@ def overlap_file(reads_path, prefix, min_overlap, output, irreducible=True, rc=T
         from . import _lib as core
         params = core.MmoParams(int(error_permille), min_overlap=int(min_overlap), **seed)
         status = np.zeros(8, dtype=np.uint64)
-        if lib().sigah_overlap_mismatch_file(reads_path.encode(), prefix.encode(), output.encode(), C.addressof(params), threads, device,
-                                             status.ctypes.data, err, 512) != 0:
+        if lib().sigah_overlap_mismatch_containments_file(reads_path.encode(), prefix.encode(), output.encode(),
+                                                          containments.encode() if containments else None, C.addressof(params), threads,
+                                                          device, status.ctypes.data, err, 512) != 0:
             raise RuntimeError("siga overlap failed: " + err.value.decode())
         return status
-    if seed:
-        raise ValueError("%r without error_permille" % sorted(seed))
+    if seed or containments:
+        raise ValueError("%r without error_permille" % (sorted(seed) + (["containments"] if containments else [])))
     r = lib().sigah_overlap_file_gpus(reads_path.encode(), prefix.encode(), min_overlap, output.encode(), int(irreducible), int(rc),
                                       threads, batch, device, gpus, err, 512)
     if r != 0:
@@ -197,7 +204,8 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
                 min_branch_length=150, min_branch_coverage=None, graph=None, removed=None, max_overlap_delta=0, max_overlap_carefully=False,
                 num_reads=None, genome_size=None, uniq_threshold=13.0, cut_edges=None, min_chimeric_length=0, min_chimeric_coverage=None,
                 max_chimeric_delta=0, chimeric_threshold=0.0, chimeric=None, max_bubble_span=0, bubble_divergence=50, bubbles=None,
-                bubble_edits=0, bubble_edit_permille=50, reduce=False, error_permille=None, consensus=None, min_votes=1, contained=None, **seed):
+                bubble_edits=0, bubble_edit_permille=50, reduce=False, error_permille=None, consensus=None, min_votes=1, contained=None, place_contained=False,
+                **seed):
     """`siga unitig`: FMIndex::load + Unitigger::run; the FASTA goes to the file `out`, or to stdout, the placements to the file
     `layout` when one is named.  piece_reads: reads per overlap call (0: 2^20); the result does not depend on it.
     cut_terminal (-x), min_branch_length (-n), min_branch_coverage (-C, None: no coverage test): tip trimming, 0 rounds = none;
@@ -220,10 +228,14 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
     seed_length, seed_stride, max_seed_hits and max_candidates (**seed); contained reads are set aside, their names go to the file
     `contained`.  consensus (None: on exactly when error_permille is given), min_votes: the consensus pass behind the unitig call.
     reduce (--reduce): the transitive reduction in the rounds.  With any of them -> the dict of bubble_edits plus reduced,
-    contained_reads, columns_changed and shallow_columns."""
+    contained_reads, columns_changed and shallow_columns.
+    place_contained (--place-contained, with error_permille only): every contained read placed where its container lies, so that
+    it votes, counts and pairs; the dict then also holds contained_placed."""
     err = C.create_string_buffer(512)
     if min_votes != 1 and not (consensus or (consensus is None and error_permille is not None)):
         raise ValueError("min_votes needs the consensus pass")
+    if place_contained and error_permille is None:
+        raise ValueError("place_contained applies to error_permille only")
     if error_permille is not None or consensus or reduce or contained is not None or seed:
         unknown = set(seed) - {"seed_length", "seed_stride", "max_seed_hits", "max_candidates"}
         if unknown:
@@ -231,7 +243,7 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
         if error_permille is None and (seed or contained is not None):
             raise ValueError("the seed options and `contained` apply to error_permille only")
         status = np.zeros(24, dtype=np.uint64)
-        if lib().sigah_unitig_consensus_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,
+        if lib().sigah_unitig_placed_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,
                                              (out or "").encode(), (layout or "").encode(), piece_reads, int(cut_terminal), int(min_branch_length),
                                              -1 if min_branch_coverage is None else int(min_branch_coverage), (graph or "").encode(),
                                              (removed or "").encode(), int(max_overlap_delta), int(max_overlap_carefully), int(num_reads or 0),
@@ -243,12 +255,13 @@ def unitig_file(reads_path, prefix, min_overlap, out=None, layout=None, irreduci
                                              -1 if error_permille is None else int(error_permille), int(seed.get("seed_length", 24)),
                                              int(seed.get("seed_stride", 12)), int(seed.get("max_seed_hits", 256)),
                                              int(seed.get("max_candidates", 512)), -1 if consensus is None else int(bool(consensus)),
-                                             int(min_votes), (contained or "").encode(), status.ctypes.data, err, 512) != 0:
+                                             int(min_votes), (contained or "").encode(), int(bool(place_contained)), status.ctypes.data, err,
+                                             512) != 0:
             raise RuntimeError("siga unitig failed: " + err.value.decode())
         return dict(zip(("unitigs", "bases", "merged", "circular", "rounds", "islands", "dead_ends", "reads_removed", "records_cut", "cut_rounds",
                          "chimeric_unitigs", "chimeric_reads", "bubbles_popped", "bubble_reads", "bubbles_kept", "indels_popped", "indel_reads",
-                         "indels_kept", "indels_not_compared", "reduced", "contained_reads", "columns_changed", "shallow_columns"),
-                        (int(x) for x in status)))
+                         "indels_kept", "indels_not_compared", "reduced", "contained_reads", "columns_changed", "shallow_columns") +
+                        (("contained_placed",) if place_contained else ()), (int(x) for x in status)))
     if bubble_edits:
         status = np.zeros(19, dtype=np.uint64)
         if lib().sigah_unitig_indel_file(reads_path.encode(), prefix.encode(), min_overlap, int(irreducible), int(rc), device,

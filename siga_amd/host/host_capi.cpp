@@ -177,8 +177,10 @@ int sigah_overlap_file(const char* reads_path, const char* prefix, uint64_t min_
 
 // `siga overlap -e`: FMIndex::loadForwardSai + MismatchOverlapper::run; status8 (may be NULL) receives the status words of
 // sigax_mmoverlap_batch
-int sigah_overlap_mismatch_file(const char* reads_path, const char* prefix, const char* output, const sigax_mmo_params* params, uint64_t threads,
-                                int device, uint64_t* status8, char* err, uint64_t errcap) {
+// containments (may be NULL or empty): `--containments FILE`
+int sigah_overlap_mismatch_containments_file(const char* reads_path, const char* prefix, const char* output, const char* containments,
+                                             const sigax_mmo_params* params, uint64_t threads, int device, uint64_t* status8, char* err,
+                                             uint64_t errcap) {
   sigah::FMIndex fmi;
   if (!params) {
     if (err && errcap) snprintf(err, errcap, "params is NULL");
@@ -189,6 +191,7 @@ int sigah_overlap_mismatch_file(const char* reads_path, const char* prefix, cons
     return -1;
   }
   sigah::MismatchOverlapper finder(*params);
+  if (containments && *containments) finder.setContainments(containments);
   if (!finder.run(fmi, reads_path, output, (size_t)threads)) {
     if (err && errcap) snprintf(err, errcap, "%s", finder.error().c_str());
     return -1;
@@ -196,6 +199,11 @@ int sigah_overlap_mismatch_file(const char* reads_path, const char* prefix, cons
   if (status8)
     for (int k = 0; k < 8; ++k) status8[k] = finder.status()[k];
   return 0;
+}
+
+int sigah_overlap_mismatch_file(const char* reads_path, const char* prefix, const char* output, const sigax_mmo_params* params, uint64_t threads,
+                                int device, uint64_t* status8, char* err, uint64_t errcap) {
+  return sigah_overlap_mismatch_containments_file(reads_path, prefix, output, nullptr, params, threads, device, status8, err, errcap);
 }
 
 // `siga rmdup`: FMIndex::load + OverlapBuilder::rmdup
@@ -438,7 +446,9 @@ int sigah_unitig_indel_file(const char* reads_path, const char* prefix, uint64_t
 // options as `siga overlap -e` takes them; contained_path "" = none) and the consensus pass (consensus < 0: on exactly with
 // error_permille; min_votes); status24 (unless NULL) = status19, then {records transitive in the final graph, contained reads,
 // columns the vote changed, columns of depth below 2, 0}
-int sigah_unitig_consensus_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+// ... and with the contained reads placed (place_contained: `--place-contained`, with error_permille only); status24[23] = the
+// contained reads placed
+int sigah_unitig_placed_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
                                 const char* fasta_path, const char* layout_path, uint64_t piece_reads, uint64_t cut_terminal,
                                 uint64_t min_branch_length, int64_t min_branch_coverage, const char* graph_path, const char* removed_path,
                                 uint64_t delta, int careful, uint64_t num_reads, uint64_t genome_size, double uniq_threshold,
@@ -446,9 +456,10 @@ int sigah_unitig_consensus_file(const char* reads_path, const char* prefix, uint
                                 double chimeric_threshold, const char* chimeric_path, uint64_t max_bubble_span, int64_t bubble_divergence,
                                 const char* bubbles_path, uint64_t bubble_edits, uint64_t bubble_edit_permille, int reduce,
                                 int64_t error_permille, uint64_t seed_length, uint64_t seed_stride, uint64_t max_seed_hits,
-                                uint64_t max_candidates, int consensus, uint64_t min_votes, const char* contained_path, uint64_t* status24,
-                                char* err, uint64_t errcap) {
+                                uint64_t max_candidates, int consensus, uint64_t min_votes, const char* contained_path, int place_contained,
+                                uint64_t* status24, char* err, uint64_t errcap) {
   sigah::Unitigger unitigger(irreducible != 0, rc != 0);
+  unitigger.setPlaceContained(place_contained != 0);
   unitigger.setTrim((size_t)cut_terminal, (size_t)min_branch_length, (long)min_branch_coverage);
   unitigger.setGraph(graph_path ? graph_path : "");
   unitigger.setRemoved(removed_path ? removed_path : "");
@@ -487,10 +498,28 @@ int sigah_unitig_consensus_file(const char* reads_path, const char* prefix, uint
                             unitigger.chimericUnitigs(), unitigger.chimericReads(), unitigger.bubblesPopped(), unitigger.bubbleReads(),
                             unitigger.bubblesKept(), unitigger.indelsPopped(), unitigger.indelReads(), unitigger.indelsKept(),
                             unitigger.indelsNotCompared(), unitigger.reducedFinal(), unitigger.containedReads(), unitigger.consensusChanged(),
-                            unitigger.consensusStatus()[3], 0};
+                            unitigger.consensusStatus()[3], unitigger.placeStatus()[3]};
     for (int k = 0; k < 24; ++k) status24[k] = s[k];
   }
   return r;
+}
+
+int sigah_unitig_consensus_file(const char* reads_path, const char* prefix, uint64_t min_overlap, int irreducible, int rc, int device,
+                                const char* fasta_path, const char* layout_path, uint64_t piece_reads, uint64_t cut_terminal,
+                                uint64_t min_branch_length, int64_t min_branch_coverage, const char* graph_path, const char* removed_path,
+                                uint64_t delta, int careful, uint64_t num_reads, uint64_t genome_size, double uniq_threshold,
+                                const char* cut_path, uint64_t min_chimeric_length, int64_t min_chimeric_coverage, uint64_t chimeric_delta,
+                                double chimeric_threshold, const char* chimeric_path, uint64_t max_bubble_span, int64_t bubble_divergence,
+                                const char* bubbles_path, uint64_t bubble_edits, uint64_t bubble_edit_permille, int reduce,
+                                int64_t error_permille, uint64_t seed_length, uint64_t seed_stride, uint64_t max_seed_hits,
+                                uint64_t max_candidates, int consensus, uint64_t min_votes, const char* contained_path, uint64_t* status24,
+                                char* err, uint64_t errcap) {
+  return sigah_unitig_placed_file(reads_path, prefix, min_overlap, irreducible, rc, device, fasta_path, layout_path, piece_reads, cut_terminal,
+                                  min_branch_length, min_branch_coverage, graph_path, removed_path, delta, careful, num_reads, genome_size,
+                                  uniq_threshold, cut_path, min_chimeric_length, min_chimeric_coverage, chimeric_delta, chimeric_threshold,
+                                  chimeric_path, max_bubble_span, bubble_divergence, bubbles_path, bubble_edits, bubble_edit_permille, reduce,
+                                  error_permille, seed_length, seed_stride, max_seed_hits, max_candidates, consensus, min_votes, contained_path, 0,
+                                  status24, err, errcap);
 }
 
 // `siga preqc`: FMIndex::loadForward + KmerSpectrum; the JSON object goes to out_path, or to stdout when it is empty

@@ -22,7 +22,8 @@ bool MismatchRecords::open(const FMIndex& index, std::string* error) {
 }
 
 bool MismatchRecords::find(const FMIndex& index, const sigax_mmo_params& params, size_t n, unsigned nt, std::vector<sigax_edge>* edges,
-                           std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error) {
+                           std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error,
+                           std::vector<sigax_mm_edge>* containments) {
   sigax_mm_edge* found = nullptr;
   struct Found {
     sigax_mm_edge** p;
@@ -30,9 +31,20 @@ bool MismatchRecords::find(const FMIndex& index, const sigax_mmo_params& params,
   } found_guard{&found};
   uint64_t n_found = 0;
   contained->assign(std::max<size_t>(n, 1), 0);
-  if (sigax_mmoverlap_batch(index.handle(), _ref, &params, &found, &n_found, contained->data(), status8) != SIGAX_OK) {
+  sigax_mmo_params p = params;
+  if (containments) p.flags |= SIGAX_MMO_CONTAINMENTS;
+  if (sigax_mmoverlap_batch(index.handle(), _ref, &p, &found, &n_found, contained->data(), status8) != SIGAX_OK) {
     *error = sigax_last_error();
     return false;
+  }
+  if (containments) {  // the dovetails to the front, in their order; the containment records aside, in theirs
+    containments->clear();
+    uint64_t kept = 0;
+    for (uint64_t i = 0; i < n_found; ++i) {
+      if (found[i].af & SIGAX_MM_CONTAINMENT) containments->push_back(found[i]);
+      else found[kept++] = found[i];
+    }
+    n_found = kept;
   }
   // the writer and the unitig calls take sigax_edge records; the mismatch counts go beside them
   edges->resize((size_t)n_found);
@@ -52,7 +64,7 @@ bool MismatchRecords::find(const FMIndex& index, const sigax_mmo_params& params,
 
 bool MismatchOverlapper::run(const FMIndex& index, const std::string& input, const std::string& output, size_t threads) const {
   for (int k = 0; k < 8; ++k) _status[k] = 0;
-  _records = 0;
+  _records = _containments = 0;
   // the reference text once, before any file is touched: an index that cannot serve is refused here
   MismatchRecords ref;
   if (!ref.open(index, &_error)) return false;
@@ -82,7 +94,32 @@ bool MismatchOverlapper::run(const FMIndex& index, const std::string& input, con
   std::vector<sigax_edge> edges;
   std::vector<uint32_t> num_diff;
   std::vector<uint8_t> contained;
-  if (!ref.find(index, _params, n, nt, &edges, &num_diff, &contained, _status, &_error)) return false;
+  std::vector<sigax_mm_edge> conts;
+  const bool want_conts = !_containments_path.empty();
+  if (!ref.find(index, _params, n, nt, &edges, &num_diff, &contained, _status, &_error, want_conts ? &conts : nullptr)) return false;
+  if (want_conts) {
+    OutFile cf(_containments_path, nt);
+    if (!cf.ok()) {
+      _error = "cannot write " + _containments_path;
+      return false;
+    }
+    std::string text;
+    for (const sigax_mm_edge& c : conts) {
+      text.append(rs.name(c.query)).push_back('\t');
+      text.append(rs.name(c.target)).push_back('\t');
+      text += std::to_string(c.reserved) + ((c.af & 4) ? "\t-\t" : "\t+\t") + std::to_string(c.num_diff) + "\n";
+      if (text.size() >= (1u << 20)) {
+        cf.write(text);
+        text.clear();
+      }
+    }
+    cf.write(text);
+    if (!cf.close()) {
+      _error = "cannot write " + _containments_path;
+      return false;
+    }
+    _containments = conts.size();
+  }
   const uint64_t n_found = edges.size();
   _records = n_found;
   OutFile out(output, nt);

@@ -139,8 +139,11 @@ class MismatchRecords {
   MismatchRecords& operator=(const MismatchRecords&) = delete;
   ~MismatchRecords();
   bool open(const FMIndex& index, std::string* error);
+  // containments given: the call asks for the containment records too (SIGAX_MMO_CONTAINMENTS) and splits them from the
+  // dovetails; both keep their order.  status8[7] then counts both kinds.
   bool find(const FMIndex& index, const sigax_mmo_params& params, size_t n, unsigned threads, std::vector<sigax_edge>* edges,
-            std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error);
+            std::vector<uint32_t>* num_diff, std::vector<uint8_t>* contained, uint64_t status8[8], std::string* error,
+            std::vector<sigax_mm_edge>* containments = nullptr);
 
  private:
   sigax_pile_ref* _ref = nullptr;
@@ -151,10 +154,14 @@ class MismatchOverlapper {
   static sigax_mmo_params defaults(uint32_t error_permille) {  // the CLI's
     sigax_mmo_params p;
     p.seed_length = 24; p.seed_stride = 12; p.max_seed_hits = 256; p.min_overlap = 45; p.error_permille = error_permille;
-    p.max_candidates = 512; p.max_read_len = 0; p.reserved = 0;
+    p.max_candidates = 512; p.max_read_len = 0; p.flags = 0;
     return p;
   }
   explicit MismatchOverlapper(const sigax_mmo_params& params) : _params(params) {}
+  // --containments FILE: one line per containment record in the records' order -- contained name, container name, the first
+  // column of the container that the contained read covers, + or - (reverse-complemented in the container), mismatches; tabs
+  void setContainments(const std::string& path) { _containments_path = path; }
+  uint64_t containments() const { return _containments; }
   // HT, VT (input order, SS:i:1 where the read is contained in another or is a duplicate of a smaller name), ED (the records'
   // order: query, target, strand and end, length; the mismatches in the last column) to `output` (gz when the name ends with .gz).
   bool run(const FMIndex& index, const std::string& input, const std::string& output, size_t threads = 1) const;
@@ -165,7 +172,8 @@ class MismatchOverlapper {
  private:
   sigax_mmo_params _params;
   mutable uint64_t _status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  mutable uint64_t _records = 0;
+  mutable uint64_t _records = 0, _containments = 0;
+  std::string _containments_path;
   mutable std::string _error;
 };
 
@@ -419,6 +427,15 @@ class Unitigger {
     _mmo = params;
     _containedOut = contained;
   }
+  // With setMismatch: the containment records are asked for too, and right behind the unitig call sigax_contained_place_host gives
+  // every contained read the placement its container implies (the rules in include/sigax.h).  Its layout then feeds the consensus
+  // pass, the KC:i: counts, the layout file (a placed contained read's line ends in "\tcontained"), the graph's CR:i: and the pairs:
+  // a pair whose contained mate is placed is a pair again, and containedMates() counts only those still unplaced.  setRemoved's
+  // file does not list a placed contained read.  The hidden unitigs are still recognised from the call's own layout, and unitig
+  // numbers stay.
+  void setPlaceContained(bool on) { _placeContained = on; }
+  const uint64_t* placeStatus() const { return _placeStatus; }  // status8 of sigax_contained_place_host
+  const uint64_t* placeClasses() const { return _placeClasses; }  // reads per SIGAX_CP_* class
   // The consensus pass (sigax_consensus_host; the rules in include/sigax.h) right behind the unitig call and before anything reads
   // the bases: every column by majority vote over the reads laid over it; every FASTA header then ends in " changed=<columns>".
   void setConsensus(bool on, size_t minVotes = 1) {
@@ -505,7 +522,8 @@ class Unitigger {
   size_t _scMinPairs = 2, _scLinkRatio = 0, _scMinUnitigBases = 0, _scMinGap = 1, _scMaxGap = 1000000;
   long long _scInsertSize = -1;
   uint64_t _scaffolds = 0, _scJoins = 0, _scAmbiguous = 0, _scGapBases = 0;
-  bool _mismatch = false, _consensus = false;
+  bool _mismatch = false, _consensus = false, _placeContained = false;
+  uint64_t _placeStatus[8] = {0, 0, 0, 0, 0, 0, 0, 0}, _placeClasses[6] = {0, 0, 0, 0, 0, 0};
   sigax_mmo_params _mmo = {24, 12, 256, 45, 0, 512, 0, 0};
   size_t _minVotes = 1;
   std::string _containedOut;

@@ -136,6 +136,9 @@ static int overlap_help() {
          "          --seed-stride=N              distance between two seeds of a read, 1..seed length (default: 12)\n"
          "          --max-seed-hits=N            skip a seed that occurs more than N times, 1..4096 (default: 256)\n"
          "          --max-candidates=N           a read with more than N candidates reports nothing itself, 1..4096 (default: 512)\n"
+         "          --containments=FILE          write one line per containment to FILE (gz when it ends with .gz): contained read,\n"
+         "                                       container, first column of the container it covers, + or - (reverse-complemented\n"
+         "                                       in the container), mismatches\n"
          "\n");
   return 256;
 }
@@ -199,9 +202,11 @@ static int run_index(int argc, char** argv) {
 }
 
 static int run_overlap(int argc, char** argv) {
-  enum { OPT_BATCH_SIZE = 1, OPT_NO_RC, OPT_DEVICE, OPT_GPUS, OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES };
+  enum { OPT_BATCH_SIZE = 1, OPT_NO_RC, OPT_DEVICE, OPT_GPUS, OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES,
+         OPT_CONTAINMENTS };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"error-permille", required_argument, nullptr, 'e'}, {"seed-length", required_argument, nullptr, OPT_SEED_LENGTH},
+                                    {"containments", required_argument, nullptr, OPT_CONTAINMENTS},
                                     {"seed-stride", required_argument, nullptr, OPT_SEED_STRIDE},
                                     {"max-seed-hits", required_argument, nullptr, OPT_MAX_SEED_HITS},
                                     {"max-candidates", required_argument, nullptr, OPT_MAX_CANDIDATES},
@@ -211,7 +216,7 @@ static int run_overlap(int argc, char** argv) {
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC},
                                     {"device", required_argument, nullptr, OPT_DEVICE}, {"gpus", required_argument, nullptr, OPT_GPUS},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
-  std::string prefix;
+  std::string prefix, containments;
   size_t threads = 1, batch = 10000, minOverlap = 10;  // code defaults of src/overlap.cpp:44
   bool exhaustive = false, norc = false, help = false;
   int device = 0, gpus = 1, c;
@@ -240,6 +245,7 @@ static int run_overlap(int argc, char** argv) {
       case OPT_SEED_STRIDE: mmo.seed_stride = num32(optarg); if (!seed_option) seed_option = "--seed-stride"; break;
       case OPT_MAX_SEED_HITS: mmo.max_seed_hits = num32(optarg); if (!seed_option) seed_option = "--max-seed-hits"; break;
       case OPT_MAX_CANDIDATES: mmo.max_candidates = num32(optarg); if (!seed_option) seed_option = "--max-candidates"; break;
+      case OPT_CONTAINMENTS: containments = optarg; if (!seed_option) seed_option = "--containments"; break;
       case 'x': exhaustive = true; break;
       case OPT_BATCH_SIZE: batch = strtoull(optarg, nullptr, 10); break;
       case OPT_NO_RC: norc = true; break;
@@ -272,6 +278,7 @@ static int run_overlap(int argc, char** argv) {
       return 1;
     }
     sigah::MismatchOverlapper finder(mmo);
+    finder.setContainments(containments);
     if (!finder.run(fmi, input, prefix + ".asqg.gz", threads)) {
       fprintf(stderr, "Failed to build overlaps from reads %s: %s\n", input.c_str(), finder.error().c_str());
       return 1;
@@ -281,6 +288,8 @@ static int run_overlap(int argc, char** argv) {
             "%llu skipped as repeats, %llu candidates tested, %llu accepted\n",
             (unsigned long long)finder.records(), (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3],
             (unsigned long long)st[4], (unsigned long long)st[5], (unsigned long long)st[6]);
+    if (!containments.empty())
+      fprintf(stderr, "siga overlap -e: %llu containments to %s\n", (unsigned long long)finder.containments(), containments.c_str());
     return 0;
   }
   // (not destroyed: the process ends when this command returns, and handing tens of GB of tables back to the driver one
@@ -661,6 +670,9 @@ static int unitig_help() {
          "          --seed-length=N, --seed-stride=N, --max-seed-hits=N, --max-candidates=N\n"
          "                                       (need -e) the seeds, as in `siga overlap -e` (defaults: 24, 12, 256, 512)\n"
          "          --contained=FILE             (needs -e) write the names of the contained reads to FILE, in input order\n"
+         "          --place-contained            (needs -e) place every contained read where its container lies, so that it votes,\n"
+         "                                       counts in KC:i: and pairs; --layout lists it with a fifth column `contained`,\n"
+         "                                       --removed no longer does, and its own unitig stays hidden\n"
          "          --consensus, --no-consensus  the vote on or off (default: on exactly with -e); without -e it changes no base and\n"
          "                                       adds changed=0 to every header\n"
          "          --consensus-min-votes=N      replace a base only by one with at least N votes (default: 1)\n"
@@ -801,7 +813,8 @@ static int run_unitig(int argc, char** argv) {
          OPT_GAPFILL, OPT_GAP_KMER, OPT_GAP_MIN_COUNT, OPT_GAP_SLACK, OPT_GAP_MAX_FILL, OPT_GAPS,
          OPT_JOIN, OPT_JOIN_MIN_OVERLAP, OPT_JOIN_MAX_OVERLAP, OPT_JOIN_SLACK, OPT_JOIN_KMER, OPT_JOIN_MIN_COUNT, OPT_JOINS,
          OPT_JOIN_MISMATCHES, OPT_JOIN_MISMATCH_PERMILLE, OPT_BUBBLE_EDITS, OPT_BUBBLE_EDIT_PERMILLE, OPT_REDUCE, OPT_REDUCED_EDGES,
-         OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES, OPT_CONSENSUS, OPT_NO_CONSENSUS, OPT_CONSENSUS_MIN_VOTES, OPT_CONTAINED };
+         OPT_SEED_LENGTH, OPT_SEED_STRIDE, OPT_MAX_SEED_HITS, OPT_MAX_CANDIDATES, OPT_CONSENSUS, OPT_NO_CONSENSUS, OPT_CONSENSUS_MIN_VOTES, OPT_CONTAINED,
+         OPT_PLACE_CONTAINED };
   static const option longopts[] = {{"log4cxx", required_argument, nullptr, 'c'},     {"ini", required_argument, nullptr, 's'},
                                     {"prefix", required_argument, nullptr, 'p'},      {"threads", required_argument, nullptr, 't'},
                                     {"min-overlap", required_argument, nullptr, 'm'}, {"exhaustive", no_argument, nullptr, OPT_EXHAUSTIVE},
@@ -848,6 +861,7 @@ static int run_unitig(int argc, char** argv) {
                                     {"consensus", no_argument, nullptr, OPT_CONSENSUS}, {"no-consensus", no_argument, nullptr, OPT_NO_CONSENSUS},
                                     {"consensus-min-votes", required_argument, nullptr, OPT_CONSENSUS_MIN_VOTES},
                                     {"contained", required_argument, nullptr, OPT_CONTAINED},
+                                    {"place-contained", no_argument, nullptr, OPT_PLACE_CONTAINED},
                                     {"no-opposite-strand", no_argument, nullptr, OPT_NO_RC}, {"device", required_argument, nullptr, OPT_DEVICE},
                                     {"help", no_argument, nullptr, 'h'}, {nullptr, 0, nullptr, 0}};
   std::string prefix, out, layout, graph, removed, cutEdges, chimericOut, pairsOut, linksOut, reducedEdges;
@@ -857,6 +871,7 @@ static int run_unitig(int argc, char** argv) {
   int consensus = -1;  // -1: on exactly when -e is given
   size_t minVotes = 1;
   std::string containedOut;
+  bool placeContained = false;
   const char* seed_option = nullptr;  // the first option on the line that only -e takes
   auto num32 = [](const char* a) {  // a number in 0 .. 2^32 - 1, or 2^32 - 1 for anything else: the library names the field out of range
     char* end = nullptr;
@@ -899,6 +914,7 @@ static int run_unitig(int argc, char** argv) {
       case OPT_MAX_SEED_HITS: mmo.max_seed_hits = num32(optarg); if (!seed_option) seed_option = "--max-seed-hits"; break;
       case OPT_MAX_CANDIDATES: mmo.max_candidates = num32(optarg); if (!seed_option) seed_option = "--max-candidates"; break;
       case OPT_CONTAINED: containedOut = optarg; if (!seed_option) seed_option = "--contained"; break;
+      case OPT_PLACE_CONTAINED: placeContained = true; if (!seed_option) seed_option = "--place-contained"; break;
       case OPT_CONSENSUS: consensus = 1; break;
       case OPT_NO_CONSENSUS: consensus = 0; break;
       case OPT_CONSENSUS_MIN_VOTES:
@@ -1125,6 +1141,7 @@ static int run_unitig(int argc, char** argv) {
   unitigger.setJoinOverlaps(joinOverlaps, joinMinOverlap, joinMaxOverlap, joinSlack, joinKmer, joinMinCount, joinsOut);
   unitigger.setJoinMismatches(joinMismatches, joinMismatchPermille);
   if (mismatches) unitigger.setMismatch(mmo, containedOut);
+  unitigger.setPlaceContained(placeContained);
   unitigger.setConsensus(vote, minVotes);
   if (!unitigger.run(fmi, input, minOverlap, out, layout, threads)) {
     fprintf(stderr, "Failed to build unitigs from reads %s: %s\n", input.c_str(), unitigger.error().c_str());
@@ -1136,6 +1153,14 @@ static int run_unitig(int argc, char** argv) {
     fprintf(stderr, "%llu contained reads set aside; %llu of the unitigs counted above are such a read on its own, which no output shows%s\n",
             (unsigned long long)unitigger.containedReads(), (unsigned long long)unitigger.unitigsHidden(),
             cutTerminal ? " (the others went as islands in the trim rounds: --removed lists them)" : "");
+  if (placeContained) {
+    const uint64_t* pc = unitigger.placeClasses();
+    fprintf(stderr, "%llu contained reads placed, %llu not: %llu without a record, %llu without a root, %llu with a removed root, %llu invalid; "
+            "longest chain %llu\n", (unsigned long long)pc[SIGAX_CP_PLACED],
+            (unsigned long long)(pc[SIGAX_CP_NO_RECORD] + pc[SIGAX_CP_NO_ROOT] + pc[SIGAX_CP_ROOT_REMOVED] + pc[SIGAX_CP_INVALID]),
+            (unsigned long long)pc[SIGAX_CP_NO_RECORD], (unsigned long long)pc[SIGAX_CP_NO_ROOT], (unsigned long long)pc[SIGAX_CP_ROOT_REMOVED],
+            (unsigned long long)pc[SIGAX_CP_INVALID], (unsigned long long)unitigger.placeStatus()[6]);
+  }
   if (vote)
     fprintf(stderr, "%llu columns changed by the vote, %llu of depth below 2, %llu ties kept, largest depth %llu\n",
             (unsigned long long)unitigger.consensusChanged(), (unsigned long long)unitigger.consensusStatus()[3],

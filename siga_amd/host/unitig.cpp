@@ -91,10 +91,12 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   _gaps = _gapsFilled = _gapFillBases = _gapBasesLeft = 0;
   _joinGaps = _joinsMade = _joinOverlapBases = _joinNRemoved = _joinsApprox = _joinCorrected = 0;
   _containedReads = _containedMates = _consChanged = _unitigsHidden = 0;
-  for (int k = 0; k < 8; ++k) _consStatus[k] = _mmStatus[k] = 0;
+  for (int k = 0; k < 8; ++k) _consStatus[k] = _mmStatus[k] = _placeStatus[k] = 0;
+  for (int k = 0; k < 6; ++k) _placeClasses[k] = 0;
   auto fail = [&](const std::string& e) { return _error = e, false; };
   if (!index.handle()) return fail("FMIndex not loaded");
   if (!_mismatch && !_containedOut.empty()) return fail("contained reads are only written with mismatch overlaps");
+  if (!_mismatch && _placeContained) return fail("contained reads are only placed with mismatch overlaps");
   if (_consensus && (_minVotes < 1 || _minVotes > 0xFFFFFFFFull)) return fail("consensus min-votes out of range");
   MismatchRecords mm;  // the reference text once, before any file is touched: an index that cannot serve is refused here
   if (_mismatch && !mm.open(index, &_error)) return false;
@@ -114,12 +116,13 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
   std::vector<uint64_t> offs;
   const size_t per = _piece ? _piece : (size_t)1 << 20;
   std::vector<uint8_t> contained;  // -e: one byte per read
+  std::vector<sigax_mm_edge> containments;  // --place-contained: where every contained read lies in its containers
   if (_mismatch) {
     if (inf.n_strings != n) return fail(input + " holds " + std::to_string(n) + " reads, the index " + std::to_string(inf.n_strings));
     sigax_mmo_params p = _mmo;
     p.min_overlap = (uint32_t)std::min<size_t>(minOverlap, 0xFFFFFFFFull);
     std::vector<uint32_t> num_diff;
-    if (!mm.find(index, p, n, nt, &edges, &num_diff, &contained, _mmStatus, &_error)) return false;
+    if (!mm.find(index, p, n, nt, &edges, &num_diff, &contained, _mmStatus, &_error, _placeContained ? &containments : nullptr)) return false;
     // a record that touches a contained read is dropped: the read stays a unitig of its own, which no output shows
     size_t kept = 0;
     for (size_t i = 0; i < edges.size(); ++i)
@@ -266,6 +269,25 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     for (uint64_t k = 0; k < u.n; ++k)
       _unitigsHidden += hidden[k] = u.lay_offs[k + 1] - u.lay_offs[k] == 1 && contained[u.layout[u.lay_offs[k]].read] ? 1 : 0;
   }
+  // --place-contained: the contained reads into the layout, before anything reads it; what is hidden was settled above
+  struct Classes {
+    uint8_t* p = nullptr;
+    ~Classes() { sigax_free(p); }
+  } cls;
+  auto placed = [&](size_t r) { return cls.p && cls.p[r] == SIGAX_CP_PLACED; };
+  if (_placeContained) {
+    const sigax_contained_opts popts = {{0, 0, 0, 0}};
+    uint64_t* lo2 = nullptr;
+    sigax_placement* lay2 = nullptr;
+    if (sigax_contained_place_host(inf.device, u.n, u.seq_offs, u.lay_offs, u.layout, lengths.data(), n, contained.data(), containments.data(),
+                                   containments.size(), &popts, &lo2, &lay2, &cls.p, _placeStatus) != SIGAX_OK)
+      return fail(std::string("placing the contained reads failed: ") + sigax_last_error());
+    sigax_free(u.lay_offs);
+    sigax_free(u.layout);
+    u.lay_offs = lo2;
+    u.layout = lay2;
+    for (size_t r = 0; r < n; ++r) _placeClasses[cls.p[r] < 6 ? cls.p[r] : 5] += 1;
+  }
   // the vote, before anything reads the bases
   struct Changed {
     uint32_t* p = nullptr;
@@ -322,7 +344,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (_mismatch)  // a pair with a contained mate is no pair
       for (size_t r = 0; r < n; ++r) {
         const uint32_t m = mate[r];
-        if (m != SIGAX_NO_MATE && m < n && (contained[r] || contained[m])) {
+        if (m != SIGAX_NO_MATE && m < n && ((contained[r] && !placed(r)) || (contained[m] && !placed(m)))) {
           if (mate[m] == r) {
             mate[m] = SIGAX_NO_MATE;
             ++_containedMates;
@@ -416,7 +438,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
     if (!rf) return fail("Failed to create " + _removed);
     t.clear();
     for (size_t r = 0; r < n; ++r)
-      if (u.removed[r]) {
+      if (u.removed[r] && !placed(r)) {
         const std::string_view name = reads.name(r);
         t.append(name.data(), name.size());
         t += '\t';
@@ -533,6 +555,7 @@ bool Unitigger::run(const FMIndex& index, const std::string& input, size_t minOv
       t.append(name.data(), name.size());
       t += (pl.flags & SIGAX_PLACED_REV) ? "\t-\t" : "\t+\t";
       append_u64(t, pl.offset);
+      if (pl.flags & SIGAX_PLACED_CONTAINED) t += "\tcontained";
       t += '\n';
     }
     if (t.size() >= ((size_t)1 << 20) || k + 1 == u.n) {

@@ -364,6 +364,47 @@ def unitigs_consensus(res, lengths, seqs, offs, min_votes=1, support=False, devi
     return out
 
 
+def unitigs_place_contained(res, lengths, contained, containments, device=0):
+    """Contained reads placed in a unitig call's layout (sigax_contained_place_host, the rules in include/sigax.h) over the dict
+    `res` any `unitigs*` call returned: lengths u32[n], contained u8[n] and the containment records (_lib.MM_EDGE_DTYPE) of
+    `FMIndexPair.overlap_mismatch(..., containments=True)` -> a copy of `res` whose lay_offs and layout hold the placed contained
+    reads too (flags | _lib.PLACED_CONTAINED), ready for `unitigs_consensus` and `unitigs_pairs`, with place_class u8[n]
+    (_lib.CP_CLASSES) and place_status u64[8] (_lib.CONTAINED_STATUS) beside them.  `res` is not modified."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    contained = np.ascontiguousarray(contained, dtype=np.uint8)
+    recs = np.ascontiguousarray(containments, dtype=_lib.MM_EDGE_DTYPE)
+    n = len(lengths)
+    if len(contained) != n:
+        raise ValueError("contained must have one entry per read")
+    so = np.ascontiguousarray(res["seq_offs"], dtype=np.uint64)
+    lo = np.ascontiguousarray(res["lay_offs"], dtype=np.uint64)
+    lay = np.ascontiguousarray(res["layout"], dtype=PLACEMENT_DTYPE)
+    u = len(so) - 1
+    if u < 0 or len(lo) != u + 1:
+        raise ValueError("seq_offs and lay_offs must have one entry more than there are unitigs")
+    if len(lay) < int(lo[u]):
+        raise ValueError("layout shorter than lay_offs says")
+    L = _lib.lib()
+    opts = _lib.ContainedOpts()
+    lo2, lay2, cls = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    status = np.zeros(8, dtype=np.uint64)
+    _check(L.sigax_contained_place_host(device, u, so.ctypes.data, lo.ctypes.data, lay.ctypes.data if len(lay) else None,
+                                        lengths.ctypes.data if n else None, n, contained.ctypes.data if n else None,
+                                        recs.ctypes.data if len(recs) else None, len(recs), C.byref(opts), C.byref(lo2), C.byref(lay2), C.byref(cls),
+                                        status.ctypes.data), "sigax_contained_place_host")
+    try:
+        out = dict(res)
+        out["lay_offs"] = _copy_records(lo2, u + 1, np.dtype(np.uint64))
+        out["layout"] = _copy_records(lay2, int(status[7]), PLACEMENT_DTYPE)
+        out["place_class"] = _copy_records(cls, n, np.dtype(np.uint8))
+        out["place_status"] = status
+    finally:
+        L.sigax_free(lo2)
+        L.sigax_free(lay2)
+        L.sigax_free(cls)
+    return out
+
+
 def unitigs_pairs(res, lengths, mate, hist_bins=1024, hist_shift=0, max_span=0, outward=False, device=0):
     """Mate-pair statistics and the links between unitig ends (sigax_unitigs_pairs_host, the rules in include/sigax.h) over the
     dict `res` any `unitigs*` call returned: lengths u32[n], mate u32[n] (`mates_by_name`; SIGAX_NO_MATE = none) -> dict(status
@@ -789,14 +830,17 @@ class FMIndexPair:
         text = out.tobytes()
         return [text[int(offs[i]):int(offs[i + 1])] for i in range(n)], valid, changed, status, int(run.value)
 
-    def overlap_mismatch(self, error_permille, min_overlap=45, **seed):
+    def overlap_mismatch(self, error_permille, min_overlap=45, containments=False, **seed):
         """`siga overlap -e` over every read of the index (sigax_mmoverlap_batch, rules in include/sigax.h) -> (edges, a structured
         array of _lib.MM_EDGE_DTYPE: the canonical dovetail records with num_diff, each once, in (query, target, af, length) order;
         contained u8[n_strings]; status u64[8], the pieces' words added up).  seed: seed_length, seed_stride, max_seed_hits,
         max_candidates, max_read_len as keywords, the CLI's defaults otherwise.  The reference text is built from the index at the
-        first call and kept.  Needs the .sai table, reads of ACGT only and set_reads()."""
+        first call and kept.  Needs the .sai table, reads of ACGT only and set_reads().  containments=True
+        (SIGAX_MMO_CONTAINMENTS) -> (edges, contained, status, containments): the containment records of rule 9 in the same dtype
+        and order -- query the contained read, target its container, af = 8 | 4 if reversed, reserved the first column of the
+        container's forward text it covers -- split from the dovetails; status[7] counts both kinds."""
         L = _lib.lib()
-        params = _lib.MmoParams(int(error_permille), min_overlap=int(min_overlap), **seed)
+        params = _lib.MmoParams(int(error_permille), min_overlap=int(min_overlap), flags=_lib.MMO_CONTAINMENTS if containments else 0, **seed)
         if getattr(self, "_pile_ref", None) is None:
             ref = C.c_void_p()
             _check(L.sigax_pile_ref_create(self._h, C.byref(ref)), "sigax_pile_ref_create")
@@ -811,6 +855,9 @@ class FMIndexPair:
             edges = _copy_records(ptr, int(count.value), _lib.MM_EDGE_DTYPE)
         finally:
             L.sigax_free(ptr)
+        if containments:
+            is_cont = (edges["af"] & _lib.MM_CONTAINMENT) != 0
+            return edges[~is_cont], contained, status, edges[is_cont]
         return edges, contained, status
 
     def get_strings(self, rows, which=0, max_len=MAX_STRING_LEN, stretch=False):
